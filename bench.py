@@ -19,15 +19,18 @@ Frames are software-pipelined across three HIP streams (render.py, render_async)
 the previous frame's compositing run underneath this frame's MLP kernel; every step still enqueues one whole frame
 of every stage (--serial times the one-stream form).
 
-At N = 1 the same JSON line also carries two more records measured in the same process after the headline loop
-(BASELINE.json configs[2] and configs[4] at full size; --no-extras skips them):
+A plain run does only what the headline needs: set up, warm up, time --steps frames, write the last timed frame if
+--dump-outputs DIR is given (DIR/pixels.npy, float32 [rows, W, 3]; rank 0 at N > 1 writes the gathered frame), and print
+the JSON line.  --full adds everything else, measured after the headline loop: the dominant kernel alone under HIP events
+(roofline, --kernel-steps frames), the CPU baseline with PSNR against the oracle (--no-cpu skips it) and, at N = 1, the
+records below (BASELINE.json configs[2] and configs[4] at full size; --no-extras skips them):
   "train_config3": one optimisation step of 4096 rays, hash grid (L=16, F=2, T=2^19) + 4x64 MLP, 128^3 grid: timed as one
                    hipGraph per step (Trainer.capture_step: device-side segment count, traversal one batch ahead) with the
                    host-segment-count form beside it (ms_per_step_host_count), the per-stage HIP-event split and the hash
                    gather / scatter kernels against the HBM roofline;
   "config5":       the 1008x756 forward-facing frame, 256^3 sparse grid, 8x256 MLP, with mlp_fwd256x16_kernel against the
                    MFMA roofline.
-The headline (metric/value/roofline/cpu_baseline) stays configs[1].
+The headline (metric/value, and under --full roofline/cpu_baseline) stays configs[1].
 
 Prints ONE JSON line on rank 0; see DESIGN.md for the roofline arithmetic.
 """
@@ -552,11 +555,14 @@ def parse():
     ap.add_argument("--poses", type=int, default=4)
     ap.add_argument("--scene", default="lego", choices=["lego", "llff"], help="lego: hemisphere poses around the Lego stand-in (configs[1]); "
                     "llff: forward-facing frustum over a sparse fern-like grid (configs[4], with --grid 256 --neurons 256)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the train_config3 / config5 records (N = 1 only)")
-    ap.add_argument("--extra-steps", type=int, default=30, help="timed steps of each extra record")
-    ap.add_argument("--kernel-steps", type=int, default=5, help="extra frames with HIP events around the MLP kernel")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the roofline, the cpu_baseline and (N = 1) "
+                    "the extra records; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed frame to DIR/pixels.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the train_config3 / config5 records (N = 1 only)")
+    ap.add_argument("--extra-steps", type=int, default=30, help="timed steps of each extra record (--full)")
+    ap.add_argument("--kernel-steps", type=int, default=5, help="extra frames with HIP events around the MLP kernel (--full)")
     ap.add_argument("--no-compact", action="store_true", help="fp32 float4 radiance + t_vals between the MLP kernel and the compositor "
                     "(the reference's convertHalfToFloat layout) instead of the network's half outputs")
     ap.add_argument("--reserve-cus", type=int, default=-1, help="CUs kept free of the persistent MLP grid (default: 4 at N > 1, else 0)")
@@ -564,7 +570,10 @@ def parse():
     ap.add_argument("--emulate-shard-of", type=int, default=0, metavar="N", help="diagnostic, single process: render only rank 0's "
                     "row shard of an N-rank run (no collective) to see what one rank's frame costs; the JSON line is marked "
                     "'emulated_shard_of' and its value is NOT a whole-job figure")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(n):
@@ -693,11 +702,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert not pipe.overflowed(), "segment capacity overflow: calibrate() margin too small"
+    last = args.warmup + args.steps - 1
+
+    # ---- --dump-outputs: the frame of the last timed step, as its caller receives it (rank 0: the gathered frame at N > 1) ----
+    if args.dump_outputs and rank == 0:
+        frame = sh.assemble(gather_bufs[last & 1]) if world > 1 else pix_bufs[last & 1][:n_local].reshape(-1, W, 3)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pixels.npy"), frame.float().cpu().numpy())
 
     # ---- N > 1: the gathered frame must be the single-GPU frame, bit for bit (outside the timed region) ----
     gather_check = None
     if world > 1:
-        last = args.warmup + args.steps - 1
         if rank == 0:
             full = render.RenderPipeline(net, R, W, H, focal, occupancy=occ, max_segments=1024)
             full.calibrate([poses[last % len(poses)]])
@@ -709,8 +724,8 @@ def main():
                 f"MISMATCH: {int((got != want).any(dim=2).sum())} of {W * H} pixels differ"
             del full
 
-    # ---- dominant kernel (fused sampler+encode+MLP), HIP events on the launch stream ----
-    kern_ms, kern_smp = time_shade(pipe, poses_d, ray_begin, n_local, args.kernel_steps)
+    # ---- --full: dominant kernel (fused sampler+encode+MLP), HIP events on the launch stream ----
+    kern_ms, kern_smp = time_shade(pipe, poses_d, ray_begin, n_local, args.kernel_steps) if args.full else (None, 0.0)
 
     rays_per_step = W * H
     value = rays_per_step * args.steps / elapsed / 1e6
@@ -765,10 +780,11 @@ def main():
                 if world > 1:
                     out["roofline"]["traffic_note"] = "PMC bytes of the full frame's launch x this rank's share of the samples"
         out["config"]["segments_per_frame_local_max"] = worst
-        out["config"]["mean_samples_per_ray"] = round(smp / max(n_local, 1), 2)
+        if args.full:
+            out["config"]["mean_samples_per_ray"] = round(smp / max(n_local, 1), 2)
 
-    # ---- cpu_baseline + PSNR vs oracle on a bounded ray sample spread over ALL bench poses (rank 0, N=1 only) ----
-    if rank == 0 and world == 1 and not args.no_cpu:
+    # ---- --full: cpu_baseline + PSNR vs oracle on a bounded ray sample spread over ALL bench poses (rank 0, N=1 only) ----
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         import oracle as O   # checker / baseline only
         cfg = O.mlp_cfg(n_neurons=args.neurons, n_hidden_layers=args.layers)
 
@@ -817,8 +833,8 @@ def main():
                       f"oracle/rtxn_oracle.c orc_render_tiled, {cpu_s:.1f} s",
         }
 
-    # ---- configs[2] and configs[4] at full size, same process, after the headline (N = 1 only) ----
-    if rank == 0 and world == 1 and not args.no_extras and not args.emulate_shard_of:
+    # ---- --full: configs[2] and configs[4] at full size, same process, after the headline (N = 1 only) ----
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.emulate_shard_of:
         del pipe
         torch.cuda.empty_cache()
         out["train_config3"], out["render_hash4x64"] = extra_train_config3(args.extra_steps, 5, args.kernel_steps)

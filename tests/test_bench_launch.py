@@ -61,3 +61,29 @@ def test_bench_gpus_2_without_a_launcher_rehearsed_on_one_gpu(gpu):
     assert rec["n_gpus"] == 2 and rec["steps"] == 2 and rec["value"] > 0
     assert rec["gather_check"].startswith("bit-identical")
     assert rec["scaling"] == "strong" and "ray-shard x2" in rec["config"]["parallelism"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_last_frame_and_full_adds_the_rest(gpu, tmp_path):
+    """A plain run prints the headline only and --dump-outputs writes the frame of its last timed step; --full adds the
+    roofline; the same arguments of the timed path give the same frame, bit for bit."""
+    import numpy as np
+    small = ["--steps", "3", "--warmup", "1", "--width", "200", "--height", "150", "--grid", "64"]
+
+    def run(*extra):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *small, *extra], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0])
+
+    plain = run("--dump-outputs", str(tmp_path / "plain"))
+    assert plain["steps"] == 3 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["unit"] == "Mrays/s" and plain["higher_is_better"] is True and plain["dtype"] == "f16"
+    assert not {"roofline", "cpu_baseline", "train_config3", "config5"} & set(plain)
+    pix = np.load(tmp_path / "plain" / "pixels.npy")
+    assert pix.dtype == np.float32 and pix.shape == (150, 200, 3)
+    assert np.isfinite(pix).all() and pix.max() > 0
+    full = run("--full", "--no-cpu", "--no-extras", "--kernel-steps", "1", "--dump-outputs", str(tmp_path / "full"))
+    assert full["roofline"]["kernel_ms"] > 0 and "mean_samples_per_ray" in full["config"]
+    assert np.array_equal(pix, np.load(tmp_path / "full" / "pixels.npy"))

@@ -14,13 +14,13 @@ repo=$(pwd)
 mkdir -p "$out"
 export TMPDIR=/tmp
 if has bench; then
-python3 bench.py > "$out/bench_n1.json" 2> "$out/bench_n1.err"
+python3 bench.py --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"
 echo "bench done"
 fi
 cd /tmp
 if has traces; then
-rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/kt_pipelined" -- python3 "$repo/bench.py" --steps 5 --warmup 2 --no-cpu > "$repo/$out/bench_n1_under_rocprof.json" 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/kt_serial" -- python3 "$repo/bench.py" --steps 5 --warmup 2 --no-cpu --no-extras --serial > "$repo/$out/serial_bench_n1_under_rocprof.json" 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/kt_pipelined" -- python3 "$repo/bench.py" --full --steps 5 --warmup 2 --no-cpu > "$repo/$out/bench_n1_under_rocprof.json" 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/kt_serial" -- python3 "$repo/bench.py" --full --steps 5 --warmup 2 --no-cpu --no-extras --serial > "$repo/$out/serial_bench_n1_under_rocprof.json" 2>/dev/null
 echo "kernel traces done"
 fi
 SQ="GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES SQ_WAIT_INST_ANY"
@@ -44,7 +44,7 @@ pmc() {   # pmc <tag> <script> <args...>: four passes of one command
   echo "pmc $tag done"
 }
 if has pmc1; then
-pmc headline "$repo/bench.py" --steps 3 --warmup 1 --no-cpu --no-extras --kernel-steps 2 --serial
+pmc headline "$repo/bench.py" --full --steps 3 --warmup 1 --no-cpu --no-extras --kernel-steps 2 --serial
 pmc config5 "$repo/tools/pmc_extras.py" config5
 fi
 if has pmc2; then
@@ -85,7 +85,7 @@ flat "$out/pmc_headline_fetch/*/*counter_collection.csv" $out/pmc_fetch_size.csv
 flat "$out/pmc_headline_write/*/*counter_collection.csv" $out/pmc_write_size.csv
 flat "$out/pmc_headline_sq/*/*counter_collection.csv" $out/pmc_sq.csv
 # PMC_MERGE=<earlier pmc_kernels.json>: a partial re-collection (phase `ref`) keeps the earlier entries whose kernels are unchanged
-python3 tools/pmc_kernels_json.py ${PMC_MERGE:+--merge $PMC_MERGE} $out/pmc_kernels.json "${PMC_NOTE:-rocprofv3 --pmc, separate passes per counter set (FETCH_SIZE | WRITE_SIZE | SQ group | TCC group) over: bench.py --steps 3 --warmup 1 --no-cpu --no-extras --kernel-steps 2 --serial; tools/pmc_extras.py config5 | config3 | ref8x128}" \
+python3 tools/pmc_kernels_json.py ${PMC_MERGE:+--merge $PMC_MERGE} $out/pmc_kernels.json "${PMC_NOTE:-rocprofv3 --pmc, separate passes per counter set (FETCH_SIZE | WRITE_SIZE | SQ group | TCC group) over: bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras --kernel-steps 2 --serial; tools/pmc_extras.py config5 | config3 | ref8x128}" \
   $(ls $out/pmc_*/*/*counter_collection.csv) > $out/pmc_kernels_summary.txt
 flat "$out/pmc_config3_tcp/*/*counter_collection.csv" $out/pmc_config3_tcp.csv
 flat "$out/pmc_config3_tcp2/*/*counter_collection.csv" $out/pmc_config3_tcp2.csv
