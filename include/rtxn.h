@@ -281,6 +281,28 @@ int rtxn_volrender_fwd_compact_nerf(const void* radiance_half4, const float* seg
                                     const int* indices, int batch_size, int num_samples_per_hit, float* pixels,
                                     rtxn_stream_t stream);
 
+/* Colour, opacity and expected depth in one pass, with an optional background colour (not in the reference; NeRF's
+ * acc_map / depth_map).  For ray r with weights w_i -- exactly those its pixel uses in vr_mode, RTXN_VR_COMPAT quirks
+ * included --
+ *   opacity[r] = A = sum w_i;   depth[r] = sum w_i d_i (unnormalised: divide by A for a surface depth);
+ *   pixels[r]  = sum w_i c_i + (1 - A) background, the background term added per channel only where it is non-zero,
+ * with d_i = t_start_j + u_i (t_end_j - t_start_j) the distance of sample i (index i in its segment j) from the ray origin:
+ * u_i = i/K (REGULAR; the sampler evaluates there although its t_vals say (i+1)/K) or (i + 0.5)/K (MIDPOINT_WORLD).
+ * Layouts as the three entry points above:
+ *   RTXN_RADIANCE_FLOAT4: radiance float[P*K][4], ray_hit float[P*K] (t_vals / step lengths) -- rtxn_volrender_fwd;
+ *   RTXN_RADIANCE_HALF4:  radiance half[P*K][4]; ray_hit NULL (RTXN_VR_COMPAT, implicit REGULAR t_vals) or segment_step
+ *                         float[P] (RTXN_VR_NERF) -- rtxn_volrender_fwd_compact[_nerf].
+ * t_start, t_end: float[P], the segments' entry and exit distances (rtxn_trace_params.t_start / t_end of a RTXN_TRACE_DDA
+ * traversal; params.h:28-29); needed only when depth != NULL.  background: HOST float[3], or NULL = black.  depth and
+ * opacity (float[B]) may each be NULL.  With a zero background the pixels are bit-identical to the entry point of the same
+ * layout (same kernel choice -- pairs for even K and aligned buffers -- and the same operations).  A ray with no segments
+ * gets opacity 0, depth 0 and pixel = background.  Rounding can put A a few ulp above 1 for opaque rays. */
+enum rtxn_radiance_layout { RTXN_RADIANCE_FLOAT4 = 0, RTXN_RADIANCE_HALF4 = 1 };
+int rtxn_volrender_fwd_aux(const void* radiance, int radiance_layout, const float* ray_hit, const int* num_hits,
+                           const int* indices, const float* t_start, const float* t_end, int batch_size,
+                           int num_samples_per_hit, int vr_mode, int sample_type, const float* background, float* pixels,
+                           float* depth, float* opacity, rtxn_stream_t stream);
+
 /* ---- hash-grid inference -------------------------------------------------------------------------------------------
  * launchSampler + HashGrid(position) (+) Frequency(direction) encoding + network->forward + the half outputs' glue
  * (main.cu:703-728 with the hash-grid model north_star names) as ONE kernel over packed segments: the hash-grid counterpart of
@@ -318,10 +340,14 @@ int rtxn_hashmlp_forward_segments(const rtxn_mlp* m, const rtxn_hashgrid* g, int
 enum rtxn_render_flags {
   RTXN_RENDER_FLOAT4 = 1,   /* hand the compositor the reference's float4 radiance + float t_vals (convertHalfToFloat layout,
                              * 20 B/sample) instead of the network's own half4 outputs (8 B/sample); same pixels bit for bit */
-  RTXN_RENDER_STABLE_INPUTS = 2   /* rtxn_render_frame_async only: the caller promises that a frame's device inputs (the 16
+  RTXN_RENDER_STABLE_INPUTS = 2,  /* rtxn_render_frame_async only: the caller promises that a frame's device inputs (the 16
                              * look_at floats, the occupancy bits) are complete BEFORE the call and stay untouched until the
                              * frame's traversal has run (pre-uploaded poses, one buffer per frame in flight).  The traversal
                              * then does not wait for the caller's stream and overlaps the previous frame's MLP kernel. */
+  RTXN_RENDER_AUX = 4       /* the traversal's write pass also stores each segment's entry and exit distance (t_start,
+                             * t_end: +8 B per segment of capacity in the workspace, +8 B written per segment), which the
+                             * depth output of rtxn_render_frame_ex needs.  RTXN_TRACE_DDA only: the RTXN_TRACE_COMPAT walk
+                             * measures its distances from each re-launched origin (as the reference's Params.t_start) */
 };
 typedef struct rtxn_render_config {
   const rtxn_mlp* mlp;
@@ -393,6 +419,25 @@ int rtxn_render_frame_async(rtxn_render* r, const float* look_at, uint32_t ray_b
  * reuse its array at once) and uploaded on the traversal stream, so the pipeline overlaps fully without any promise. */
 int rtxn_render_frame_async_host(rtxn_render* r, const float* look_at_host, uint32_t ray_begin, uint32_t ray_count,
                                  float* pixels, rtxn_stream_t stream, rtxn_stream_t* composite_stream);
+/* What a frame call writes beyond the pixels (rtxn_volrender_fwd_aux has the definitions).  pixels: float[ray_count][3]
+ * (required); depth, opacity: float[ray_count], each may be NULL -- depth needs a renderer created with RTXN_RENDER_AUX,
+ * opacity and the background work on every renderer.  background: added as (1 - opacity) x background per channel where it
+ * is non-zero; all zero = the pixels of rtxn_render_frame bit for bit.  The background travels as a kernel argument: a
+ * captured graph keeps the background it was captured with. */
+typedef struct rtxn_render_outputs {
+  float* pixels;
+  float* depth;
+  float* opacity;
+  float background[3];
+} rtxn_render_outputs;
+/* rtxn_render_frame and rtxn_render_frame_async[_host] with the outputs above: same stages, same streams, same ordering
+ * contract, and every output complete where the pixels are (on `stream`, resp. on *composite_stream).  pose_on_host != 0:
+ * look_at is a HOST array, as rtxn_render_frame_async_host.  rtxn_render_frame_ex is capturable like rtxn_render_frame;
+ * the async form, like its counterparts, is not. */
+int rtxn_render_frame_ex(rtxn_render* r, int slot, const float* look_at, uint32_t ray_begin, uint32_t ray_count,
+                         const rtxn_render_outputs* outputs, rtxn_stream_t stream);
+int rtxn_render_frame_async_ex(rtxn_render* r, const float* look_at, int pose_on_host, uint32_t ray_begin, uint32_t ray_count,
+                               const rtxn_render_outputs* outputs, rtxn_stream_t stream, rtxn_stream_t* composite_stream);
 /* Make `stream` wait for everything rtxn_render_frame_async has enqueued on the internal streams. */
 int rtxn_render_drain(rtxn_render* r, rtxn_stream_t stream);
 /* Overflow report without polling the device.  Every frame updates four per-slot counters ON THE DEVICE (segments of the

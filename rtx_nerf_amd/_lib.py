@@ -126,6 +126,11 @@ class RenderStats(C.Structure):
                                         "max_segments")]
 
 
+class RenderOutputs(C.Structure):
+    """struct rtxn_render_outputs (include/rtxn.h)."""
+    _fields_ = [("pixels", C.c_void_p), ("depth", C.c_void_p), ("opacity", C.c_void_p), ("background", C.c_float * 3)]
+
+
 # every symbol include/rtxn.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
 SYMBOLS = {
@@ -157,6 +162,7 @@ SYMBOLS = {
     "rtxn_mlp_forward_segments_compact": (_I, [_P, _P, _P, _P, _P, _L, _P, _P]),
     "rtxn_volrender_fwd_compact": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "rtxn_volrender_fwd_compact_nerf": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "rtxn_volrender_fwd_aux": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtxn_hashmlp_supported": (_I, [_P, _P, _I]),
     "rtxn_hashmlp_forward_segments": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P]),
     "rtxn_render_workspace_bytes": (C.c_size_t, [C.POINTER(RenderConfig)]),
@@ -167,6 +173,8 @@ SYMBOLS = {
     "rtxn_render_frame": (_I, [_P, _I, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "rtxn_render_frame_async": (_I, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(_P)]),
     "rtxn_render_frame_async_host": (_I, [_P, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, _P, _P, C.POINTER(_P)]),
+    "rtxn_render_frame_ex": (_I, [_P, _I, _P, C.c_uint32, C.c_uint32, C.POINTER(RenderOutputs), _P]),
+    "rtxn_render_frame_async_ex": (_I, [_P, _P, _I, C.c_uint32, C.c_uint32, C.POINTER(RenderOutputs), _P, C.POINTER(_P)]),
     "rtxn_render_drain": (_I, [_P, _P]),
     "rtxn_render_status": (_I, [_P, _I, C.POINTER(RenderStats)]),
     "rtxn_render_slot_buffers": (_I, [_P, _I] + [C.POINTER(_P)] * 11),

@@ -326,6 +326,31 @@ def volrender_compact_nerf(radiance_half4, segment_step, num_hits, indices, batc
           "rtxn_volrender_fwd_compact_nerf")
 
 
+RADIANCE_FLOAT4, RADIANCE_HALF4 = 0, 1   # enum rtxn_radiance_layout
+
+
+def volrender_fwd_aux(radiance, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, pixels, *, mode=VR_COMPAT,
+                      sample_type=SAMPLING_REGULAR, t_start=None, t_end=None, depth=None, opacity=None, background=None):
+    """Colour, opacity (sum of the weights) and expected depth (sum w_i d_i) in one pass, with an optional background colour
+    added as (1 - opacity) * background.  radiance: float32[N, 4] with ray_hit = t_vals / step lengths float32[N], or
+    float16[N, 4] with ray_hit = None (VR_COMPAT) / segment_step float32[P] (VR_NERF).  t_start, t_end: float32[P] segment
+    entry / exit distances, needed for depth.  depth, opacity: float32[B] or None.  background: 3 floats or None."""
+    layout = RADIANCE_HALF4 if radiance.dtype == torch.float16 else RADIANCE_FLOAT4
+    bg = None
+    if background is not None:
+        bg = (C.c_float * 3)(*[float(v) for v in background])
+    check(_lib.lib().rtxn_volrender_fwd_aux(_ptr(radiance, radiance.dtype if layout == RADIANCE_HALF4 else torch.float32, "radiance"),
+                                            layout, _ptr(ray_hit, torch.float32, "ray_hit"),
+                                            _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"),
+                                            _ptr(t_start, torch.float32, "t_start"), _ptr(t_end, torch.float32, "t_end"),
+                                            batch_size, num_samples_per_hit, mode, sample_type,
+                                            C.cast(bg, C.c_void_p) if bg is not None else None,
+                                            _ptr(pixels, torch.float32, "pixels"), _ptr(depth, torch.float32, "depth"),
+                                            _ptr(opacity, torch.float32, "opacity"), _stream()),
+          "rtxn_volrender_fwd_aux")
+    return pixels, depth, opacity
+
+
 def hashmlp_supported(net, grid):
     """True if the fused hash-encode + MLP inference kernel is built for this model / grid pair."""
     return bool(_lib.lib().rtxn_hashmlp_supported(net._h, grid._h, grid.n_dir_freqs))

@@ -41,6 +41,8 @@ struct Slot {
   void* radiance;     // half4[m*32] (compact) or float4[m*32]
   float* t_vals;      // float[m*32]: RTXN_RENDER_FLOAT4 only
   float* seg_step;    // float[m]: compact RTXN_VR_NERF only
+  float* t_start;     // float[m] each: RTXN_RENDER_AUX only (the segments' entry / exit distances, for the depth output)
+  float* t_end;
   // host side
   int* acct_host;     // pinned int[4], copy of acct
   float* pose_host;   // pinned float[16]: staging of rtxn_render_frame_async_host's pose
@@ -98,7 +100,11 @@ int validate(const rtxn_render_config* c, const char* who) {
                "%s: sample_type %d (the deterministic modes only: REGULAR, MIDPOINT_WORLD)", who, c->sample_type);
   RTXN_REQUIRE(c->max_segments > 0 && c->max_segments <= (1L << 31) / 32 * 31, "%s: max_segments = %ld", who, c->max_segments);
   RTXN_REQUIRE(c->n_slots >= 1 && c->n_slots <= kMaxSlots, "%s: n_slots = %d out of [1,%d]", who, c->n_slots, kMaxSlots);
-  RTXN_REQUIRE((c->flags & ~(RTXN_RENDER_FLOAT4 | RTXN_RENDER_STABLE_INPUTS)) == 0, "%s: unknown flags 0x%x", who, c->flags);
+  RTXN_REQUIRE((c->flags & ~(RTXN_RENDER_FLOAT4 | RTXN_RENDER_STABLE_INPUTS | RTXN_RENDER_AUX)) == 0, "%s: unknown flags 0x%x", who, c->flags);
+  if ((c->flags & RTXN_RENDER_AUX) && c->trace_mode != RTXN_TRACE_DDA) {
+    rtxn::set_error("%s: RTXN_RENDER_AUX needs RTXN_TRACE_DDA (the compat walk's t are measured from each re-launched origin, not from the camera)", who);
+    return RTXN_ERR_UNSUPPORTED;
+  }
   RTXN_REQUIRE(c->sub_rays >= 0 && c->sub_rays <= 64 && (c->sub_rays & (c->sub_rays - 1)) == 0, "%s: sub_rays = %d must be 0 or a power of two up to 64", who, c->sub_rays);
   const uint64_t launch = (uint64_t)c->width * c->height;
   RTXN_REQUIRE(c->max_rays <= launch, "%s: max_rays = %u exceeds the %u x %u launch", who, c->max_rays, c->width, c->height);
@@ -162,6 +168,10 @@ size_t layout(const rtxn_render_config* c, uint8_t* base, rtxn_render* r) {
       s.radiance = cv.take<uint8_t>(m * K * 16);
       s.t_vals = cv.take<float>(m * K);
     }
+    if (c->flags & RTXN_RENDER_AUX) {
+      s.t_start = cv.take<float>(m);
+      s.t_end = cv.take<float>(m);
+    }
     if (r) r->slots[i] = s;
   }
   return cv.off;
@@ -212,6 +222,8 @@ void trace_params(const rtxn_render* r, const Slot& g, uint32_t ray_begin, uint3
     p.start_points = g.start;
     p.end_points = g.end;
     p.seg_view = g.seg_view;
+    p.t_start = g.t_start;       // NULL without RTXN_RENDER_AUX
+    p.t_end = g.t_end;
     p.num_stored = g.num_stored;
     p.segment_capacity = c.max_segments;
   }
@@ -302,6 +314,24 @@ int composite(rtxn_render* r, Slot& g, uint32_t n, float* pixels, hipStream_t s)
     return rtxn_volrender_fwd_compact(g.radiance, g.num_stored, g.indices, (int)n, K, pixels, s);
   }
   return rtxn_volrender_fwd(nullptr, static_cast<const float*>(g.radiance), g.num_stored, g.indices, g.t_vals, (int)n, K, pixels, c.vr_mode, s);
+}
+
+// composite() with the outputs of rtxn_render_outputs: the plain compositor when only pixels are asked for, else the aux one
+// (same weights, same pixels bit for bit with a zero background)
+int composite_out(rtxn_render* r, Slot& g, uint32_t n, const rtxn_render_outputs& o, hipStream_t s) {
+  const bool bg = o.background[0] != 0.0f || o.background[1] != 0.0f || o.background[2] != 0.0f;
+  if (!o.depth && !o.opacity && !bg) return composite(r, g, n, o.pixels, s);
+  const rtxn_render_config& c = r->cfg;
+  const float* hit = r->compact ? (c.vr_mode == RTXN_VR_NERF ? g.seg_step : nullptr) : g.t_vals;
+  return rtxn_volrender_fwd_aux(g.radiance, r->compact ? RTXN_RADIANCE_HALF4 : RTXN_RADIANCE_FLOAT4, hit, g.num_stored, g.indices,
+                                g.t_start, g.t_end, (int)n, RTXN_NUM_SAMPLES_PER_SEGMENT, c.vr_mode, c.sample_type, o.background,
+                                o.pixels, o.depth, o.opacity, s);
+}
+
+int check_outputs(const rtxn_render* r, const rtxn_render_outputs* o, const char* who) {
+  RTXN_REQUIRE(o && o->pixels, "%s: NULL outputs or pixels", who);
+  RTXN_REQUIRE(!o->depth || (r->cfg.flags & RTXN_RENDER_AUX), "%s: depth needs a renderer created with RTXN_RENDER_AUX", who);
+  return RTXN_OK;
 }
 
 }  // namespace
@@ -425,6 +455,28 @@ extern "C" int rtxn_render_count_segments(rtxn_render* r, const float* look_at, 
   return RTXN_OK;
 }
 
+namespace {
+
+int frame_serial(rtxn_render* r, int slot, const float* look_at, uint32_t ray_begin, uint32_t ray_count, const rtxn_render_outputs& o,
+                 hipStream_t s) {
+  Slot& g = r->slots[slot];
+  if (!capturing(s)) harvest(r, g, false);
+  int rc = geometry(r, g, look_at, false, ray_begin, ray_count, s);
+  if (rc != RTXN_OK) return rc;
+  rc = shade(r, g, s);
+  if (rc != RTXN_OK) return rc;
+  return composite_out(r, g, ray_count, o, s);
+}
+
+rtxn_render_outputs pixels_only(float* pixels) {
+  rtxn_render_outputs o;
+  memset(&o, 0, sizeof(o));
+  o.pixels = pixels;
+  return o;
+}
+
+}  // namespace
+
 extern "C" int rtxn_render_frame(rtxn_render* r, int slot, const float* look_at, uint32_t ray_begin, uint32_t ray_count, float* pixels,
                                  rtxn_stream_t stream) {
   RTXN_REQUIRE(r && look_at && pixels, "rtxn_render_frame: NULL argument");
@@ -432,14 +484,19 @@ extern "C" int rtxn_render_frame(rtxn_render* r, int slot, const float* look_at,
   int rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame");
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
-  hipStream_t s = rtxn::as_stream(stream);
-  Slot& g = r->slots[slot];
-  if (!capturing(s)) harvest(r, g, false);
-  rc = geometry(r, g, look_at, false, ray_begin, ray_count, s);
+  return frame_serial(r, slot, look_at, ray_begin, ray_count, pixels_only(pixels), rtxn::as_stream(stream));
+}
+
+extern "C" int rtxn_render_frame_ex(rtxn_render* r, int slot, const float* look_at, uint32_t ray_begin, uint32_t ray_count,
+                                    const rtxn_render_outputs* outputs, rtxn_stream_t stream) {
+  RTXN_REQUIRE(r && look_at, "rtxn_render_frame_ex: NULL argument");
+  int rc = check_outputs(r, outputs, "rtxn_render_frame_ex");
   if (rc != RTXN_OK) return rc;
-  rc = shade(r, g, s);
+  RTXN_REQUIRE(slot >= 0 && slot < r->n_slots, "rtxn_render_frame_ex: slot %d out of [0,%d)", slot, r->n_slots);
+  rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame_ex");
   if (rc != RTXN_OK) return rc;
-  return composite(r, g, ray_count, pixels, s);
+  RTXN_DEVICE_OR_FAIL();
+  return frame_serial(r, slot, look_at, ray_begin, ray_count, *outputs, rtxn::as_stream(stream));
 }
 
 namespace {
@@ -452,8 +509,8 @@ namespace {
 //  * with RTXN_RENDER_STABLE_INPUTS (the caller's promise that a frame's inputs are complete and stay untouched from the call
 //    until the frame's traversal has run: pre-uploaded poses) or with a HOST pose (staged through pinned memory here): only on
 //    a slot's first use and after rtxn_render_set_occupancy -- the fully overlapped pipeline.
-int frame_async(rtxn_render* r, const float* look_at, bool pose_on_host, uint32_t ray_begin, uint32_t ray_count, float* pixels,
-                hipStream_t main_s, rtxn_stream_t* composite_stream) {
+int frame_async(rtxn_render* r, const float* look_at, bool pose_on_host, uint32_t ray_begin, uint32_t ray_count,
+                const rtxn_render_outputs& outputs, hipStream_t main_s, rtxn_stream_t* composite_stream) {
   const int b = (int)(r->frame % r->n_slots);
   r->frame++;
   Slot& g = r->slots[b];
@@ -482,7 +539,7 @@ int frame_async(rtxn_render* r, const float* look_at, bool pose_on_host, uint32_
   if (rc != RTXN_OK) return rc;
   RTXN_HIP(hipEventRecord(g.ev_mlp, main_s));
   RTXN_HIP(hipStreamWaitEvent(r->comp, g.ev_mlp, 0));
-  rc = composite(r, g, ray_count, pixels, r->comp);
+  rc = composite_out(r, g, ray_count, outputs, r->comp);
   if (rc != RTXN_OK) return rc;
   RTXN_HIP(hipEventRecord(g.ev_comp, r->comp));
   g.used = true;
@@ -500,7 +557,7 @@ extern "C" int rtxn_render_frame_async(rtxn_render* r, const float* look_at, uin
   RTXN_DEVICE_OR_FAIL();
   hipStream_t main_s = rtxn::as_stream(stream);
   RTXN_REQUIRE(!capturing(main_s), "rtxn_render_frame_async: not capturable (internal streams); capture rtxn_render_frame instead");
-  return frame_async(r, look_at, false, ray_begin, ray_count, pixels, main_s, composite_stream);
+  return frame_async(r, look_at, false, ray_begin, ray_count, pixels_only(pixels), main_s, composite_stream);
 }
 
 extern "C" int rtxn_render_frame_async_host(rtxn_render* r, const float* look_at_host, uint32_t ray_begin, uint32_t ray_count,
@@ -511,7 +568,20 @@ extern "C" int rtxn_render_frame_async_host(rtxn_render* r, const float* look_at
   RTXN_DEVICE_OR_FAIL();
   hipStream_t main_s = rtxn::as_stream(stream);
   RTXN_REQUIRE(!capturing(main_s), "rtxn_render_frame_async_host: not capturable (internal streams, host staging)");
-  return frame_async(r, look_at_host, true, ray_begin, ray_count, pixels, main_s, composite_stream);
+  return frame_async(r, look_at_host, true, ray_begin, ray_count, pixels_only(pixels), main_s, composite_stream);
+}
+
+extern "C" int rtxn_render_frame_async_ex(rtxn_render* r, const float* look_at, int pose_on_host, uint32_t ray_begin, uint32_t ray_count,
+                                          const rtxn_render_outputs* outputs, rtxn_stream_t stream, rtxn_stream_t* composite_stream) {
+  RTXN_REQUIRE(r && look_at, "rtxn_render_frame_async_ex: NULL argument");
+  int rc = check_outputs(r, outputs, "rtxn_render_frame_async_ex");
+  if (rc != RTXN_OK) return rc;
+  rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame_async_ex");
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  hipStream_t main_s = rtxn::as_stream(stream);
+  RTXN_REQUIRE(!capturing(main_s), "rtxn_render_frame_async_ex: not capturable (internal streams); capture rtxn_render_frame_ex instead");
+  return frame_async(r, look_at, pose_on_host != 0, ray_begin, ray_count, *outputs, main_s, composite_stream);
 }
 
 extern "C" int rtxn_render_drain(rtxn_render* r, rtxn_stream_t stream) {

@@ -20,7 +20,7 @@
 //
 // HBM-bound on its outputs: 24 B/ray (origin 12 + direction 8 + count 4) and
 // 32 B/segment in packed mode (start 12 + end 12 + seg_view 8; t_start/t_end,
-// which nothing downstream reads, optional +8).  The occupancy bitfield
+// read only by the depth output of the compositor (RTXN_RENDER_AUX), optional +8).  The occupancy bitfield
 // (R^3/8 bytes: 256 KiB at 128^3, 2 MiB at 256^3) is L2-resident.
 #include "common.h"
 

@@ -608,6 +608,232 @@ __global__ __launch_bounds__(256) void volrender_l2_fused_multi_kernel(const flo
   }
 }
 
+// Colour, opacity A = sum w_i and expected depth sum w_i d_i in one pass (rtxn_volrender_fwd_aux): the two forward kernels
+// above with two more accumulators, as separate instantiations so that the plain kernels keep their machine code.  The
+// weights and the colour accumulation are those kernels' own, operation for operation, so with a zero background the pixels
+// are bit-identical to theirs.  d_i = t_start_j + u_i (t_end_j - t_start_j) is the distance at which sample i of segment j
+// was evaluated: u_i = (i + u0) / K (u0 = 0 REGULAR, 0.5 MIDPOINT_WORLD); t_start / t_end (one float each per segment, 8 B per
+// K samples) are read only when depth is requested.  The background is added per channel where it is non-zero:
+// pixel += (1 - A) bg (no 0 * x term, which would turn a -0.0 pixel into +0.0).
+struct AuxArgs {
+  const float* t_start;
+  const float* t_end;
+  float u0;
+  float bg[3];
+  float* depth;     // may be NULL
+  float* opacity;   // may be NULL
+};
+
+template <int MODE, bool COMPACT>
+__global__ __launch_bounds__(256) void volrender_aux_kernel(const float4* __restrict__ radiance,
+                                                            const int* __restrict__ num_hits,
+                                                            const int* __restrict__ indices,
+                                                            const float* __restrict__ ray_hit, int batch_size, int K,
+                                                            float* __restrict__ pixels, AuxArgs aux) {
+  const int lane = threadIdx.x & 63;
+  const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ray >= batch_size) return;
+  const long seg = indices[ray];
+  const long base = seg * K;
+  const long n = (long)num_hits[ray] * K;
+  const bool want_depth = aux.depth != nullptr;
+  float T_carry = 0.0f, t_carry = 0.0f;
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f, ad = 0.0f;
+  for (long s0 = 0; s0 < n; s0 += 64) {
+    const bool act = s0 + lane < n;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    float t = 0.0f, d = 0.0f;
+    if (act) {
+      if (COMPACT) {
+        const half4 c16 = reinterpret_cast<const half4*>(radiance)[base + s0 + lane];
+        c = make_float4(__half2float(c16.x), __half2float(c16.y), __half2float(c16.z), __half2float(c16.w));
+        if (MODE == RTXN_VR_COMPAT) t = (float)((int)((s0 + lane) % K) + 1) * (1.0f / (float)K);
+        else t = ray_hit[(base + s0 + lane) / K];
+      } else {
+        c = radiance[base + s0 + lane];
+        t = ray_hit[base + s0 + lane];
+      }
+      if (want_depth) {
+        const long j = seg + (s0 + lane) / K;
+        const float ts = aux.t_start[j], te = aux.t_end[j];
+        d = fmaf(((float)((s0 + lane) % K) + aux.u0) * (1.0f / (float)K), te - ts, ts);
+      }
+    }
+    float x, w;
+    if (MODE == RTXN_VR_COMPAT) {
+      float tp = lane_below(t);
+      if (lane == 0) tp = t_carry;
+      const float delta = fabsf(t - tp);
+      x = act ? delta * c.w : 0.0f;
+      const float T = T_carry + wave_incl_scan_f(x, lane);
+      w = act ? expf(-T) * (1.0f - expf(-x)) : 0.0f;
+      T_carry = lane63(T);
+      t_carry = lane63(t);
+    } else {
+      x = act ? t * c.w : 0.0f;
+      const float incl = wave_incl_scan_f(x, lane);
+      const float T_excl = T_carry + incl - x;
+      w = act ? expf(-T_excl) * (1.0f - expf(-x)) : 0.0f;
+      T_carry += lane63(incl);
+    }
+    ar = fmaf(w, c.x, ar);
+    ag = fmaf(w, c.y, ag);
+    ab = fmaf(w, c.z, ab);
+    aw += w;
+    ad = fmaf(w, d, ad);
+  }
+  ar = wave_sum(ar);
+  ag = wave_sum(ag);
+  ab = wave_sum(ab);
+  aw = wave_sum(aw);
+  if (want_depth) ad = wave_sum(ad);
+  if (lane == 0) {
+    const float rest = 1.0f - aw;
+    if (aux.bg[0] != 0.0f) ar = fmaf(rest, aux.bg[0], ar);
+    if (aux.bg[1] != 0.0f) ag = fmaf(rest, aux.bg[1], ag);
+    if (aux.bg[2] != 0.0f) ab = fmaf(rest, aux.bg[2], ab);
+    pixels[3 * (long)ray] = ar;
+    pixels[3 * (long)ray + 1] = ag;
+    pixels[3 * (long)ray + 2] = ab;
+    if (aux.opacity) aux.opacity[ray] = aw;
+    if (want_depth) aux.depth[ray] = ad;
+  }
+}
+
+template <int MODE, bool COMPACT>
+__global__ __launch_bounds__(256) void volrender_aux_pair_kernel(const float4* __restrict__ radiance,
+                                                                 const int* __restrict__ num_hits,
+                                                                 const int* __restrict__ indices,
+                                                                 const float* __restrict__ ray_hit, int batch_size, int K,
+                                                                 float* __restrict__ pixels, AuxArgs aux) {
+  const int lane = threadIdx.x & 63;
+  const int ray0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kRaysPerWave;
+  if (ray0 >= batch_size) return;
+  const float rK = 1.0f / (float)K;
+  const bool want_depth = aux.depth != nullptr;
+  struct Pair { float4 c0, c1; float t0, t1, d0, d1; };
+  const int my = ray0 + lane < batch_size && lane < kRaysPerWave ? ray0 + lane : ray0;
+  const int idx_l = indices[my], nh_l = num_hits[my];
+  float out = 0.0f;                                   // lane 3 r + ch: pixel channel ch of ray r
+  float out_a = 0.0f;                                 // lanes 3 r .. 3 r + 2: opacity of ray r (the background's weight)
+  float out_o = 0.0f, out_d = 0.0f;                   // lane r: opacity and depth of ray r
+  const int kmask = (K & (K - 1)) == 0 ? K - 1 : 0;
+  const int kshift = kmask ? __builtin_ctz((unsigned)K) : 0;
+  auto load = [&](long base, long seg0, int n, int s0, Pair& p) {
+    const int i0 = s0 + 2 * lane;
+    p.c0 = p.c1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    p.t0 = p.t1 = p.d0 = p.d1 = 0.0f;
+    if (i0 < n) {
+      const int j = kmask ? i0 >> kshift : i0 / K;          // a pair never straddles two segments (K even)
+      if (COMPACT) {
+        const uint4 raw = *reinterpret_cast<const uint4*>(reinterpret_cast<const half4*>(radiance) + base + i0);
+        const __half2 a = *reinterpret_cast<const __half2*>(&raw.x), b = *reinterpret_cast<const __half2*>(&raw.y);
+        const __half2 c = *reinterpret_cast<const __half2*>(&raw.z), d = *reinterpret_cast<const __half2*>(&raw.w);
+        p.c0 = make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
+        p.c1 = make_float4(__low2float(c), __high2float(c), __low2float(d), __high2float(d));
+        if (MODE == RTXN_VR_COMPAT) {
+          const int k0 = kmask ? (i0 & kmask) : i0 % K;
+          p.t0 = (float)(k0 + 1) * rK;
+          p.t1 = (float)(k0 + 2) * rK;
+        } else {
+          p.t0 = p.t1 = ray_hit[seg0 + j];
+        }
+      } else {
+        p.c0 = radiance[base + i0];
+        p.c1 = radiance[base + i0 + 1];
+        const float2 tt = *reinterpret_cast<const float2*>(ray_hit + base + i0);
+        p.t0 = tt.x;
+        p.t1 = tt.y;
+      }
+      if (want_depth) {
+        const int k0 = kmask ? (i0 & kmask) : i0 % K;
+        const float ts = aux.t_start[seg0 + j], len = aux.t_end[seg0 + j] - ts;
+        p.d0 = fmaf(((float)k0 + aux.u0) * rK, len, ts);
+        p.d1 = fmaf(((float)(k0 + 1) + aux.u0) * rK, len, ts);
+      }
+    }
+  };
+  long base_r[kRaysPerWave], seg_r[kRaysPerWave];
+  int n_r[kRaysPerWave];
+  Pair first[kRaysPerWave];
+#pragma unroll
+  for (int r = 0; r < kRaysPerWave; ++r) {
+    seg_r[r] = (long)__shfl(idx_l, r, 64);
+    base_r[r] = seg_r[r] * K;
+    n_r[r] = ray0 + r < batch_size ? __shfl(nh_l, r, 64) * K : 0;
+    if (n_r[r] > 0) load(base_r[r], seg_r[r], n_r[r], 0, first[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < kRaysPerWave; ++r) {
+    if (ray0 + r >= batch_size) break;
+    const long base = base_r[r];
+    const int n = n_r[r];
+    float T_carry = 0.0f, t_carry = 0.0f;
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f, ad = 0.0f;
+    Pair cur = first[r], nxt;
+    for (int s0 = 0; s0 < n; s0 += 128) {
+      if (s0 + 128 < n) load(base, seg_r[r], n, s0 + 128, nxt);
+      const bool act = s0 + 2 * lane < n;
+      float x0, x1, w0, w1;
+      if (MODE == RTXN_VR_COMPAT) {
+        float tp = lane_below(cur.t1);
+        if (lane == 0) tp = t_carry;
+        x0 = act ? fabsf(cur.t0 - tp) * cur.c0.w : 0.0f;
+        x1 = act ? fabsf(cur.t1 - cur.t0) * cur.c1.w : 0.0f;
+        const float pr = x0 + x1;
+        const float T0 = (T_carry + (wave_incl_scan_f(pr, lane) - pr)) + x0;
+        const float T1 = T0 + x1;
+        const float e0 = __expf(-T0), ex0 = __expf(-x0), ex1 = __expf(-x1);
+        w0 = act ? e0 * (1.0f - ex0) : 0.0f;
+        w1 = act ? (e0 * ex1) * (1.0f - ex1) : 0.0f;
+        T_carry = lane63(T1);
+        t_carry = lane63(cur.t1);
+      } else {
+        x0 = act ? cur.t0 * cur.c0.w : 0.0f;
+        x1 = act ? cur.t1 * cur.c1.w : 0.0f;
+        const float pr = x0 + x1;
+        const float incl = wave_incl_scan_f(pr, lane);
+        const float T0 = T_carry + (incl - pr);
+        const float e0 = __expf(-T0), ex0 = __expf(-x0), ex1 = __expf(-x1);
+        w0 = act ? e0 * (1.0f - ex0) : 0.0f;
+        w1 = act ? (e0 * ex0) * (1.0f - ex1) : 0.0f;
+        T_carry += lane63(incl);
+      }
+      ar = fmaf(w1, cur.c1.x, fmaf(w0, cur.c0.x, ar));
+      ag = fmaf(w1, cur.c1.y, fmaf(w0, cur.c0.y, ag));
+      ab = fmaf(w1, cur.c1.z, fmaf(w0, cur.c0.z, ab));
+      aw += w0 + w1;
+      ad = fmaf(w1, cur.d1, fmaf(w0, cur.d0, ad));
+      cur = nxt;
+    }
+    if (n > 0) {                                      // wave-uniform
+      ar = wave_sum(ar);
+      ag = wave_sum(ag);
+      ab = wave_sum(ab);
+      aw = wave_sum(aw);
+      if (want_depth) ad = wave_sum(ad);
+    }
+    if (lane == 3 * r) out = ar;
+    if (lane == 3 * r + 1) out = ag;
+    if (lane == 3 * r + 2) out = ab;
+    if (lane / 3 == r) out_a = aw;
+    if (lane == r) {
+      out_o = aw;
+      out_d = ad;
+    }
+  }
+  if (lane < 3 * kRaysPerWave && ray0 + lane / 3 < batch_size) {
+    const int ch = lane - 3 * (lane / 3);
+    const float bg = ch == 0 ? aux.bg[0] : ch == 1 ? aux.bg[1] : aux.bg[2];
+    if (bg != 0.0f) out = fmaf(1.0f - out_a, bg, out);
+    pixels[3 * (long)ray0 + lane] = out;
+  }
+  if (lane < kRaysPerWave && ray0 + lane < batch_size) {
+    if (aux.opacity) aux.opacity[ray0 + lane] = out_o;
+    if (want_depth) aux.depth[ray0 + lane] = out_d;
+  }
+}
+
 }  // namespace
 
 extern "C" int rtxn_volrender_fwd(const float* network_inputs, const float* network_outputs, const int* num_hits,
@@ -735,5 +961,53 @@ extern "C" int rtxn_volrender_l2_train(const float* network_outputs, const float
                                                                    static_cast<__half*>(loss_gradients_half), loss_sum,
                                                                    static_cast<half4*>(radiance_gradients));
   RTXN_LAUNCH_CHECK("volrender_l2_fused_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_volrender_fwd_aux(const void* radiance, int radiance_layout, const float* ray_hit, const int* num_hits,
+                                      const int* indices, const float* t_start, const float* t_end, int batch_size,
+                                      int num_samples_per_hit, int vr_mode, int sample_type, const float* background,
+                                      float* pixels, float* depth, float* opacity, rtxn_stream_t stream) {
+  RTXN_REQUIRE(batch_size >= 0, "rtxn_volrender_fwd_aux: batch_size = %d < 0", batch_size);
+  RTXN_REQUIRE(num_samples_per_hit > 0, "rtxn_volrender_fwd_aux: num_samples_per_hit = %d", num_samples_per_hit);
+  RTXN_REQUIRE(vr_mode == RTXN_VR_COMPAT || vr_mode == RTXN_VR_NERF, "rtxn_volrender_fwd_aux: unknown mode %d", vr_mode);
+  RTXN_REQUIRE(radiance_layout == RTXN_RADIANCE_FLOAT4 || radiance_layout == RTXN_RADIANCE_HALF4,
+               "rtxn_volrender_fwd_aux: unknown radiance layout %d", radiance_layout);
+  RTXN_REQUIRE(sample_type == RTXN_SAMPLING_REGULAR || sample_type == RTXN_SAMPLING_MIDPOINT_WORLD,
+               "rtxn_volrender_fwd_aux: sample_type %d (the deterministic modes only: REGULAR, MIDPOINT_WORLD)", sample_type);
+  RTXN_REQUIRE(!depth || (t_start && t_end), "rtxn_volrender_fwd_aux: depth needs t_start and t_end");
+  RTXN_DEVICE_OR_FAIL();
+  if (batch_size == 0) return RTXN_OK;
+  const bool half = radiance_layout == RTXN_RADIANCE_HALF4;
+  RTXN_REQUIRE(radiance && num_hits && indices && pixels && (ray_hit || (half && vr_mode == RTXN_VR_COMPAT)),
+               "rtxn_volrender_fwd_aux: NULL buffer");
+  RTXN_REQUIRE(((uintptr_t)radiance & (half ? 7 : 15)) == 0, "rtxn_volrender_fwd_aux: radiance must be %d-byte aligned", half ? 8 : 16);
+  AuxArgs aux;
+  aux.t_start = t_start;
+  aux.t_end = t_end;
+  aux.u0 = sample_type == RTXN_SAMPLING_MIDPOINT_WORLD ? 0.5f : 0.0f;
+  for (int c = 0; c < 3; ++c) aux.bg[c] = background ? background[c] : 0.0f;
+  aux.depth = depth;
+  aux.opacity = opacity;
+  // the plain entry points' choice between the pair and the one-sample kernel, so that the pixels match theirs bit for bit
+  const int K = num_samples_per_hit;
+  const bool pairs = K % 2 == 0 && (half ? ((uintptr_t)radiance & 15) == 0 : ((uintptr_t)ray_hit & 7) == 0);
+  const float4* rad = static_cast<const float4*>(radiance);
+  hipStream_t s = rtxn::as_stream(stream);
+  const dim3 block(256), grid((batch_size + 3) / 4), pgrid((batch_size + 4 * kRaysPerWave - 1) / (4 * kRaysPerWave));
+#define RTXN_AUX_LAUNCH(MODE, COMPACT)                                                                              \
+  do {                                                                                                              \
+    if (pairs) volrender_aux_pair_kernel<MODE, COMPACT><<<pgrid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels, aux); \
+    else volrender_aux_kernel<MODE, COMPACT><<<grid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels, aux); \
+  } while (0)
+  if (half) {
+    if (vr_mode == RTXN_VR_COMPAT) RTXN_AUX_LAUNCH(RTXN_VR_COMPAT, true);
+    else RTXN_AUX_LAUNCH(RTXN_VR_NERF, true);
+  } else {
+    if (vr_mode == RTXN_VR_COMPAT) RTXN_AUX_LAUNCH(RTXN_VR_COMPAT, false);
+    else RTXN_AUX_LAUNCH(RTXN_VR_NERF, false);
+  }
+#undef RTXN_AUX_LAUNCH
+  RTXN_LAUNCH_CHECK("volrender_aux_kernel");
   return RTXN_OK;
 }

@@ -23,13 +23,14 @@ from . import _lib, api
 
 RENDER_FLOAT4 = 1     # enum rtxn_render_flags
 RENDER_STABLE_INPUTS = 2
+RENDER_AUX = 4        # the traversal also keeps each segment's entry / exit distance: the depth output of render_ex
 
 
 class RenderPipeline:
     def __init__(self, network, grid_res, width, height, focal_length, aspect_ratio=None, occupancy=None,
                  max_rays=None, max_segments=None, trace_mode=api.TRACE_DDA, vr_mode=api.VR_COMPAT,
                  device="cuda", window=(0, 0), step_scale=1.0, sub_rays=None, compact=None, on_overflow="raise",
-                 hashgrid=None, table=None, sample_type=None, n_slots=None, stable_inputs=False):
+                 hashgrid=None, table=None, sample_type=None, n_slots=None, stable_inputs=False, aux=False):
         self.net = network
         self.hg, self.table = hashgrid, table
         if (hashgrid is None) != (table is None):
@@ -81,6 +82,11 @@ class RenderPipeline:
         import os
         self.n_slots = int(n_slots) if n_slots else int(os.environ.get("RTXN_ASYNC_SLOTS", "3"))
         self.pixels = torch.empty((n_rays, 3), device=self.dev)
+        # aux: depth output of render_ex (RTXN_RENDER_AUX: +8 B per segment of capacity and slot); opacity and the background
+        # work on every pipeline
+        self.aux = bool(aux)
+        self.depth = torch.empty(n_rays, device=self.dev) if self.aux else None
+        self.opacity = torch.empty(n_rays, device=self.dev)
         self.look_at = torch.zeros(16, device=self.dev)
         self._h = None
         self._comp_stream = None
@@ -103,7 +109,8 @@ class RenderPipeline:
         c.vr_mode, c.sample_type, c.step_scale = self.vr_mode, self.sample_type, self.step_scale
         c.max_segments = self.max_segments
         c.n_slots = self.n_slots
-        c.flags = (0 if self.compact else RENDER_FLOAT4) | (RENDER_STABLE_INPUTS if self.stable_inputs else 0)
+        c.flags = ((0 if self.compact else RENDER_FLOAT4) | (RENDER_STABLE_INPUTS if self.stable_inputs else 0)
+                   | (RENDER_AUX if self.aux else 0))
         return c
 
     def _destroy(self):
@@ -226,6 +233,33 @@ class RenderPipeline:
                                                 api._ptr(pixels, torch.float32, "pixels"), api._stream()), "rtxn_render_frame")
         return pixels
 
+    def _outputs(self, n, background, depth, opacity, out):
+        """struct rtxn_render_outputs over the pipeline's buffers (or out = (pixels, depth, opacity))."""
+        if out is None:
+            out = (self.pixels[:n], self.depth[:n] if self.depth is not None else None, self.opacity[:n])
+        pixels, d, a = out
+        if depth and d is None:
+            raise ValueError("render_ex(depth=True) needs a pipeline built with aux=True (RTXN_RENDER_AUX)")
+        o = _lib.RenderOutputs()
+        o.pixels = api._ptr(pixels, torch.float32, "pixels")
+        o.depth = api._ptr(d, torch.float32, "depth") if depth else None
+        o.opacity = api._ptr(a, torch.float32, "opacity") if opacity else None
+        if background is not None:
+            o.background[:] = [float(v) for v in background]
+        return o, (pixels, d if depth else None, a if opacity else None)
+
+    def render_ex(self, ray_begin=0, ray_count=None, background=None, depth=True, opacity=True, out=None):
+        """render() with the expected depth (sum w_i d_i, unnormalised; float[ray_count]) and the opacity (sum w_i) of every
+        ray, and an optional background colour (3 floats) composited as (1 - opacity) * background (rtxn_render_frame_ex).
+        Returns (pixels, depth, opacity); an output not asked for is None.  With no background the pixels are render()'s
+        bit for bit."""
+        n = self.max_rays if ray_count is None else ray_count
+        o, res = self._outputs(n, background, depth, opacity, out)
+        self._check_overflow()
+        _lib.check(_lib.lib().rtxn_render_frame_ex(self._h, 0, C.c_void_p(self.look_at.data_ptr()), ray_begin, n, C.byref(o),
+                                                   api._stream()), "rtxn_render_frame_ex")
+        return res
+
     def finish(self):
         """Wait for every enqueued frame and apply the overflow policy to all of them (raises under "raise")."""
         self.drain_async()
@@ -262,6 +296,25 @@ class RenderPipeline:
             self._comp_stream = torch.cuda.ExternalStream(comp.value, device=self.dev)
         return pixels, None, self._comp_stream
 
+    def render_async_ex(self, look_at, ray_begin=0, ray_count=None, background=None, depth=True, opacity=True, out=None):
+        """render_async() with render_ex()'s outputs (rtxn_render_frame_async_ex).  Returns (pixels, depth, opacity,
+        comp_stream): all three are complete on `comp_stream`."""
+        n = self.max_rays if ray_count is None else ray_count
+        o, res = self._outputs(n, background, depth, opacity, out)
+        self._check_overflow()
+        comp = C.c_void_p()
+        if isinstance(look_at, torch.Tensor) and look_at.is_cuda:
+            la, on_host = api._ptr(look_at, torch.float32, "look_at"), 0
+        else:
+            import numpy as np
+            host = np.ascontiguousarray(np.asarray(look_at, dtype=np.float32).reshape(16))
+            la, on_host = C.c_void_p(host.ctypes.data), 1
+        _lib.check(_lib.lib().rtxn_render_frame_async_ex(self._h, la, on_host, ray_begin, n, C.byref(o), api._stream(), C.byref(comp)),
+                   "rtxn_render_frame_async_ex")
+        if self._comp_stream is None or self._comp_stream.cuda_stream != comp.value:
+            self._comp_stream = torch.cuda.ExternalStream(comp.value, device=self.dev)
+        return res + (self._comp_stream,)
+
     def drain_async(self):
         """Make the current stream wait for every frame enqueued with render_async."""
         if self._h:
@@ -275,6 +328,14 @@ class RenderPipeline:
         with torch.cuda.graph(g):
             pixels = self.render(ray_begin, ray_count, out)
         return g, pixels
+
+    def capture_ex(self, ray_begin=0, ray_count=None, background=None, depth=True, opacity=True, out=None):
+        """capture() over render_ex().  Returns (graph, pixels, depth, opacity).  The background is a kernel argument of the
+        captured compositor: the graph keeps the background it was captured with."""
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            res = self.render_ex(ray_begin, ray_count, background, depth, opacity, out)
+        return (g,) + res
 
     def overflowed(self):
         """True if a frame was ever truncated (synchronises: also looks at the frames still in flight)."""
