@@ -52,7 +52,8 @@
 namespace {
 
 // Build-time knobs of the inference kernels (defaults are the measured best):
-//   RTXN_SHARE_DIR 1: segment input computes a segment's direction features once per lane group (DirShare16)
+//   RTXN_SHARE_DIR 1: segment input computes a segment's direction features and their layer-0 product once per segment
+//                     (mlp_fwd16_kernel: rtxn::dir_bias16; the 256-wide kernel: the features only, DirShare16)
 //   RTXN_PIPE16 depth of the A-fragment register ring                        -- mlp_internal.h
 //   RTXN_STAMPS diagnostic build: per-stage s_memtime stamps of block 0 (tools/probe/stamps.py); never in the shipped library
 #ifndef RTXN_SHARE_DIR
@@ -95,21 +96,35 @@ struct FwdArgs {
 //     layer l: element = Wl[perm_feature(kk,h,j)][32rt + r], rows = in_width(l) padded to 32, K = out rows
 //              (16 for the output layer: one k-step; W otherwise).
 struct Enc16Dims { int PD, PF, DD, DF, E, k0; };
-// Layer-0 input order of the 16x16x32 kernel.  Lane group g (0..3) owns a BLOCK of consecutive frequencies of every
-// dimension, FB = ceil(F / 4) of them starting at FB g.  A B-fragment dword is one (dimension, k) pair of the block:
-// j-slot 2D holds sin, 2D+1 cos of 2^(FB g + k) pi x -- so a lane evaluates v_sin_f32 / v_cos_f32 once per dimension, at
-// k = 0, and gets the block's other octaves by angle doubling (octave_unit).  Dword order: direction dims (DD x FB_D),
-// position dims (PD x FB_P), padding dwords (features enc_width.. = 1.0), then nothing.  Frequencies beyond F (block 3 of a
-// 10-frequency dimension holds f = 9 only) are computed and meet zero weights.  Returns the tcnn feature index (Composite:
-// position block, then direction block, then padding) of j-slot u in lane group g, or -1.
+// Position block of the 16x16x32 kernels (PD = 3 dimensions x PF = 10 octaves): eight dwords per lane group, the 30
+// (dimension, octave) pairs spread over the four groups.  Group g holds octaves pos16_start .. + pos16_count - 1 of every
+// dimension (x, z: 3, 3, 2, 2 octaves from 0, 3, 6, 8; y: 2, 2, 3, 3 from 0, 2, 4, 7 -- 8 / 8 / 7 / 7 pairs), computed by one
+// octave_unit<3> per dimension from inputs pre-scaled by 2^pos16_start / 2 (exact).  Slot s (dword s of the block):
+// 2 dim + k for s < 6 (octaves k = 0, 1 of every dimension), slot 6 octave 2 of x (groups 0, 1) or y (groups 2, 3), slot 7
+// octave 2 of z.  Octaves a group does not own meet zero weights.
+__host__ __device__ inline int pos16_start(int dim, int g) {
+  return dim == 1 ? (g == 0 ? 0 : g == 1 ? 2 : g == 2 ? 4 : 7) : (g == 0 ? 0 : g == 1 ? 3 : g == 2 ? 6 : 8);
+}
+__host__ __device__ inline int pos16_count(int dim, int g) { return dim == 1 ? (g < 2 ? 2 : 3) : (g < 2 ? 3 : 2); }
+// Layer-0 input order of the 16x16x32 kernel.  Direction first: lane group g owns a BLOCK of FB_D = ceil(DF / 4) consecutive
+// frequencies of every direction dimension, starting at FB_D g.  A B-fragment dword is one (dimension, k) pair of the block:
+// j-slot 2D holds sin, 2D+1 cos of 2^(FB_D g + k) pi x -- so a lane evaluates v_sin_f32 / v_cos_f32 once per dimension, at
+// k = 0, and gets the block's other octaves by angle doubling (octave_unit).  Dword order: direction dims (DD x FB_D), padding
+// dwords (features enc_width.. = 1.0), zeros up to a whole number KSD of k-steps, then the position block (pos16_start) in
+// the last two k-steps.  The direction k-steps are the same for every sample of a segment: the segment kernel computes their
+// product once per segment (rtxn::dir_bias16).  Frequencies beyond DF are computed and meet zero weights.  Returns the tcnn
+// feature index (Composite: position block, then direction block, then padding) of j-slot u in lane group g, or -1.
 __host__ __device__ inline int enc16_feature(const Enc16Dims& d, int u, int g) {
-  const int FBD = (d.DF + 3) / 4, FBP = (d.PF + 3) / 4, ND = d.DD * FBD, NP = d.PD * FBP;
+  const int FBD = (d.DF + 3) / 4, ND = d.DD * FBD;
   const int width = 2 * (d.PD * d.PF + d.DD * d.DF);
+  const int NPADW = (d.E - width + 7) / 8, KSD = (ND + NPADW + 3) / 4;
   const int D = u >> 1, ph = u & 1;
   if (D < ND) { const int dd = D / FBD, f = FBD * g + D % FBD; return f < d.DF ? 2 * d.PD * d.PF + (dd * d.DF + f) * 2 + ph : -1; }
-  if (D < ND + NP) { const int v = D - ND, dim = v / FBP, f = FBP * g + v % FBP; return f < d.PF ? (dim * d.PF + f) * 2 + ph : -1; }
-  const int feat = width + 4 * (2 * (D - ND - NP) + ph) + g;
-  return feat < d.E ? feat : -1;
+  if (D < ND + NPADW) { const int feat = width + 4 * (2 * (D - ND) + ph) + g; return feat < d.E ? feat : -1; }
+  const int s = D - 4 * KSD;
+  if (s < 0 || s >= 8) return -1;
+  const int dim = s < 6 ? s >> 1 : (s == 7 ? 2 : (g < 2 ? 0 : 1)), k = s < 6 ? (s & 1) : 2;
+  return k < pos16_count(dim, g) ? (dim * d.PF + pos16_start(dim, g) + k) * 2 + ph : -1;
 }
 
 //   output layer: FOUR variants of its single 16-row tile, [variant v][kstep]: variant 0 is the layer as it is (all 16
@@ -206,7 +221,7 @@ __global__ void pack_kernel(const _Float16* __restrict__ params, _Float16* __res
 // Block geometry, LDS plan, staging protocol and wave-group skew: see the file header.  Who holds what: lane (c = l & 15, g = l >> 4) owns sample 16 ct + c of the wave's four 16-column tiles
 // and, of every 32 features, the eight perm_feature16 gives its lane group.
 // Layer 0 / the encoder.  Lane group g evaluates a block of FB = ceil(F/4) consecutive frequencies of every input dimension
-// (enc16_feature): the inputs are pre-scaled once per tile by 2^(FB g) / 2 (exact), the block's lowest octave comes from ONE
+// (enc16_feature, pos16_start): the inputs are pre-scaled once per tile by 2^(the block's first octave) / 2 (exact), the block's lowest octave comes from ONE
 // v_sin_f32 + ONE v_cos_f32 (exact range reduction as before) and its other octaves from the double-angle identities
 // s' = 2 s c, c' = 1 - 2 s^2 -- three 4-cycle instructions per octave instead of two 8-cycle transcendentals with their
 // range reductions: 64 issue cycles per (dimension, column tile) for six features, where the direct form took 120.  The error
@@ -214,15 +229,18 @@ __global__ void pack_kernel(const _Float16* __restrict__ params, _Float16* __res
 // these values (tests/test_gpu_parity.py reports the measured maximum per octave).
 template <int PD, int PF, int DD, int DF>
 struct EncSpec16 {
-  static constexpr int FBP = (PF + 3) / 4, FBD = (DF + 3) / 4;     // octaves per lane group and dimension
-  static_assert(FBP >= 1 && FBP <= 3 && FBD >= 1 && FBD <= 3, "octave_unit is written for 1-3 octaves per block");
+  static_assert(PD == 3 && PF == 10, "the position block is laid out for 3 dimensions x 10 octaves (pos16_start)");
+  static constexpr int FBD = (DF + 3) / 4;                         // direction octaves per lane group and dimension
+  static_assert(FBD >= 1 && FBD <= 3, "octave_unit is written for 1-3 octaves per block");
   static constexpr int enc_width = 2 * (PD * PF + DD * DF);
   static constexpr int enc_padded = (enc_width + 15) / 16 * 16;
-  static constexpr int ND = DD * FBD, NP = PD * FBP;               // dwords: direction, position
+  static constexpr int ND = DD * FBD;                              // direction dwords
   static constexpr int NPADW = (enc_padded - enc_width + 7) / 8;   // padding dwords (8 features each over the four groups)
-  static constexpr int n_dwords = ND + NP + NPADW;
-  static constexpr int k0 = (n_dwords + 3) / 4 * 32;               // first-layer K as staged (4 dwords = 32 k per k-step)
-  static_assert(ND <= 8, "direction dwords are placed before the pipeline starts: k-steps 0 and 1 only");
+  static constexpr int KSD = (ND + NPADW + 3) / 4, KSP = 2;        // k-steps: direction + padding, position (8 dwords)
+  static constexpr int POS0 = 4 * KSD;                             // first position dword
+  static constexpr int n_dwords = POS0 + 8;
+  static constexpr int k0 = (KSD + KSP) * 32;                      // first-layer K as staged (4 dwords = 32 k per k-step)
+  static_assert(KSD <= 2, "direction dwords are placed before the pipeline starts: k-steps 0 and 1 only");
 };
 
 // One dimension of one sample: NK dwords {sin, cos} of octaves 0..NK-1 of the lane group's block.  xg = x 2^(FB g) / 2: the
@@ -307,9 +325,12 @@ __device__ __forceinline__ void share_direction16(const float (&dir_g)[DD], int 
 // during the encode, and the chip is issue- and power-bound, not latency-bound -- at 189 instead of 231-251 VGPRs (32
 // accumulator registers live in layer 0 instead of 128).  That is what lets the traversal and compositor kernels of the
 // neighbouring frames co-reside with two of these waves per SIMD (render.py, render_async): MLP-to-MLP gaps 12-20 us.
-template <class ES, int PD, int PF, int DD, int DF, int KS0, int NB, int CT, bool SHARE>
+// POS_ONLY: the position k-steps only, into bf[0 .. KSP-1] (the segment kernel's direction k-steps are per segment: bd below).
+// lo: the lane is in lane group 0 or 1 (position slot 6 holds x's octave 2 there, y's elsewhere).
+template <class ES, int PD, int PF, int DD, int DF, int KS0, int NB, int CT, bool SHARE, bool POS_ONLY = false>
 __device__ __forceinline__ void encode_layer0_input(const float (&xq)[CT][5], const int (&dirs)[CT / 2][DirShare16<PD, PF, DD, DF>::n_dwords],
-                                                    half8 (&bf)[NB][CT]) {
+                                                    bool lo, half8 (&bf)[NB][CT]) {
+  static_assert(KS0 == ES::KSD + ES::KSP, "k-steps as staged");
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
     rtxn::int4v t[KS0];
@@ -317,10 +338,11 @@ __device__ __forceinline__ void encode_layer0_input(const float (&xq)[CT][5], co
     for (int kk = 0; kk < KS0; ++kk)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int D = 4 * kk + e;   // padding dwords {1.0, 1.0} (features beyond enc_padded meet zero weights); beyond n_dwords: 0
-        t[kk][e] = (D >= ES::ND + ES::NP && D < ES::n_dwords) ? 0x3c003c00 : 0;
+        const int D = 4 * kk + e;   // padding dwords {1.0, 1.0} (features beyond enc_padded meet zero weights); up to POS0: 0
+        t[kk][e] = (D >= ES::ND && D < ES::ND + ES::NPADW) ? 0x3c003c00 : 0;
       }
-    if constexpr (SHARE) {
+    if constexpr (POS_ONLY) {
+    } else if constexpr (SHARE) {
 #pragma unroll
       for (int D = 0; D < ES::ND; ++D) t[D / 4][D % 4] = dirs[ct / 2][D];
     } else {
@@ -332,23 +354,55 @@ __device__ __forceinline__ void encode_layer0_input(const float (&xq)[CT][5], co
         for (int k = 0; k < ES::FBD; ++k) t[(dd * ES::FBD + k) / 4][(dd * ES::FBD + k) % 4] = d[k];
       }
     }
+    int p[PD][3];
 #pragma unroll
-    for (int dim = 0; dim < PD; ++dim) {
-      int d[3];
-      octave_unit<ES::FBP>(xq[ct][dim], d);
+    for (int dim = 0; dim < PD; ++dim) octave_unit<3>(xq[ct][dim], p[dim]);
+    int slot[8];                                    // pos16_start: slot 2 dim + k = octave k of dim; 6 x or y; 7 z
 #pragma unroll
-      for (int k = 0; k < ES::FBP; ++k) t[(ES::ND + ES::FBP * dim + k) / 4][(ES::ND + ES::FBP * dim + k) % 4] = d[k];
+    for (int dim = 0; dim < PD; ++dim) slot[2 * dim] = p[dim][0], slot[2 * dim + 1] = p[dim][1];
+    slot[6] = lo ? p[0][2] : p[1][2];
+    slot[7] = p[2][2];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[(ES::POS0 + i) / 4][(ES::POS0 + i) % 4] = slot[i];
+    if constexpr (POS_ONLY) {
+#pragma unroll
+      for (int kk = 0; kk < ES::KSP; ++kk) bf[kk][ct] = __builtin_bit_cast(half8, t[ES::KSD + kk]);
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < KS0; ++kk) bf[kk][ct] = __builtin_bit_cast(half8, t[kk]);
+    }
+    // Segment input: the two column tiles of a segment get IDENTICAL k-step-0 fragments (direction dwords only), and hipcc
+    // then merges their MFMAs (one result feeding both accumulator chains: an out-of-place MFMA for one tile, in-place for the
+    // other).  Legal for the compiler -- but that kernel came out wrong on the hardware, and not reproducibly so (first column
+    // tile of a wave's first segment), while every build that keeps the accumulator chains separate is exact and
+    // bit-deterministic.  The hand-placed asm slices of the pipeline rely on the chains being what the source says, so the
+    // fragment is made opaque to value numbering.  (mlp_fwd16_kernel does that product once per segment instead: dir_bias16.)
+    if constexpr (SHARE && !POS_ONLY) asm volatile("" : "+v"(bf[0][ct]));
+  }
+}
+
+// The direction B fragments of dir_bias16: column c holds segment c & 1's direction features for the lane's group (the
+// octave units run on that segment's inputs, no cross-lane exchange), then the padding dwords, then zeros.
+template <class ES, int PD, int DD, int CT>
+__device__ __forceinline__ void encode_direction_pair(const float (&xq)[CT][5], int c, half8 (&bd)[ES::KSD]) {
+  rtxn::int4v t[ES::KSD];
+#pragma unroll
+  for (int kk = 0; kk < ES::KSD; ++kk)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int D = 4 * kk + e;
+      t[kk][e] = (D >= ES::ND && D < ES::ND + ES::NPADW) ? 0x3c003c00 : 0;
     }
 #pragma unroll
-    for (int kk = 0; kk < KS0; ++kk) bf[kk][ct] = __builtin_bit_cast(half8, t[kk]);
-    // Segment input: the two column tiles of a segment get IDENTICAL k-step-0 fragments when that k-step holds direction
-    // dwords only, and hipcc then merges their MFMAs (one result feeding both accumulator chains: an out-of-place MFMA for one
-    // tile, in-place for the other).  Legal for the compiler -- but that kernel came out wrong on the hardware, and not
-    // reproducibly so (first column tile of a wave's first segment), while every build that keeps the four accumulator
-    // chains separate is exact and bit-deterministic.  The hand-placed asm slices of the pipeline rely on the chains being
-    // what the source says, so the fragment is made opaque to value numbering.
-    if constexpr (SHARE) asm volatile("" : "+v"(bf[0][ct]));
+  for (int dd = 0; dd < DD; ++dd) {
+    const float x = (c & 1) ? xq[2][PD + dd] : xq[0][PD + dd];   // column tiles 0, 1: segment 0; 2, 3: segment 1
+    int d[3];
+    octave_unit<ES::FBD>(x, d);
+#pragma unroll
+    for (int k = 0; k < ES::FBD; ++k) t[(dd * ES::FBD + k) / 4][(dd * ES::FBD + k) % 4] = d[k];
   }
+#pragma unroll
+  for (int kk = 0; kk < ES::KSD; ++kk) bd[kk] = __builtin_bit_cast(half8, t[kk]);
 }
 
 // Diagnostic build only (-DRTXN_STAMPS, tools/probe/stamps.py; never in the shipped library): block 0 records s_memtime at
@@ -412,7 +466,10 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
   stage<OUT_BYTES, THREADS>(a.packed + layer_off(n_layers - 1), smem + L0_BYTES, tid);
   int qs = 0;                               // hidden stages this wave has begun (ring slot = qs % 3)
 
-  const float pos_scale = 0.5f * (float)(1u << (ES::FBP * g)), dir_scale = 0.5f * (float)(1u << (ES::FBD * g));   // 2^(FB g) / 2 turns per unit: see EncSpec16
+  // 2^(octave of the lane group's block) / 2 turns per unit: see EncSpec16, pos16_start
+  const float dir_scale = 0.5f * (float)(1u << (ES::FBD * g));
+  const float pos_scale[3] = {0.5f * (float)(1u << pos16_start(0, g)), 0.5f * (float)(1u << pos16_start(1, g)),
+                              0.5f * (float)(1u << pos16_start(2, g))};
   float xq[CT][5];                          // inputs of the lane's four samples, already scaled for its lane group
   auto sample_of = [&](int tile, int ct, bool& valid) -> long {
     if (IN_MODE == 1) {
@@ -466,13 +523,13 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           const float og = raw_s[sgi][k];
-          xq[ct][k] = fmaf(t, raw_e[sgi][k] - og, og) * pos_scale;   // REGULAR sample, sampler.cu:52-66; exact scaling
+          xq[ct][k] = fmaf(t, raw_e[sgi][k] - og, og) * pos_scale[k];   // REGULAR sample, sampler.cu:52-66; exact scaling
         }
         xq[ct][3] = raw_v[sgi][0] * dir_scale;
         xq[ct][4] = raw_v[sgi][1] * dir_scale;
       } else {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) xq[ct][k] = raw_x[ct][k] * (k < PD ? pos_scale : dir_scale);
+        for (int k = 0; k < 5; ++k) xq[ct][k] = raw_x[ct][k] * (k < PD ? pos_scale[k < PD ? k : 0] : dir_scale);
       }
     }
   };
@@ -501,17 +558,11 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
       const long seg = (long)tile * TILE_SEGS + wave_u * 2 + (lane_t >> 5);
       if (seg < total_seg) a.t_vals[seg * 32 + (lane_t & 31)] = (float)((lane_t & 31) + 1) * (1.0f / 32);
     }
-    constexpr bool SHARE = RTXN_SHARE_DIR && IN_MODE == 1 && DirShare16<PD, PF, DD, DF>::possible;
+    // Segment input: layer 0's direction k-steps once per segment (dir_bias16), the position k-steps per sample from there.
+    constexpr bool BIAS = RTXN_SHARE_DIR && IN_MODE == 1;
     int dirs[CT / 2][DirShare16<PD, PF, DD, DF>::n_dwords];
-    if constexpr (SHARE) {
-#pragma unroll
-      for (int sg = 0; sg < CT / 2; ++sg) {
-        float dg[DD];
-#pragma unroll
-        for (int dd = 0; dd < DD; ++dd) dg[dd] = xq[2 * sg][PD + dd];
-        share_direction16<PD, PF, DD, DF>(dg, lane, dirs[sg]);
-      }
-    }
+    half8 bd[ES::KSD];
+    if constexpr (BIAS) encode_direction_pair<ES, PD, DD, CT>(xq, c, bd);
     half8 bf[NB][CT], bg[NB][CT];
     rtxn::floatx4 acc2[2][CT];
     rtxn::StageJob sj;
@@ -600,11 +651,17 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
       }
     };
     {
-      encode_layer0_input<ES, PD, PF, DD, DF, KS0, NB, CT, SHARE>(xq, dirs, bf);   // VALU only: before the stage barrier, not behind it
+      encode_layer0_input<ES, PD, PF, DD, DF, KS0, NB, CT, false, BIAS>(xq, dirs, g < 2, bf);   // VALU only: before the stage barrier, not behind it
       RTXN_STAMP(1);
       const uint8_t* w = begin_stage(0);
       RTXN_STAMP(2);
-      rtxn::pipe_layer16<RT, KS0, NB, CT, false>(w, sj, bf, bg, acc2, wave_u, lane);
+      if constexpr (BIAS) {
+        rtxn::floatx4 bias[RT];
+        rtxn::dir_bias16<RT, ES::KSD, KS0>(w, bd, bias, lane);
+        rtxn::pipe_layer16<RT, ES::KSP, NB, CT, false, KS0, ES::KSD, true>(w, sj, bf, bg, acc2, wave_u, lane, bias);
+      } else {
+        rtxn::pipe_layer16<RT, KS0, NB, CT, false>(w, sj, bf, bg, acc2, wave_u, lane);
+      }
       RTXN_STAMP(3);
     }
     int l = 1;
@@ -694,7 +751,10 @@ __global__ __launch_bounds__(kThreads256, 2) void mlp_fwd256x16_kernel(FwdArgs a
   const int g_end = my_tiles * n_chunks;
   int gq = 0;  // chunks consumed so far by this block
 
-  const float pos_scale = 0.5f * (float)(1u << (ES::FBP * g)), dir_scale = 0.5f * (float)(1u << (ES::FBD * g));   // 2^(FB g) / 2 turns per unit: see EncSpec16
+  // 2^(octave of the lane group's block) / 2 turns per unit: see EncSpec16, pos16_start
+  const float dir_scale = 0.5f * (float)(1u << (ES::FBD * g));
+  const float pos_scale[3] = {0.5f * (float)(1u << pos16_start(0, g)), 0.5f * (float)(1u << pos16_start(1, g)),
+                              0.5f * (float)(1u << pos16_start(2, g))};
   float xq[CT][5];
   auto sample_of = [&](int tile, int ct, bool& valid) -> long {
     if (IN_MODE == 1) {
@@ -740,13 +800,13 @@ __global__ __launch_bounds__(kThreads256, 2) void mlp_fwd256x16_kernel(FwdArgs a
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           const float og = raw_s[k];
-          xq[ct][k] = fmaf(t, raw_e[k] - og, og) * pos_scale;   // REGULAR sample, sampler.cu:52-66; exact scaling
+          xq[ct][k] = fmaf(t, raw_e[k] - og, og) * pos_scale[k];   // REGULAR sample, sampler.cu:52-66; exact scaling
         }
         xq[ct][3] = raw_v[0] * dir_scale;
         xq[ct][4] = raw_v[1] * dir_scale;
       } else {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) xq[ct][k] = raw_x[ct][k] * (k < PD ? pos_scale : dir_scale);
+        for (int k = 0; k < 5; ++k) xq[ct][k] = raw_x[ct][k] * (k < PD ? pos_scale[k < PD ? k : 0] : dir_scale);
       }
     }
   };
@@ -800,7 +860,7 @@ __global__ __launch_bounds__(kThreads256, 2) void mlp_fwd256x16_kernel(FwdArgs a
     }
     half8 bf[NB][CT], bg[NB][CT];
     rtxn::floatx4 acc2[2][CT];
-    encode_layer0_input<ES, PD, PF, DD, DF, KS0, NB, CT, SHARE>(xq, dirs, bf);
+    encode_layer0_input<ES, PD, PF, DD, DF, KS0, NB, CT, SHARE>(xq, dirs, g < 2, bf);
     chunk_in_tile = 0;
     prefetch_tile = tile + tile_step < n_tiles ? tile + tile_step : -1;
 

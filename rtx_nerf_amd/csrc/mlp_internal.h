@@ -359,32 +359,39 @@ __device__ __forceinline__ void convert_slice16(const floatx4 (&acc)[CT], half8 
 #define RTXN_MAX16(U) "v_pk_max_i16 %[r" U "], %[r" U "], 0\n\t"
 #define RTXN_UNIT16(U) RTXN_CVT16(U) RTXN_MAX16(U)
 #define RTXN_IN16 [a] "v"(a), [b0] "v"(b0), [b1] "v"(b1)
-#define RTXN_PAIR16_CASES(M0, M1, ACC0, ACC1)                                                                                          \
-  if constexpr (NUP == 0) asm volatile(M0 M1 : ACC0, ACC1 : RTXN_IN16);                                                                  \
-  else if constexpr (NUP == 1) asm volatile(M0 RTXN_CVT16("0") M1 RTXN_MAX16("0") : ACC0, ACC1, RTXN_UOUT(0, 0) : RTXN_IN16, RTXN_UIN(0, 0)); \
+#define RTXN_IN16Z [a] "v"(a), [b0] "v"(b0), [b1] "v"(b1), [z] "v"(z)
+#define RTXN_PAIR16_CASES(M0, M1, ACC0, ACC1, IN)                                                                                      \
+  if constexpr (NUP == 0) asm volatile(M0 M1 : ACC0, ACC1 : IN);                                                                         \
+  else if constexpr (NUP == 1) asm volatile(M0 RTXN_CVT16("0") M1 RTXN_MAX16("0") : ACC0, ACC1, RTXN_UOUT(0, 0) : IN, RTXN_UIN(0, 0));        \
   else if constexpr (NUP == 2)                                                                                                    \
-    asm volatile(M0 RTXN_UNIT16("0") M1 RTXN_UNIT16("1") : ACC0, ACC1, RTXN_UOUT(0, 0), RTXN_UOUT(1, 1) : RTXN_IN16, RTXN_UIN(0, 0), RTXN_UIN(1, 1)); \
+    asm volatile(M0 RTXN_UNIT16("0") M1 RTXN_UNIT16("1") : ACC0, ACC1, RTXN_UOUT(0, 0), RTXN_UOUT(1, 1) : IN, RTXN_UIN(0, 0), RTXN_UIN(1, 1)); \
   else                                                                                                                            \
     asm volatile(M0 RTXN_UNIT16("0") RTXN_UNIT16("1") M1 RTXN_UNIT16("2") RTXN_UNIT16("3")                                         \
                  : ACC0, ACC1, RTXN_UOUT(0, 0), RTXN_UOUT(1, 1), RTXN_UOUT(2, 2), RTXN_UOUT(3, 3)                                         \
-                 : RTXN_IN16, RTXN_UIN(0, 0), RTXN_UIN(1, 1), RTXN_UIN(2, 2), RTXN_UIN(3, 3));
-template <bool ZERO, int NUP>
+                 : IN, RTXN_UIN(0, 0), RTXN_UIN(1, 1), RTXN_UIN(2, 2), RTXN_UIN(3, 3));
+// ZERO: C = 0.  BZ: both MFMAs start from the bias z (a VALU result: the two wait states of a VALU write -> MFMA read are the
+// s_nop 1 in front).  Otherwise the accumulators accumulate in place.
+template <bool ZERO, int NUP, bool BZ = false>
 __device__ __forceinline__ void pair16(floatx4& acc0, floatx4& acc1, const half8& a, const half8& b0, const half8& b1,
-                                       int (&r)[NUP > 0 ? NUP : 1], const float (&x)[NUP > 0 ? NUP : 1], const float (&y)[NUP > 0 ? NUP : 1]) {
+                                       int (&r)[NUP > 0 ? NUP : 1], const float (&x)[NUP > 0 ? NUP : 1], const float (&y)[NUP > 0 ? NUP : 1],
+                                       const floatx4& z = floatx4{}) {
   static_assert(NUP == 0 || NUP == 1 || NUP == 2 || NUP == 4, "unit pattern not written");
-  if constexpr (ZERO) {
-    RTXN_PAIR16_CASES(RTXN_M16("c0", "b0", "0"), RTXN_M16("c1", "b1", "0"), [c0] "=&v"(acc0), [c1] "=&v"(acc1))
+  static_assert(!(ZERO && BZ), "one C source");
+  if constexpr (BZ) {
+    RTXN_PAIR16_CASES("s_nop 1\n\t" RTXN_M16("c0", "b0", "%[z]"), RTXN_M16("c1", "b1", "%[z]"), [c0] "=&v"(acc0), [c1] "=&v"(acc1), RTXN_IN16Z)
+  } else if constexpr (ZERO) {
+    RTXN_PAIR16_CASES(RTXN_M16("c0", "b0", "0"), RTXN_M16("c1", "b1", "0"), [c0] "=&v"(acc0), [c1] "=&v"(acc1), RTXN_IN16)
   } else {
-    RTXN_PAIR16_CASES(RTXN_M16("c0", "b0", "%[c0]"), RTXN_M16("c1", "b1", "%[c1]"), [c0] "+v"(acc0), [c1] "+v"(acc1))
+    RTXN_PAIR16_CASES(RTXN_M16("c0", "b0", "%[c0]"), RTXN_M16("c1", "b1", "%[c1]"), [c0] "+v"(acc0), [c1] "+v"(acc1), RTXN_IN16)
   }
 }
-// units [P0, P0 + NU) of the finished tile RTI go behind the step's CT MFMAs, pair by pair
-template <int NB, int CT, int RTI, int P0, int NU, bool ZERO, int PAIR>
+// units [P0, P0 + NU) of the finished tile RTI go behind the step's CT MFMAs, pair by pair.  BZ: pair p starts from bz[p].
+template <int NB, int CT, int RTI, int P0, int NU, bool ZERO, int PAIR, bool BZ = false>
 struct PairRun16 {
   static constexpr int NPAIR = CT / 2;
   static constexpr int u0 = (NU * PAIR + NPAIR - 1) / NPAIR, u1 = (NU * (PAIR + 1) + NPAIR - 1) / NPAIR, NUP = u1 - u0;   // earlier pairs take the odd one
   __device__ static __forceinline__ void run(const half8& a, const half8 (&b)[CT], floatx4 (&acc)[CT], const floatx4 (&fin)[CT],
-                                             half8 (&dst)[NB][CT]) {
+                                             half8 (&dst)[NB][CT], const floatx4 (&bz)[NPAIR]) {
     int r[NUP > 0 ? NUP : 1];
     float x[NUP > 0 ? NUP : 1], y[NUP > 0 ? NUP : 1];
 #pragma unroll
@@ -393,7 +400,7 @@ struct PairRun16 {
       x[i] = fin[P / 2][2 * (P % 2)];
       y[i] = fin[P / 2][2 * (P % 2) + 1];
     }
-    pair16<ZERO, NUP>(acc[2 * PAIR], acc[2 * PAIR + 1], a, b[2 * PAIR], b[2 * PAIR + 1], r, x, y);
+    pair16<ZERO, NUP, BZ>(acc[2 * PAIR], acc[2 * PAIR + 1], a, b[2 * PAIR], b[2 * PAIR + 1], r, x, y, bz[PAIR]);
 #pragma unroll
     for (int i = 0; i < NUP; ++i) {
       const int P = P0 + u0 + i, ct = P / 2, e = P % 2;
@@ -401,14 +408,14 @@ struct PairRun16 {
       t[2 * (RTI & 1) + e] = r[i];
       dst[RTI >> 1][ct] = __builtin_bit_cast(half8, t);
     }
-    if constexpr (PAIR + 1 < NPAIR) PairRun16<NB, CT, RTI, P0, NU, ZERO, PAIR + 1>::run(a, b, acc, fin, dst);
+    if constexpr (PAIR + 1 < NPAIR) PairRun16<NB, CT, RTI, P0, NU, ZERO, PAIR + 1, BZ>::run(a, b, acc, fin, dst, bz);
   }
 };
-template <int NB, int CT, int RTI, int P0, int P1, bool ZERO>
+template <int NB, int CT, int RTI, int P0, int P1, bool ZERO, bool BZ = false>
 __device__ __forceinline__ void mfma_convert_step16(const half8& a, const half8 (&b)[CT], floatx4 (&acc)[CT], const floatx4 (&fin)[CT],
-                                                    half8 (&dst)[NB][CT]) {
+                                                    half8 (&dst)[NB][CT], const floatx4 (&bz)[CT / 2] = {}) {
   static_assert(CT % 2 == 0, "MFMAs go in pairs");
-  PairRun16<NB, CT, RTI, P0, (P1 > P0 ? P1 - P0 : 0), ZERO, 0>::run(a, b, acc, fin, dst);
+  PairRun16<NB, CT, RTI, P0, (P1 > P0 ? P1 - P0 : 0), ZERO, 0, BZ>::run(a, b, acc, fin, dst, bz);
 }
 template <int CT, int U, int KK>
 struct UnitRange16 {
@@ -417,7 +424,13 @@ struct UnitRange16 {
 
 // RT 16-row tiles (RT == 0: the output layer's single tile, left raw in acc[0]); KS 32-wide k-steps.
 // PEND: acc[1] holds the previous layer's last row tile (an odd tile: dwords 2, 3 of bf[KS-1]).
-template <int RT, int KS, int NB, int CT, bool PEND, int I>
+// A fragment (rt, kk) is read from chunk rt * KSTR + KOFF + kk of the layer's LDS image (a layer that runs only the last KS of
+// its KSTR k-steps: layer 0 of the segment input, whose direction k-steps are dir_bias16's).
+// BIAS: every row tile starts from bias[rt] instead of zero -- column tiles 0, 1 from the bias of the wave's segment 0, 2, 3
+// from segment 1's (dir_bias16 leaves segment c & 1 in column c; a quad_perm DPP copies the right one to every lane of a quad).
+// The copies are VALU results read as C by the step's first MFMA of each pair: pair16 pads the two wait states.  They stay live
+// through the next k-step, so that no register an MFMA still has to read as C is handed to a VALU write by the allocator.
+template <int RT, int KS, int NB, int CT, bool PEND, int I, int KSTR = KS, int KOFF = 0, bool BIAS = false>
 struct PipeStep16 {
   static constexpr int D = RTXN_PIPE16, N = (RT ? RT : 1) * KS;
   static constexpr int U = (2 * CT + KS - 1) / KS;                 // units per k-step, row tiles 1..
@@ -425,10 +438,14 @@ struct PipeStep16 {
   static constexpr int UP = (2 * CT + WIN - 1) / WIN;
   static constexpr int WAVES = RTXN_NW;
   static constexpr int CHUNKS = N < 32 / WAVES ? N : 32 / WAVES;
+  static constexpr int NBIAS = BIAS ? RT : 1;
+  __host__ __device__ static constexpr int frag_off(int i) { return ((i / KS) * KSTR + KOFF + i % KS) * 1024; }
   __device__ static __forceinline__ void run(unsigned addr, half8 (&bf)[NB][CT], half8 (&nbf)[NB][CT], half8 (&ring)[D],
-                                             floatx4 (&acc)[2][CT], const StageJob& sj, int wave_u, int lane) {
+                                             floatx4 (&acc)[2][CT], const StageJob& sj, int wave_u, int lane,
+                                             const floatx4 (&bias)[NBIAS], floatx4 (&bz)[CT / 2]) {
     constexpr int rt = I / KS, kk = I % KS, cur = rt & 1;
     constexpr int outstanding = (N - 1 - I) < (D - 1) ? (N - 1 - I) : (D - 1);
+    constexpr bool ZERO = kk == 0 && !BIAS, BZ = kk == 0 && BIAS;
 #if RTXN_PRIO_BANDS
     // Issue priority falls with progress through the layer (3, 2, 1, 0 over its four quarters): of the two waves that share a
     // SIMD the one that is behind wins the arbitration, so neither runs the end of the stage alone (a lone wave issues its
@@ -443,45 +460,123 @@ struct PipeStep16 {
     if constexpr (kk == 0 && RT >= 4 && rt % (RT / 4) == 0) asm volatile("s_setprio %0" ::"n"(rt / (RT / 4)));
 #endif
 #endif
+    if constexpr (BZ) {
+      static_assert(CT == 4, "two segments per wave");
+      // as asm: __builtin_amdgcn_mov_dpp on the four elements of a vector came out as ONE DPP of element 0 copied to all four
+      // (this toolchain).  The source is an asm MFMA result: its wait states are dir_bias16's (row tiles 0, 1) or a row tile
+      // of this pipeline (the others).
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float s0, s1;
+        asm volatile("v_mov_b32_dpp %0, %2 quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %1, %2 quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf"
+                     : "=&v"(s0), "=&v"(s1) : "v"(bias[rt][e]));
+        bz[0][e] = s0;
+        bz[1][e] = s1;
+      }
+    }
     lds_wait_insn<outstanding>();
     if constexpr (rt > 0) {
       using R = UnitRange16<CT, U, kk>;
-      mfma_convert_step16<NB, CT, rt - 1, R::p0, R::p1, kk == 0>(ring[I % D], bf[kk], acc[cur], acc[cur ^ 1], nbf);
+      mfma_convert_step16<NB, CT, rt - 1, R::p0, R::p1, ZERO, BZ>(ring[I % D], bf[kk], acc[cur], acc[cur ^ 1], nbf, bz);
     } else if constexpr (PEND && kk < WIN) {
       using R = UnitRange16<CT, UP, kk>;
-      mfma_convert_step16<NB, CT, 2 * KS - 1, R::p0, R::p1, kk == 0>(ring[I % D], bf[kk], acc[cur], acc[1], bf);
+      mfma_convert_step16<NB, CT, 2 * KS - 1, R::p0, R::p1, ZERO, BZ>(ring[I % D], bf[kk], acc[cur], acc[1], bf, bz);
     } else {
-      mfma_convert_step16<NB, CT, 0, 0, 0, kk == 0>(ring[I % D], bf[kk], acc[cur], acc[cur], nbf);
+      mfma_convert_step16<NB, CT, 0, 0, 0, ZERO, BZ>(ring[I % D], bf[kk], acc[cur], acc[cur], nbf, bz);
     }
+    if constexpr (BIAS && kk == 1) asm volatile("" ::"v"(bz[0]), "v"(bz[1]));   // the copies live through this k-step
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (I + D < N) lds_read_frag<(I + D) * 1024>(ring[I % D], addr);
+    if constexpr (I + D < N) lds_read_frag<frag_off(I + D)>(ring[I % D], addr);
     if constexpr (I < CHUNKS) {
       stage_chunk<I, WAVES>(sj, wave_u, lane);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (I + 1 < N) PipeStep16<RT, KS, NB, CT, PEND, I + 1>::run(addr, bf, nbf, ring, acc, sj, wave_u, lane);
+    if constexpr (I + 1 < N)
+      PipeStep16<RT, KS, NB, CT, PEND, I + 1, KSTR, KOFF, BIAS>::run(addr, bf, nbf, ring, acc, sj, wave_u, lane, bias, bz);
   }
 };
 
-template <int RT, int KS, int NB, int CT, bool PEND>
+template <int RT, int KS, int NB, int CT, bool PEND, int KSTR = KS, int KOFF = 0, bool BIAS = false>
 __device__ __forceinline__ void pipe_layer16(const uint8_t* lds_buf, const StageJob& sj, half8 (&bf)[NB][CT], half8 (&nbf)[NB][CT],
-                                             floatx4 (&acc)[2][CT], int wave_u, int lane) {
+                                             floatx4 (&acc)[2][CT], int wave_u, int lane,
+                                             const floatx4 (&bias)[PipeStep16<RT, KS, NB, CT, PEND, 0, KSTR, KOFF, BIAS>::NBIAS] = {}) {
+  using P = PipeStep16<RT, KS, NB, CT, PEND, 0, KSTR, KOFF, BIAS>;
   constexpr int D = RTXN_PIPE16, N = (RT ? RT : 1) * KS;
   static_assert(D >= 1 && D <= 4, "ring depth");
   static_assert(RT % 2 == 0, "the pending row tile must land in acc[1] and be the odd tile of its pair");
   static_assert(CT >= 2, "a unit must never read the accumulator of the MFMA issued just before it");
   static_assert(!PEND || KS >= 2, "the pending tile's fragment is first read at k-step KS-1; it is written during k-steps < KS-1");
+  static_assert(!BIAS || (KS >= 2 && !PEND && RT >= 4), "bias copies live one k-step past their MFMAs; dir_bias16's hazard distance");
   static_assert(NB >= KS, "fragment set too small");
-  static_assert(N * 1024 <= 65535 + 1024, "fragment offsets must fit the 16-bit ds offset");
+  static_assert(P::frag_off(N - 1) <= 65535, "fragment offsets must fit the 16-bit ds offset");
   half8 ring[D];
+  floatx4 bz[CT / 2];
   const unsigned addr = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)lds_buf + lane * 16;
-  lds_read_frag<0>(ring[0], addr);
-  if constexpr (D > 1 && N > 1) lds_read_frag<1024>(ring[1 % D], addr);
-  if constexpr (D > 2 && N > 2) lds_read_frag<2048>(ring[2 % D], addr);
-  if constexpr (D > 3 && N > 3) lds_read_frag<3072>(ring[3 % D], addr);
-  PipeStep16<RT, KS, NB, CT, PEND, 0>::run(addr, bf, nbf, ring, acc, sj, wave_u, lane);
+  lds_read_frag<P::frag_off(0)>(ring[0], addr);
+  if constexpr (D > 1 && N > 1) lds_read_frag<P::frag_off(1)>(ring[1 % D], addr);
+  if constexpr (D > 2 && N > 2) lds_read_frag<P::frag_off(2)>(ring[2 % D], addr);
+  if constexpr (D > 3 && N > 3) lds_read_frag<P::frag_off(3)>(ring[3 % D], addr);
+  P::run(addr, bf, nbf, ring, acc, sj, wave_u, lane, bias, bz);
   // RT == 0: the caller reads acc[0] with ordinary code right behind this: see mfma_results_settle
   if constexpr (RT == 0) mfma_results_settle(acc[0]);
+}
+
+// The direction k-steps of layer 0 for a wave's two segments, once per segment (IN_MODE 1 of mlp_fwd16_kernel): a segment's
+// 32 samples share one view direction, so those k-steps' products take two distinct values per wave.  bd: B fragments whose
+// column c holds segment c & 1's direction features (and the 1.0 padding); bias[rt] = the KSD direction k-steps of row tile
+// rt, chained as pipe_layer16 would chain them for one sample (zero C, then in place), so that a position k-step started from
+// bias[rt] is bit for bit what the per-sample layer computes.  Two row tiles per asm statement (one MFMA between the two of a
+// chain); A fragments (rt, kk) at chunk rt * KS0 + kk, the next pair's read while this pair's MFMAs run, all reads waited
+// for before the caller's pipeline issues its own.  Hazards: pipe_layer16 reads bias[rt] in row tile rt >= 0 -- at least
+// the MFMA-result wait states spent at the end for row tiles 0 and 1, the later ones at least a row tile of the pipeline behind.
+template <int RT, int KSD, int KS0, int P>
+struct DirBias16 {
+  static constexpr int NF = 2 * KSD;            // fragments per pair: (2P, kk), (2P + 1, kk), kk = 0 .. KSD-1
+  static constexpr int frag_off(int f) { return ((2 * P + (f & 1)) * KS0 + (f >> 1)) * 1024; }
+  __device__ static __forceinline__ void read(half8 (&ring)[NF], unsigned addr) {
+    lds_read_frag<frag_off(0)>(ring[0], addr);
+    lds_read_frag<frag_off(1)>(ring[1], addr);
+    if constexpr (KSD > 1) {
+      lds_read_frag<frag_off(2)>(ring[2], addr);
+      lds_read_frag<frag_off(3)>(ring[3], addr);
+    }
+  }
+  __device__ static __forceinline__ void run(unsigned addr, const half8 (&bd)[KSD], floatx4 (&bias)[RT], half8 (&ring)[2][NF]) {
+    static_assert(KSD == 1 || KSD == 2, "statements written for one or two direction k-steps");
+    if constexpr (2 * P + 2 < RT) {
+      DirBias16<RT, KSD, KS0, P + 1>::read(ring[(P + 1) & 1], addr);
+      lds_wait_insn<NF>();
+    } else {
+      lds_wait_insn<0>();
+    }
+    const half8(&a)[NF] = ring[P & 1];
+#define RTXN_MB16(ACC, A, B, C) "v_mfma_f32_16x16x32_f16 %[" ACC "], %[" A "], %[" B "], " C "\n\t"
+    if constexpr (KSD == 1) {
+      asm volatile(RTXN_MB16("c0", "a0", "d0", "0") RTXN_MB16("c1", "a1", "d0", "0")
+                   : [c0] "=&v"(bias[2 * P]), [c1] "=&v"(bias[2 * P + 1])
+                   : [d0] "v"(bd[0]), [a0] "v"(a[0]), [a1] "v"(a[1]));
+    } else {
+      asm volatile(RTXN_MB16("c0", "a0", "d0", "0") RTXN_MB16("c1", "a1", "d0", "0")
+                   RTXN_MB16("c0", "a2", "d1", "%[c0]") RTXN_MB16("c1", "a3", "d1", "%[c1]")
+                   : [c0] "=&v"(bias[2 * P]), [c1] "=&v"(bias[2 * P + 1])
+                   : [d0] "v"(bd[0]), [d1] "v"(bd[1]), [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]));
+    }
+#undef RTXN_MB16
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (2 * P + 2 < RT) DirBias16<RT, KSD, KS0, P + 1>::run(addr, bd, bias, ring);
+  }
+};
+template <int RT, int KSD, int KS0>
+__device__ __forceinline__ void dir_bias16(const uint8_t* lds_buf, const half8 (&bd)[KSD], floatx4 (&bias)[RT], int lane) {
+  static_assert(RT % 2 == 0 && RT >= 4, "row tiles in pairs; see the hazard note");
+  static_assert(((RT - 1) * KS0 + KSD - 1) * 1024 <= 65535, "fragment offsets must fit the 16-bit ds offset");
+  half8 ring[2][2 * KSD];
+  const unsigned addr = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)lds_buf + lane * 16;
+  DirBias16<RT, KSD, KS0, 0>::read(ring[0], addr);
+  DirBias16<RT, KSD, KS0, 0>::run(addr, bd, bias, ring);
+  // row tiles 0 and 1 are read first, possibly only one pair of MFMAs after their last write: their wait states, through them
+  asm volatile("s_nop 15\n\ts_nop 7" : "+v"(bias[0]), "+v"(bias[1]));
 }
 
 // The same 16x16x32 pipeline over one CHUNK of a streamed layer (the 256-wide kernel: a layer is 128 KiB of fragments and goes
