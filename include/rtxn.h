@@ -196,6 +196,40 @@ int rtxn_volrender_l2_train(const float* network_outputs, const float* ray_hit, 
                             int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
                             void* loss_gradients_half, float* loss_sum, void* radiance_gradients, rtxn_stream_t stream);
 
+/* The training compositor over a background (not in the reference, whose pixels are sum w_i c_i: a black background; NeRF's
+ * white_bkgd / instant-ngp's random background).  rtxn_volrender_l2_train with, per ray r,
+ *   pixel_r = sum w_i c_i + (1 - A) bg_r,   A = sum w_i   (the weights and A of rtxn_volrender_fwd_aux, RTXN_VR_NERF)
+ * fitted by the same L2 (values (pixel - t)^2 / (3B), gradients half(loss_scale 2 (pixel - t) / (3B))) to the target t_r:
+ *   target_channels 3: float[B][3], used as given;
+ *   target_channels 4: float[B][4] straight (not premultiplied) RGBA, t_c = alpha rgb_c + (1 - alpha) bg_c (fp32).
+ * The background bg_r of ray r (its index in the batch):
+ *   RTXN_BG_CONSTANT: color[0..2];
+ *   RTXN_BG_RANDOM:   fmix32(h) = MurmurHash3's finaliser (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35;
+ *                     h ^= h >> 16), h0 = fmix32(seed + 0x9E3779B9u * (uint32)step), bg_c = (float)(fmix32(h0 ^ (3u r + c)) >> 8)
+ *                     * 2^-24 for c = 0, 1, 2; `step` is read from the device, so a captured graph draws new backgrounds on
+ *                     every replay once the counter moves.
+ * The radiance gradient is the exact gradient of that pixel: written as bg + sum w_k (c_k - bg) it is the plain compositor
+ * with colours c_k - bg, so dL/dc_i = g T_i a_i (unchanged) and dL/dsigma_i = d_i (T_i e^-x_i g.(c_i - bg) - sum_{k>i} w_k
+ * g.(c_k - bg)).  A ray with no segments gets pixel = bg exactly and writes no radiance gradient.
+ * Rules (RTXN_ERR_INVALID with a message, before any device is touched): mode NONE | CONSTANT | RANDOM; target_channels 3 | 4;
+ * RANDOM needs 4 channels (a 3-channel target cannot know the background); NONE allows 3 only; no background with
+ * RTXN_VR_COMPAT (its backward is not the gradient of its forward).  bg == NULL, or NONE with 3 channels: exactly the plain
+ * entry point. */
+enum rtxn_train_background_mode { RTXN_BG_NONE = 0, RTXN_BG_CONSTANT = 1, RTXN_BG_RANDOM = 2 };
+typedef struct rtxn_train_background {
+  int mode;                         /* rtxn_train_background_mode */
+  float color[3];                   /* CONSTANT */
+  unsigned seed;                    /* RANDOM */
+  const int* step;                  /* RANDOM: DEVICE int hashed with the seed; NULL = 0 (rtxn_train_step_ex: NULL = opt.step before
+                                       its increment) */
+  int target_channels;              /* 3: float[n][3] targets as given; 4: float[n][4] straight RGBA, composited over this ray's
+                                       background */
+} rtxn_train_background;
+int rtxn_volrender_l2_train_ex(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                               int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
+                               void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                               const rtxn_train_background* bg, rtxn_stream_t stream);
+
 /* ---- MLP (tiny-cuda-nn surface used by main.cu) ------------------------------- */
 /* Replaces tcnn::create_from_config(5, 4, config) (main.cu:35-69,325),
  * network->n_params / set_params / initialize_params (main.cu:327-349),
@@ -671,6 +705,9 @@ typedef struct rtxn_train_batch {
                                        rtxn_mlp_train_lean_supported): no activations are saved, the weight gradient recomputes them */
 } rtxn_train_batch;
 int rtxn_train_gradients(const rtxn_train_batch* batch, rtxn_stream_t stream);
+/* rtxn_train_gradients over a background (rtxn_volrender_l2_train_ex): batch->targets are float[n_rays][bg->target_channels];
+ * RTXN_VR_NERF only.  bg == NULL or NONE with 3 channels: exactly rtxn_train_gradients. */
+int rtxn_train_gradients_ex(const rtxn_train_batch* batch, const rtxn_train_background* bg, rtxn_stream_t stream);
 
 /* ---- one optimisation step as one call -------------------------------------------------------------------------------
  * The body of the reference's training loop for one batch of rays (main.cu:619-805): traversal (count -> scan -> write, the
@@ -703,6 +740,9 @@ typedef struct rtxn_train_step_args {
   rtxn_train_state opt;
 } rtxn_train_step_args;
 int rtxn_train_step(const rtxn_train_step_args* args, rtxn_stream_t stream);
+/* rtxn_train_step over a background (rtxn_train_gradients_ex).  RANDOM with bg->step == NULL hashes opt.step as it is BEFORE
+ * this call increments it: a replayed graph of the call draws the backgrounds of step 0, 1, 2, ... */
+int rtxn_train_step_ex(const rtxn_train_step_args* args, const rtxn_train_background* bg, rtxn_stream_t stream);
 
 /* ---- segments that carry a loss gradient ---------------------------------------------------------------------------
  * In NeRF training most samples lie behind the first surface: their transmittance, and with it dL/d(radiance), is exactly
@@ -765,7 +805,10 @@ int rtxn_half2_add_pairs(void* values, long n_entries, const void* pairs, long c
  * Reads <basename>/transforms_<split>.json and its PNG frames.  images: float[n][H][W][3],
  * poses: float[n][16] row-major 4x4 (both malloc'ed, host).  flags = 0 reproduces the reference
  * (alpha dropped without compositing, gamma-2.2 linearisation, focal = .5*800/tan(.5*camera_angle_x),
- * SURVEY Q11/Q12); bit 0: composite alpha over white; bit 1: keep v/255 (no gamma). */
+ * SURVEY Q11/Q12); bit 0: composite alpha over white; bit 1: keep v/255 (no gamma); bit 2 (RTXN_LOAD_RGBA): images are
+ * float[n][H][W][4] and image_channels = 4 -- RGB exactly as without bit 2, alpha = a/255 (no gamma, as stb treats alpha),
+ * 1 for files without alpha; together with bit 0 it is an error. */
+enum { RTXN_LOAD_RGBA = 4 };
 typedef struct rtxn_image_dataset {
   int n_images;
   unsigned image_width, image_height, image_channels;

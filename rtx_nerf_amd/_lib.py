@@ -110,6 +110,11 @@ class TrainStepArgs(C.Structure):
                 ("batch", TrainBatch), ("opt", TrainState)]
 
 
+class TrainBackground(C.Structure):
+    """struct rtxn_train_background (include/rtxn.h)."""
+    _fields_ = [("mode", C.c_int), ("color", C.c_float * 3), ("seed", C.c_uint), ("step", C.c_void_p), ("target_channels", C.c_int)]
+
+
 class RenderConfig(C.Structure):
     """struct rtxn_render_config (include/rtxn.h)."""
     _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("table_fp16", C.c_void_p), ("n_dir_freqs", C.c_int),
@@ -146,6 +151,7 @@ SYMBOLS = {
     "rtxn_volrender_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
     "rtxn_volrender_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
     "rtxn_volrender_l2_train": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _P, _P]),
+    "rtxn_volrender_l2_train_ex": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(TrainBackground), _P]),
     "rtxn_mlp_create": (_I, [C.POINTER(MlpConfig), C.POINTER(_P)]),
     "rtxn_mlp_destroy": (_I, [_P]),
     "rtxn_mlp_n_params": (_L, [_P]),
@@ -221,6 +227,8 @@ SYMBOLS = {
     "rtxn_mlp_train_backward_lean_segments": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),
     "rtxn_train_gradients": (_I, [C.POINTER(TrainBatch), _P]),
     "rtxn_train_step": (_I, [C.POINTER(TrainStepArgs), _P]),
+    "rtxn_train_gradients_ex": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), _P]),
+    "rtxn_train_step_ex": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), _P]),
     "rtxn_live_segments_workspace_bytes": (C.c_size_t, [_L]),
     "rtxn_live_segments": (_I, [_P, _L, _L, _P, _P]),
     "rtxn_mlp_train_backward_recompute_live": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P]),

@@ -203,6 +203,45 @@ def volrender_l2_train(network_outputs, ray_hit, num_hits, indices, batch_size, 
                                              _stream()), "rtxn_volrender_l2_train")
 
 
+BG_NONE, BG_CONSTANT, BG_RANDOM = 0, 1, 2   # enum rtxn_train_background_mode
+
+
+def train_background(background=None, *, seed=0, step=None, target_channels=3):
+    """struct rtxn_train_background (include/rtxn.h) or None: background None (mode NONE), three floats (CONSTANT) or "random"
+    (RANDOM: hashed from `seed` and the device int32 tensor `step` -- None: 0, or opt.step for train_step).  target_channels:
+    3, or 4 for straight RGBA targets composited over the ray's background in the kernel.  The tensor must outlive the calls."""
+    b = _lib.TrainBackground()
+    b.target_channels = int(target_channels)
+    if background is None:
+        b.mode = BG_NONE
+    elif isinstance(background, str):
+        if background != "random":
+            raise ValueError(f"background {background!r}: None, (r, g, b) or 'random'")
+        b.mode = BG_RANDOM
+    else:
+        vals = [float(v) for v in background]
+        if len(vals) != 3:
+            raise ValueError(f"background {background!r}: three floats")
+        b.mode = BG_CONSTANT
+        b.color[:] = vals
+    b.seed = int(seed) & 0xFFFFFFFF
+    b.step = _ptr(step, torch.int32, "step")
+    return b
+
+
+def volrender_l2_train_ex(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
+                          loss_gradients, loss_sum, radiance_gradients, background):
+    """volrender_l2_train over a background (background: train_background(...) or None = the plain call): pixel = sum w c +
+    (1 - A) bg, fitted to the (composited) target; exact gradients of that pixel."""
+    check(_lib.lib().rtxn_volrender_l2_train_ex(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
+                                                _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
+                                                num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
+                                                _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
+                                                _ptr(loss_sum, torch.float32, "loss_sum"), _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
+                                                C.byref(background) if background is not None else None, _stream()),
+          "rtxn_volrender_l2_train_ex")
+
+
 # --------------------------------------------------------------------------- MLP
 class Network:
     """tcnn::create_from_config(n_input_dims=5, n_output_dims=4, config) (main.cu:35-69,325)."""
@@ -703,18 +742,25 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
                     total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                     encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                     loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                    workspace_lean=False):
-    """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781)."""
-    b = train_batch(**{k: v for k, v in locals().items()})
-    check(_lib.lib().rtxn_train_gradients(C.byref(b), _stream()), "rtxn_train_gradients")
+                    workspace_lean=False, background=None):
+    """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781).
+    background: train_background(...) -> rtxn_train_gradients_ex (targets float[n_rays][background.target_channels])."""
+    kw = {k: v for k, v in locals().items() if k != "background"}
+    if background is None:
+        b = train_batch(**kw)
+        check(_lib.lib().rtxn_train_gradients(C.byref(b), _stream()), "rtxn_train_gradients")
+    else:
+        b = train_batch(**kw, target_channels=background.target_channels)
+        check(_lib.lib().rtxn_train_gradients_ex(C.byref(b), C.byref(background), _stream()), "rtxn_train_gradients_ex")
 
 
 def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_points, seg_view, num_stored, indices,
                 total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                 encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                 loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                workspace_lean=False):
-    """struct rtxn_train_batch over the given tensors (which the caller keeps alive), sizes checked against the capacity."""
+                workspace_lean=False, target_channels=3):
+    """struct rtxn_train_batch over the given tensors (which the caller keeps alive), sizes checked against the capacity
+    (targets: target_channels floats per ray)."""
     b = _lib.TrainBatch()
     b.mlp, b.grid = net._h, (grid._h if grid is not None else None)
     b.n_dir_freqs = int(n_dir_freqs)
@@ -743,15 +789,19 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
                         ("t_vals", t_vals, 32 * int(segment_capacity)), ("radiance_gradients", radiance_gradients, 32 * int(segment_capacity) * 4),
                         ("start_points", start_points, 3 * int(segment_capacity)), ("end_points", end_points, 3 * int(segment_capacity)),
                         ("seg_view", seg_view, 2 * int(segment_capacity)), ("pixels", pixels, 3 * int(n_rays)),
-                        ("targets", targets, 3 * int(n_rays)), ("num_stored", num_stored, int(n_rays)), ("indices", indices, int(n_rays))):
+                        ("targets", targets, int(target_channels) * int(n_rays)), ("num_stored", num_stored, int(n_rays)), ("indices", indices, int(n_rays))):
         if t.numel() < need:
             raise _lib.RtxnError(f"train_gradients: {nm} holds {t.numel()} elements, {need} needed for capacity {segment_capacity} / {n_rays} rays")
     return b
 
 
-def train_step(args):
-    """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream."""
-    check(_lib.lib().rtxn_train_step(C.byref(args), _stream()), "rtxn_train_step")
+def train_step(args, background=None):
+    """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
+    background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment)."""
+    if background is None:
+        check(_lib.lib().rtxn_train_step(C.byref(args), _stream()), "rtxn_train_step")
+    else:
+        check(_lib.lib().rtxn_train_step_ex(C.byref(args), C.byref(background), _stream()), "rtxn_train_step_ex")
 
 
 def half2_workspace(values, block_entries):

@@ -21,6 +21,10 @@ int require_device();
 // path uses it any more.
 hipError_t zero_words(void* p, size_t n_words, hipStream_t stream);
 
+// The rules of a training background (rtxn_train_background, include/rtxn.h), host only: RTXN_ERR_INVALID with a message, or
+// RTXN_OK with *active = whether a background is composited at all.
+int check_train_background(const rtxn_train_background* bg, int vr_mode, const char* who, bool* active);
+
 }  // namespace rtxn
 
 #define RTXN_HIP(expr)                                           \

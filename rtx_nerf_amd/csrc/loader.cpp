@@ -407,7 +407,9 @@ bool decode_png(const std::vector<unsigned char>& file, int& width, int& height,
 
 // stbi_loadf(..., desired_channels = 3): convert to 3 channels (alpha dropped, gray replicated), then
 // ldr -> hdr with gamma 2.2 (flags bit 1 set: keep v/255; bit 0 set: composite alpha over white first).
+// Bit 2 (RTXN_LOAD_RGBA): 4 floats per pixel, the same RGB followed by alpha = a/255 (stb leaves alpha linear), 1 without alpha.
 void to_float_rgb(const std::vector<unsigned char>& px, int channels, size_t npx, int flags, float* out) {
+  const int oc = (flags & RTXN_LOAD_RGBA) ? 4 : 3;
   for (size_t i = 0; i < npx; ++i) {
     float rgb[3];
     const unsigned char* p = &px[i * channels];
@@ -419,8 +421,9 @@ void to_float_rgb(const std::vector<unsigned char>& px, int channels, size_t npx
       float v = rgb[k] / 255.0f;
       if (!(flags & 2)) v = (float)(pow(v, 2.2f) * 1.0f);
       if ((flags & 1) && has_alpha) v = v * alpha + (1.0f - alpha);
-      out[i * 3 + k] = v;
+      out[i * oc + k] = v;
     }
+    if (oc == 4) out[i * 4 + 3] = alpha;
   }
 }
 
@@ -438,6 +441,8 @@ static int load_images_json_impl(const char* basename, const char* split, int fl
 // No C++ exception may cross the C ABI (a bad_alloc from a hostile or corrupt file would otherwise terminate the host).
 extern "C" int rtxn_load_images_json(const char* basename, const char* split, int flags, rtxn_image_dataset* out) {
   RTXN_REQUIRE(basename && split && out, "rtxn_load_images_json: NULL argument");
+  RTXN_REQUIRE(!((flags & RTXN_LOAD_RGBA) && (flags & 1)),
+               "rtxn_load_images_json: flags %d: RTXN_LOAD_RGBA keeps alpha, bit 0 composites it away over white; choose one", flags);
   memset(out, 0, sizeof(*out));
   try {
     return load_images_json_impl(basename, split, flags, out);
@@ -476,6 +481,7 @@ static int load_images_json_impl(const char* basename, const char* split, int fl
   const float camera_angle_x = (float)cam->num;
   const size_t n = frames->arr.size();
   int W = 0, H = 0;
+  const int oc = (flags & RTXN_LOAD_RGBA) ? 4 : 3;
   std::vector<float> images, poses(n * 16);
   for (size_t i = 0; i < n; ++i) {
     const JVal& fr = frames->arr[i];
@@ -500,12 +506,12 @@ static int load_images_json_impl(const char* basename, const char* split, int fl
       rtxn::set_error("Failed to load the image %s%s%s", png_path.c_str(), err.empty() ? "" : ": ", err.c_str());
       return RTXN_ERR_IO;  // the reference returns an EMPTY dataset here (:74-78); the C++ wrapper mirrors that
     }
-    if (i == 0) { W = w; H = h; images.resize(n * (size_t)W * H * 3); }
+    if (i == 0) { W = w; H = h; images.resize(n * (size_t)W * H * oc); }
     if (w != W || h != H) {
       rtxn::set_error("%s: %dx%d differs from the first frame's %dx%d", png_path.c_str(), w, h, W, H);
       return RTXN_ERR_IO;
     }
-    to_float_rgb(px, ch, (size_t)W * H, flags, &images[i * (size_t)W * H * 3]);
+    to_float_rgb(px, ch, (size_t)W * H, flags, &images[i * (size_t)W * H * oc]);
   }
   // a pose or field of view that is not a number (a JSON reader accepts "nan" / "1e999") would only surface as garbage rays
   if (!all_finite(poses) || !std::isfinite(camera_angle_x)) {
@@ -515,7 +521,7 @@ static int load_images_json_impl(const char* basename, const char* split, int fl
   out->n_images = (int)n;
   out->image_width = (unsigned)W;
   out->image_height = (unsigned)H;
-  out->image_channels = 3;                                                                    // desired_channels, :52
+  out->image_channels = (unsigned)oc;                                                         // desired_channels, :52
   out->focal = (float)(.5 * 800 / std::tan(.5 * camera_angle_x));                             // :85 (800 hard-coded, Q12)
   out->camera_angle_x = camera_angle_x;
   out->images = (float*)malloc(images.size() * sizeof(float));
@@ -604,6 +610,7 @@ int load_llff_impl(const char* basedir, int factor, int flags, rtxn_image_datase
     return RTXN_ERR_IO;
   }
   int W = 0, H = 0;
+  const int oc = (flags & RTXN_LOAD_RGBA) ? 4 : 3;
   std::vector<float> images, poses(n * 16), bounds(n * 2);
   for (size_t i = 0; i < n; ++i) {
     const double* row = pb + i * 17;   // row-major 3x5 then near, far
@@ -625,12 +632,12 @@ int load_llff_impl(const char* basedir, int factor, int flags, rtxn_image_datase
       rtxn::set_error("Failed to load the image %s%s%s", png_path.c_str(), err.empty() ? "" : ": ", err.c_str());
       return RTXN_ERR_IO;
     }
-    if (i == 0) { W = w; H = h; images.resize(n * (size_t)W * H * 3); }
+    if (i == 0) { W = w; H = h; images.resize(n * (size_t)W * H * oc); }
     if (w != W || h != H) {
       rtxn::set_error("%s: %dx%d differs from the first frame's %dx%d", png_path.c_str(), w, h, W, H);
       return RTXN_ERR_IO;
     }
-    to_float_rgb(px, ch, (size_t)W * H, flags, &images[i * (size_t)W * H * 3]);
+    to_float_rgb(px, ch, (size_t)W * H, flags, &images[i * (size_t)W * H * oc]);
   }
   const double f_full = n ? pb[14] : 0.0, w_full = n ? pb[9] : 0.0;   // hwf column of the first pose: H = [4], W = [9], focal = [14]
   if (!all_finite(poses) || !all_finite(bounds) || !std::isfinite(f_full) || !std::isfinite(w_full)) {
@@ -640,7 +647,7 @@ int load_llff_impl(const char* basedir, int factor, int flags, rtxn_image_datase
   out->n_images = (int)n;
   out->image_width = (unsigned)W;
   out->image_height = (unsigned)H;
-  out->image_channels = 3;
+  out->image_channels = (unsigned)oc;
   out->focal = (float)(w_full > 0 ? f_full * (double)W / w_full : f_full);   // focal in pixels of the LOADED resolution
   out->camera_angle_x = out->focal > 0 ? (float)(2.0 * std::atan(0.5 * W / out->focal)) : 0.0f;
   out->images = (float*)malloc(images.size() * sizeof(float) + 1);
@@ -662,6 +669,8 @@ int load_llff_impl(const char* basedir, int factor, int flags, rtxn_image_datase
 extern "C" int rtxn_load_llff(const char* basedir, int factor, int flags, rtxn_image_dataset* out, float** bounds) {
   RTXN_REQUIRE(basedir && out, "rtxn_load_llff: NULL argument");
   RTXN_REQUIRE(factor >= 0 && factor <= 64, "rtxn_load_llff: factor = %d", factor);
+  RTXN_REQUIRE(!((flags & RTXN_LOAD_RGBA) && (flags & 1)),
+               "rtxn_load_llff: flags %d: RTXN_LOAD_RGBA keeps alpha, bit 0 composites it away over white; choose one", flags);
   memset(out, 0, sizeof(*out));
   if (bounds) *bounds = nullptr;
   try {

@@ -3885,7 +3885,7 @@ extern "C" int rtxn_hashgrid_backward_segments_live(const rtxn_hashgrid* g, cons
 }
 
 // ------------------------------------------------------------------------- a whole batch, segment count on the device
-extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) {
+static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
   RTXN_REQUIRE(b && b->mlp, "rtxn_train_gradients: NULL batch or model");
   const rtxn_mlp* m = b->mlp;
   int rc = check_train(m, "rtxn_train_gradients");
@@ -3942,8 +3942,10 @@ extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t str
   if (rc != RTXN_OK) return rc;
   // launch_volrender_cuda, loss->evaluate, launch_volrender_backward_cuda (main.cu:737-767): per ray, no sample count needed
   if (b->vr_mode == RTXN_VR_NERF) {
-    rc = rtxn_volrender_l2_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale, b->pixels,
-                                 b->loss_gradients_half, b->loss_sum, b->radiance_gradients, stream);
+    rc = bg ? rtxn_volrender_l2_train_ex(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
+                                         b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, stream)
+            : rtxn_volrender_l2_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale, b->pixels,
+                                      b->loss_gradients_half, b->loss_sum, b->radiance_gradients, stream);
     if (rc != RTXN_OK) return rc;
   } else {
     rc = rtxn_volrender_fwd(nullptr, b->radiance, b->num_stored, b->indices, b->t_vals, b->n_rays, 32, b->pixels, b->vr_mode, stream);
@@ -3978,4 +3980,15 @@ extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t str
     rc = hashgrid_backward_impl(b->grid, bsrc, b->dencT, cap_samples, b->dtable, b->dtable_hashed_half, dc, stream, ll, lc);
   }
   return rc;
+}
+
+extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, stream); }
+
+// over a background: the one difference is the compositor (rtxn_volrender_l2_train_ex); NULL / NONE + 3 channels: the plain call
+extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
+  RTXN_REQUIRE(b, "rtxn_train_gradients_ex: NULL batch");
+  bool active = false;
+  const int rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_ex", &active);
+  if (rc != RTXN_OK) return rc;
+  return train_gradients_impl(b, active ? bg : nullptr, stream);
 }

@@ -18,7 +18,7 @@ __global__ void advance_step_kernel(int* step, float lr, float beta1, float beta
 
 }  // namespace
 
-extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) {
+static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
@@ -60,7 +60,7 @@ extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stre
   if (rc != RTXN_OK) return rc;
 
   // ---- sampler ... backward (main.cu:703-781), segment count read on the device ----
-  rc = rtxn_train_gradients(&b, stream);
+  rc = bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
   if (rc != RTXN_OK) return rc;
 
   // ---- optimizer->step (main.cu:787): every gradient is cleared as it is consumed ----
@@ -91,4 +91,18 @@ extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stre
     }
   }
   return RTXN_OK;
+}
+
+extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, stream); }
+
+extern "C" int rtxn_train_step_ex(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
+  RTXN_REQUIRE(a, "rtxn_train_step_ex: NULL arguments");
+  bool active = false;
+  const int rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_ex", &active);
+  if (rc != RTXN_OK) return rc;
+  if (!active) return train_step_impl(a, nullptr, stream);
+  // RANDOM without a counter of its own: the optimizer's, read by the compositor before advance_step_kernel increments it
+  rtxn_train_background own = *bg;
+  if (own.mode == RTXN_BG_RANDOM && !own.step) own.step = a->opt.step;
+  return train_step_impl(a, &own, stream);
 }

@@ -834,7 +834,315 @@ __global__ __launch_bounds__(256) void volrender_aux_pair_kernel(const float4* _
   }
 }
 
+// The training compositor over a background (rtxn_volrender_l2_train_ex): pixel = sum w c + (1 - A) bg with
+// A = sum w.  Written as bg + sum w_k (c_k - bg) it is the plain compositor with colours c_k - bg: dL/dc_i is unchanged, the
+// optical-depth gradient dots g with c_k - bg, and the second sweep's total is S' = g . (sum w c) - (g . bg) A.  Separate
+// templates beside the plain ones, which keep their machine code.
+struct BgArgs {
+  int mode;              // RTXN_BG_CONSTANT | RTXN_BG_RANDOM
+  float color[3];        // CONSTANT
+  unsigned seed;         // RANDOM
+  const int* step;       // RANDOM: device int hashed with the seed, or NULL (0)
+  int target_channels;   // 3 | 4 (straight RGBA, composited over the ray's background)
+};
+
+__device__ __forceinline__ unsigned fmix32(unsigned h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// the ray's background and its (composited) target: wave-uniform values
+__device__ __forceinline__ void ray_background(const BgArgs& bg, const float* __restrict__ target, int ray, float (&b)[3],
+                                               float (&t)[3]) {
+  if (bg.mode == RTXN_BG_RANDOM) {
+    const unsigned step = bg.step ? (unsigned)*bg.step : 0u;
+    const unsigned h0 = fmix32(bg.seed + 0x9E3779B9u * step);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[c] = (float)(fmix32(h0 ^ (3u * (unsigned)ray + (unsigned)c)) >> 8) * 0x1p-24f;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[c] = bg.color[c];
+  }
+  if (bg.target_channels == 4) {
+    const float* p = target + 4 * (long)ray;
+    const float a = p[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = a * p[c] + (1.0f - a) * b[c];
+  } else {
+    const float* p = target + 3 * (long)ray;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = p[c];
+  }
+}
+
+// one ray per wave, 64 samples per step: the form for odd K or misaligned buffers (volrender_l2_fused_kernel's arithmetic)
+__global__ __launch_bounds__(256) void volrender_l2_bg_kernel(const float4* __restrict__ radiance, const float* __restrict__ step_len,
+                                                              const int* __restrict__ num_hits, const int* __restrict__ indices,
+                                                              int batch_size, int K, const float* __restrict__ target,
+                                                              float loss_scale, float* __restrict__ pixels,
+                                                              __half* __restrict__ loss_gradients, float* __restrict__ loss_sum,
+                                                              half4* __restrict__ grads, BgArgs bga) {
+  const int lane = threadIdx.x & 63;
+  const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ray >= batch_size) return;
+  const long base = (long)indices[ray] * K;
+  const long n = (long)num_hits[ray] * K;
+  const float inv_n = 1.0f / (float)(3L * batch_size);
+  float bg[3], tg[3];
+  ray_background(bga, target, ray, bg, tg);
+  // sweep 1: colour and opacity sums
+  float T_carry = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f;
+  for (long s0 = 0; s0 < n; s0 += 64) {
+    const bool act = s0 + lane < n;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    float d = 0.0f;
+    if (act) {
+      c = radiance[base + s0 + lane];
+      d = step_len[base + s0 + lane];
+    }
+    const float x = d * c.w;
+    const float incl = wave_incl_scan_f(x, lane);
+    const float w = act ? expf(-(T_carry + incl - x)) * (1.0f - expf(-x)) : 0.0f;
+    ar = fmaf(w, c.x, ar);
+    ag = fmaf(w, c.y, ag);
+    ab = fmaf(w, c.z, ab);
+    aw += w;
+    T_carry += lane63(incl);
+  }
+  ar = wave_sum(ar);
+  ag = wave_sum(ag);
+  ab = wave_sum(ab);
+  aw = wave_sum(aw);
+  const float rest = 1.0f - aw;
+  const float pr = fmaf(rest, bg[0], ar), pg = fmaf(rest, bg[1], ag), pb = fmaf(rest, bg[2], ab);
+  const float d0 = pr - tg[0], d1 = pg - tg[1], d2 = pb - tg[2];
+  const __half h0 = __float2half(loss_scale * 2.0f * d0 * inv_n), h1 = __float2half(loss_scale * 2.0f * d1 * inv_n),
+               h2 = __float2half(loss_scale * 2.0f * d2 * inv_n);
+  const float g0 = __half2float(h0), g1 = __half2float(h1), g2 = __half2float(h2);
+  if (lane == 0) {
+    pixels[3 * (long)ray] = pr;
+    pixels[3 * (long)ray + 1] = pg;
+    pixels[3 * (long)ray + 2] = pb;
+    if (loss_gradients) {
+      loss_gradients[3 * (long)ray] = h0;
+      loss_gradients[3 * (long)ray + 1] = h1;
+      loss_gradients[3 * (long)ray + 2] = h2;
+    }
+    if (loss_sum) atomicAdd(loss_sum, (d0 * d0 + d1 * d1 + d2 * d2) * inv_n);
+  }
+  const float gbg = g0 * bg[0] + g1 * bg[1] + g2 * bg[2];
+  const float S = (g0 * ar + g1 * ag + g2 * ab) - gbg * aw;     // = sum_k w_k (g . (c_k - bg))
+  // sweep 2: per-sample gradients
+  T_carry = 0.0f;
+  float P_carry = 0.0f;
+  for (long s0 = 0; s0 < n; s0 += 64) {
+    const bool act = s0 + lane < n;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    float d = 0.0f;
+    if (act) {
+      c = radiance[base + s0 + lane];
+      d = step_len[base + s0 + lane];
+    }
+    const float x = d * c.w;
+    const float incl = wave_incl_scan_f(x, lane);
+    const float Ti = expf(-(T_carry + incl - x));
+    const float ex = expf(-x);
+    const float a = 1.0f - ex;
+    const float gc = (g0 * c.x + g1 * c.y + g2 * c.z) - gbg;
+    const float wgc = act ? Ti * a * gc : 0.0f;
+    const float pincl = P_carry + wave_incl_scan_f(wgc, lane);
+    if (act) {
+      const float suffix = S - pincl;
+      half4 o;
+      o.x = __float2half(g0 * Ti * a);
+      o.y = __float2half(g1 * Ti * a);
+      o.z = __float2half(g2 * Ti * a);
+      o.w = __float2half(d * (Ti * ex * gc - suffix));
+      grads[base + s0 + lane] = o;
+    }
+    T_carry += lane63(incl);
+    P_carry = lane63(pincl);
+  }
+}
+
+// U blocks of 128 samples per step, two per lane (volrender_l2_fused_multi_kernel's schedule and arithmetic, plus the opacity
+// sum in sweep 1 and the background's dot product in sweep 2)
+template <int U>
+__global__ __launch_bounds__(256) void volrender_l2_bg_multi_kernel(const float4* __restrict__ radiance, const float* __restrict__ step_len,
+                                                                    const int* __restrict__ num_hits, const int* __restrict__ indices,
+                                                                    int batch_size, int K, const float* __restrict__ target,
+                                                                    float loss_scale, float* __restrict__ pixels,
+                                                                    __half* __restrict__ loss_gradients, float* __restrict__ loss_sum,
+                                                                    half4* __restrict__ grads, BgArgs bga) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ray = blockIdx.x * 4 + wave;
+  float loss_part = 0.0f;
+  if (ray < batch_size) {
+    const long base = (long)indices[ray] * K;
+    const long n = (long)num_hits[ray] * K;          // even
+    const float inv_n = 1.0f / (float)(3L * batch_size);
+    float bg[3], tg[3];
+    ray_background(bga, target, ray, bg, tg);
+    constexpr long STEP = 128L * U;
+    struct Pair { float4 c0, c1; float d0, d1; };
+    auto load = [&](long s0, Pair (&p)[U]) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long i0 = s0 + 128 * u + 2 * lane;
+        p[u].c0 = p[u].c1 = make_float4(0.f, 0.f, 0.f, 0.f);
+        p[u].d0 = p[u].d1 = 0.0f;
+        if (i0 < n) {
+          p[u].c0 = radiance[base + i0];
+          p[u].c1 = radiance[base + i0 + 1];
+          const float2 dd = *reinterpret_cast<const float2*>(step_len + base + i0);
+          p[u].d0 = dd.x;
+          p[u].d1 = dd.y;
+        }
+      }
+    };
+    // sweep 1: colour and opacity sums
+    float T_carry = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f;
+    Pair cur[U], nxt[U];
+    if (n > 0) load(0, cur);
+    for (long s0 = 0; s0 < n; s0 += STEP) {
+      if (s0 + STEP < n) load(s0 + STEP, nxt);
+      float x0[U], x1[U], pr[U], incl[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        x0[u] = cur[u].d0 * cur[u].c0.w;                 // inactive lanes hold zeros: x = 0, w = 0
+        x1[u] = cur[u].d1 * cur[u].c1.w;
+        pr[u] = x0[u] + x1[u];
+        incl[u] = wave_incl_scan_f(pr[u], lane);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float T0 = T_carry + (incl[u] - pr[u]);
+        const float w0 = expf(-T0) * (1.0f - expf(-x0[u])), w1 = expf(-(T0 + x0[u])) * (1.0f - expf(-x1[u]));
+        ar = fmaf(w1, cur[u].c1.x, fmaf(w0, cur[u].c0.x, ar));
+        ag = fmaf(w1, cur[u].c1.y, fmaf(w0, cur[u].c0.y, ag));
+        ab = fmaf(w1, cur[u].c1.z, fmaf(w0, cur[u].c0.z, ab));
+        aw += w0 + w1;
+        T_carry += lane63(incl[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+    }
+    ar = wave_sum(ar);
+    ag = wave_sum(ag);
+    ab = wave_sum(ab);
+    aw = wave_sum(aw);
+    const float rest = 1.0f - aw;
+    const float pxr = fmaf(rest, bg[0], ar), pxg = fmaf(rest, bg[1], ag), pxb = fmaf(rest, bg[2], ab);
+    const float e0 = pxr - tg[0], e1 = pxg - tg[1], e2 = pxb - tg[2];
+    const __half h0 = __float2half(loss_scale * 2.0f * e0 * inv_n), h1 = __float2half(loss_scale * 2.0f * e1 * inv_n),
+                 h2 = __float2half(loss_scale * 2.0f * e2 * inv_n);
+    const float g0 = __half2float(h0), g1 = __half2float(h1), g2 = __half2float(h2);
+    if (lane == 0) {
+      pixels[3 * (long)ray] = pxr;
+      pixels[3 * (long)ray + 1] = pxg;
+      pixels[3 * (long)ray + 2] = pxb;
+      if (loss_gradients) {
+        loss_gradients[3 * (long)ray] = h0;
+        loss_gradients[3 * (long)ray + 1] = h1;
+        loss_gradients[3 * (long)ray + 2] = h2;
+      }
+    }
+    loss_part = (e0 * e0 + e1 * e1 + e2 * e2) * inv_n;
+    const float gbg = g0 * bg[0] + g1 * bg[1] + g2 * bg[2];
+    const float S = (g0 * ar + g1 * ag + g2 * ab) - gbg * aw;     // = sum_k w_k (g . (c_k - bg))
+    // sweep 2: per-sample gradients (the radiance is re-read: cache hits)
+    T_carry = 0.0f;
+    float P_carry = 0.0f;
+    if (n > 0) load(0, cur);
+    for (long s0 = 0; s0 < n; s0 += STEP) {
+      if (s0 + STEP < n) load(s0 + STEP, nxt);
+      float x0[U], x1[U], pr[U], incl[U], T0[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        x0[u] = cur[u].d0 * cur[u].c0.w;
+        x1[u] = cur[u].d1 * cur[u].c1.w;
+        pr[u] = x0[u] + x1[u];
+        incl[u] = wave_incl_scan_f(pr[u], lane);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        T0[u] = T_carry + (incl[u] - pr[u]);
+        T_carry += lane63(incl[u]);
+      }
+      float Ti0[U], Ti1[U], ex0[U], ex1[U], gc0[U], gc1[U], wgc1[U], pin[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        Ti0[u] = expf(-T0[u]);
+        Ti1[u] = expf(-(T0[u] + x0[u]));
+        ex0[u] = expf(-x0[u]);
+        ex1[u] = expf(-x1[u]);
+        gc0[u] = (g0 * cur[u].c0.x + g1 * cur[u].c0.y + g2 * cur[u].c0.z) - gbg;
+        gc1[u] = (g0 * cur[u].c1.x + g1 * cur[u].c1.y + g2 * cur[u].c1.z) - gbg;
+        // inactive lanes: Ti (1 - ex) = 0 (x = 0), so the -gbg of their zero colour adds nothing to the prefix
+        const float wgc0 = Ti0[u] * (1.0f - ex0[u]) * gc0[u];
+        wgc1[u] = Ti1[u] * (1.0f - ex1[u]) * gc1[u];
+        pin[u] = wave_incl_scan_f(wgc0 + wgc1[u], lane);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long i0 = s0 + 128 * u + 2 * lane;
+        const float pincl1 = P_carry + pin[u];          // inclusive prefix at the pair's second sample
+        const float pincl0 = pincl1 - wgc1[u];
+        P_carry += lane63(pin[u]);
+        if (i0 < n) {
+          const float a0 = 1.0f - ex0[u], a1 = 1.0f - ex1[u];
+          half4 o0, o1;
+          o0.x = __float2half(g0 * Ti0[u] * a0);
+          o0.y = __float2half(g1 * Ti0[u] * a0);
+          o0.z = __float2half(g2 * Ti0[u] * a0);
+          o0.w = __float2half(cur[u].d0 * (Ti0[u] * ex0[u] * gc0[u] - (S - pincl0)));
+          o1.x = __float2half(g0 * Ti1[u] * a1);
+          o1.y = __float2half(g1 * Ti1[u] * a1);
+          o1.z = __float2half(g2 * Ti1[u] * a1);
+          o1.w = __float2half(cur[u].d1 * (Ti1[u] * ex1[u] * gc1[u] - (S - pincl1)));
+          uint4 packed;
+          packed.x = *reinterpret_cast<const unsigned*>(&o0.x);
+          packed.y = *reinterpret_cast<const unsigned*>(&o0.z);
+          packed.z = *reinterpret_cast<const unsigned*>(&o1.x);
+          packed.w = *reinterpret_cast<const unsigned*>(&o1.z);
+          *reinterpret_cast<uint4*>(grads + base + i0) = packed;      // two half4: one 16-byte store
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+    }
+  }
+  if (loss_sum) {
+    if (lane == 0) red[wave] = loss_part;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss_sum, (red[0] + red[1]) + (red[2] + red[3]));
+  }
+}
+
 }  // namespace
+
+// The background rules of every _ex training entry point (include/rtxn.h), checked before any device is touched.  *active: a
+// background is to be composited (NULL, or NONE with 3-channel targets, run exactly what the plain entry point runs).
+int rtxn::check_train_background(const rtxn_train_background* bg, int vr_mode, const char* who, bool* active) {
+  *active = false;
+  if (!bg) return RTXN_OK;
+  RTXN_REQUIRE(bg->mode == RTXN_BG_NONE || bg->mode == RTXN_BG_CONSTANT || bg->mode == RTXN_BG_RANDOM,
+               "%s: unknown background mode %d", who, bg->mode);
+  RTXN_REQUIRE(bg->target_channels == 3 || bg->target_channels == 4, "%s: target_channels = %d (3 or 4)", who, bg->target_channels);
+  RTXN_REQUIRE(!(bg->mode == RTXN_BG_RANDOM && bg->target_channels == 3),
+               "%s: a RANDOM background needs 4-channel (RGBA) targets: a 3-channel target cannot know the background", who);
+  RTXN_REQUIRE(!(bg->mode == RTXN_BG_NONE && bg->target_channels == 4),
+               "%s: 4-channel (RGBA) targets need a CONSTANT or RANDOM background to be composited over", who);
+  *active = bg->mode != RTXN_BG_NONE;
+  RTXN_REQUIRE(!(*active && vr_mode == RTXN_VR_COMPAT),
+               "%s: a background needs the RTXN_VR_NERF compositor (RTXN_VR_COMPAT's backward is not the gradient of its forward)", who);
+  return RTXN_OK;
+}
 
 extern "C" int rtxn_volrender_fwd(const float* network_inputs, const float* network_outputs, const int* num_hits,
                                   const int* indices, const float* ray_hit, int batch_size,
@@ -961,6 +1269,47 @@ extern "C" int rtxn_volrender_l2_train(const float* network_outputs, const float
                                                                    static_cast<__half*>(loss_gradients_half), loss_sum,
                                                                    static_cast<half4*>(radiance_gradients));
   RTXN_LAUNCH_CHECK("volrender_l2_fused_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_volrender_l2_train_ex(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                                          int batch_size, int num_samples_per_hit, const float* target, float loss_scale,
+                                          float* pixels, void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                                          const rtxn_train_background* bg, rtxn_stream_t stream) {
+  bool active = false;
+  const int rc = rtxn::check_train_background(bg, RTXN_VR_NERF, "rtxn_volrender_l2_train_ex", &active);
+  if (rc != RTXN_OK) return rc;
+  if (!active)
+    return rtxn_volrender_l2_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
+                                   pixels, loss_gradients_half, loss_sum, radiance_gradients, stream);
+  RTXN_REQUIRE(batch_size >= 0, "rtxn_volrender_l2_train_ex: batch_size = %d < 0", batch_size);
+  RTXN_REQUIRE(num_samples_per_hit > 0, "rtxn_volrender_l2_train_ex: num_samples_per_hit = %d", num_samples_per_hit);
+  RTXN_DEVICE_OR_FAIL();
+  hipStream_t s = rtxn::as_stream(stream);
+  if (loss_sum) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
+  if (batch_size == 0) return RTXN_OK;
+  RTXN_REQUIRE(network_outputs && ray_hit && num_hits && indices && target && pixels && radiance_gradients,
+               "rtxn_volrender_l2_train_ex: NULL buffer");
+  RTXN_REQUIRE(((uintptr_t)network_outputs & 15) == 0 && ((uintptr_t)radiance_gradients & 7) == 0,
+               "rtxn_volrender_l2_train_ex: radiance must be 16-byte and gradients 8-byte aligned");
+  BgArgs a;
+  a.mode = bg->mode;
+  for (int c = 0; c < 3; ++c) a.color[c] = bg->color[c];
+  a.seed = bg->seed;
+  a.step = bg->step;
+  a.target_channels = bg->target_channels;
+  const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)ray_hit & 7) == 0 && ((uintptr_t)radiance_gradients & 15) == 0;
+  if (pairs)
+    volrender_l2_bg_multi_kernel<4><<<(batch_size + 3) / 4, 256, 0, s>>>(reinterpret_cast<const float4*>(network_outputs), ray_hit, num_hits,
+                                                                         indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
+                                                                         static_cast<__half*>(loss_gradients_half), loss_sum,
+                                                                         static_cast<half4*>(radiance_gradients), a);
+  else
+    volrender_l2_bg_kernel<<<(batch_size + 3) / 4, 256, 0, s>>>(reinterpret_cast<const float4*>(network_outputs), ray_hit, num_hits,
+                                                                indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
+                                                                static_cast<__half*>(loss_gradients_half), loss_sum,
+                                                                static_cast<half4*>(radiance_gradients), a);
+  RTXN_LAUNCH_CHECK("volrender_l2_bg_kernel");
   return RTXN_OK;
 }
 

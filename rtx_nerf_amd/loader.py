@@ -8,13 +8,16 @@ import numpy as np
 
 from . import _lib
 
+RTXN_LOAD_RGBA = 4     # flags bit 2: float[n,H,W,4] straight RGBA (alpha a/255, 1 without alpha); not with bit 0
+
 SYNTHETIC_NAMES = {"CHAIR": "chair/", "DRUMS": "drums/", "FICUS": "ficus/", "HOTDOG": "hotdog/", "LEGO": "lego/",
                    "MATERIALS": "fern/",   # sic: data_loader.cpp:128-130 (quirk Q12)
                    "MIC": "mic/", "SHIP": "ship/"}
 
 
 class ImageDataset:
-    """loader/data_loader.h:20-27: images float[n,H,W,3], poses float[n,16], focal, width, height, channels."""
+    """loader/data_loader.h:20-27: images float[n,H,W,channels] (3, or 4 with RTXN_LOAD_RGBA), poses float[n,16], focal, width,
+    height, channels."""
 
     def __init__(self, images, poses, focal, width, height, channels, camera_angle_x=0.0):
         self.images, self.poses, self.focal = images, poses, focal
@@ -34,7 +37,8 @@ def load_images_json(basename, s, flags=0):
             sys.exit(1)
         return ImageDataset(np.zeros((0, 0, 0, 3), np.float32), np.zeros((0, 16), np.float32), 0.0, 0, 0, 0)
     n, w, h = d.n_images, d.image_width, d.image_height
-    images = np.ctypeslib.as_array(d.images, shape=(n, h, w, 3)).copy() if n else np.zeros((0, h, w, 3), np.float32)
+    ch = d.image_channels or 3           # 4 with RTXN_LOAD_RGBA (flags bit 2)
+    images = np.ctypeslib.as_array(d.images, shape=(n, h, w, ch)).copy() if n else np.zeros((0, h, w, ch), np.float32)
     poses = np.ctypeslib.as_array(d.poses, shape=(n, 16)).copy() if n else np.zeros((0, 16), np.float32)
     out = ImageDataset(images, poses, d.focal, w, h, d.image_channels, d.camera_angle_x)
     _lib.lib().rtxn_free_image_dataset(C.byref(d))
@@ -61,7 +65,8 @@ def load_llff_data(directory, factor=8, flags=0):
         print(_lib.lib().rtxn_last_error().decode(), file=sys.stderr)
         return []
     n, w, h = d.n_images, d.image_width, d.image_height
-    images = np.ctypeslib.as_array(d.images, shape=(n, h, w, 3)).copy() if n else np.zeros((0, h, w, 3), np.float32)
+    ch = d.image_channels or 3           # 4 with RTXN_LOAD_RGBA (flags bit 2)
+    images = np.ctypeslib.as_array(d.images, shape=(n, h, w, ch)).copy() if n else np.zeros((0, h, w, ch), np.float32)
     poses = np.ctypeslib.as_array(d.poses, shape=(n, 16)).copy() if n else np.zeros((0, 16), np.float32)
     out = ImageDataset(images, poses, d.focal, w, h, d.image_channels, d.camera_angle_x)
     out.bounds = np.ctypeslib.as_array(b, shape=(n, 2)).copy() if n else np.zeros((0, 2), np.float32)

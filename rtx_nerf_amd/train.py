@@ -56,7 +56,13 @@ class _Stage:
 class Trainer:
     def __init__(self, grid_res, occupancy=None, encoding="hash", n_neurons=64, n_hidden_layers=4,
                  hashgrid=None, n_dir_freqs=4, batch_rays=4096, max_segments=None, lr=1e-3, loss_scale=128.0,
-                 density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None):
+                 density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
+                 target_channels=None):
+        """background: None (black, the reference's compositor), (r, g, b) -- train over that constant colour -- or "random":
+        a fresh colour per ray and step (librtxn: rtxn_volrender_l2_train_ex / rtxn_train_gradients_ex /
+        rtxn_train_step_ex).  Targets are [n, 3] or straight RGBA [n, 4] (composited over the ray's background in the kernel);
+        "random" needs RGBA.  target_channels: the width of graph_targets for the captured / one-call steps (default 4 with
+        "random", else 3).  background_seed: RANDOM's seed (the rank is mixed in when data parallel)."""
         self.R = grid_res
         self.dev = torch.device(device)
         self.occ = occupancy
@@ -68,6 +74,7 @@ class Trainer:
         self.lr, self.loss_scale, self.density_scale = lr, loss_scale, density_scale
         self.step_count = 0
         self._stage_ev = None      # list of (stage, start event, end event) while time_stages() is collecting
+        self._init_background(background, background_seed, target_channels)      # refused before anything is allocated
         d = self.dev
         # ---- model -------------------------------------------------------------------------------
         self.encoding = encoding
@@ -189,6 +196,46 @@ class Trainer:
                            if (self.deterministic and encoding == "hash") else None)
 
     # ------------------------------------------------------------------------------------------
+    def _init_background(self, background, seed, target_channels):
+        if isinstance(background, str) and background != "random":
+            raise ValueError(f"Trainer: background {background!r}: None, (r, g, b) or 'random'")
+        if background is not None and not isinstance(background, str):
+            background = tuple(float(v) for v in background)
+            if len(background) != 3:
+                raise ValueError(f"Trainer: background {background!r}: three floats")
+        if background is not None and self.mode != "nerf":
+            raise ValueError("Trainer: a background needs mode='nerf': the compat compositor's backward is not the gradient of its "
+                             "forward, so it has no background form")
+        if background is not None and os.environ.get("RTXN_TRAIN_FUSE_COMPOSITOR", "1") == "0":
+            raise ValueError("Trainer: a background needs the fused training compositor (RTXN_TRAIN_FUSE_COMPOSITOR=0 selects the "
+                             "three-launch compositor, which has no background form)")
+        random = background == "random"
+        tc = int(target_channels) if target_channels is not None else (4 if random else 3)
+        if tc not in (3, 4) or (random and tc == 3) or (background is None and tc == 4):
+            raise ValueError(f"Trainer: target_channels = {tc} with background {background!r} (3 or 4; 'random' needs 4 (RGBA), "
+                             "RGBA needs a background)")
+        self.background, self.background_seed, self.target_channels = background, int(seed), tc
+        # RANDOM hashes the step number from a DEVICE int: this one for step(), the captured counter for step_captured(),
+        # the optimizer's own for step_entry() -- the same step number draws the same backgrounds on all three paths
+        self._bg_step = torch.zeros(1, dtype=torch.int32, device=self.dev) if random else None
+        self._bg_step_host = 0
+
+    def _bg(self, step, n_channels):
+        """api.train_background for this trainer's background, `step` the device int32 counter (None: 0 / opt.step)."""
+        if self.background is None:
+            return None
+        seed = self.background_seed
+        if _world() > 1:                        # every rank draws its own backgrounds
+            seed = (seed + 0x632BE5AB * dist.get_rank()) & 0xFFFFFFFF
+        return api.train_background(self.background, seed=seed, step=step, target_channels=n_channels)
+
+    def _target_width(self, targets, n):
+        tc = int(targets.shape[-1]) if targets.dim() == 2 and targets.shape[0] >= n else -1
+        if tc not in ((3, 4) if self.background is not None else (3,)):
+            raise ValueError(f"Trainer: targets of shape {tuple(targets.shape)} for {n} rays: [n, 3]" +
+                             (" or [n, 4] (straight RGBA)" if self.background is not None else " (RGBA targets need a background)"))
+        return tc
+
     def _det_select(self):
         api.set_deterministic(self._det_mlp, self._det_table)
 
@@ -264,8 +311,9 @@ class Trainer:
             else:
                 self.net.train_forward(self.encT, S, self.ws, self.out, self.radiance)
 
-    def render_rays(self, rays_o, rays_d, radiance_fn=None):
-        """Forward only.  radiance_fn(samples[S,5]) -> float[S,4] replaces the network (teacher rendering)."""
+    def render_rays(self, rays_o, rays_d, radiance_fn=None, background=None):
+        """Forward only.  radiance_fn(samples[S,5]) -> float[S,4] replaces the network (teacher rendering).  background: three
+        floats composited as (1 - opacity) * background (rtxn_volrender_fwd_aux), None: black."""
         n = rays_o.shape[0]
         P = self._segments(rays_o, rays_d, n)
         S = P * api.NUM_SAMPLES_PER_SEGMENT
@@ -277,8 +325,12 @@ class Trainer:
             else:
                 self.radiance[:S] = radiance_fn(self.samples[:S])
         vr = api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT
-        api.launch_volrender_cuda(None, self.radiance, self.num_stored, self.indices, self.t_vals, n,
-                                  api.NUM_SAMPLES_PER_SEGMENT, self.pixels[:n], mode=vr)
+        if background is not None:
+            api.volrender_fwd_aux(self.radiance, self.t_vals, self.num_stored, self.indices, n, api.NUM_SAMPLES_PER_SEGMENT,
+                                  self.pixels[:n], mode=vr, background=background)
+        else:
+            api.launch_volrender_cuda(None, self.radiance, self.num_stored, self.indices, self.t_vals, n,
+                                      api.NUM_SAMPLES_PER_SEGMENT, self.pixels[:n], mode=vr)
         return self.pixels[:n]
 
     def render_pipeline(self, width, height, focal_length, max_segments=None, **kw):
@@ -316,6 +368,10 @@ class Trainer:
         n = rays_o.shape[0]
         K = api.NUM_SAMPLES_PER_SEGMENT
         vr = api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT
+        bg = self._bg(self._bg_step, self._target_width(targets, n))
+        if self._bg_step is not None and self._bg_step_host != self.step_count:
+            self._bg_step.fill_(self.step_count)
+            self._bg_step_host = self.step_count
         self._det_select()
         P = self._segments(rays_o, rays_d, n)
         S = P * K
@@ -330,15 +386,23 @@ class Trainer:
                     self.dtable.zero_()
         self._dp_pending = None
         if S == 0:
-            self.loss.zero_()
+            if bg is not None:            # every pixel is its background: loss and pixels, no radiance to differentiate
+                api.volrender_l2_train_ex(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
+                                          self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg)
+            else:
+                self.loss.zero_()
             return 0
         if not self.fold_sampler:
             self._sample(n, P)
         self._forward(S, save=not self.two_pass)
         if self.mode == "nerf" and self.fuse_compositor:
             with _Stage(self, "composite_fwd+l2+bwd"):   # one launch: the backward's first sweep IS the forward
-                api.volrender_l2_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                       self.pixels[:n], self.loss_grads[:n], self.loss, self.dout)
+                if bg is not None:
+                    api.volrender_l2_train_ex(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
+                                              self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg)
+                else:
+                    api.volrender_l2_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
+                                           self.pixels[:n], self.loss_grads[:n], self.loss, self.dout)
         else:
             with _Stage(self, "composite_fwd"):
                 api.launch_volrender_cuda(None, self.radiance, self.num_stored, self.indices, self.t_vals, n, K,
@@ -602,7 +666,7 @@ class Trainer:
         self.graph_rays_o = torch.zeros((n, 3), device=d)
         self.graph_rays_d = torch.zeros((n, 3), device=d)
         self.graph_rays_d[:, 2] = 1.0
-        self.graph_targets = torch.zeros((n, 3), device=d)
+        self.graph_targets = torch.zeros((n, self.target_channels), device=d)
         self._g_n, self._g_cap, self._g_prefetch = n, cap, bool(prefetch)
         # the traversal's outputs, once per buffer set (set 0 = the trainer's own buffers)
         names = ("view_dirs", "num_hits", "indices", "num_stored", "sub_hits", "total", "start", "end", "seg_view")
@@ -614,7 +678,7 @@ class Trainer:
                 s1[k] = torch.zeros((cap,) + tuple(set0[k].shape[1:]), device=d)
             sets.append(s1)
         for st in sets:
-            st["targets"] = torch.zeros((n, 3), device=d)
+            st["targets"] = torch.zeros((n, self.target_channels), device=d)
             st["total_host"] = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._g_sets = sets
         self._g_pending = None          # prefetch: the set that holds a traversed, not yet trained batch
@@ -631,6 +695,8 @@ class Trainer:
                 break
         self._g_lr_table = torch.from_numpy(tab).to(d)
         self._g_step = torch.full((1,), self.step_count, dtype=torch.int64, device=d)
+        # RANDOM hashes the low 32-bit word of that counter (little endian), which _captured_apply advances after the gradients
+        self._g_bg = self._bg(self._g_step.view(torch.int32)[:1], self.target_channels)
         self._g_idx = torch.zeros(1, dtype=torch.int64, device=d)
         self._g_lr = torch.zeros((1, 2), device=d)
         world = _world()
@@ -731,7 +797,7 @@ class Trainer:
             self.graph_rays_o = torch.zeros((n, 3), device=d)
             self.graph_rays_d = torch.zeros((n, 3), device=d)
             self.graph_rays_d[:, 2] = 1.0
-            self.graph_targets = torch.zeros((n, 3), device=d)
+            self.graph_targets = torch.zeros((n, self.target_channels), device=d)
         self.entry_step = torch.full((1,), self.step_count, dtype=torch.int32, device=d)
         self._entry_lr = torch.zeros(1, device=d)
         hash_ = self.encoding == "hash"
@@ -752,7 +818,10 @@ class Trainer:
                                   pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss, dparams=self.dparams,
                                   dtable=self.dtable if hash_ else None,
                                   dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
-                                  live_ws=self.live_ws if self.live_segments else None, workspace_lean=self.lean)
+                                  live_ws=self.live_ws if self.live_segments else None, workspace_lean=self.lean,
+                                  target_channels=self.graph_targets.shape[1])
+        # RANDOM: step NULL = the call's own counter (entry_step) before its increment
+        self._entry_bg = self._bg(None, self.graph_targets.shape[1])
         o = a.opt
         o.mlp_master, o.mlp_params_fp16 = self.master.data_ptr(), self.params.data_ptr()
         o.mlp_m, o.mlp_v = self.adam_m.data_ptr(), self.adam_v.data_ptr()
@@ -781,7 +850,7 @@ class Trainer:
             self._clear_grads()
         if int(self.step_count) != getattr(self, "_entry_step_host", self.step_count):
             self.entry_step.fill_(self.step_count)
-        api.train_step(self._entry_args)
+        api.train_step(self._entry_args, self._entry_bg)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -822,7 +891,7 @@ class Trainer:
                             pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss, dparams=self.dparams,
                             dtable=self.dtable if hash_ else None, dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
                             live_ws=self.live_ws if self.live_segments else None, skip_table_backward=self._g_split,
-                            workspace_lean=self.lean)
+                            workspace_lean=self.lean, background=self._g_bg)
 
     def _captured_table_bwd(self, k):
         """the hash scatter of set k's batch over the live list the gradient graph left (its count is on the device)"""
@@ -1033,7 +1102,8 @@ class RayDataset:
             o, d = camera_rays(pose, focal, W, H, device=device, origin_scale=origin_scale)
             ro.append(o)
             rd.append(d)
-        pix = torch.from_numpy(np.ascontiguousarray(dataset.images, dtype=np.float32).reshape(-1, 3)).to(device)
+        ch = int(dataset.image_channels) or 3             # RTXN_LOAD_RGBA datasets keep their alpha: [N, 4]
+        pix = torch.from_numpy(np.ascontiguousarray(dataset.images, dtype=np.float32).reshape(-1, ch)).to(device)
         return cls(torch.cat(ro), torch.cat(rd), pix), focal
 
     def sample_batch(self, batch, generator=None):

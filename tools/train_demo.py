@@ -20,7 +20,14 @@ teacher_field = scenes.teacher_field   # kept under this name for the tests that
 
 
 def run(steps=300, encoding="hash", grid=32, res=64, batch=4096, n_poses=12, seed=0, verbose=True, neurons=64, layers=2,
-        hash_levels=8, hash_log2=15, hash_base=8):
+        hash_levels=8, hash_log2=15, hash_base=8, background=None, rgba=False):
+    """Returns (PSNR before, PSNR after, losses) on the held-out pose.  background=None, rgba=False: the teacher over black,
+    trained over black.  background=(r, g, b): the training targets are the teacher composited over that colour, or with
+    rgba=True its straight RGBA (colour / opacity, opacity); "random" (needs rgba): RGBA targets over a fresh background per
+    ray and step.  With a background both PSNRs are dicts {"white": dB, "black": dB}: the model against the teacher, both
+    composited over white / over black."""
+    if background == "random" and not rgba:
+        raise ValueError("train_demo.run: background='random' trains on RGBA targets (rgba=True)")
     torch.cuda.set_device(0)
     dense = scenes.sphere_density(grid, 0.72)
     occ = torch.from_numpy(scenes.pack_occupancy(dense).view(np.int32).copy()).cuda()
@@ -28,23 +35,40 @@ def run(steps=300, encoding="hash", grid=32, res=64, batch=4096, n_poses=12, see
                     per_level_scale=1.5)
     tr = Trainer(grid, occ, encoding=encoding, n_neurons=neurons, n_hidden_layers=layers, hashgrid=hashgrid,
                  batch_rays=max(batch, res * res), max_segments=max(batch, res * res) * 40, lr=1e-2 if encoding == "hash" else 2e-3,
-                 loss_scale=128.0, density_scale=150.0, mode="nerf", seed=seed)
+                 loss_scale=128.0, density_scale=150.0, mode="nerf", seed=seed, background=background,
+                 target_channels=4 if rgba else None)
+
+    def teacher(o, d):
+        """the training target of these rays"""
+        black = tr.render_rays(o, d, radiance_fn=teacher_field).clone()
+        if background is None:
+            return black
+        if not rgba:
+            return tr.render_rays(o, d, radiance_fn=teacher_field, background=background).clone()
+        # straight RGBA from the renders over black (sum w c) and over white (+ 1 - A)
+        alpha = (1.0 - (tr.render_rays(o, d, radiance_fn=teacher_field, background=(1.0, 1.0, 1.0)) - black).mean(1, keepdim=True)).clamp(0, 1)
+        rgb = torch.where(alpha > 1e-6, black / alpha.clamp_min(1e-6), torch.zeros_like(black))
+        return torch.cat([rgb, alpha], 1).contiguous()
+
     focal = scenes.lego_focal_length(True)
     rays_o, rays_d, targets = [], [], []
     for i in range(n_poses):
         la = scenes.pose_spherical(360.0 * i / n_poses, -20.0 - 25.0 * (i % 3), origin_scale=10.0)
         o, d = camera_rays(la, focal, res, res)
-        pix = tr.render_rays(o, d, radiance_fn=teacher_field).clone()
-        rays_o.append(o); rays_d.append(d); targets.append(pix)
+        rays_o.append(o); rays_d.append(d); targets.append(teacher(o, d))
     rays_o, rays_d, targets = torch.cat(rays_o), torch.cat(rays_d), torch.cat(targets)
     la_test = scenes.pose_spherical(77.0, -33.0, origin_scale=10.0)
     o_t, d_t = camera_rays(la_test, focal, res, res)
-    gt_t = tr.render_rays(o_t, d_t, radiance_fn=teacher_field).clone()
+    evals = {None: None} if background is None else {"white": (1.0, 1.0, 1.0), "black": (0.0, 0.0, 0.0)}
+    gt_t = {k: tr.render_rays(o_t, d_t, radiance_fn=teacher_field, background=b).clone() for k, b in evals.items()}
 
     def psnr():
-        pred = tr.render_rays(o_t, d_t)
-        mse = float(((pred - gt_t) ** 2).mean())
-        return 10 * np.log10(1.0 / max(mse, 1e-12))
+        out = {}
+        for k, b in evals.items():
+            pred = tr.render_rays(o_t, d_t, background=b)
+            mse = float(((pred - gt_t[k]) ** 2).mean())
+            out[k] = 10 * np.log10(1.0 / max(mse, 1e-12))
+        return out[None] if background is None else out
 
     g = torch.Generator(device="cuda").manual_seed(seed)
     p0 = psnr()
@@ -62,7 +86,9 @@ def run(steps=300, encoding="hash", grid=32, res=64, batch=4096, n_poses=12, see
     dt = time.perf_counter() - t0
     p1 = psnr()
     if verbose:
-        print(f"encoding={encoding} steps={steps} batch={batch}: PSNR {p0:.2f} -> {p1:.2f} dB; "
+        fmt = (lambda p: f"{p:.2f}") if background is None else (lambda p: " / ".join(f"{k} {v:.2f}" for k, v in p.items()))
+        print(f"encoding={encoding} steps={steps} batch={batch}{'' if background is None else f' background={background} rgba={rgba}'}: "
+              f"PSNR {fmt(p0)} -> {fmt(p1)} dB; "
               f"{steps * batch / dt / 1e6:.3f} Mrays/s trained ({1e3 * dt / steps:.2f} ms/step)")
     return p0, p1, losses
 
