@@ -644,7 +644,11 @@ int rtxn_adam_step_sparse(long n, float* master, void* params_fp16, void* grads,
  *   table_shadow: rtxn_deterministic_workspace_bytes(rtxn_hashgrid_n_params) bytes, zeroed once, or NULL (no hash grid).
  * Process-wide and read when a backward / scatter entry point is CALLED (so: baked into a captured graph); (NULL, NULL)
  * restores the default.  The folds leave the shadows zero.  Costs: 8-byte atomics in the scatter (about 2x its time) and one
- * sweep over each shadow per call.  Not covered: the reported loss sum (a float atomic; it feeds nothing back). */
+ * sweep over each shadow per call.  Not covered: the reported loss sum (a float atomic; it feeds nothing back).
+ * Range: a single contribution that is NaN, +-Inf or of magnitude >= 2^22 marks its element (a bitmap behind the sums, part of
+ * the workspace size) and the fold writes a quiet NaN there -- as the float atomics would propagate NaN / Inf.  What is NOT
+ * caught: in-range contributions whose running sum passes +-2^23 wrap around in the 64-bit integer and fold to a finite, wrong
+ * value; keep |gradient element| < 2^23 (loss scale) in this mode. */
 size_t rtxn_deterministic_workspace_bytes(long n_params);
 int rtxn_set_deterministic_workspace(void* mlp_shadow, void* table_shadow);
 

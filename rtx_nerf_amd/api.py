@@ -732,10 +732,25 @@ def deterministic_shadow(n_params, device="cuda"):
     return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
 
 
+# the shadows the library holds pointers to: kept alive here until the next set_deterministic call replaces them
+_det_registered = (None, None)
+
+
 def set_deterministic(mlp_shadow=None, table_shadow=None):
-    """rtxn_set_deterministic_workspace: process-wide; (None, None) restores the float atomics.  The caller keeps the tensors alive."""
+    """rtxn_set_deterministic_workspace: process-wide; (None, None) restores the float atomics.  The tensors stay referenced
+    here until the next call, so the library never holds a pointer into freed memory."""
+    global _det_registered
     check(_lib.lib().rtxn_set_deterministic_workspace(_ptr(mlp_shadow, torch.int64, "mlp_shadow"), _ptr(table_shadow, torch.int64, "table_shadow")),
           "rtxn_set_deterministic_workspace")
+    _det_registered = (mlp_shadow, table_shadow)
+
+
+def release_deterministic(mlp_shadow, table_shadow):
+    """Restore the float atomics (set_deterministic(None, None)) if exactly these shadows are the registered ones; otherwise
+    leave the selection alone.  What a deterministic Trainer runs when it is finalized."""
+    m, t = _det_registered
+    if m is mlp_shadow and t is table_shadow and (m is not None or t is not None):
+        set_deterministic(None, None)
 
 
 def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_points, seg_view, num_stored, indices,

@@ -79,14 +79,25 @@ constexpr long kMaxTrainSamples = (1L << 32) / 10 - kTile;
 // gradient buffer instead (value x 2^40, integer atomics: associative, so any arrival order gives the same bits) and are folded
 // back -- one rounding per element -- by det_fold_kernel behind the kernels that fed them.  What a workgroup sums on its own
 // (registers, LDS, the wave-level run sums of the scatter) has a fixed order already.  q is parallel to the float buffer `base`.
+// A contribution the fixed point cannot hold -- NaN, +-Inf, |v| >= 2^22 (float -> int64 of those has no defined result) -- sets
+// its element's bit in `bad`, the bitmap behind q (an OR: order-free too), and the fold writes NaN there: a gradient the float
+// atomics would have made non-finite, or one this mode cannot represent, never comes out finite.  What stays: in-range
+// contributions whose SUM passes +-2^23 wrap (int64 overflow) and fold to a finite wrong value.
 struct DetCtx {
   const float* base;
   long long* q;
+  unsigned long long* bad;  // [(n + 63) / 64] words at q + n
 };
 constexpr float kDetScale = 1099511627776.0f;            // 2^40: 9e-13 resolution, 8e6 range
+constexpr float kDetLimit = 4194304.0f;                  // 2^22: one contribution at most; the sum's range is 2^23
 __device__ __forceinline__ void grad_add(float* addr, float v, const DetCtx& det) {
-  if (det.q) atomicAdd(reinterpret_cast<unsigned long long*>(det.q + (addr - det.base)), (unsigned long long)__float2ll_rn(v * kDetScale));
-  else atomicAdd(addr, v);
+  if (det.q) {
+    const long i = addr - det.base;
+    if (fabsf(v) < kDetLimit) atomicAdd(reinterpret_cast<unsigned long long*>(det.q + i), (unsigned long long)__float2ll_rn(v * kDetScale));
+    else atomicOr(det.bad + (i >> 6), 1ull << (i & 63));   // NaN fails the compare as well
+  } else {
+    atomicAdd(addr, v);
+  }
 }
 
 // ------------------------------------------------------------------------- encoders
@@ -410,7 +421,7 @@ __global__ __launch_bounds__(kThreads) void hashgrid_backward_kernel(HgLevels lv
                                                                      const _Float16* __restrict__ dencT, long S, long Sp,
                                                                      float* __restrict__ dtable, _Float16* __restrict__ dtable_h,
                                                                      long hashed_lo, DevCount dc, const int* __restrict__ live_list,
-                                                                     const int* __restrict__ live_count, DetCtx det = DetCtx{nullptr, nullptr}) {
+                                                                     const int* __restrict__ live_count, DetCtx det = DetCtx{nullptr, nullptr, nullptr}) {
   static_assert(!(PK && DET), "the deterministic scatter is the fp32-shaped one");
   S = live_samples(dc, S);
   if (live_list) S = 32L * *live_count;                         // the launch walks the listed segments only
@@ -463,9 +474,12 @@ __global__ __launch_bounds__(kThreads) void hashgrid_backward_kernel(HgLevels lv
   rtxn::hg_corner_indices(g, lv.res[l], lv.size[l], hashed_level, i_lo, i_hi);
   int run_start = lane;
   bool run_last = true;
-  const unsigned k0 = ok ? (g[0] | (g[1] << 16)) : 0xffffffffu, k1 = ok ? g[2] : (unsigned)lane;
-  const unsigned p0 = (unsigned)dpp_i<0x138, 0xf>((int)k0), p1 = (unsigned)dpp_i<0x138, 0xf>((int)k1);   // wave_shr:1: lane - 1's keys
-  const bool head = lane == 0 || p0 != k0 || p1 != k1;
+  // A run = same cell: all three coordinates compared.  (Packing two into one key, g0 | g1 << 16, merged the runs of cells
+  // with g0 = -1 -- positions left of the domain -- whatever their g1, and sent their sums to the wrong entry.)  Lanes past the
+  // batch (!ok: the wave's tail) are heads, so no run of live samples ends on one of them.
+  const unsigned p0 = (unsigned)dpp_i<0x138, 0xf>((int)g[0]), p1 = (unsigned)dpp_i<0x138, 0xf>((int)g[1]),
+                 p2 = (unsigned)dpp_i<0x138, 0xf>((int)g[2]);   // wave_shr:1: lane - 1's cell
+  const bool head = lane == 0 || !ok || p0 != g[0] || p1 != g[1] || p2 != g[2];
   const bool aggregate = __ballot(head) != ~0ull;   // wave-uniform: finest levels have no runs and skip the scans
   RunSteps steps = {};
   if (aggregate) {
@@ -2709,13 +2723,21 @@ __global__ __launch_bounds__(kThreads) void adam_sparse_kernel(long n, float* __
 // travels in fp16 (tcnn keeps that gradient in fp16 to begin with), see rtx_nerf_amd/train.py
 // deterministic mode: fold the fixed-point sums into the gradient buffers they shadow (accumulate semantics, one rounding per
 // element) and clear them.  dst_h != NULL: elements from hashed_lo on live in the fp16 buffer (the hashed levels' table gradient).
+// An element marked in the bitmap behind q (see DetCtx) becomes a quiet NaN.
 __global__ __launch_bounds__(kThreads) void det_fold_kernel(long long* __restrict__ q, long n, float* __restrict__ dst, _Float16* __restrict__ dst_h,
                                                             long hashed_lo) {
+  unsigned long long* bad = reinterpret_cast<unsigned long long*>(q + n);
   for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
     const long long v = q[i];
-    if (v == 0) continue;
+    const unsigned long long bit = 1ull << (i & 63);
+    const bool poisoned = (bad[i >> 6] & bit) != 0;
+    if (v == 0 && !poisoned) continue;
     q[i] = 0;
-    const float g = (float)((double)v * (1.0 / (double)kDetScale));
+    float g = (float)((double)v * (1.0 / (double)kDetScale));
+    if (poisoned) {
+      atomicAnd(bad + (i >> 6), ~bit);                     // the word's other bits belong to other lanes
+      g = __builtin_nanf("");
+    }
     if (dst_h && i >= hashed_lo) dst_h[i - hashed_lo] = (_Float16)((float)dst_h[i - hashed_lo] + g);
     else dst[i] += g;
   }
@@ -2757,9 +2779,9 @@ int check_train(const rtxn_mlp* m, const char* who) {
 // deterministic mode: the fixed-point shadows the caller registered (rtxn_set_deterministic_workspace), or NULL
 std::atomic<long long*> g_det_mlp{nullptr}, g_det_table{nullptr};
 
-DetCtx det_ctx(const float* base, std::atomic<long long*>& slot) {
+DetCtx det_ctx(const float* base, long n, std::atomic<long long*>& slot) {
   long long* q = slot.load(std::memory_order_relaxed);
-  return DetCtx{q ? base : nullptr, q};
+  return DetCtx{q ? base : nullptr, q, q ? reinterpret_cast<unsigned long long*>(q + n) : nullptr};
 }
 
 int det_fold(long long* q, long n, float* dst, void* dst_half, long hashed_lo, hipStream_t s) {
@@ -2773,7 +2795,10 @@ int det_fold(long long* q, long n, float* dst, void* dst_half, long hashed_lo, h
 }  // namespace
 
 // ============================================================================ C ABI
-extern "C" size_t rtxn_deterministic_workspace_bytes(long n_params) { return n_params < 0 ? 0 : (size_t)n_params * sizeof(long long); }
+// n_params fixed-point sums, then one bit per element: the out-of-range / non-finite marks (DetCtx)
+extern "C" size_t rtxn_deterministic_workspace_bytes(long n_params) {
+  return n_params < 0 ? 0 : (size_t)(n_params + (n_params + 63) / 64) * sizeof(long long);
+}
 
 extern "C" int rtxn_set_deterministic_workspace(void* mlp_shadow, void* table_shadow) {
   RTXN_REQUIRE((((uintptr_t)mlp_shadow | (uintptr_t)table_shadow) & 7) == 0, "rtxn_set_deterministic_workspace: shadows must be 8-byte aligned");
@@ -3000,7 +3025,7 @@ static int train_backward_impl(const rtxn_mlp* m, const void* encT, const void* 
   // weight gradients of all layers in one launch: dW_l += dZ_l X_l^T, X_0 = enc, X_l = acts[l-1], X_L = acts[L-1]
   RTXN_REQUIRE(L + 1 <= 17, "rtxn_mlp_train_backward: %d layers exceed the weight-gradient launch table", L + 1);
   WgradArgs wa;
-  wa.det = det_ctx(dparams, g_det_mlp);
+  wa.det = det_ctx(dparams, m->n_params, g_det_mlp);
   wa.Sp = Sp;
   wa.dc = dc;
   wa.live_tiles = a.live_tiles;
@@ -3111,7 +3136,7 @@ static int train_backward_lean_impl(const rtxn_mlp* m, const void* encT, const v
   la.live_tiles = a.live_tiles;
   la.live_list = live_list;
   la.live_count = live_count;
-  la.det = det_ctx(dparams, g_det_mlp);
+  la.det = det_ctx(dparams, m->n_params, g_det_mlp);
   if (src) la.src = *src;
   la.packed_bwd = static_cast<const uint8_t*>(m->packed_t);
   int dev = 0, n_cu = 0;
@@ -3289,7 +3314,7 @@ static int train_backward_recompute_impl(const rtxn_mlp* m, const void* encT, co
   a.dparams = dparams;
   a.live_list = live_list;
   a.live_count = live_count;
-  a.det = det_ctx(dparams, g_det_mlp);
+  a.det = det_ctx(dparams, m->n_params, g_det_mlp);
   const int RT = 2, KS = 4;
   const size_t lds = (size_t)(a.KS0 * RT + (L - 1) * KS * RT) * 1024 + (size_t)(RT + (L - 1) * RT * KS + ((E + 31) / 32) * KS) * 1024 +
                      8 * (size_t)kImgBytes;
@@ -3659,7 +3684,7 @@ static int hashgrid_backward_impl(const rtxn_hashgrid* g, const SampleSrc& input
   const HgLevels lv = levels_of(g);
   const _Float16* de = static_cast<const _Float16*>(dencT);
   const unsigned sblocks = (unsigned)((n_samples + kThreads - 1) / kThreads);
-  const DetCtx det = det_ctx(dtable, g_det_table);
+  const DetCtx det = det_ctx(dtable, g->n_params, g_det_table);
   if (det.q) {
     // deterministic: every level as fp32-shaped contributions into the fixed-point shadow, then one fold into dtable / dtable_h
     hashgrid_backward_kernel<false, true><<<dim3(sblocks, (unsigned)NL), kThreads, 0, st>>>(

@@ -22,6 +22,7 @@ torch only owns buffers and a few trivial elementwise glue ops.
 import json
 import os
 import struct
+import weakref
 
 import numpy as np
 import torch
@@ -194,6 +195,11 @@ class Trainer:
         self._det_mlp = api.deterministic_shadow(self.master.numel(), device=d) if self.deterministic else None
         self._det_table = (api.deterministic_shadow(self.table_master.numel(), device=d)
                            if (self.deterministic and encoding == "hash") else None)
+        # A trainer collected while its shadows are still the registered ones switches the library back to the float atomics:
+        # direct backward calls made afterwards (Network.train_backward*, HashGrid.backward*, api.train_gradients) run in
+        # default mode, not into this trainer's shadows.
+        if self.deterministic:
+            weakref.finalize(self, api.release_deterministic, self._det_mlp, self._det_table).atexit = False
 
     # ------------------------------------------------------------------------------------------
     def _init_background(self, background, seed, target_channels):
@@ -237,6 +243,8 @@ class Trainer:
         return tc
 
     def _det_select(self):
+        """Register this trainer's shadows (deterministic) or none.  They stay registered after the step: a direct backward call
+        that follows runs deterministically into them while this trainer lives, and in default mode once it is collected."""
         api.set_deterministic(self._det_mlp, self._det_table)
 
     def _segments(self, rays_o, rays_d, n):
@@ -350,7 +358,6 @@ class Trainer:
             kw.update(hashgrid=self.hg, table=self.table)
         pipe = render.RenderPipeline(self.net, self.R, width, height, focal_length, occupancy=self.occ, max_segments=max_segments,
                                      vr_mode=api.VR_NERF if nerf else api.VR_COMPAT, step_scale=self.density_scale if nerf else 1.0, **kw)
-        import weakref
         self._pipelines = [r for r in getattr(self, "_pipelines", []) if r() is not None] + [weakref.ref(pipe)]
         return pipe
 
