@@ -8,6 +8,14 @@ Stated bars (the oracle itself is "parity unpinned", see its header):
   volrender  forward 1e-5 abs (wave scan sums in a different order; device expf);
              backward: fp16 outputs within 1 fp16 ulp (device expf vs glibc)
   MLP        fp16 sigmoid outputs within 1e-2 abs, mean abs error < 1e-3 (MFMA summation order)
+
+The traversal's empty-space skip has a file of its own, tests/test_gpu_trace_hierarchy.py: every level combination
+(coarse, super, bricks), sub_rays 0/2/8/64 in the strided and the packed layout, explicit, lattice, grazing, inside and
+windowed rays, bit-exact against the oracle's flat walk.  Its grid sizes follow the two LDS stages of trace_kernel:
+the coarse mip is staged while ceil((R/4)^3/32) <= kCoarseLdsWords = 8192 words (R <= 256), the super mip while
+ceil((R/16)^3/32) <= kSuperLdsWords = 512 words (R <= 400, 489 words); R = 272..400 reads the coarse mip from
+global memory beside a staged super mip, R >= 416 reads both from global memory.  The mip, brick and
+density->occupancy builders are compared with plain numpy reductions there as well.
 """
 import numpy as np
 import pytest
@@ -43,7 +51,8 @@ def test_scan_hits(gpu, oracle, n):
 
 # ------------------------------------------------------------------ traversal
 def _trace_gpu(torch, api, *, R, mode, look_at=None, f=1.0, W=0, H=0, rays_o=None, rays_d=None, occ=None,
-               coarse=None, ray_begin=0, ray_count=None, S=None, bricks=None):
+               coarse=None, ray_begin=0, ray_count=None, S=None, bricks=None, occupancy_super=None, sub_rays=0, sub_hits=None,
+               window_chunk=0, window_stride=0):
     n_all = W * H if look_at is not None else rays_o.shape[0]
     n = n_all - ray_begin if ray_count is None else ray_count
     S = 3 * R if S is None else S
@@ -58,7 +67,8 @@ def _trace_gpu(torch, api, *, R, mode, look_at=None, f=1.0, W=0, H=0, rays_o=Non
                    ray_begin=ray_begin, ray_count=n, occupancy=occ, occupancy_coarse=coarse, occupancy_bricks=bricks, mode=mode,
                    ray_origins=out["origins"], viewing_direction=out["view_dirs"], num_hits=out["num_hits"],
                    intersection_arr_size=S, start_points=out["start"], end_points=out["end"],
-                   t_start=out["t_start"], t_end=out["t_end"])
+                   t_start=out["t_start"], t_end=out["t_end"], occupancy_super=occupancy_super, sub_rays=sub_rays, sub_hits=sub_hits,
+                   window_chunk=window_chunk, window_stride=window_stride)
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in out.items()}
 

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Fuzz the traversal kernel against the oracle: random poses, grid sizes, occupancies and modes; every
-num_hits / start / end / t must match bit for bit (theta/phi to 2e-6).  python tools/fuzz_trace.py [--iters 200]"""
+num_hits / start / end / t must match bit for bit (theta/phi to 2e-6).  Grid sizes include 272, 320 and 416, where the
+coarse and then the super mip are read from global memory instead of LDS, and a third of the cases take explicit rays
+(random, zero-component, lattice, grazing) and occupancies from the generators the test suite uses (tools/_trace_cases.py).
+python tools/fuzz_trace.py [--iters 200]"""
 import argparse
 import os
 import sys
@@ -12,6 +15,8 @@ import torch
 import oracle as O
 from rtx_nerf_amd import api, scenes
 
+import _trace_cases as TC
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=200)
 ap.add_argument("--seed", type=int, default=0)
@@ -20,7 +25,7 @@ rng = np.random.default_rng(a.seed)
 torch.cuda.set_device(0)
 bad = 0
 for it in range(a.iters):
-    R = int(rng.choice([4, 8, 12, 16, 20, 32, 48, 64, 100, 128]))
+    R = int(rng.choice([4, 8, 12, 16, 20, 32, 48, 64, 100, 128, 272, 320, 416]))
     W, H = int(rng.integers(8, 64)), int(rng.integers(8, 64))
     mode = int(rng.integers(0, 2))
     la = scenes.pose_spherical(rng.uniform(0, 360), rng.uniform(-89, 20), radius=rng.uniform(0.2, 6.0), origin_scale=10.0)
@@ -29,16 +34,26 @@ for it in range(a.iters):
     f = float(rng.uniform(0.5, 4.0))
     dense = None
     words = None
+    explicit = None
+    if rng.random() < 0.33:      # explicit rays from the shared generators: exact plane ties at block boundaries of every level
+        explicit = TC.rays(str(rng.choice(["random", "zero_comp", "lattice", "grazing"])), R, seed=a.seed * 100003 + it)
     r = rng.random()
-    if r < 0.6:
+    if R > 128 or (explicit is not None and r < 0.5):   # the shared occupancy families (no float64 R^3 temporaries at 416^3)
+        fam = [f for f in TC.OCC_FAMILIES if (f != "lego" or R <= 128) and f != "zeros"]
+        dense = TC.occupancy(str(rng.choice(fam)), R, int(rng.integers(0, 4)))[0]
+    elif r < 0.6:
         dense = rng.random((R, R, R)) < rng.uniform(0.0, 0.3)
     elif r < 0.8:
         dense = scenes.sphere_density(R, rng.uniform(0.2, 0.9))
     if dense is not None:
-        words = scenes.pack_occupancy(dense)
+        words = TC.pack_words(dense)
     use_coarse = dense is not None and mode == 1 and R % 4 == 0 and rng.random() < 0.7
     S = 3 * R
-    want = O.trace(look_at=la, focal=f, aspect=W / H, W=W, H=H, R=R, occ=words, mode=mode, S=S)
+    if explicit is not None:
+        W, H = explicit["rays_o"].shape[0], 1
+        want = O.trace(rays_o=explicit["rays_o"], rays_d=explicit["rays_d"], R=R, occ=words, mode=mode, S=S)
+    else:
+        want = O.trace(look_at=la, focal=f, aspect=W / H, W=W, H=H, R=R, occ=words, mode=mode, S=S)
     n = W * H
     occ = None if words is None else torch.from_numpy(words.view(np.int32).copy()).cuda()
     coarse = api.build_occupancy_mip(occ, R) if use_coarse else None
@@ -54,9 +69,13 @@ for it in range(a.iters):
     # sub-ray walk (DDA only): Q lanes per ray, counting pass first (it fills sub_hits), then the write pass
     Q = int(rng.choice([1, 1, 2, 4, 8, 16, 32, 64])) if mode == 1 else 1
     sub = torch.zeros(n * Q, dtype=torch.int32, device="cuda") if Q > 1 else None
-    la_d = torch.from_numpy(la.reshape(16)).cuda()
+    la_d = None if explicit is not None else torch.from_numpy(la.reshape(16)).cuda()
+    if explicit is not None:
+        common_rays = dict(rays_o=torch.from_numpy(explicit["rays_o"]).cuda(), rays_d=torch.from_numpy(explicit["rays_d"]).cuda())
+    else:
+        common_rays = {}
     common = dict(grid_res=R, occupancy=occ, occupancy_coarse=coarse, occupancy_bricks=bricks, occupancy_super=sup, mode=mode,
-                  num_hits=nh, intersection_arr_size=S, sub_rays=Q, sub_hits=sub)
+                  num_hits=nh, intersection_arr_size=S, sub_rays=Q, sub_hits=sub, **common_rays)
     if Q > 1:
         api.trace_grid(la_d, f, W / H, W, H, **common)
         assert np.array_equal(nh.cpu().numpy(), want["num_hits"]), "counting pass"
@@ -72,7 +91,7 @@ for it in range(a.iters):
     if not ok:
         bad += 1
         d = np.nonzero(nh.cpu().numpy() != want["num_hits"])[0]
-        print(f"MISMATCH it={it} Q={Q} R={R} {W}x{H} mode={mode} occ={'none' if words is None else 'yes'} coarse={use_coarse} "
+        print(f"MISMATCH it={it} Q={Q} R={R} {W}x{H} {'explicit rays' if explicit is not None else 'pinhole'} mode={mode} occ={'none' if words is None else 'yes'} coarse={use_coarse} "
               f"rays with different num_hits: {d[:8]}", flush=True)
         for name, g_, w_ in (("start", sp, want["start"]), ("end", ep, want["end"]), ("t_start", t0, want["t_start"]),
                              ("t_end", t1, want["t_end"]), ("origins", og, want["origins"]), ("view", vd, want["view_dirs"])):
@@ -83,7 +102,10 @@ for it in range(a.iters):
                 print(f"   {name}: {len(neq[0])} differing entries; first at {k}: gpu {gg[k]} oracle {w_[k]}", flush=True)
                 if name in ("start", "end", "t_start", "t_end"):
                     ray = k // S
-                    o_, d_, v_ = O.make_ray(la, f, W / H, W, H, ray % W, ray // W)
+                    if explicit is not None:
+                        o_, d_ = explicit["rays_o"][ray], explicit["rays_d"][ray]
+                    else:
+                        o_, d_, v_ = O.make_ray(la, f, W / H, W, H, ray % W, ray // W)
                     print(f"   ray {ray}: o={o_} d={d_} nh={want['num_hits'][ray]} slot={k % S}", flush=True)
 print(f"fuzz_trace: {a.iters} cases, {bad} mismatches")
 sys.exit(1 if bad else 0)
