@@ -19,6 +19,8 @@
 // the 1e-5 absolute tolerance on pixels stated in tests/.
 // RTXN_VR_NERF is the canonical quadrature (exclusive transmittance, ray_hit
 // holds each sample's world-space step length) with its exact gradient.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -30,7 +32,7 @@ template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_term(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
 }
-__device__ __forceinline__ float wave_incl_scan_f(float v, int /*lane*/) {
+__device__ __forceinline__ float wave_incl_scan_f(float v) {
   v += dpp_term<0x111, 0xf>(v);
   v += dpp_term<0x112, 0xf>(v);
   v += dpp_term<0x114, 0xf>(v);
@@ -46,7 +48,7 @@ __device__ __forceinline__ float lane63(float v) {
 // Sum over the wave, returned in every lane: the DPP inclusive scan above leaves the total in lane 63, read back as a scalar
 // (six VALU adds + v_readlane; the __shfl_xor butterfly was six dependent ds_swizzle / ds_bpermute round trips, three times
 // per ray in the compositors).
-__device__ __forceinline__ float wave_sum(float v) { return lane63(wave_incl_scan_f(v, 0)); }
+__device__ __forceinline__ float wave_sum(float v) { return lane63(wave_incl_scan_f(v)); }
 // lane - 1's value (lane 0: 0): DPP wave_shr:1
 __device__ __forceinline__ float lane_below(float v) { return dpp_term<0x138, 0xf>(v); }
 
@@ -54,27 +56,48 @@ struct alignas(8) half4 {
   __half x, y, z, w;
 };
 
+// Colour, opacity A = sum w_i and expected depth sum w_i d_i in one pass (rtxn_volrender_fwd_aux): the forward kernels with two
+// more accumulators.  One-sample schedule: ONE body, fwd_body<MODE, COMPACT, AUX>, instantiated by volrender_fwd_kernel
+// (AUX = false) and volrender_aux_kernel (AUX = true); everything the extended form adds sits under `if constexpr (AUX)`, so
+// with a zero background the pixels are bit-identical by construction.  Pair schedule: volrender_aux_pair_kernel is still a
+// copy of volrender_fwd_pair_kernel with the additions written in, weights and colour accumulation operation for operation
+// (a body that is inlined into a kernel is optimised once on its own and once more inside the kernel, and for the pair and
+// the training kernels that second round changes the code of the plain kernel, whose measurements are keyed on its bytes:
+// DESIGN 5.5).  tests/test_compositor_isa.py pins the machine code of every kernel here.
+// d_i = t_start_j + u_i (t_end_j - t_start_j) is the distance at which sample i of segment j
+// was evaluated: u_i = (i + u0) / K (u0 = 0 REGULAR, 0.5 MIDPOINT_WORLD); t_start / t_end (one float each per segment, 8 B per
+// K samples) are read only when depth is requested.  The background is added per channel where it is non-zero:
+// pixel += (1 - A) bg (no 0 * x term, which would turn a -0.0 pixel into +0.0).
+struct AuxArgs {
+  const float* t_start;
+  const float* t_end;
+  float u0;
+  float bg[3];
+  float* depth;     // may be NULL
+  float* opacity;   // may be NULL
+};
+
 // COMPACT: radiance is half[N][4] (the network's own output, 8 B/sample instead of 16) and per-sample t_vals are not read at
 // all.  RTXN_VR_COMPAT: REGULAR sampling makes them the function (i + 1) / K of the sample index (sampler.cu:52-66);
 // RTXN_VR_NERF: every sample of a segment has the same world-space step, so `ray_hit` is one float per SEGMENT (4 B per K
 // samples).  Same arithmetic from there on, so the pixels are bit-identical to the float4 + t_vals form at 40 % of its bytes.
-template <int MODE, bool COMPACT = false>
-__global__ __launch_bounds__(256) void volrender_fwd_kernel(const float4* __restrict__ radiance,
-                                                            const int* __restrict__ num_hits,
-                                                            const int* __restrict__ indices,
-                                                            const float* __restrict__ ray_hit, int batch_size, int K,
-                                                            float* __restrict__ pixels) {
+template <int MODE, bool COMPACT, bool AUX>
+__device__ __forceinline__ void fwd_body(const float4* __restrict__ radiance, const int* __restrict__ num_hits,
+                                         const int* __restrict__ indices, const float* __restrict__ ray_hit, int batch_size, int K,
+                                         float* __restrict__ pixels, const AuxArgs& aux) {
   const int lane = threadIdx.x & 63;
   const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (ray >= batch_size) return;
-  const long base = (long)indices[ray] * K;
+  const long seg = indices[ray];
+  const long base = seg * K;
   const long n = (long)num_hits[ray] * K;
+  const bool want_depth = AUX && aux.depth != nullptr;
   float T_carry = 0.0f, t_carry = 0.0f;
-  float ar = 0.0f, ag = 0.0f, ab = 0.0f;
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f, ad = 0.0f;   // aw, ad: AUX only
   for (long s0 = 0; s0 < n; s0 += 64) {
     const bool act = s0 + lane < n;
     float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    float t = 0.0f;
+    float t = 0.0f, d = 0.0f;
     if (act) {
       if (COMPACT) {
         const half4 c16 = reinterpret_cast<const half4*>(radiance)[base + s0 + lane];
@@ -85,6 +108,13 @@ __global__ __launch_bounds__(256) void volrender_fwd_kernel(const float4* __rest
         c = radiance[base + s0 + lane];
         t = ray_hit[base + s0 + lane];
       }
+      if constexpr (AUX) {
+        if (want_depth) {
+          const long j = seg + (s0 + lane) / K;
+          const float ts = aux.t_start[j], te = aux.t_end[j];
+          d = fmaf(((float)((s0 + lane) % K) + aux.u0) * (1.0f / (float)K), te - ts, ts);
+        }
+      }
     }
     float x, w;
     if (MODE == RTXN_VR_COMPAT) {
@@ -92,14 +122,14 @@ __global__ __launch_bounds__(256) void volrender_fwd_kernel(const float4* __rest
       if (lane == 0) tp = t_carry;
       const float delta = fabsf(t - tp);
       x = act ? delta * c.w : 0.0f;
-      const float T = T_carry + wave_incl_scan_f(x, lane);
+      const float T = T_carry + wave_incl_scan_f(x);
       w = act ? expf(-T) * (1.0f - expf(-x)) : 0.0f;
       T_carry = lane63(T);
       // last ACTIVE lane's t carries over; inactive lanes only occur in the final step
       t_carry = lane63(t);
     } else {
       x = act ? t * c.w : 0.0f;  // ray_hit = step length
-      const float incl = wave_incl_scan_f(x, lane);
+      const float incl = wave_incl_scan_f(x);
       const float T_excl = T_carry + incl - x;
       w = act ? expf(-T_excl) * (1.0f - expf(-x)) : 0.0f;
       T_carry += lane63(incl);
@@ -107,15 +137,49 @@ __global__ __launch_bounds__(256) void volrender_fwd_kernel(const float4* __rest
     ar = fmaf(w, c.x, ar);
     ag = fmaf(w, c.y, ag);
     ab = fmaf(w, c.z, ab);
+    if constexpr (AUX) {
+      aw += w;
+      ad = fmaf(w, d, ad);
+    }
   }
   ar = wave_sum(ar);
   ag = wave_sum(ag);
   ab = wave_sum(ab);
+  if constexpr (AUX) {
+    aw = wave_sum(aw);
+    if (want_depth) ad = wave_sum(ad);
+  }
   if (lane == 0) {
+    if constexpr (AUX) {
+      const float rest = 1.0f - aw;
+      if (aux.bg[0] != 0.0f) ar = fmaf(rest, aux.bg[0], ar);
+      if (aux.bg[1] != 0.0f) ag = fmaf(rest, aux.bg[1], ag);
+      if (aux.bg[2] != 0.0f) ab = fmaf(rest, aux.bg[2], ab);
+    }
     pixels[3 * (long)ray] = ar;
     pixels[3 * (long)ray + 1] = ag;
     pixels[3 * (long)ray + 2] = ab;
+    if constexpr (AUX) {
+      if (aux.opacity) aux.opacity[ray] = aw;
+      if (want_depth) aux.depth[ray] = ad;
+    }
   }
+}
+template <int MODE, bool COMPACT = false>
+__global__ __launch_bounds__(256) void volrender_fwd_kernel(const float4* __restrict__ radiance,
+                                                            const int* __restrict__ num_hits,
+                                                            const int* __restrict__ indices,
+                                                            const float* __restrict__ ray_hit, int batch_size, int K,
+                                                            float* __restrict__ pixels) {
+  fwd_body<MODE, COMPACT, false>(radiance, num_hits, indices, ray_hit, batch_size, K, pixels, AuxArgs{});
+}
+template <int MODE, bool COMPACT>
+__global__ __launch_bounds__(256) void volrender_aux_kernel(const float4* __restrict__ radiance,
+                                                            const int* __restrict__ num_hits,
+                                                            const int* __restrict__ indices,
+                                                            const float* __restrict__ ray_hit, int batch_size, int K,
+                                                            float* __restrict__ pixels, AuxArgs aux) {
+  fwd_body<MODE, COMPACT, true>(radiance, num_hits, indices, ray_hit, batch_size, K, pixels, aux);
 }
 
 // Two samples per lane, 128 per step, and the next step's loads in flight while this step is scanned.  The one-sample form
@@ -205,7 +269,7 @@ __global__ __launch_bounds__(256) void volrender_fwd_pair_kernel(const float4* _
         x0 = act ? fabsf(cur.t0 - tp) * cur.c0.w : 0.0f;
         x1 = act ? fabsf(cur.t1 - cur.t0) * cur.c1.w : 0.0f;
         const float pr = x0 + x1;
-        const float T0 = (T_carry + (wave_incl_scan_f(pr, lane) - pr)) + x0;   // inclusive optical depth at sample 0 of the pair
+        const float T0 = (T_carry + (wave_incl_scan_f(pr) - pr)) + x0;   // inclusive optical depth at sample 0 of the pair
         const float T1 = T0 + x1;
         // three hardware exponentials per pair (v_exp_f32 on x log2 e; exp(-T1) = exp(-T0) exp(-x1)) instead of four libm
         // expf of ~12 instructions each: the compact form of this kernel is bound by its instruction count, not by HBM
@@ -218,7 +282,7 @@ __global__ __launch_bounds__(256) void volrender_fwd_pair_kernel(const float4* _
         x0 = act ? cur.t0 * cur.c0.w : 0.0f;          // ray_hit = step length
         x1 = act ? cur.t1 * cur.c1.w : 0.0f;
         const float pr = x0 + x1;
-        const float incl = wave_incl_scan_f(pr, lane);
+        const float incl = wave_incl_scan_f(pr);
         const float T0 = T_carry + (incl - pr);       // exclusive transmittance exponent of sample 0
         const float e0 = __expf(-T0), ex0 = __expf(-x0), ex1 = __expf(-x1);
         w0 = act ? e0 * (1.0f - ex0) : 0.0f;
@@ -321,7 +385,7 @@ __global__ __launch_bounds__(256) void volrender_bwd_nerf_kernel(const __half* _
       d = step_len[base + s0 + lane];
     }
     const float x = d * c.w;
-    const float incl = wave_incl_scan_f(x, lane);
+    const float incl = wave_incl_scan_f(x);
     const float w = expf(-(T_carry + incl - x)) * (1.0f - expf(-x));
     S += w * (g0 * c.x + g1 * c.y + g2 * c.z);
     T_carry += lane63(incl);
@@ -339,13 +403,13 @@ __global__ __launch_bounds__(256) void volrender_bwd_nerf_kernel(const __half* _
       d = step_len[base + s0 + lane];
     }
     const float x = d * c.w;
-    const float incl = wave_incl_scan_f(x, lane);
+    const float incl = wave_incl_scan_f(x);
     const float Ti = expf(-(T_carry + incl - x));
     const float ex = expf(-x);
     const float a = 1.0f - ex;
     const float gc = g0 * c.x + g1 * c.y + g2 * c.z;
     const float wgc = Ti * a * gc;
-    const float pincl = P_carry + wave_incl_scan_f(wgc, lane);
+    const float pincl = P_carry + wave_incl_scan_f(wgc);
     if (act) {
       const float suffix = S - pincl;
       half4 o;
@@ -390,7 +454,7 @@ __global__ __launch_bounds__(256) void volrender_l2_fused_kernel(const float4* _
       d = step_len[base + s0 + lane];
     }
     const float x = d * c.w;
-    const float incl = wave_incl_scan_f(x, lane);
+    const float incl = wave_incl_scan_f(x);
     const float w = act ? expf(-(T_carry + incl - x)) * (1.0f - expf(-x)) : 0.0f;
     ar = fmaf(w, c.x, ar);
     ag = fmaf(w, c.y, ag);
@@ -429,13 +493,13 @@ __global__ __launch_bounds__(256) void volrender_l2_fused_kernel(const float4* _
       d = step_len[base + s0 + lane];
     }
     const float x = d * c.w;
-    const float incl = wave_incl_scan_f(x, lane);
+    const float incl = wave_incl_scan_f(x);
     const float Ti = expf(-(T_carry + incl - x));
     const float ex = expf(-x);
     const float a = 1.0f - ex;
     const float gc = g0 * c.x + g1 * c.y + g2 * c.z;
     const float wgc = Ti * a * gc;
-    const float pincl = P_carry + wave_incl_scan_f(wgc, lane);
+    const float pincl = P_carry + wave_incl_scan_f(wgc);
     if (act) {
       const float suffix = S - pincl;
       half4 o;
@@ -500,7 +564,7 @@ __global__ __launch_bounds__(256) void volrender_l2_fused_multi_kernel(const flo
         x0[u] = cur[u].d0 * cur[u].c0.w;                 // inactive lanes hold zeros: x = 0, w = 0
         x1[u] = cur[u].d1 * cur[u].c1.w;
         pr[u] = x0[u] + x1[u];
-        incl[u] = wave_incl_scan_f(pr[u], lane);
+        incl[u] = wave_incl_scan_f(pr[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -552,7 +616,7 @@ __global__ __launch_bounds__(256) void volrender_l2_fused_multi_kernel(const flo
         x0[u] = cur[u].d0 * cur[u].c0.w;
         x1[u] = cur[u].d1 * cur[u].c1.w;
         pr[u] = x0[u] + x1[u];
-        incl[u] = wave_incl_scan_f(pr[u], lane);
+        incl[u] = wave_incl_scan_f(pr[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -570,7 +634,7 @@ __global__ __launch_bounds__(256) void volrender_l2_fused_multi_kernel(const flo
         gc1[u] = g0 * cur[u].c1.x + g1 * cur[u].c1.y + g2 * cur[u].c1.z;
         const float wgc0 = Ti0[u] * (1.0f - ex0[u]) * gc0[u];
         wgc1[u] = Ti1[u] * (1.0f - ex1[u]) * gc1[u];
-        pin[u] = wave_incl_scan_f(wgc0 + wgc1[u], lane);
+        pin[u] = wave_incl_scan_f(wgc0 + wgc1[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -605,98 +669,6 @@ __global__ __launch_bounds__(256) void volrender_l2_fused_multi_kernel(const flo
     if (lane == 0) red[wave] = loss_part;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(loss_sum, (red[0] + red[1]) + (red[2] + red[3]));
-  }
-}
-
-// Colour, opacity A = sum w_i and expected depth sum w_i d_i in one pass (rtxn_volrender_fwd_aux): the two forward kernels
-// above with two more accumulators, as separate instantiations so that the plain kernels keep their machine code.  The
-// weights and the colour accumulation are those kernels' own, operation for operation, so with a zero background the pixels
-// are bit-identical to theirs.  d_i = t_start_j + u_i (t_end_j - t_start_j) is the distance at which sample i of segment j
-// was evaluated: u_i = (i + u0) / K (u0 = 0 REGULAR, 0.5 MIDPOINT_WORLD); t_start / t_end (one float each per segment, 8 B per
-// K samples) are read only when depth is requested.  The background is added per channel where it is non-zero:
-// pixel += (1 - A) bg (no 0 * x term, which would turn a -0.0 pixel into +0.0).
-struct AuxArgs {
-  const float* t_start;
-  const float* t_end;
-  float u0;
-  float bg[3];
-  float* depth;     // may be NULL
-  float* opacity;   // may be NULL
-};
-
-template <int MODE, bool COMPACT>
-__global__ __launch_bounds__(256) void volrender_aux_kernel(const float4* __restrict__ radiance,
-                                                            const int* __restrict__ num_hits,
-                                                            const int* __restrict__ indices,
-                                                            const float* __restrict__ ray_hit, int batch_size, int K,
-                                                            float* __restrict__ pixels, AuxArgs aux) {
-  const int lane = threadIdx.x & 63;
-  const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (ray >= batch_size) return;
-  const long seg = indices[ray];
-  const long base = seg * K;
-  const long n = (long)num_hits[ray] * K;
-  const bool want_depth = aux.depth != nullptr;
-  float T_carry = 0.0f, t_carry = 0.0f;
-  float ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f, ad = 0.0f;
-  for (long s0 = 0; s0 < n; s0 += 64) {
-    const bool act = s0 + lane < n;
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    float t = 0.0f, d = 0.0f;
-    if (act) {
-      if (COMPACT) {
-        const half4 c16 = reinterpret_cast<const half4*>(radiance)[base + s0 + lane];
-        c = make_float4(__half2float(c16.x), __half2float(c16.y), __half2float(c16.z), __half2float(c16.w));
-        if (MODE == RTXN_VR_COMPAT) t = (float)((int)((s0 + lane) % K) + 1) * (1.0f / (float)K);
-        else t = ray_hit[(base + s0 + lane) / K];
-      } else {
-        c = radiance[base + s0 + lane];
-        t = ray_hit[base + s0 + lane];
-      }
-      if (want_depth) {
-        const long j = seg + (s0 + lane) / K;
-        const float ts = aux.t_start[j], te = aux.t_end[j];
-        d = fmaf(((float)((s0 + lane) % K) + aux.u0) * (1.0f / (float)K), te - ts, ts);
-      }
-    }
-    float x, w;
-    if (MODE == RTXN_VR_COMPAT) {
-      float tp = lane_below(t);
-      if (lane == 0) tp = t_carry;
-      const float delta = fabsf(t - tp);
-      x = act ? delta * c.w : 0.0f;
-      const float T = T_carry + wave_incl_scan_f(x, lane);
-      w = act ? expf(-T) * (1.0f - expf(-x)) : 0.0f;
-      T_carry = lane63(T);
-      t_carry = lane63(t);
-    } else {
-      x = act ? t * c.w : 0.0f;
-      const float incl = wave_incl_scan_f(x, lane);
-      const float T_excl = T_carry + incl - x;
-      w = act ? expf(-T_excl) * (1.0f - expf(-x)) : 0.0f;
-      T_carry += lane63(incl);
-    }
-    ar = fmaf(w, c.x, ar);
-    ag = fmaf(w, c.y, ag);
-    ab = fmaf(w, c.z, ab);
-    aw += w;
-    ad = fmaf(w, d, ad);
-  }
-  ar = wave_sum(ar);
-  ag = wave_sum(ag);
-  ab = wave_sum(ab);
-  aw = wave_sum(aw);
-  if (want_depth) ad = wave_sum(ad);
-  if (lane == 0) {
-    const float rest = 1.0f - aw;
-    if (aux.bg[0] != 0.0f) ar = fmaf(rest, aux.bg[0], ar);
-    if (aux.bg[1] != 0.0f) ag = fmaf(rest, aux.bg[1], ag);
-    if (aux.bg[2] != 0.0f) ab = fmaf(rest, aux.bg[2], ab);
-    pixels[3 * (long)ray] = ar;
-    pixels[3 * (long)ray + 1] = ag;
-    pixels[3 * (long)ray + 2] = ab;
-    if (aux.opacity) aux.opacity[ray] = aw;
-    if (want_depth) aux.depth[ray] = ad;
   }
 }
 
@@ -781,7 +753,7 @@ __global__ __launch_bounds__(256) void volrender_aux_pair_kernel(const float4* _
         x0 = act ? fabsf(cur.t0 - tp) * cur.c0.w : 0.0f;
         x1 = act ? fabsf(cur.t1 - cur.t0) * cur.c1.w : 0.0f;
         const float pr = x0 + x1;
-        const float T0 = (T_carry + (wave_incl_scan_f(pr, lane) - pr)) + x0;
+        const float T0 = (T_carry + (wave_incl_scan_f(pr) - pr)) + x0;
         const float T1 = T0 + x1;
         const float e0 = __expf(-T0), ex0 = __expf(-x0), ex1 = __expf(-x1);
         w0 = act ? e0 * (1.0f - ex0) : 0.0f;
@@ -792,7 +764,7 @@ __global__ __launch_bounds__(256) void volrender_aux_pair_kernel(const float4* _
         x0 = act ? cur.t0 * cur.c0.w : 0.0f;
         x1 = act ? cur.t1 * cur.c1.w : 0.0f;
         const float pr = x0 + x1;
-        const float incl = wave_incl_scan_f(pr, lane);
+        const float incl = wave_incl_scan_f(pr);
         const float T0 = T_carry + (incl - pr);
         const float e0 = __expf(-T0), ex0 = __expf(-x0), ex1 = __expf(-x1);
         w0 = act ? e0 * (1.0f - ex0) : 0.0f;
@@ -837,7 +809,7 @@ __global__ __launch_bounds__(256) void volrender_aux_pair_kernel(const float4* _
 // The training compositor over a background (rtxn_volrender_l2_train_ex): pixel = sum w c + (1 - A) bg with
 // A = sum w.  Written as bg + sum w_k (c_k - bg) it is the plain compositor with colours c_k - bg: dL/dc_i is unchanged, the
 // optical-depth gradient dots g with c_k - bg, and the second sweep's total is S' = g . (sum w c) - (g . bg) A.  Separate
-// templates beside the plain ones, which keep their machine code.
+// kernels beside the plain ones (copies with the additions written in: a shared inlined body changes the plain kernels' bytes).
 struct BgArgs {
   int mode;              // RTXN_BG_CONSTANT | RTXN_BG_RANDOM
   float color[3];        // CONSTANT
@@ -905,7 +877,7 @@ __global__ __launch_bounds__(256) void volrender_l2_bg_kernel(const float4* __re
       d = step_len[base + s0 + lane];
     }
     const float x = d * c.w;
-    const float incl = wave_incl_scan_f(x, lane);
+    const float incl = wave_incl_scan_f(x);
     const float w = act ? expf(-(T_carry + incl - x)) * (1.0f - expf(-x)) : 0.0f;
     ar = fmaf(w, c.x, ar);
     ag = fmaf(w, c.y, ag);
@@ -948,13 +920,13 @@ __global__ __launch_bounds__(256) void volrender_l2_bg_kernel(const float4* __re
       d = step_len[base + s0 + lane];
     }
     const float x = d * c.w;
-    const float incl = wave_incl_scan_f(x, lane);
+    const float incl = wave_incl_scan_f(x);
     const float Ti = expf(-(T_carry + incl - x));
     const float ex = expf(-x);
     const float a = 1.0f - ex;
     const float gc = (g0 * c.x + g1 * c.y + g2 * c.z) - gbg;
     const float wgc = act ? Ti * a * gc : 0.0f;
-    const float pincl = P_carry + wave_incl_scan_f(wgc, lane);
+    const float pincl = P_carry + wave_incl_scan_f(wgc);
     if (act) {
       const float suffix = S - pincl;
       half4 o;
@@ -1017,7 +989,7 @@ __global__ __launch_bounds__(256) void volrender_l2_bg_multi_kernel(const float4
         x0[u] = cur[u].d0 * cur[u].c0.w;                 // inactive lanes hold zeros: x = 0, w = 0
         x1[u] = cur[u].d1 * cur[u].c1.w;
         pr[u] = x0[u] + x1[u];
-        incl[u] = wave_incl_scan_f(pr[u], lane);
+        incl[u] = wave_incl_scan_f(pr[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1067,7 +1039,7 @@ __global__ __launch_bounds__(256) void volrender_l2_bg_multi_kernel(const float4
         x0[u] = cur[u].d0 * cur[u].c0.w;
         x1[u] = cur[u].d1 * cur[u].c1.w;
         pr[u] = x0[u] + x1[u];
-        incl[u] = wave_incl_scan_f(pr[u], lane);
+        incl[u] = wave_incl_scan_f(pr[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1086,7 +1058,7 @@ __global__ __launch_bounds__(256) void volrender_l2_bg_multi_kernel(const float4
         // inactive lanes: Ti (1 - ex) = 0 (x = 0), so the -gbg of their zero colour adds nothing to the prefix
         const float wgc0 = Ti0[u] * (1.0f - ex0[u]) * gc0[u];
         wgc1[u] = Ti1[u] * (1.0f - ex1[u]) * gc1[u];
-        pin[u] = wave_incl_scan_f(wgc0 + wgc1[u], lane);
+        pin[u] = wave_incl_scan_f(wgc0 + wgc1[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1144,6 +1116,47 @@ int rtxn::check_train_background(const rtxn_train_background* bg, int vr_mode, c
   return RTXN_OK;
 }
 
+namespace {
+
+// The forward family's launch: every entry point's choice between the pair and the one-sample kernel (two samples per lane
+// need an even K and loads that stay aligned: 16 bytes of half4 radiance, or 8 bytes of t_vals beside float4 radiance) and
+// the instantiation for its mode and radiance layout.  aux == NULL: the plain kernels.  `who` names the entry point in
+// errors, `what` the kernel in a launch failure.
+int launch_fwd(const char* who, const char* what, const void* radiance, bool half, int mode, const float* ray_hit,
+               const int* num_hits, const int* indices, int batch_size, int K, float* pixels, const AuxArgs* aux,
+               rtxn_stream_t stream) {
+  RTXN_REQUIRE(((uintptr_t)radiance & (half ? 7 : 15)) == 0, "%s: %s must be %d-byte aligned", who,
+               aux || half ? "radiance" : "network_outputs", half ? 8 : 16);
+  const bool pairs = K % 2 == 0 && (half ? ((uintptr_t)radiance & 15) == 0 : ((uintptr_t)ray_hit & 7) == 0);
+  const float4* rad = static_cast<const float4*>(radiance);
+  hipStream_t s = rtxn::as_stream(stream);
+  const dim3 block(256), grid((batch_size + 3) / 4), pgrid((batch_size + 4 * kRaysPerWave - 1) / (4 * kRaysPerWave));
+  auto launch = [&](auto mode_c, auto compact_c) {
+    constexpr int MODE = decltype(mode_c)::value;
+    constexpr bool COMPACT = decltype(compact_c)::value;
+    if (aux) {
+      if (pairs) volrender_aux_pair_kernel<MODE, COMPACT><<<pgrid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels, *aux);
+      else volrender_aux_kernel<MODE, COMPACT><<<grid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels, *aux);
+    } else {
+      if (pairs) volrender_fwd_pair_kernel<MODE, COMPACT><<<pgrid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels);
+      else volrender_fwd_kernel<MODE, COMPACT><<<grid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels);
+    }
+  };
+  using compat = std::integral_constant<int, RTXN_VR_COMPAT>;
+  using nerf = std::integral_constant<int, RTXN_VR_NERF>;
+  if (half) {
+    if (mode == RTXN_VR_COMPAT) launch(compat{}, std::true_type{});
+    else launch(nerf{}, std::true_type{});
+  } else {
+    if (mode == RTXN_VR_COMPAT) launch(compat{}, std::false_type{});
+    else launch(nerf{}, std::false_type{});
+  }
+  RTXN_LAUNCH_CHECK(what);
+  return RTXN_OK;
+}
+
+}  // namespace
+
 extern "C" int rtxn_volrender_fwd(const float* network_inputs, const float* network_outputs, const int* num_hits,
                                   const int* indices, const float* ray_hit, int batch_size,
                                   int num_samples_per_hit, float* pixels, int mode, rtxn_stream_t stream) {
@@ -1154,21 +1167,8 @@ extern "C" int rtxn_volrender_fwd(const float* network_inputs, const float* netw
   RTXN_DEVICE_OR_FAIL();
   if (batch_size == 0) return RTXN_OK;
   RTXN_REQUIRE(network_outputs && num_hits && indices && ray_hit && pixels, "rtxn_volrender_fwd: NULL buffer");
-  RTXN_REQUIRE(((uintptr_t)network_outputs & 15) == 0, "rtxn_volrender_fwd: network_outputs must be 16-byte aligned");
-  hipStream_t s = rtxn::as_stream(stream);
-  dim3 grid((batch_size + 3) / 4), block(256);
-  const float4* rad = reinterpret_cast<const float4*>(network_outputs);
-  const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)ray_hit & 7) == 0;   // two samples per lane (see the kernel)
-  dim3 pgrid((batch_size + 4 * kRaysPerWave - 1) / (4 * kRaysPerWave));
-  if (mode == RTXN_VR_COMPAT) {
-    if (pairs) volrender_fwd_pair_kernel<RTXN_VR_COMPAT, false><<<pgrid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, num_samples_per_hit, pixels);
-    else volrender_fwd_kernel<RTXN_VR_COMPAT><<<grid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, num_samples_per_hit, pixels);
-  } else {
-    if (pairs) volrender_fwd_pair_kernel<RTXN_VR_NERF, false><<<pgrid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, num_samples_per_hit, pixels);
-    else volrender_fwd_kernel<RTXN_VR_NERF><<<grid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, num_samples_per_hit, pixels);
-  }
-  RTXN_LAUNCH_CHECK("volrender_fwd_kernel");
-  return RTXN_OK;
+  return launch_fwd("rtxn_volrender_fwd", "volrender_fwd_kernel", network_outputs, false, mode, ray_hit, num_hits, indices, batch_size,
+                    num_samples_per_hit, pixels, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_fwd_compact(const void* radiance_half4, const int* num_hits, const int* indices, int batch_size,
@@ -1178,16 +1178,8 @@ extern "C" int rtxn_volrender_fwd_compact(const void* radiance_half4, const int*
   RTXN_DEVICE_OR_FAIL();
   if (batch_size == 0) return RTXN_OK;
   RTXN_REQUIRE(radiance_half4 && num_hits && indices && pixels, "rtxn_volrender_fwd_compact: NULL buffer");
-  RTXN_REQUIRE(((uintptr_t)radiance_half4 & 7) == 0, "rtxn_volrender_fwd_compact: radiance must be 8-byte aligned");
-  dim3 grid((batch_size + 3) / 4), block(256);
-  if (num_samples_per_hit % 2 == 0 && ((uintptr_t)radiance_half4 & 15) == 0)
-    volrender_fwd_pair_kernel<RTXN_VR_COMPAT, true><<<dim3((batch_size + 4 * kRaysPerWave - 1) / (4 * kRaysPerWave)), block, 0, rtxn::as_stream(stream)>>>(
-        static_cast<const float4*>(radiance_half4), num_hits, indices, nullptr, batch_size, num_samples_per_hit, pixels);
-  else
-    volrender_fwd_kernel<RTXN_VR_COMPAT, true><<<grid, block, 0, rtxn::as_stream(stream)>>>(
-        static_cast<const float4*>(radiance_half4), num_hits, indices, nullptr, batch_size, num_samples_per_hit, pixels);
-  RTXN_LAUNCH_CHECK("volrender_fwd_kernel<compact>");
-  return RTXN_OK;
+  return launch_fwd("rtxn_volrender_fwd_compact", "volrender_fwd_kernel<compact>", radiance_half4, true, RTXN_VR_COMPAT, nullptr, num_hits,
+                    indices, batch_size, num_samples_per_hit, pixels, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_fwd_compact_nerf(const void* radiance_half4, const float* segment_step, const int* num_hits,
@@ -1198,16 +1190,8 @@ extern "C" int rtxn_volrender_fwd_compact_nerf(const void* radiance_half4, const
   RTXN_DEVICE_OR_FAIL();
   if (batch_size == 0) return RTXN_OK;
   RTXN_REQUIRE(radiance_half4 && segment_step && num_hits && indices && pixels, "rtxn_volrender_fwd_compact_nerf: NULL buffer");
-  RTXN_REQUIRE(((uintptr_t)radiance_half4 & 7) == 0, "rtxn_volrender_fwd_compact_nerf: radiance must be 8-byte aligned");
-  dim3 grid((batch_size + 3) / 4), block(256);
-  if (num_samples_per_hit % 2 == 0 && ((uintptr_t)radiance_half4 & 15) == 0)
-    volrender_fwd_pair_kernel<RTXN_VR_NERF, true><<<dim3((batch_size + 4 * kRaysPerWave - 1) / (4 * kRaysPerWave)), block, 0, rtxn::as_stream(stream)>>>(
-        static_cast<const float4*>(radiance_half4), num_hits, indices, segment_step, batch_size, num_samples_per_hit, pixels);
-  else
-    volrender_fwd_kernel<RTXN_VR_NERF, true><<<grid, block, 0, rtxn::as_stream(stream)>>>(
-        static_cast<const float4*>(radiance_half4), num_hits, indices, segment_step, batch_size, num_samples_per_hit, pixels);
-  RTXN_LAUNCH_CHECK("volrender_fwd_kernel<compact, nerf>");
-  return RTXN_OK;
+  return launch_fwd("rtxn_volrender_fwd_compact_nerf", "volrender_fwd_kernel<compact, nerf>", radiance_half4, true, RTXN_VR_NERF,
+                    segment_step, num_hits, indices, batch_size, num_samples_per_hit, pixels, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_bwd(const float* loss_values, const void* loss_gradients,
@@ -1243,33 +1227,48 @@ extern "C" int rtxn_volrender_bwd(const float* loss_values, const void* loss_gra
   return RTXN_OK;
 }
 
-extern "C" int rtxn_volrender_l2_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
-                                       int batch_size, int num_samples_per_hit, const float* target, float loss_scale,
-                                       float* pixels, void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
-                                       rtxn_stream_t stream) {
-  RTXN_REQUIRE(batch_size >= 0, "rtxn_volrender_l2_train: batch_size = %d < 0", batch_size);
-  RTXN_REQUIRE(num_samples_per_hit > 0, "rtxn_volrender_l2_train: num_samples_per_hit = %d", num_samples_per_hit);
+namespace {
+
+// rtxn_volrender_l2_train (bg == NULL: the plain kernels) and rtxn_volrender_l2_train_ex over an active background
+int l2_train(const char* who, const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices, int batch_size,
+             int num_samples_per_hit, const float* target, float loss_scale, float* pixels, void* loss_gradients_half, float* loss_sum,
+             void* radiance_gradients, const BgArgs* bg, rtxn_stream_t stream) {
+  RTXN_REQUIRE(batch_size >= 0, "%s: batch_size = %d < 0", who, batch_size);
+  RTXN_REQUIRE(num_samples_per_hit > 0, "%s: num_samples_per_hit = %d", who, num_samples_per_hit);
   RTXN_DEVICE_OR_FAIL();
   hipStream_t s = rtxn::as_stream(stream);
   if (loss_sum) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
   if (batch_size == 0) return RTXN_OK;
-  RTXN_REQUIRE(network_outputs && ray_hit && num_hits && indices && target && pixels && radiance_gradients,
-               "rtxn_volrender_l2_train: NULL buffer");
+  RTXN_REQUIRE(network_outputs && ray_hit && num_hits && indices && target && pixels && radiance_gradients, "%s: NULL buffer", who);
   RTXN_REQUIRE(((uintptr_t)network_outputs & 15) == 0 && ((uintptr_t)radiance_gradients & 7) == 0,
-               "rtxn_volrender_l2_train: radiance must be 16-byte and gradients 8-byte aligned");
+               "%s: radiance must be 16-byte and gradients 8-byte aligned", who);
+  // 512 samples per step, two per lane: an even K, 8-byte-aligned step lengths and 16-byte-aligned gradients
   const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)ray_hit & 7) == 0 && ((uintptr_t)radiance_gradients & 15) == 0;
-  if (pairs)
-    volrender_l2_fused_multi_kernel<4><<<(batch_size + 3) / 4, 256, 0, s>>>(reinterpret_cast<const float4*>(network_outputs), ray_hit, num_hits,
-                                                                        indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
-                                                                        static_cast<__half*>(loss_gradients_half), loss_sum,
-                                                                        static_cast<half4*>(radiance_gradients));
-  else
-    volrender_l2_fused_kernel<<<(batch_size + 3) / 4, 256, 0, s>>>(reinterpret_cast<const float4*>(network_outputs), ray_hit, num_hits,
-                                                                   indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
-                                                                   static_cast<__half*>(loss_gradients_half), loss_sum,
-                                                                   static_cast<half4*>(radiance_gradients));
-  RTXN_LAUNCH_CHECK("volrender_l2_fused_kernel");
+  const dim3 grid((batch_size + 3) / 4), block(256);
+  const float4* rad = reinterpret_cast<const float4*>(network_outputs);
+  __half* lg = static_cast<__half*>(loss_gradients_half);
+  half4* out = static_cast<half4*>(radiance_gradients);
+  const int K = num_samples_per_hit;
+  if (bg) {
+    if (pairs) volrender_l2_bg_multi_kernel<4><<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out, *bg);
+    else volrender_l2_bg_kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out, *bg);
+    RTXN_LAUNCH_CHECK("volrender_l2_bg_kernel");
+  } else {
+    if (pairs) volrender_l2_fused_multi_kernel<4><<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out);
+    else volrender_l2_fused_kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out);
+    RTXN_LAUNCH_CHECK("volrender_l2_fused_kernel");
+  }
   return RTXN_OK;
+}
+
+}  // namespace
+
+extern "C" int rtxn_volrender_l2_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                                       int batch_size, int num_samples_per_hit, const float* target, float loss_scale,
+                                       float* pixels, void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                                       rtxn_stream_t stream) {
+  return l2_train("rtxn_volrender_l2_train", network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
+                  pixels, loss_gradients_half, loss_sum, radiance_gradients, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_l2_train_ex(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
@@ -1279,38 +1278,18 @@ extern "C" int rtxn_volrender_l2_train_ex(const float* network_outputs, const fl
   bool active = false;
   const int rc = rtxn::check_train_background(bg, RTXN_VR_NERF, "rtxn_volrender_l2_train_ex", &active);
   if (rc != RTXN_OK) return rc;
-  if (!active)
-    return rtxn_volrender_l2_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
-                                   pixels, loss_gradients_half, loss_sum, radiance_gradients, stream);
-  RTXN_REQUIRE(batch_size >= 0, "rtxn_volrender_l2_train_ex: batch_size = %d < 0", batch_size);
-  RTXN_REQUIRE(num_samples_per_hit > 0, "rtxn_volrender_l2_train_ex: num_samples_per_hit = %d", num_samples_per_hit);
-  RTXN_DEVICE_OR_FAIL();
-  hipStream_t s = rtxn::as_stream(stream);
-  if (loss_sum) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
-  if (batch_size == 0) return RTXN_OK;
-  RTXN_REQUIRE(network_outputs && ray_hit && num_hits && indices && target && pixels && radiance_gradients,
-               "rtxn_volrender_l2_train_ex: NULL buffer");
-  RTXN_REQUIRE(((uintptr_t)network_outputs & 15) == 0 && ((uintptr_t)radiance_gradients & 7) == 0,
-               "rtxn_volrender_l2_train_ex: radiance must be 16-byte and gradients 8-byte aligned");
   BgArgs a;
-  a.mode = bg->mode;
-  for (int c = 0; c < 3; ++c) a.color[c] = bg->color[c];
-  a.seed = bg->seed;
-  a.step = bg->step;
-  a.target_channels = bg->target_channels;
-  const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)ray_hit & 7) == 0 && ((uintptr_t)radiance_gradients & 15) == 0;
-  if (pairs)
-    volrender_l2_bg_multi_kernel<4><<<(batch_size + 3) / 4, 256, 0, s>>>(reinterpret_cast<const float4*>(network_outputs), ray_hit, num_hits,
-                                                                         indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
-                                                                         static_cast<__half*>(loss_gradients_half), loss_sum,
-                                                                         static_cast<half4*>(radiance_gradients), a);
-  else
-    volrender_l2_bg_kernel<<<(batch_size + 3) / 4, 256, 0, s>>>(reinterpret_cast<const float4*>(network_outputs), ray_hit, num_hits,
-                                                                indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
-                                                                static_cast<__half*>(loss_gradients_half), loss_sum,
-                                                                static_cast<half4*>(radiance_gradients), a);
-  RTXN_LAUNCH_CHECK("volrender_l2_bg_kernel");
-  return RTXN_OK;
+  if (active) {
+    a.mode = bg->mode;
+    for (int c = 0; c < 3; ++c) a.color[c] = bg->color[c];
+    a.seed = bg->seed;
+    a.step = bg->step;
+    a.target_channels = bg->target_channels;
+  }
+  // NULL, or NONE with 3-channel targets: exactly what the plain entry point runs, under its name
+  return l2_train(active ? "rtxn_volrender_l2_train_ex" : "rtxn_volrender_l2_train", network_outputs, ray_hit, num_hits, indices, batch_size,
+                  num_samples_per_hit, target, loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, active ? &a : nullptr,
+                  stream);
 }
 
 extern "C" int rtxn_volrender_fwd_aux(const void* radiance, int radiance_layout, const float* ray_hit, const int* num_hits,
@@ -1330,7 +1309,6 @@ extern "C" int rtxn_volrender_fwd_aux(const void* radiance, int radiance_layout,
   const bool half = radiance_layout == RTXN_RADIANCE_HALF4;
   RTXN_REQUIRE(radiance && num_hits && indices && pixels && (ray_hit || (half && vr_mode == RTXN_VR_COMPAT)),
                "rtxn_volrender_fwd_aux: NULL buffer");
-  RTXN_REQUIRE(((uintptr_t)radiance & (half ? 7 : 15)) == 0, "rtxn_volrender_fwd_aux: radiance must be %d-byte aligned", half ? 8 : 16);
   AuxArgs aux;
   aux.t_start = t_start;
   aux.t_end = t_end;
@@ -1338,25 +1316,6 @@ extern "C" int rtxn_volrender_fwd_aux(const void* radiance, int radiance_layout,
   for (int c = 0; c < 3; ++c) aux.bg[c] = background ? background[c] : 0.0f;
   aux.depth = depth;
   aux.opacity = opacity;
-  // the plain entry points' choice between the pair and the one-sample kernel, so that the pixels match theirs bit for bit
-  const int K = num_samples_per_hit;
-  const bool pairs = K % 2 == 0 && (half ? ((uintptr_t)radiance & 15) == 0 : ((uintptr_t)ray_hit & 7) == 0);
-  const float4* rad = static_cast<const float4*>(radiance);
-  hipStream_t s = rtxn::as_stream(stream);
-  const dim3 block(256), grid((batch_size + 3) / 4), pgrid((batch_size + 4 * kRaysPerWave - 1) / (4 * kRaysPerWave));
-#define RTXN_AUX_LAUNCH(MODE, COMPACT)                                                                              \
-  do {                                                                                                              \
-    if (pairs) volrender_aux_pair_kernel<MODE, COMPACT><<<pgrid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels, aux); \
-    else volrender_aux_kernel<MODE, COMPACT><<<grid, block, 0, s>>>(rad, num_hits, indices, ray_hit, batch_size, K, pixels, aux); \
-  } while (0)
-  if (half) {
-    if (vr_mode == RTXN_VR_COMPAT) RTXN_AUX_LAUNCH(RTXN_VR_COMPAT, true);
-    else RTXN_AUX_LAUNCH(RTXN_VR_NERF, true);
-  } else {
-    if (vr_mode == RTXN_VR_COMPAT) RTXN_AUX_LAUNCH(RTXN_VR_COMPAT, false);
-    else RTXN_AUX_LAUNCH(RTXN_VR_NERF, false);
-  }
-#undef RTXN_AUX_LAUNCH
-  RTXN_LAUNCH_CHECK("volrender_aux_kernel");
-  return RTXN_OK;
+  return launch_fwd("rtxn_volrender_fwd_aux", "volrender_aux_kernel", radiance, half, vr_mode, ray_hit, num_hits, indices, batch_size,
+                    num_samples_per_hit, pixels, &aux, stream);
 }
