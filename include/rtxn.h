@@ -486,6 +486,50 @@ int rtxn_render_slot_buffers(rtxn_render* r, int slot, const int** num_hits, con
                              const float** seg_view, const void** radiance, const float** t_vals, const float** segment_step,
                              const float** viewing_direction);
 
+/* ---- early termination of the frame entry --------------------------------------------------------------------------
+ * Not in the reference, whose loop shades every sample of every ray (main.cu:703-737).  With a termination set,
+ * rtxn_render_frame and rtxn_render_frame_ex shade a frame's rays front to back in n_rounds ROUNDS and stop shading a ray
+ * once its transmittance is spent.  Round k < n_rounds - 1 takes the next first_round_segments * 2^k segments of every ray
+ * still alive, round n_rounds - 1 all that remain; a ray enters round 0 if it has a stored segment (num_stored, so a frame
+ * over capacity is truncated exactly as before), and after a round's samples are composited it stays alive iff it has
+ * segments left and T <= t_stop = -logf(min_transmittance) (host, once), T being the optical depth its compositing mode
+ * has accumulated over the samples shaded so far (RTXN_VR_COMPAT: the running T of vol_render.cu:60, un-reset t_prev
+ * included; RTXN_VR_NERF: sum sigma delta).  The outputs are those of rtxn_volrender_fwd_aux over the shaded prefix of each
+ * ray, nothing renormalised: opacity = sum w_i, depth = sum w_i d_i, pixels = sum w_i c_i + (1 - opacity) background.
+ * Both modes give w_i <= exp(-T_{i-1}) - exp(-T_i), so what is left out sums to at most exp(-T) < min_transmittance:
+ * against the unterminated frame, opacity and every pixel channel (colours in [0,1]) move by at most min_transmittance,
+ * depth by at most min_transmittance x the largest sample distance.
+ * The caller owns a SECOND workspace of rtxn_render_termination_workspace_bytes() bytes (256-byte aligned; 0 with a message
+ * for bad arguments): per slot one round's packed segment records and radiance at capacity max_segments, and 44 B per ray
+ * of round counts, offsets and carried state.  Every count stays on the device, so terminated frames are capturable like
+ * plain ones.  Supported: the compact hand-overs (not RTXN_RENDER_FLOAT4: RTXN_ERR_UNSUPPORTED).  While a termination is
+ * set the rtxn_render_frame_async* entries return RTXN_ERR_UNSUPPORTED.  rtxn_render_set_termination validates its
+ * arguments before any device is touched, synchronises the device (a set-up call) and resets the termination counters;
+ * term == NULL switches termination off (workspace ignored): frames are then the plain ones, bit for bit. */
+#define RTXN_RENDER_MAX_ROUNDS 8
+typedef struct rtxn_render_termination {
+  float min_transmittance;     /* a ray is not shaded further once exp(-T) < this at a round boundary; inside (0, 1) */
+  int first_round_segments;    /* segments per living ray in round 0; >= 1 */
+  int n_rounds;                /* 1..RTXN_RENDER_MAX_ROUNDS; 1 shades everything in one round */
+} rtxn_render_termination;
+size_t rtxn_render_termination_workspace_bytes(const rtxn_render_config* cfg, const rtxn_render_termination* term);
+int rtxn_render_set_termination(rtxn_render* r, const rtxn_render_termination* term, void* workspace, size_t bytes);
+/* Segment counts of terminated frames.  Each such frame adds to 64-bit per-slot counters ON THE DEVICE and copies them to
+ * pinned host memory (async), so a frame replayed from a captured hipGraph counts once per replay.  total = segments the
+ * frame stored (what the plain frame shades), shaded = segments the rounds shaded; last_* quote the slot used most recently.
+ * wait != 0 synchronises the device first; wait == 0 reports what has arrived. */
+typedef struct rtxn_render_termination_stats {
+  long frames;
+  long last_shaded_segments;
+  long last_total_segments;
+  long shaded_segments;
+  long total_segments;
+} rtxn_render_termination_stats;
+int rtxn_render_termination_status(rtxn_render* r, int wait, rtxn_render_termination_stats* out);
+/* shaded_per_ray: DEVICE int[max_rays] of slot `slot`, the segments of each ray the last terminated frame shaded (tests,
+ * tools).  RTXN_ERR_INVALID before the first rtxn_render_set_termination. */
+int rtxn_render_termination_buffers(rtxn_render* r, int slot, const int** shaded_per_ray);
+
 /* ---- training path (tiny-cuda-nn surface of main.cu:721-787) ------------------------ */
 /* Per-sample training tensors are FEATURE-MAJOR fp16: X[feature][S_pad] with
  * S_pad = rtxn_padded_samples(S) (S rounded up to 256), padding columns zero. */

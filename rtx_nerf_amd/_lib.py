@@ -136,6 +136,17 @@ class RenderOutputs(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("depth", C.c_void_p), ("opacity", C.c_void_p), ("background", C.c_float * 3)]
 
 
+class RenderTermination(C.Structure):
+    """struct rtxn_render_termination (include/rtxn.h)."""
+    _fields_ = [("min_transmittance", C.c_float), ("first_round_segments", C.c_int), ("n_rounds", C.c_int)]
+
+
+class RenderTerminationStats(C.Structure):
+    """struct rtxn_render_termination_stats (include/rtxn.h)."""
+    _fields_ = [(n, C.c_long) for n in ("frames", "last_shaded_segments", "last_total_segments", "shaded_segments",
+                                        "total_segments")]
+
+
 # every symbol include/rtxn.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
 SYMBOLS = {
@@ -184,6 +195,10 @@ SYMBOLS = {
     "rtxn_render_drain": (_I, [_P, _P]),
     "rtxn_render_status": (_I, [_P, _I, C.POINTER(RenderStats)]),
     "rtxn_render_slot_buffers": (_I, [_P, _I] + [C.POINTER(_P)] * 11),
+    "rtxn_render_termination_workspace_bytes": (C.c_size_t, [C.POINTER(RenderConfig), C.POINTER(RenderTermination)]),
+    "rtxn_render_set_termination": (_I, [_P, C.POINTER(RenderTermination), _P, C.c_size_t]),
+    "rtxn_render_termination_status": (_I, [_P, _I, C.POINTER(RenderTerminationStats)]),
+    "rtxn_render_termination_buffers": (_I, [_P, _I, C.POINTER(_P)]),
     "rtxn_padded_samples": (_L, [_L]),
     "rtxn_encode_frequency": (_I, [_P, _P, _P, _L, _P]),
     "rtxn_hashgrid_create": (_I, [C.POINTER(HashGridConfig), C.POINTER(_P)]),

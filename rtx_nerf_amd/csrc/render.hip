@@ -14,10 +14,12 @@
 // i-1 run on two internal streams underneath the MLP kernel of frame i, over n_slots buffer slots.
 #include "common.h"
 
+#include <cmath>
 #include <cstring>
 #include <new>
 
 #include "mlp_internal.h"
+#include "terminate_internal.h"
 
 namespace {
 
@@ -49,6 +51,16 @@ struct Slot {
   hipEvent_t total_ev, ev_geo, ev_mlp, ev_comp, ev_pose;
   bool total_pending, used, pose_pending;
   int seen_frames, seen_overflows;
+};
+
+// Early termination (rtxn_render_set_termination; the rounds' kernels are in terminate.hip): the schedule, and per slot the
+// round scratch and per-ray state laid out in the caller's SECOND workspace.
+struct Termination {
+  bool on;
+  float t_stop;        // -logf(min_transmittance), computed once here on the host
+  int s0, n_rounds;
+  rtxn::TermBuffers slots[kMaxSlots];
+  int last_slot;       // slot of the most recently enqueued terminated frame (whose counters the last_* statistics quote)
 };
 
 size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
@@ -85,6 +97,8 @@ struct rtxn_render {
   int* pinned;          // n_slots x (int[4] counters + float[16] pose staging)
   long frame;           // async frames enqueued
   rtxn_render_stats st;
+  Termination term;
+  long* term_pinned;    // n_slots x long[8]: host copies of the slots' termination counters
 };
 
 namespace {
@@ -173,6 +187,56 @@ size_t layout(const rtxn_render_config* c, uint8_t* base, rtxn_render* r) {
       s.t_end = cv.take<float>(m);
     }
     if (r) r->slots[i] = s;
+  }
+  return cv.off;
+}
+
+constexpr int kTermAcctWords = 8;   // long[8] per slot, five used
+
+int validate_termination(const rtxn_render_termination* t, const char* who) {
+  RTXN_REQUIRE(t->min_transmittance > 0.0f && t->min_transmittance < 1.0f, "%s: min_transmittance = %g must lie inside (0, 1)", who,
+               (double)t->min_transmittance);
+  RTXN_REQUIRE(t->first_round_segments >= 1, "%s: first_round_segments = %d must be at least 1", who, t->first_round_segments);
+  RTXN_REQUIRE(t->n_rounds >= 1 && t->n_rounds <= RTXN_RENDER_MAX_ROUNDS, "%s: n_rounds = %d out of [1,%d]", who, t->n_rounds,
+               RTXN_RENDER_MAX_ROUNDS);
+  return RTXN_OK;
+}
+
+int termination_supported(const rtxn_render_config* c, const char* who) {
+  if (c->flags & RTXN_RENDER_FLOAT4) {
+    rtxn::set_error("%s: early termination works on the compact (half4) hand-overs; this renderer uses RTXN_RENDER_FLOAT4", who);
+    return RTXN_ERR_UNSUPPORTED;
+  }
+  return RTXN_OK;
+}
+
+// Lay the termination buffers out in the second workspace (t == nullptr: measure only): per slot the per-ray round counts,
+// offsets and state, a scan workspace, and ONE round's worth of packed records and radiance at capacity max_segments (a round
+// never holds more than the frame stores).
+size_t term_layout(const rtxn_render_config* c, uint8_t* base, Termination* t) {
+  Carver cv{base, 0};
+  const size_t n = max_rays_of(c), m = (size_t)c->max_segments, K = RTXN_NUM_SAMPLES_PER_SEGMENT;
+  const size_t ws_bytes = rtxn_scan_workspace_bytes((int)n);
+  for (int i = 0; i < c->n_slots; ++i) {
+    rtxn::TermBuffers b;
+    memset(&b, 0, sizeof(b));
+    b.take = cv.take<int>(n);
+    b.off = cv.take<int>(n);
+    b.done = cv.take<int>(n);
+    b.round_total = cv.take<int>(RTXN_RENDER_MAX_ROUNDS);
+    b.state = cv.take<float4>(2 * n);
+    b.scan_ws = cv.take<uint8_t>(ws_bytes);
+    b.acct = cv.take<long>(kTermAcctWords);
+    b.start = cv.take<float>(3 * m);
+    b.end = cv.take<float>(3 * m);
+    b.seg_view = cv.take<float>(2 * m);
+    b.radiance = cv.take<uint8_t>(m * K * 8);
+    b.seg_step = c->vr_mode == RTXN_VR_NERF ? cv.take<float>(m) : nullptr;
+    if (c->flags & RTXN_RENDER_AUX) {
+      b.t_start = cv.take<float>(m);
+      b.t_end = cv.take<float>(m);
+    }
+    if (t) t->slots[i] = b;
   }
   return cv.off;
 }
@@ -364,6 +428,9 @@ extern "C" int rtxn_render_create(const rtxn_render_config* cfg, void* workspace
   auto fail = [&](int code) { rtxn_render_destroy(r); return code; };
   hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&r->pinned), kPinnedPerSlot * sizeof(int) * kMaxSlots, hipHostMallocDefault);
   if (e != hipSuccess) return fail(rtxn::fail_hip(e, "hipHostMalloc(pinned segment counts)"));
+  e = hipHostMalloc(reinterpret_cast<void**>(&r->term_pinned), kTermAcctWords * sizeof(long) * kMaxSlots, hipHostMallocDefault);
+  if (e != hipSuccess) return fail(rtxn::fail_hip(e, "hipHostMalloc(pinned termination counters)"));
+  memset(r->term_pinned, 0, kTermAcctWords * sizeof(long) * kMaxSlots);
   if ((e = hipStreamCreateWithFlags(&r->geo, hipStreamNonBlocking)) != hipSuccess) return fail(rtxn::fail_hip(e, "hipStreamCreate(geometry)"));
   if ((e = hipStreamCreateWithFlags(&r->comp, hipStreamNonBlocking)) != hipSuccess) return fail(rtxn::fail_hip(e, "hipStreamCreate(composite)"));
   for (int i = 0; i < 2; ++i)
@@ -405,6 +472,7 @@ extern "C" int rtxn_render_destroy(rtxn_render* r) {
   if (r->geo) (void)hipStreamDestroy(r->geo);
   if (r->comp) (void)hipStreamDestroy(r->comp);
   if (r->pinned) (void)hipHostFree(r->pinned);
+  if (r->term_pinned) (void)hipHostFree(r->term_pinned);
   delete r;
   return RTXN_OK;
 }
@@ -457,12 +525,55 @@ extern "C" int rtxn_render_count_segments(rtxn_render* r, const float* look_at, 
 
 namespace {
 
+// The frame with early termination: after the geometry, N rounds of   scan -> gather -> MLP on the round scratch -> resume
+// back to back on `s` (terminate.hip).  The selection of round 0 is term_begin; the resume kernel of round k selects round
+// k + 1 (it holds the ray's optical depth in a register at that point).  Round k < N - 1 takes s0 * 2^k segments per living
+// ray, round N - 1 whatever is left.  Nothing is read back: every round's launches are sized by the capacity and bounded by
+// device-side counts, whether or not any ray is still alive.
+int frame_terminated(rtxn_render* r, int slot, uint32_t n, const rtxn_render_outputs& o, hipStream_t s) {
+  const rtxn_render_config& c = r->cfg;
+  const Termination& t = r->term;
+  Slot& g = r->slots[slot];
+  const rtxn::TermBuffers& b = t.slots[slot];
+  auto quota = [&](int k) {
+    if (k >= t.n_rounds - 1) return 0x7fffffff;
+    const long q = (long)t.s0 << k;             // s0 < 2^31, k < 8
+    return q > 0x7fffffffL ? 0x7fffffff : (int)q;
+  };
+  rtxn::TermOutputs out;
+  out.pixels = o.pixels;
+  out.depth = o.depth;
+  out.opacity = o.opacity;
+  memcpy(out.bg, o.background, sizeof(out.bg));
+  const float u0 = c.sample_type == RTXN_SAMPLING_MIDPOINT_WORLD ? 0.5f : 0.0f;
+  int rc = rtxn::term_begin(g.num_stored, (int)n, quota(0), b, s);
+  if (rc != RTXN_OK) return rc;
+  for (int k = 0; k < t.n_rounds; ++k) {
+    int* total = b.round_total + k;
+    rc = rtxn_scan_hits(b.take, b.off, total, (int)n, b.scan_ws, r->scan_ws_bytes, s);
+    if (rc != RTXN_OK) return rc;
+    rc = rtxn::term_gather(b, g.indices, (int)n, c.max_segments, g.start, g.end, g.seg_view, g.t_start, g.t_end, s);
+    if (rc != RTXN_OK) return rc;
+    if (r->hash)
+      rc = rtxn_hashmlp_forward_segments(c.mlp, c.grid, c.n_dir_freqs, c.table_fp16, b.start, b.end, b.seg_view, total, c.max_segments,
+                                         c.sample_type, c.step_scale, b.radiance, b.seg_step, s);
+    else
+      rc = rtxn_mlp_forward_segments_compact(c.mlp, b.start, b.end, b.seg_view, total, c.max_segments, b.radiance, s);
+    if (rc != RTXN_OK) return rc;
+    rc = rtxn::term_resume(b, g.num_stored, (int)n, c.vr_mode, u0, k == 0, quota(k + 1), t.t_stop, out, s);
+    if (rc != RTXN_OK) return rc;
+  }
+  r->term.last_slot = slot;
+  return rtxn::term_account(b, t.n_rounds, g.total, (int)c_max_segments(r), s);
+}
+
 int frame_serial(rtxn_render* r, int slot, const float* look_at, uint32_t ray_begin, uint32_t ray_count, const rtxn_render_outputs& o,
                  hipStream_t s) {
   Slot& g = r->slots[slot];
   if (!capturing(s)) harvest(r, g, false);
   int rc = geometry(r, g, look_at, false, ray_begin, ray_count, s);
   if (rc != RTXN_OK) return rc;
+  if (r->term.on) return frame_terminated(r, slot, ray_count, o, s);
   rc = shade(r, g, s);
   if (rc != RTXN_OK) return rc;
   return composite_out(r, g, ray_count, o, s);
@@ -509,6 +620,13 @@ namespace {
 //  * with RTXN_RENDER_STABLE_INPUTS (the caller's promise that a frame's inputs are complete and stay untouched from the call
 //    until the frame's traversal has run: pre-uploaded poses) or with a HOST pose (staged through pinned memory here): only on
 //    a slot's first use and after rtxn_render_set_occupancy -- the fully overlapped pipeline.
+int refuse_terminated(const rtxn_render* r, const char* who) {
+  if (!r->term.on) return RTXN_OK;
+  rtxn::set_error("%s: early termination is set (rtxn_render_set_termination); the pipelined entries do not run its rounds -- use "
+                  "rtxn_render_frame[_ex] or clear it with a NULL termination", who);
+  return RTXN_ERR_UNSUPPORTED;
+}
+
 int frame_async(rtxn_render* r, const float* look_at, bool pose_on_host, uint32_t ray_begin, uint32_t ray_count,
                 const rtxn_render_outputs& outputs, hipStream_t main_s, rtxn_stream_t* composite_stream) {
   const int b = (int)(r->frame % r->n_slots);
@@ -552,6 +670,7 @@ int frame_async(rtxn_render* r, const float* look_at, bool pose_on_host, uint32_
 extern "C" int rtxn_render_frame_async(rtxn_render* r, const float* look_at, uint32_t ray_begin, uint32_t ray_count, float* pixels,
                                        rtxn_stream_t stream, rtxn_stream_t* composite_stream) {
   RTXN_REQUIRE(r && look_at && pixels, "rtxn_render_frame_async: NULL argument");
+  if (int tr = refuse_terminated(r, "rtxn_render_frame_async")) return tr;
   int rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame_async");
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
@@ -563,6 +682,7 @@ extern "C" int rtxn_render_frame_async(rtxn_render* r, const float* look_at, uin
 extern "C" int rtxn_render_frame_async_host(rtxn_render* r, const float* look_at_host, uint32_t ray_begin, uint32_t ray_count,
                                             float* pixels, rtxn_stream_t stream, rtxn_stream_t* composite_stream) {
   RTXN_REQUIRE(r && look_at_host && pixels, "rtxn_render_frame_async_host: NULL argument");
+  if (int tr = refuse_terminated(r, "rtxn_render_frame_async_host")) return tr;
   int rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame_async_host");
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
@@ -576,6 +696,7 @@ extern "C" int rtxn_render_frame_async_ex(rtxn_render* r, const float* look_at, 
   RTXN_REQUIRE(r && look_at, "rtxn_render_frame_async_ex: NULL argument");
   int rc = check_outputs(r, outputs, "rtxn_render_frame_async_ex");
   if (rc != RTXN_OK) return rc;
+  if (int tr = refuse_terminated(r, "rtxn_render_frame_async_ex")) return tr;
   rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame_async_ex");
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
@@ -630,5 +751,83 @@ extern "C" int rtxn_render_slot_buffers(rtxn_render* r, int slot, const int** nu
   if (t_vals) *t_vals = g.t_vals;
   if (segment_step) *segment_step = g.seg_step;
   if (viewing_direction) *viewing_direction = g.view_dirs;
+  return RTXN_OK;
+}
+
+extern "C" size_t rtxn_render_termination_workspace_bytes(const rtxn_render_config* cfg, const rtxn_render_termination* term) {
+  const char* who = "rtxn_render_termination_workspace_bytes";
+  if (validate(cfg, who) != RTXN_OK) return 0;
+  if (!term) {
+    rtxn::set_error("%s: NULL termination", who);
+    return 0;
+  }
+  if (validate_termination(term, who) != RTXN_OK || termination_supported(cfg, who) != RTXN_OK) return 0;
+  return term_layout(cfg, nullptr, nullptr);
+}
+
+extern "C" int rtxn_render_set_termination(rtxn_render* r, const rtxn_render_termination* term, void* workspace, size_t bytes) {
+  const char* who = "rtxn_render_set_termination";
+  if (term) {
+    int rc = validate_termination(term, who);
+    if (rc != RTXN_OK) return rc;
+  }
+  RTXN_REQUIRE(r != nullptr, "%s: NULL renderer", who);
+  if (!term) {                 // off: frames already enqueued keep the rounds they were enqueued with
+    r->term.on = false;
+    return RTXN_OK;
+  }
+  int rc = termination_supported(&r->cfg, who);
+  if (rc != RTXN_OK) return rc;
+  const size_t need = term_layout(&r->cfg, nullptr, nullptr);
+  RTXN_REQUIRE(workspace && ((uintptr_t)workspace & (kAlign - 1)) == 0, "%s: workspace NULL or not %zu-byte aligned", who, kAlign);
+  RTXN_REQUIRE(bytes >= need, "%s: workspace holds %zu bytes, rtxn_render_termination_workspace_bytes says %zu", who, bytes, need);
+  RTXN_DEVICE_OR_FAIL();
+  RTXN_HIP(hipDeviceSynchronize());          // frames in flight may still use the previous termination workspace
+  r->term.on = false;
+  term_layout(&r->cfg, static_cast<uint8_t*>(workspace), &r->term);
+  memset(r->term_pinned, 0, kTermAcctWords * sizeof(long) * kMaxSlots);
+  for (int i = 0; i < r->n_slots; ++i) {
+    rtxn::TermBuffers& b = r->term.slots[i];
+    b.acct_host = r->term_pinned + kTermAcctWords * i;
+    // counters, round totals and shaded_per_ray start at 0 (a status or buffer query before the first frame reads them)
+    RTXN_HIP(rtxn::zero_words(b.acct, 2 * kTermAcctWords, nullptr));
+    RTXN_HIP(rtxn::zero_words(b.round_total, RTXN_RENDER_MAX_ROUNDS, nullptr));
+    RTXN_HIP(rtxn::zero_words(b.done, r->max_rays, nullptr));
+  }
+  RTXN_HIP(hipStreamSynchronize(nullptr));
+  r->term.t_stop = -logf(term->min_transmittance);
+  r->term.s0 = term->first_round_segments;
+  r->term.n_rounds = term->n_rounds;
+  r->term.last_slot = 0;
+  r->term.on = true;
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_render_termination_status(rtxn_render* r, int wait, rtxn_render_termination_stats* out) {
+  RTXN_REQUIRE(r && out, "rtxn_render_termination_status: NULL argument");
+  memset(out, 0, sizeof(*out));
+  if (!r->term.slots[0].acct_host) return RTXN_OK;       // never set: all zero
+  if (wait) {
+    RTXN_DEVICE_OR_FAIL();
+    RTXN_HIP(hipDeviceSynchronize());
+  }
+  for (int i = 0; i < r->n_slots; ++i) {
+    const volatile long* a = r->term.slots[i].acct_host;
+    out->frames += a[0];
+    out->shaded_segments += a[3];
+    out->total_segments += a[4];
+    if (i == r->term.last_slot) {
+      out->last_shaded_segments = a[1];
+      out->last_total_segments = a[2];
+    }
+  }
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_render_termination_buffers(rtxn_render* r, int slot, const int** shaded_per_ray) {
+  RTXN_REQUIRE(r != nullptr, "rtxn_render_termination_buffers: NULL renderer");
+  RTXN_REQUIRE(slot >= 0 && slot < r->n_slots, "rtxn_render_termination_buffers: slot %d out of [0,%d)", slot, r->n_slots);
+  RTXN_REQUIRE(r->term.slots[slot].done != nullptr, "rtxn_render_termination_buffers: no termination workspace has been set");
+  if (shaded_per_ray) *shaded_per_ray = r->term.slots[slot].done;
   return RTXN_OK;
 }

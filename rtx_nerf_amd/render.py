@@ -30,7 +30,8 @@ class RenderPipeline:
     def __init__(self, network, grid_res, width, height, focal_length, aspect_ratio=None, occupancy=None,
                  max_rays=None, max_segments=None, trace_mode=api.TRACE_DDA, vr_mode=api.VR_COMPAT,
                  device="cuda", window=(0, 0), step_scale=1.0, sub_rays=None, compact=None, on_overflow="raise",
-                 hashgrid=None, table=None, sample_type=None, n_slots=None, stable_inputs=False, aux=False):
+                 hashgrid=None, table=None, sample_type=None, n_slots=None, stable_inputs=False, aux=False,
+                 min_transmittance=None, first_round_segments=4, termination_rounds=5):
         self.net = network
         self.hg, self.table = hashgrid, table
         if (hashgrid is None) != (table is None):
@@ -88,6 +89,13 @@ class RenderPipeline:
         self.depth = torch.empty(n_rays, device=self.dev) if self.aux else None
         self.opacity = torch.empty(n_rays, device=self.dev)
         self.look_at = torch.zeros(16, device=self.dev)
+        # early termination (rtxn_render_set_termination): render / render_ex / capture[_ex] shade each ray front to back in
+        # `termination_rounds` rounds (first_round_segments * 2^k segments per living ray, the last round the rest) and stop a
+        # ray once exp(-optical depth) < min_transmittance at a round boundary: every output moves by at most
+        # min_transmittance (depth: times the largest sample distance).  None = off: the plain frame.
+        self.min_transmittance = None if min_transmittance is None else float(min_transmittance)
+        self.first_round_segments, self.termination_rounds = int(first_round_segments), int(termination_rounds)
+        self._term_ws = None
         self._h = None
         self._comp_stream = None
         self._create()
@@ -138,6 +146,46 @@ class RenderPipeline:
         self._slots = [self._slot_views(i) for i in range(self.n_slots)]
         for f in ("num_hits", "num_hits_c", "indices", "total", "start", "end", "seg_view", "radiance", "t_vals", "seg_step", "view_dirs"):
             setattr(self, f, getattr(self._slots[0], f))
+        self._term_ws = None
+        if self.min_transmittance is not None:
+            self.set_termination(self.min_transmittance, self.first_round_segments, self.termination_rounds)
+
+    # ------------------------------------------------------------------------------------------ early termination
+    def set_termination(self, min_transmittance=None, first_round_segments=4, termination_rounds=5):
+        """Set (or, with min_transmittance=None, clear) early termination on the C renderer.  Setting it allocates the
+        second workspace (one round's packed scratch per slot + per-ray state), synchronises the device and resets
+        termination_stats(); render_async* raise while it is set."""
+        lib = _lib.lib()
+        if min_transmittance is None:
+            _lib.check(lib.rtxn_render_set_termination(self._h, None, None, 0), "rtxn_render_set_termination")
+            self.min_transmittance = None
+            return
+        t = _lib.RenderTermination(float(min_transmittance), int(first_round_segments), int(termination_rounds))
+        cfg = self._config()
+        need = lib.rtxn_render_termination_workspace_bytes(C.byref(cfg), C.byref(t))
+        if need == 0:
+            msg = lib.rtxn_last_error()
+            raise _lib.RtxnError(f"rtxn_render_termination_workspace_bytes: {msg.decode() if msg else '?'}")
+        ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        _lib.check(lib.rtxn_render_set_termination(self._h, C.byref(t), C.c_void_p(ws.data_ptr()), need), "rtxn_render_set_termination")
+        self._term_ws = ws                     # the previous one (if any) is released only now: the setter has synchronised
+        self.min_transmittance = float(min_transmittance)
+        self.first_round_segments, self.termination_rounds = int(first_round_segments), int(termination_rounds)
+
+    def termination_stats(self, wait=True):
+        """struct rtxn_render_termination_stats as a dict (wait: synchronise first, so every enqueued or replayed frame counts)."""
+        st = _lib.RenderTerminationStats()
+        _lib.check(_lib.lib().rtxn_render_termination_status(self._h, 1 if wait else 0, C.byref(st)), "rtxn_render_termination_status")
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+    def shaded_per_ray(self, slot=0):
+        """int32[max_rays] view of the segments of each ray the slot's last terminated frame shaded (device; no copy)."""
+        if self._term_ws is None:
+            raise RuntimeError("shaded_per_ray: early termination has not been set on this pipeline")
+        p = C.c_void_p()
+        _lib.check(_lib.lib().rtxn_render_termination_buffers(self._h, slot, C.byref(p)), "rtxn_render_termination_buffers")
+        off = p.value - self._term_ws.data_ptr()
+        return self._term_ws[off:off + 4 * self.max_rays].view(torch.int32)
 
     def _slot_views(self, i):
         """torch views of slot i's device buffers inside the workspace (tests, tools; the C side owns the layout)."""
