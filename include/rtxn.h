@@ -354,6 +354,75 @@ int rtxn_hashmlp_forward_segments(const rtxn_mlp* m, const rtxn_hashgrid* g, int
                                   const int* total_segments, long max_segments, int sample_type, float t_scale,
                                   void* radiance_half4, float* segment_step, rtxn_stream_t stream);
 
+/* ---- occupancy refresh from the live model ------------------------------------------------------------------------
+ * Not in the reference, which builds the dense grid once (main.cu:393-399); the update rule is instant-ngp's.  ONE call that
+ * evaluates sigma at one point per cell of the R^3 grid with the fused inference kernels above, folds it into a decaying
+ * running maximum, thresholds it and rewrites the whole traversal hierarchy IN PLACE -- on `stream`, without a
+ * synchronisation, a host read or an allocation, so it is hipGraph-capturable and graphs that read the four buffers stay valid.
+ *
+ * Evaluation.  Cells (x, y, 32k .. 32k+31) form a RUN, handed to the segment kernels as one pseudo-segment whose 32 REGULAR
+ * samples are the cells' sample points; NK = ceil(R/32) runs per row, global run index g = (x*R + y)*NK + k, samples of a tail
+ * run beyond the grid are shaded and dropped; seg_view = (0, 0).  float32, each operation rounded on its own, in this order:
+ *   h = 2.0f / (float)R;   p_x = ((float)x + 0.5f) * h - 1.0f, p_y from y, p_z from z0 = 32k;
+ *   jitter != 0: step = (uint32)*step (NULL: 0), h0 = fmix32(seed + 0x9E3779B9u * step) (fmix32: see RTXN_BG_RANDOM), and for
+ *                c = 0, 1, 2:  u_c = (float)(fmix32(h0 ^ (3u * (uint32)g + c)) >> 8) * 2^-24,  p_c = p_c + (u_c - 0.5f) * h
+ *                -- one offset in [-0.5, 0.5) h per axis and RUN, shared by its 32 cells (a segment's samples are equally spaced on a
+ *                line: a translation is the only jitter it can carry);
+ *   start = p;   end = (p_x, p_y, p_z + 32.0f * h);   sample i is where the segment kernel puts it: start + (i/32)(end - start).
+ * Hash models (grid != NULL) go through rtxn_hashmlp_forward_segments(RTXN_SAMPLING_REGULAR), Composite-Frequency models
+ * through rtxn_mlp_forward_segments_compact; sigma is component 3 of their half[.][4] output.
+ * Update, for every cell c = (x*R + y)*R + z, s = (float)sigma of its sample, NaN taken as 0:
+ *   v = s * thickness_scale;   d = density[c] * decay;   density[c] = v > d ? v : d
+ * (decay 0 and a zeroed density: density = max(0, v), a plain point sample).  The mean of the new density is formed in a
+ * fixed order -- per run a butterfly over the 32 lanes (float), the runs' sums in double, ascending g per lane of one block,
+ * then a tree -- so it does not depend on the pass size or on scheduling.
+ *   thr = threshold (RTXN_OCC_ABSOLUTE) | fminf(threshold, mean) (RTXN_OCC_MIN_MEAN), read on the device;
+ *   occupancy bit c = density[c] > thr (ceil(R^3/32) words, tail bits 0), then coarse = rtxn_build_occupancy_mip(occupancy),
+ *   bricks = rtxn_build_occupancy_bricks(occupancy), super_mip = rtxn_build_occupancy_mip(coarse, R/4).
+ * coarse and bricks must be given exactly when R % 4 == 0, super_mip exactly when R % 16 == 0 (NULL otherwise).
+ * Passes: the runs are shaded runs_per_pass at a time through ONE caller-provided workspace of
+ * rtxn_occupancy_refresh_workspace_bytes(grid_res, runs_per_pass) bytes (256-byte aligned; 0 with a message for bad arguments):
+ * 32 B of segment records + 256 B of radiance per run of a pass, and 4 B per run of the grid.  Results are bit-identical for
+ * every runs_per_pass.
+ * rtxn_occupancy_refresh_supported: 1 for a Composite-Frequency model with a fused inference kernel (grid == NULL) and for a
+ * hash model exactly when rtxn_hashmlp_supported; otherwise the entry returns RTXN_ERR_UNSUPPORTED.  Argument errors are
+ * RTXN_ERR_INVALID with a message before any device is touched.  rtxn_mlp_set_params must have run since the last
+ * rtxn_mlp_set_params_training of a frequency model (the inference kernels' rule). */
+enum rtxn_occupancy_threshold_mode { RTXN_OCC_ABSOLUTE = 0, RTXN_OCC_MIN_MEAN = 1 };
+typedef struct rtxn_occupancy_refresh_args {
+  /* model and grid */
+  const rtxn_mlp* mlp;
+  const rtxn_hashgrid* grid;        /* NULL: Composite-Frequency model */
+  int n_dir_freqs;                  /* hash grid only */
+  const void* table_fp16;           /* hash grid only: half[rtxn_hashgrid_n_params] */
+  int grid_res;                     /* R in [1, 1024] */
+  /* update rule */
+  float* density;                   /* float[R^3], index (x*R+y)*R+z: the running maximum, updated in place (start from zeros) */
+  float decay;                      /* in [0, 1] */
+  float thickness_scale;            /* sigma -> optical thickness of a cell: density scale x cell size 2/R */
+  float threshold;
+  int threshold_mode;               /* enum rtxn_occupancy_threshold_mode */
+  /* jitter */
+  int jitter;                       /* 0: cell centres */
+  unsigned seed;
+  const int* step;                  /* DEVICE int hashed with the seed, or NULL = 0: a captured graph draws new offsets per replay */
+  /* hierarchy outputs, rewritten in place */
+  uint32_t* occupancy;              /* ceil(R^3/32) words */
+  uint32_t* coarse;                 /* R % 4 == 0: ceil((R/4)^3/32) words; else NULL */
+  uint64_t* bricks;                 /* R % 4 == 0: (R/4)^3 words; else NULL */
+  uint32_t* super_mip;              /* R % 16 == 0: ceil((R/16)^3/32) words; else NULL */
+  /* optional outputs */
+  int* occupied;                    /* DEVICE int or NULL: number of set fine bits */
+  float* mean;                      /* DEVICE float or NULL: mean of the new density */
+  /* workspace */
+  void* workspace;
+  size_t workspace_bytes;
+  long runs_per_pass;               /* >= 1; R*R*ceil(R/32) shades the grid in one pass */
+} rtxn_occupancy_refresh_args;
+int rtxn_occupancy_refresh_supported(const rtxn_mlp* m, const rtxn_hashgrid* g, int n_dir_freqs);
+size_t rtxn_occupancy_refresh_workspace_bytes(int grid_res, long runs_per_pass);
+int rtxn_occupancy_refresh(const rtxn_occupancy_refresh_args* args, rtxn_stream_t stream);
+
 /* ---- one frame behind one call ------------------------------------------------------------------------------------
  * The per-image host sequence of the reference -- fill Params and optixLaunch (main.cu:473-508), copy every traversal
  * buffer to the host and re-pack it (:510-543, :646-673), thrust compaction (:631-637), launchSampler (:704),

@@ -147,6 +147,16 @@ class RenderTerminationStats(C.Structure):
                                         "total_segments")]
 
 
+class OccupancyRefreshArgs(C.Structure):
+    """struct rtxn_occupancy_refresh_args (include/rtxn.h)."""
+    _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("n_dir_freqs", C.c_int), ("table_fp16", C.c_void_p),
+                ("grid_res", C.c_int), ("density", C.c_void_p), ("decay", C.c_float), ("thickness_scale", C.c_float),
+                ("threshold", C.c_float), ("threshold_mode", C.c_int), ("jitter", C.c_int), ("seed", C.c_uint),
+                ("step", C.c_void_p), ("occupancy", C.c_void_p), ("coarse", C.c_void_p), ("bricks", C.c_void_p),
+                ("super_mip", C.c_void_p), ("occupied", C.c_void_p), ("mean", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("runs_per_pass", C.c_long)]
+
+
 # every symbol include/rtxn.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
 SYMBOLS = {
@@ -182,6 +192,9 @@ SYMBOLS = {
     "rtxn_volrender_fwd_aux": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtxn_hashmlp_supported": (_I, [_P, _P, _I]),
     "rtxn_hashmlp_forward_segments": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P]),
+    "rtxn_occupancy_refresh_supported": (_I, [_P, _P, _I]),
+    "rtxn_occupancy_refresh_workspace_bytes": (C.c_size_t, [_I, _L]),
+    "rtxn_occupancy_refresh": (_I, [C.POINTER(OccupancyRefreshArgs), _P]),
     "rtxn_render_workspace_bytes": (C.c_size_t, [C.POINTER(RenderConfig)]),
     "rtxn_render_create": (_I, [C.POINTER(RenderConfig), _P, C.c_size_t, C.POINTER(_P)]),
     "rtxn_render_destroy": (_I, [_P]),

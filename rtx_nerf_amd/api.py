@@ -138,6 +138,60 @@ def occupancy_from_density(density, threshold, grid_res):
     return occ
 
 
+OCC_ABSOLUTE, OCC_MIN_MEAN = 0, 1
+
+
+def occupancy_refresh_supported(net, grid=None):
+    """True if rtxn_occupancy_refresh can evaluate this model (a fused inference kernel exists for it)."""
+    return bool(_lib.lib().rtxn_occupancy_refresh_supported(net._h, grid._h if grid is not None else None,
+                                                            grid.n_dir_freqs if grid is not None else 0))
+
+
+def occupancy_refresh_runs(grid_res):
+    """Runs of 32 z-cells in a grid_res^3 grid: the runs_per_pass that shades it in one pass."""
+    return grid_res * grid_res * ((grid_res + NUM_SAMPLES_PER_SEGMENT - 1) // NUM_SAMPLES_PER_SEGMENT)
+
+
+def occupancy_refresh_workspace(grid_res, runs_per_pass, device="cuda"):
+    """The workspace of occupancy_refresh for passes of runs_per_pass runs (rtxn_occupancy_refresh_workspace_bytes)."""
+    nbytes = int(_lib.lib().rtxn_occupancy_refresh_workspace_bytes(int(grid_res), int(runs_per_pass)))
+    if nbytes == 0:
+        check(1, "rtxn_occupancy_refresh_workspace_bytes")
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def occupancy_refresh(net, *, grid=None, table=None, grid_res, density, decay, thickness_scale, threshold,
+                      threshold_mode=OCC_MIN_MEAN, jitter=False, seed=0, step=None, occupancy, coarse=None, bricks=None,
+                      super_mip=None, occupied=None, mean=None, workspace, runs_per_pass):
+    """rtxn_occupancy_refresh: sigma at one (optionally jittered) point per cell from the live model -> density = max(density *
+    decay, sigma * thickness_scale) -> bits, 4^3 mip, bricks and 16^3 mip rewritten in place.  One call on the current stream,
+    no host read: capturable.  step: int32 device tensor hashed into the jitter (None: 0); occupied (int32[1]) and mean
+    (float32[1]) are optional device outputs."""
+    R, a = int(grid_res), _lib.OccupancyRefreshArgs()
+    a.mlp, a.grid = net._h, (grid._h if grid is not None else None)
+    a.n_dir_freqs = int(grid.n_dir_freqs) if grid is not None else 0
+    a.table_fp16 = _ptr(table, torch.float16, "table")
+    a.grid_res = R
+    a.density = _ptr(density, torch.float32, "density")
+    a.decay, a.thickness_scale, a.threshold, a.threshold_mode = float(decay), float(thickness_scale), float(threshold), int(threshold_mode)
+    a.jitter, a.seed, a.step = (1 if jitter else 0), int(seed) & 0xFFFFFFFF, _ptr(step, torch.int32, "step")
+    a.occupancy, a.coarse = _ptr(occupancy, torch.int32, "occupancy"), _ptr(coarse, torch.int32, "coarse")
+    a.bricks, a.super_mip = _ptr(bricks, torch.int64, "bricks"), _ptr(super_mip, torch.int32, "super_mip")
+    a.occupied, a.mean = _ptr(occupied, torch.int32, "occupied"), _ptr(mean, torch.float32, "mean")
+    a.workspace = _ptr(workspace, None, "workspace")
+    a.workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    a.runs_per_pass = int(runs_per_pass)
+    rc, rs = R // 4, R // 16
+    for nm, t, need in (("density", density, R ** 3), ("occupancy", occupancy, (R ** 3 + 31) // 32),
+                        ("coarse", coarse, (rc ** 3 + 31) // 32), ("bricks", bricks, rc ** 3), ("super_mip", super_mip, (rs ** 3 + 31) // 32),
+                        ("occupied", occupied, 1), ("mean", mean, 1), ("step", step, 1)):
+        if t is not None and t.numel() < need:
+            raise _lib.RtxnError(f"occupancy_refresh: {nm} holds {t.numel()} elements, {need} needed for grid_res {R}")
+    if grid is not None and table is not None and table.numel() < grid.n_params():
+        raise _lib.RtxnError(f"occupancy_refresh: table holds {table.numel()} parameters, the grid has {grid.n_params()}")
+    check(_lib.lib().rtxn_occupancy_refresh(C.byref(a), _stream()), "rtxn_occupancy_refresh")
+
+
 # --------------------------------------------------------------------------- CSR compaction
 def scan_hits(num_hits, indices=None, total=None, workspace=None):
     """thrust::reduce + thrust::exclusive_scan (main.cu:631-637); total stays on the device."""

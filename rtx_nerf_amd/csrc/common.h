@@ -25,6 +25,17 @@ hipError_t zero_words(void* p, size_t n_words, hipStream_t stream);
 // RTXN_OK with *active = whether a background is composited at all.
 int check_train_background(const rtxn_train_background* bg, int vr_mode, const char* who, bool* active);
 
+// MurmurHash3's 32-bit finaliser: the integer hash behind RTXN_BG_RANDOM and the occupancy refresh's jitter (include/rtxn.h
+// states both uses bit for bit)
+__host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
 }  // namespace rtxn
 
 #define RTXN_HIP(expr)                                           \

@@ -818,14 +818,7 @@ struct BgArgs {
   int target_channels;   // 3 | 4 (straight RGBA, composited over the ray's background)
 };
 
-__device__ __forceinline__ unsigned fmix32(unsigned h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
+using rtxn::fmix32;
 
 // the ray's background and its (composited) target: wave-uniform values
 __device__ __forceinline__ void ray_background(const BgArgs& bg, const float* __restrict__ target, int ray, float (&b)[3],

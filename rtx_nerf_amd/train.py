@@ -74,7 +74,10 @@ class Trainer:
         self.mode = mode
         self.lr, self.loss_scale, self.density_scale = lr, loss_scale, density_scale
         self.step_count = 0
-        self._stage_ev = None      # list of (stage, start event, end event) while time_stages() is collecting
+        self.occ_density = None    # refresh_occupancy(): the running maximum, its workspace and its device outputs, on first use
+        self._occ_ws = self._occ_out = self._occ_step = None
+        self._occ_seed = seed
+        self._stage_ev = None     # list of (stage, start event, end event) while time_stages() is collecting
         self._init_background(background, background_seed, target_channels)      # refused before anything is allocated
         d = self.dev
         # ---- model -------------------------------------------------------------------------------
@@ -1041,6 +1044,69 @@ class Trainer:
         thick = sigma * (self.density_scale * 2.0 / R)
         self._set_occupancy(api.occupancy_from_density(thick, threshold, R))
         return float((thick > threshold).float().mean().item())
+
+    @torch.no_grad()
+    def refresh_occupancy(self, threshold=0.01, decay=0.95, jitter=True, threshold_mode="min_mean", runs_per_pass=None):
+        """The occupancy refresh of an instant-ngp-style loop, on the device (librtxn: rtxn_occupancy_refresh):
+        sigma at one point per cell -- jittered inside the cell per run of 32 z-cells and per step -- from the live model
+        through the fused inference kernels, occ_density = max(occ_density * decay, sigma * density_scale * cell size), bit =
+        occ_density > threshold ("absolute") or > min(threshold, mean of occ_density) ("min_mean"), and the 4^3 mip, bricks and
+        16^3 mip rebuilt.  All four are rewritten IN PLACE: captured graphs stay valid, nothing is read back and nothing
+        synchronises, so the call can follow every few step_captured() without stalling them (occupancy_stats() is the call
+        that looks).  runs_per_pass: runs shaded per pass (default: the grid in one pass up to 65536 runs = 2 M samples, 17 MB
+        of workspace).  Frequency models re-pack their inference weights first (sync_inference_weights)."""
+        R = self.R
+        modes = {"absolute": api.OCC_ABSOLUTE, "min_mean": api.OCC_MIN_MEAN}
+        if threshold_mode not in modes:
+            raise ValueError(f"refresh_occupancy: threshold_mode {threshold_mode!r} (absolute | min_mean)")
+        if not api.occupancy_refresh_supported(self.net, self.hg):
+            raise api._lib.RtxnError("refresh_occupancy: no fused inference kernel for this model (built: frequency models, and hash "
+                                     "models 64 wide with <= 8 hidden layers, 2 features per level and an even number of levels); "
+                                     "use update_occupancy(), which evaluates the cells through the training path")
+        d = self.dev
+        if self.occ is None:
+            # a trainer that started dense has no buffers for its graphs to read: they are dropped, as by _set_occupancy
+            self.occ = torch.full(((R ** 3 + 31) // 32,), -1, dtype=torch.int32, device=d)
+            if R % 4 == 0:
+                self.coarse = torch.full((((R // 4) ** 3 + 31) // 32,), -1, dtype=torch.int32, device=d)
+                self.bricks = torch.full(((R // 4) ** 3,), -1, dtype=torch.int64, device=d)
+            if R % 16 == 0:
+                self.super_mip = torch.full((((R // 16) ** 3 + 31) // 32,), -1, dtype=torch.int32, device=d)
+            if getattr(self, "_graphs", None) is not None:
+                self._graphs = None
+        runs = api.occupancy_refresh_runs(R)
+        P = max(1, min(runs, int(runs_per_pass) if runs_per_pass else 1 << 16))
+        if self.occ_density is None:
+            self.occ_density = torch.zeros(R ** 3, device=d)
+            self._occ_out = (torch.zeros(1, dtype=torch.int32, device=d), torch.zeros(1, device=d))      # occupied bits, mean
+        need = api._lib.lib().rtxn_occupancy_refresh_workspace_bytes(R, P)
+        if self._occ_ws is None or self._occ_ws.numel() * 4 < need:
+            self._occ_ws = api.occupancy_refresh_workspace(R, P, device=d)
+        if getattr(self, "_g_step", None) is not None:
+            step = self._g_step.view(torch.int32)[:1]        # the captured steps' device counter (little-endian low word)
+        else:
+            if self._occ_step is None:
+                self._occ_step = torch.zeros(1, dtype=torch.int32, device=d)
+            self._occ_step.fill_(self.step_count)
+            step = self._occ_step
+        if self.encoding != "hash":
+            self.sync_inference_weights()
+        api.occupancy_refresh(self.net, grid=self.hg, table=self.table if self.encoding == "hash" else None, grid_res=R,
+                              density=self.occ_density, decay=decay, thickness_scale=self.density_scale * 2.0 / R,
+                              threshold=threshold, threshold_mode=modes[threshold_mode], jitter=jitter, seed=self._occ_seed,
+                              step=step, occupancy=self.occ, coarse=self.coarse, bricks=self.bricks, super_mip=self.super_mip,
+                              occupied=self._occ_out[0], mean=self._occ_out[1], workspace=self._occ_ws, runs_per_pass=P)
+        for ref in getattr(self, "_pipelines", []):
+            pipe = ref()
+            if pipe is not None and pipe.occ is not None:
+                pipe.set_occupancy(self.occ)     # stream-ordered behind the refresh: the renderer rebuilds its own hierarchy
+        return None
+
+    def occupancy_stats(self):
+        """(occupied fraction, mean of occ_density) as the last refresh_occupancy() left them; synchronises."""
+        if self._occ_out is None:
+            raise RuntimeError("occupancy_stats: call refresh_occupancy() first")
+        return int(self._occ_out[0].item()) / float(self.R ** 3), float(self._occ_out[1].item())
 
     def _set_occupancy(self, occ):
         """Install a new occupancy bitfield.  The four traversal inputs (fine bits, 4^3 mip, bricks, 16^3 mip) keep their
