@@ -21,6 +21,14 @@ int require_device();
 // path uses it any more.
 hipError_t zero_words(void* p, size_t n_words, hipStream_t stream);
 
+// Per-device launch helpers (a process may drive several GPUs, and they need not be alike).  Library-internal: hidden, so the
+// exported symbol list stays the C ABI's.
+// Compute units of the current device, for the persistent grids; 256 where the runtime reports none.
+__attribute__((visibility("hidden"))) hipError_t cu_count(int* n_cu);
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel), again only for a larger size: not repeated in front
+// of every launch, and never inside a stream capture after the first, un-captured, call.
+__attribute__((visibility("hidden"))) hipError_t set_lds_once(const void* fn, size_t bytes);
+
 // The rules of a training background (rtxn_train_background, include/rtxn.h), host only: RTXN_ERR_INVALID with a message, or
 // RTXN_OK with *active = whether a background is composited at all.
 int check_train_background(const rtxn_train_background* bg, int vr_mode, const char* who, bool* active);

@@ -1,8 +1,10 @@
-// Error plumbing and version of librtxn.so.
+// Error plumbing, per-device launch helpers and version of librtxn.so.
 #include "common.h"
 
 #include <cstdarg>
 #include <cstdio>
+#include <mutex>
+#include <vector>
 
 namespace rtxn {
 
@@ -42,6 +44,34 @@ hipError_t zero_words(void* p, size_t n_words, hipStream_t stream) {
   const size_t blocks = (n_words + 255) / 256;
   zero_words_kernel<<<(unsigned)(blocks > 1024 ? 1024 : blocks), 256, 0, stream>>>(static_cast<unsigned*>(p), n_words);
   return hipGetLastError();
+}
+
+hipError_t cu_count(int* n_cu) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e == hipSuccess && *n_cu <= 0) *n_cu = 256;
+  return e;
+}
+
+hipError_t set_lds_once(const void* fn, size_t bytes) {
+  struct Seen { int dev; const void* fn; size_t bytes; };
+  static std::mutex mu;
+  static std::vector<Seen> seen;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  for (Seen& q : seen)
+    if (q.dev == dev && q.fn == fn) {
+      if (q.bytes >= bytes) return hipSuccess;
+      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+      if (e == hipSuccess) q.bytes = bytes;
+      return e;
+    }
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) seen.push_back(Seen{dev, fn, bytes});
+  return e;
 }
 
 }  // namespace rtxn

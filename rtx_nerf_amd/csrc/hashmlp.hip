@@ -26,7 +26,6 @@
 #include "common.h"
 
 #include <cstring>
-#include <mutex>
 
 #include "hashgrid_internal.h"
 #include "mlp_internal.h"
@@ -344,27 +343,12 @@ __global__ __launch_bounds__(kThreads, 3) void mlp_enc_fwd16_kernel(EncFwdArgs a
 typedef void (*hashmlp_fn)(HashMlpArgs);
 typedef void (*encfwd_fn)(EncFwdArgs);
 
-// hipFuncSetAttribute once per (device, kernel, size): never inside a stream capture after the first, un-captured, call
-hipError_t set_lds_once(const void* fn, size_t lds) {
-  struct Seen { int dev; const void* fn; size_t lds; };
-  static std::mutex mu;
-  static Seen seen[128];
-  static int n_seen = 0;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lock(mu);
-  for (int i = 0; i < n_seen; ++i)
-    if (seen[i].dev == dev && seen[i].fn == fn && seen[i].lds >= lds) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess && n_seen < 128) seen[n_seen++] = Seen{dev, fn, lds};
-  return e;
-}
+using rtxn::set_lds_once;
 
 // persistent grid: as many blocks as stay resident (LDS- and register-bound: 3 per CU for the 4x64 model)
 long persistent_grid(long n_wave_tiles, size_t lds, int reserved_cus) {
-  int dev = 0, n_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
+  int n_cu = 0;
+  if (rtxn::cu_count(&n_cu) != hipSuccess) n_cu = 256;
   const int by_lds = (int)((160 * 1024) / lds), per_cu = by_lds < 3 ? (by_lds > 0 ? by_lds : 1) : 3;
   long grid = (n_wave_tiles + kWaves - 1) / kWaves;
   const long cap = (long)(n_cu - reserved_cus > 1 ? n_cu - reserved_cus : 1) * per_cu;

@@ -43,7 +43,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -1052,26 +1051,14 @@ int launch_fwd(const rtxn_mlp* m, FwdArgs& a, int in_mode, int out_mode, long n_
   a.n_hidden = m->cfg.n_hidden_layers;
   a.out_act = m->cfg.output_activation;
   // CU count and the dynamic-LDS attribute are per DEVICE: a process may drive several GPUs (and they need not be alike)
-  int dev = 0, n_cu = 0;
-  RTXN_HIP(hipGetDevice(&dev));
-  RTXN_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (n_cu <= 0) n_cu = 256;
+  int n_cu = 0;
+  RTXN_HIP(rtxn::cu_count(&n_cu));
   const int cus = n_cu - m->reserved_cus > 1 ? n_cu - m->reserved_cus : 1;
   long grid = n_tiles < (long)cus * v.blocks_per_cu ? n_tiles : (long)cus * v.blocks_per_cu;  // persistent grid
   if (grid < 1) grid = 1;
   fwd_fn fn = v.fn[in_mode][out_mode];
   if (!fn) { rtxn::set_error("mlp forward: no kernel for input mode %d / output mode %d", in_mode, out_mode); return RTXN_ERR_UNSUPPORTED; }
-  {
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_set[kMaxDev][16][2][4] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    const bool known = dev >= 0 && dev < kMaxDev && attr_set[dev][m->variant][in_mode][out_mode];
-    if (!known) {
-      RTXN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds));
-      if (dev >= 0 && dev < kMaxDev) attr_set[dev][m->variant][in_mode][out_mode] = true;
-    }
-  }
+  RTXN_HIP(rtxn::set_lds_once(reinterpret_cast<const void*>(fn), v.lds));
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)v.threads), v.lds, s, a);
   RTXN_LAUNCH_CHECK("mlp_fwd16_kernel");
   return RTXN_OK;

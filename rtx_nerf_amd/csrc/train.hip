@@ -2809,11 +2809,82 @@ extern "C" int rtxn_set_deterministic_workspace(void* mlp_shadow, void* table_sh
 
 extern "C" long rtxn_padded_samples(long n_samples) { return n_samples < 0 ? -1 : padded(n_samples); }
 
+// ---------------------------------------------------------------------------- host layer: what the entries below share
+// Environment switches of this file.  Read ONCE per process (function-local statics of train_forward_impl, at its first call):
+//   RTXN_TRAIN_FWD16=0       outputs-only forward, 64 wide: the 32x32x16 kernel of this file, not hashmlp.hip's 16x16x32 one (A/B)
+//   RTXN_TRAIN_FWD_WAVES=8   128 wide: 8-wave forward blocks with double-buffered weights (experiment)
+//   RTXN_TRAIN_FWD_ALONE=1   diagnostic: 40 KiB of unused LDS, so that one forward block fits a CU
+// Read on EVERY call (a test or a probe switches them between two trainers of one process):
+//   RTXN_TRAIN_LEAN_FUSED=0  rtxn_train_gradients on the lean path: the staged encoder, not the folded one (A/B)
+//   RTXN_LEAN_SPLIT          lean weight gradient: "s1,s2" = CU split of the three passes, 0 = one launch per pass
+
+// dc of every per-stage entry point: the host's count as passed (see DevCount)
+constexpr DevCount kHostCount{nullptr, 0};
+
+// The training workspace, saved-activation (rtxn_mlp_train_workspace_bytes) or lean (rtxn_mlp_train_lean_workspace_bytes), as byte
+// offsets from its base.  The ONE place that knows the layout: the *_workspace_bytes entries return `bytes`, the forward and
+// the backward launchers take every pointer from here.
+//   [acts [L][W][Sp] |] dz [L][W][Sp] | dzL [16][Sp] | sign masks [L][Sp] x 16 B | one live flag per 256-sample tile, padded to 16 B
+// fp16 up to the masks; lean: no acts.
+struct TrainWs {
+  size_t acts, dz, dzL, masks, live_tiles, bytes;   // acts: 0 and not used when lean
+  TrainWs(const rtxn_mlp* m, long n_samples, bool lean) {
+    const size_t Sp = (size_t)padded(n_samples), L = (size_t)m->cfg.n_hidden_layers, W = (size_t)m->cfg.n_neurons;
+    acts = 0;
+    dz = lean ? 0 : L * W * Sp * sizeof(_Float16);
+    dzL = dz + L * W * Sp * sizeof(_Float16);
+    masks = dzL + 16 * Sp * sizeof(_Float16);
+    live_tiles = masks + L * Sp * 16;
+    bytes = live_tiles + (Sp / kTile + 15) / 16 * 16;
+  }
+  template <class T>
+  static T* at(void* workspace, size_t offset) { return reinterpret_cast<T*>(static_cast<uint8_t*>(workspace) + offset); }
+};
+
+// live-segment workspace (rtxn_live_segments): [int count | 12 B pad | int list[capacity] | uint8 flags[capacity]]
+static size_t live_ws_bytes(long capacity) { return (size_t)(16 + 4 * capacity + ((capacity + 15) / 16) * 16); }
+static const int* live_count_of(const void* ws) { return static_cast<const int*>(ws); }
+static const int* live_list_of(const void* ws) { return reinterpret_cast<const int*>(static_cast<const uint8_t*>(ws) + 16); }
+static uint8_t* live_flags_of(void* ws, long capacity) { return static_cast<uint8_t*>(ws) + 16 + 4 * capacity; }
+
+// The segments a launcher runs over: empty = all of them, in order; otherwise the list and the device count of a live-segment workspace
+struct LiveRef {
+  const int* list = nullptr;
+  const int* count = nullptr;
+  LiveRef() = default;
+  explicit LiveRef(const void* live_ws) : list(live_ws ? live_list_of(live_ws) : nullptr), count(live_ws ? live_count_of(live_ws) : nullptr) {}
+};
+
+// What the forward and both backward chains set the same way; a launcher adds its weights, its tensors and its outputs
+static TrainArgs train_args(const rtxn_mlp* m, long n_samples, DevCount dc, LiveRef live) {
+  TrainArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n_hidden = m->cfg.n_hidden_layers, a.out_act = m->cfg.output_activation, a.E = m->enc_padded;
+  a.S = n_samples, a.Sp = padded(n_samples), a.dc = dc;
+  a.live_list = live.list, a.live_count = live.count;
+  return a;
+}
+
+// n_samples of a training entry: in range, and whole segments where a live list (32-sample segments) is involved
+static int check_n_samples(const char* who, long n_samples, bool whole_segments) {
+  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples && (!whole_segments || n_samples % 32 == 0),
+               whole_segments ? "%s: n_samples = %ld must be whole segments in [0, %ld]" : "%s: n_samples = %ld out of [0, %ld]", who, n_samples, kMaxTrainSamples);
+  return RTXN_OK;
+}
+
+// The checks every training entry opens with, in this order: the model, the sample count, the device
+static int check_entry(const rtxn_mlp* m, const char* who, long n_samples, bool whole_segments) {
+  int rc = check_train(m, who);
+  if (rc != RTXN_OK) return rc;
+  rc = check_n_samples(who, n_samples, whole_segments);
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  return RTXN_OK;
+}
+
 extern "C" size_t rtxn_mlp_train_workspace_bytes(const rtxn_mlp* m, long n_samples) {
   if (!m || n_samples < 0) return 0;
-  const long Sp = padded(n_samples), W = m->cfg.n_neurons, L = m->cfg.n_hidden_layers;
-  // acts | dz | dzL | sign masks (16 B per sample and layer) | one live flag per 256-sample tile
-  return (size_t)((2 * L * W + 16 + 8 * L) * Sp) * sizeof(_Float16) + (size_t)((Sp / kTile + 15) / 16 * 16);
+  return TrainWs(m, n_samples, false).bytes;
 }
 
 // In every *_impl below: dc.total_segments == NULL: n_samples is the batch's; otherwise n_samples is the CAPACITY (grids, row
@@ -2836,7 +2907,7 @@ extern "C" int rtxn_encode_frequency(const rtxn_mlp* m, const float* input, void
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(input && encT, "rtxn_encode_frequency: NULL buffer");
   const SampleSrc src{input, nullptr, nullptr, nullptr, 0};
-  return encode_frequency_impl(m, src, encT, nullptr, 1.0f, n_samples, DevCount{nullptr, 0}, stream);
+  return encode_frequency_impl(m, src, encT, nullptr, 1.0f, n_samples, kHostCount, stream);
 }
 
 static int check_segments(const char* who, const float* start_points, const float* end_points, const float* seg_view,
@@ -2859,169 +2930,121 @@ extern "C" int rtxn_encode_frequency_segments(const rtxn_mlp* m, const float* st
   if (n_segments == 0) return RTXN_OK;
   RTXN_REQUIRE(encT, "rtxn_encode_frequency_segments: NULL buffer");
   const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return encode_frequency_impl(m, src, encT, t_vals, t_scale, n_segments * 32, DevCount{nullptr, 0}, stream);
+  return encode_frequency_impl(m, src, encT, t_vals, t_scale, n_segments * 32, kHostCount, stream);
 }
 
-// live-segment workspace (rtxn_live_segments): [int count | 12 B pad | int list[capacity] | uint8 flags[capacity]]
-static size_t live_ws_bytes(long capacity) { return (size_t)(16 + 4 * capacity + ((capacity + 15) / 16) * 16); }
-static const int* live_count_of(const void* ws) { return static_cast<const int*>(ws); }
-static const int* live_list_of(const void* ws) { return reinterpret_cast<const int*>(static_cast<const uint8_t*>(ws) + 16); }
+using rtxn::set_lds_once;
 
-// hipFuncSetAttribute once per (device, kernel): not repeated in front of every launch (and never inside a stream capture
-// after the first, un-captured, call)
-static hipError_t set_lds_once(const void* fn, int bytes) {
-  struct Seen { int dev; const void* fn; int bytes; };
-  static std::mutex mu;
-  static std::vector<Seen> seen;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lock(mu);
-  for (Seen& q : seen)
-    if (q.dev == dev && q.fn == fn) {
-      if (q.bytes >= bytes) return hipSuccess;
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-      if (e == hipSuccess) q.bytes = bytes;
-      return e;
-    }
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) seen.push_back(Seen{dev, fn, bytes});
-  return e;
-}
+// What a forward launch may ask for beyond its buffers; a caller names what it sets
+struct FwdOpts {
+  int save = kSaveAll;             // kSaveNone: outputs only, `workspace` is not touched (the forward half of the recompute path);
+                                   // kSaveAll: `workspace` is the saved-activation workspace; kSaveMasks: it is the lean one
+  LiveRef live;
+  const SampleSrc* src = nullptr;  // kSaveMasks only: the encoder fused into the kernel (the reference's Composite-Frequency(3 x 10, 2 x 12)); encT is not read
+  float* t_vals = nullptr;         // with src: the sampler's t_vals, if asked for
+  float t_scale = 1.0f;
+};
 
-// workspace == NULL: outputs only (the forward half of the recompute path)
-// lean: `workspace` is the lean workspace (rtxn_mlp_train_lean_workspace_bytes): outputs + sign masks, no activations
-// src != NULL (lean only): the encoder fused into the kernel (the reference's Composite-Frequency(3 x 10, 2 x 12)); encT is not read
 static int train_forward_impl(const rtxn_mlp* m, const void* encT, long n_samples, void* workspace, void* output_half,
-                              float* radiance, DevCount dc, rtxn_stream_t stream, const int* live_list = nullptr,
-                              const int* live_count = nullptr, bool lean = false, const SampleSrc* src = nullptr, float* t_vals = nullptr,
-                              float t_scale = 1.0f) {
+                              float* radiance, DevCount dc, rtxn_stream_t stream, const FwdOpts& o) {
   const int W = m->cfg.n_neurons;
   const long Sp = padded(n_samples);
   // outputs only, 64 wide: the all-asm 16x16x32 kernel with the weights resident in LDS (hashmlp.hip) -- the same layer stack
   // the fused hash-grid inference kernel runs.  RTXN_TRAIN_FWD16=0: the 32x32x16 kernel below (A/B).
-  if (!workspace && rtxn::enc_forward16_supported(m)) {
+  if (o.save == kSaveNone && rtxn::enc_forward16_supported(m)) {
     static const bool use16 = !(getenv("RTXN_TRAIN_FWD16") && atoi(getenv("RTXN_TRAIN_FWD16")) == 0);
     if (use16) return rtxn::launch_enc_forward16(m, encT, n_samples, Sp, dc.total_segments, dc.capacity, output_half, radiance, rtxn::as_stream(stream));
   }
-  TrainArgs a;
-  memset(&a, 0, sizeof(a));
+  TrainArgs a = train_args(m, n_samples, dc, o.live);
   a.packed = static_cast<const uint8_t*>(m->packed_train);
-  a.n_hidden = m->cfg.n_hidden_layers;
-  a.out_act = m->cfg.output_activation;
-  a.E = m->enc_padded;
-  a.S = n_samples;
-  a.Sp = Sp;
-  a.dc = dc;
   a.encT = static_cast<const _Float16*>(encT);
-  if (workspace && lean) {
-    a.masks = reinterpret_cast<unsigned long long*>(static_cast<_Float16*>(workspace) + ((long)m->cfg.n_hidden_layers * W + 16) * Sp);
-  } else if (workspace) {
-    a.acts = static_cast<_Float16*>(workspace);
-    a.masks = reinterpret_cast<unsigned long long*>(static_cast<_Float16*>(workspace) + (2L * m->cfg.n_hidden_layers * W + 16) * Sp);
+  if (o.save != kSaveNone) {
+    const TrainWs ws(m, n_samples, o.save == kSaveMasks);
+    if (o.save == kSaveAll) a.acts = TrainWs::at<_Float16>(workspace, ws.acts);
+    a.masks = TrainWs::at<unsigned long long>(workspace, ws.masks);
   }
   a.out_half = static_cast<_Float16*>(output_half);
   a.radiance = reinterpret_cast<float4*>(radiance);
-  a.live_list = live_list;
-  a.live_count = live_count;
-  if (src) {
-    a.src = *src;
-    a.t_vals = t_vals;
-    a.t_scale = t_scale;
+  if (o.src) {
+    a.src = *o.src;
+    a.t_vals = o.t_vals;
+    a.t_scale = o.t_scale;
   }
   const int RT = W / 32, KS = W / 16, KS0 = a.E / 16;
   // 128 wide, RTXN_TRAIN_FWD_WAVES=8: 8-wave blocks of 512 samples with double-buffered weights.  Built on the guess that the kernel
   // is paced by its weight stream; the same-box A/B says it is not (outputs only 1.050 against 1.068 ms per 4.7 M samples, with the
   // sign masks 1.43 against 1.35: the double buffer's vmcnt(0) also waits for the mask stores), so the 4-wave form stays the default.
   static const bool waves8 = getenv("RTXN_TRAIN_FWD_WAVES") && atoi(getenv("RTXN_TRAIN_FWD_WAVES")) == 8;
-  const int NW = W == 128 && waves8 && !src ? 8 : 4;
+  const int NW = W == 128 && waves8 && !o.src ? 8 : 4;
   // (RTXN_TRAIN_FWD_ALONE=1, diagnostic: 40 KiB of LDS nobody uses, so that only ONE block fits a CU -- what a block's phases cost
   // without a partner on its SIMDs: profiles/r04/fwd_stamps.txt)
   static const bool alone = getenv("RTXN_TRAIN_FWD_ALONE") && atoi(getenv("RTXN_TRAIN_FWD_ALONE")) == 1;
   const size_t lds = (size_t)(KS0 > KS ? KS0 : KS) * RT * 1024 * (NW == 8 ? 2 : 1) + NW * kEncScratch + (alone ? 40 * 1024 : 0);
-  hipStream_t s = rtxn::as_stream(stream);
-  const dim3 grid((unsigned)((Sp + 64 * NW - 1) / (64 * NW))), block(64 * NW);
-#define RTXN_FWD_LAUNCH(WW, SAVE, NWV)                                                                        \
-  do {                                                                                                        \
-    RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(mlp_train_fwd_kernel<WW, SAVE, NWV>), (int)lds));      \
-    hipLaunchKernelGGL((mlp_train_fwd_kernel<WW, SAVE, NWV>), grid, block, lds, s, a);                         \
-  } while (0)
-  if (src) {
-    RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(mlp_train_fwd_kernel<128, kSaveMasks, 4, 1>), (int)lds));
-    hipLaunchKernelGGL((mlp_train_fwd_kernel<128, kSaveMasks, 4, 1>), grid, block, lds, s, a);
-  } else if (W == 64) { if (workspace) RTXN_FWD_LAUNCH(64, kSaveAll, 4); else RTXN_FWD_LAUNCH(64, kSaveNone, 4); }
-  else if (NW == 8) {
-    if (lean) RTXN_FWD_LAUNCH(128, kSaveMasks, 8);
-    else if (workspace) RTXN_FWD_LAUNCH(128, kSaveAll, 8);
-    else RTXN_FWD_LAUNCH(128, kSaveNone, 8);
-  } else if (lean) RTXN_FWD_LAUNCH(128, kSaveMasks, 4);
-  else         { if (workspace) RTXN_FWD_LAUNCH(128, kSaveAll, 4); else RTXN_FWD_LAUNCH(128, kSaveNone, 4); }
-#undef RTXN_FWD_LAUNCH
-  RTXN_LAUNCH_CHECK(workspace ? "mlp_train_fwd_kernel" : "mlp_train_fwd_kernel<outputs only>");
+  typedef void (*fwd_fn)(TrainArgs);
+  // [128 wide][save mode][4 waves | 8 waves | 4 waves with the encoder fused]; NULL: not built (64 wide has one form and no lean path)
+  static const fwd_fn table[2][3][3] = {
+      {{mlp_train_fwd_kernel<64, kSaveNone, 4>, nullptr, nullptr}, {mlp_train_fwd_kernel<64, kSaveAll, 4>, nullptr, nullptr}, {nullptr, nullptr, nullptr}},
+      {{mlp_train_fwd_kernel<128, kSaveNone, 4>, mlp_train_fwd_kernel<128, kSaveNone, 8>, nullptr},
+       {mlp_train_fwd_kernel<128, kSaveAll, 4>, mlp_train_fwd_kernel<128, kSaveAll, 8>, nullptr},
+       {mlp_train_fwd_kernel<128, kSaveMasks, 4>, mlp_train_fwd_kernel<128, kSaveMasks, 8>, mlp_train_fwd_kernel<128, kSaveMasks, 4, 1>}}};
+  const fwd_fn fn = table[W == 128][o.save][o.src ? 2 : NW == 8];
+  if (!fn) { rtxn::set_error("mlp_train_fwd_kernel: not built %d wide with save mode %d%s", W, o.save, o.src ? " and the encoder fused" : ""); return RTXN_ERR_UNSUPPORTED; }
+  RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(fn), lds));
+  hipLaunchKernelGGL(fn, dim3((unsigned)((Sp + 64 * NW - 1) / (64 * NW))), dim3(64 * NW), lds, rtxn::as_stream(stream), a);
+  RTXN_LAUNCH_CHECK(o.save != kSaveNone ? "mlp_train_fwd_kernel" : "mlp_train_fwd_kernel<outputs only>");
   return RTXN_OK;
 }
 
 extern "C" int rtxn_mlp_train_forward(const rtxn_mlp* m, const void* encT, long n_samples, void* workspace,
                                       void* output_half, float* radiance, rtxn_stream_t stream) {
-  int rc = check_train(m, "rtxn_mlp_train_forward");
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples, "rtxn_mlp_train_forward: n_samples = %ld out of [0, %ld]", n_samples, kMaxTrainSamples);
-  RTXN_DEVICE_OR_FAIL();
-  if (n_samples == 0) return RTXN_OK;
+  const int rc = check_entry(m, "rtxn_mlp_train_forward", n_samples, false);
+  if (rc != RTXN_OK || n_samples == 0) return rc;
   RTXN_REQUIRE(encT && workspace && output_half, "rtxn_mlp_train_forward: NULL buffer");
-  return train_forward_impl(m, encT, n_samples, workspace, output_half, radiance, DevCount{nullptr, 0}, stream);
+  return train_forward_impl(m, encT, n_samples, workspace, output_half, radiance, kHostCount, stream, FwdOpts());
 }
 
 extern "C" int rtxn_mlp_train_forward_live(const rtxn_mlp* m, const void* encT, long n_samples, void* workspace, const void* live_ws,
                                            rtxn_stream_t stream) {
-  int rc = check_train(m, "rtxn_mlp_train_forward_live");
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples && n_samples % 32 == 0,
-               "rtxn_mlp_train_forward_live: n_samples = %ld must be whole segments in [0, %ld]", n_samples, kMaxTrainSamples);
-  RTXN_DEVICE_OR_FAIL();
-  if (n_samples == 0) return RTXN_OK;
+  const int rc = check_entry(m, "rtxn_mlp_train_forward_live", n_samples, true);
+  if (rc != RTXN_OK || n_samples == 0) return rc;
   RTXN_REQUIRE(encT && workspace && live_ws, "rtxn_mlp_train_forward_live: NULL buffer");
-  return train_forward_impl(m, encT, n_samples, workspace, nullptr, nullptr, DevCount{nullptr, 0}, stream, live_list_of(live_ws),
-                            live_count_of(live_ws));
+  FwdOpts o;
+  o.live = LiveRef(live_ws);
+  return train_forward_impl(m, encT, n_samples, workspace, nullptr, nullptr, kHostCount, stream, o);
+}
+
+// The backward chain over a: dZ of every layer (a.dz, a.dzL), the tiles that carry one (a.live_tiles), dencT if asked for
+static int launch_bwd_chain(const rtxn_mlp* m, const TrainArgs& a, hipStream_t s) {
+  const int W = m->cfg.n_neurons, RT = W / 32, KS = W / 16, RTE = (a.E + 31) / 32;
+  const size_t lds = (size_t)(RTE > RT ? RTE : RT) * KS * 1024;
+  typedef void (*bwd_fn)(TrainArgs);
+  const bwd_fn fn = W == 64 ? mlp_bwd_kernel<64> : mlp_bwd_kernel<128>;
+  RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(fn), lds));
+  hipLaunchKernelGGL(fn, dim3((unsigned)(a.Sp / kTile)), dim3(kThreads), lds, s, a);
+  RTXN_LAUNCH_CHECK("mlp_bwd_kernel");
+  return RTXN_OK;
 }
 
 static int train_backward_impl(const rtxn_mlp* m, const void* encT, const void* output_half, const void* dout_half4,
                                long n_samples, void* workspace, float* dparams, void* dencT, DevCount dc, rtxn_stream_t stream,
-                               const int* live_list = nullptr, const int* live_count = nullptr) {
+                               LiveRef live = LiveRef()) {
   const int W = m->cfg.n_neurons, L = m->cfg.n_hidden_layers, E = m->enc_padded;
   const long Sp = padded(n_samples);
-  _Float16* ws = static_cast<_Float16*>(workspace);
-  TrainArgs a;
-  memset(&a, 0, sizeof(a));
+  const TrainWs ws(m, n_samples, false);
+  TrainArgs a = train_args(m, n_samples, dc, live);
   a.packed = static_cast<const uint8_t*>(m->packed_t);
-  a.n_hidden = L;
-  a.out_act = m->cfg.output_activation;
-  a.E = E;
-  a.S = n_samples;
-  a.Sp = Sp;
-  a.dc = dc;
   a.encT = static_cast<const _Float16*>(encT);
-  a.acts = ws;
-  a.dz = ws + (long)L * W * Sp;
-  a.dzL = ws + 2L * L * W * Sp;
-  a.masks = reinterpret_cast<unsigned long long*>(ws + (2L * L * W + 16) * Sp);
-  a.live_tiles = reinterpret_cast<uint8_t*>(ws + (2L * L * W + 16 + 8L * L) * Sp);
-  a.live_list = live_list;
-  a.live_count = live_count;
+  a.acts = TrainWs::at<_Float16>(workspace, ws.acts);
+  a.dz = TrainWs::at<_Float16>(workspace, ws.dz);
+  a.dzL = TrainWs::at<_Float16>(workspace, ws.dzL);
+  a.masks = TrainWs::at<unsigned long long>(workspace, ws.masks);
+  a.live_tiles = TrainWs::at<uint8_t>(workspace, ws.live_tiles);
   a.out_half = const_cast<_Float16*>(static_cast<const _Float16*>(output_half));
   a.dout = static_cast<const _Float16*>(dout_half4);
   a.dencT = static_cast<_Float16*>(dencT);
-  const int RT = W / 32, KS = W / 16, RTE = (E + 31) / 32;
-  const size_t lds = (size_t)(RTE > RT ? RTE : RT) * KS * 1024;
   hipStream_t s = rtxn::as_stream(stream);
-  if (W == 64) {
-    RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(mlp_bwd_kernel<64>), (int)lds));
-    hipLaunchKernelGGL(mlp_bwd_kernel<64>, dim3((unsigned)(Sp / kTile)), dim3(kThreads), lds, s, a);
-  } else {
-    RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(mlp_bwd_kernel<128>), (int)lds));
-    hipLaunchKernelGGL(mlp_bwd_kernel<128>, dim3((unsigned)(Sp / kTile)), dim3(kThreads), lds, s, a);
-  }
-  RTXN_LAUNCH_CHECK("mlp_bwd_kernel");
+  int rc = launch_bwd_chain(m, a, s);
+  if (rc != RTXN_OK) return rc;
   // weight gradients of all layers in one launch: dW_l += dZ_l X_l^T, X_0 = enc, X_l = acts[l-1], X_L = acts[L-1]
   RTXN_REQUIRE(L + 1 <= 17, "rtxn_mlp_train_backward: %d layers exceed the weight-gradient launch table", L + 1);
   WgradArgs wa;
@@ -3029,8 +3052,7 @@ static int train_backward_impl(const rtxn_mlp* m, const void* encT, const void* 
   wa.Sp = Sp;
   wa.dc = dc;
   wa.live_tiles = a.live_tiles;
-  wa.live_list = live_list;
-  wa.live_count = live_count;
+  wa.live_list = live.list, wa.live_count = live.count;
   wa.chunk = 1024;
   const unsigned kblocks = (unsigned)((Sp + 4 * wa.chunk - 1) / (4 * wa.chunk));
   long poff = 0;
@@ -3056,7 +3078,7 @@ static int train_backward_impl(const rtxn_mlp* m, const void* encT, const void* 
   }
   if (wa.lds_path) {
     WgradArgs wl = wa;
-    wl.chunk = wgrad_chunk(Sp, L + 1, live_list != nullptr);
+    wl.chunk = wgrad_chunk(Sp, L + 1, live.list != nullptr);
     RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(wgrad_lds_kernel), kWgStages * kWgStage));
     wgrad_lds_kernel<<<dim3((unsigned)((Sp + wl.chunk - 1) / wl.chunk), (unsigned)(L + 1)), kThreads, kWgStages * kWgStage, s>>>(wl);
     RTXN_LAUNCH_CHECK("wgrad_lds_kernel");
@@ -3067,17 +3089,14 @@ static int train_backward_impl(const rtxn_mlp* m, const void* encT, const void* 
 extern "C" int rtxn_mlp_train_backward(const rtxn_mlp* m, const void* encT, const void* output_half,
                                        const void* dout_half4, long n_samples, void* workspace, float* dparams,
                                        void* dencT, rtxn_stream_t stream) {
-  int rc = check_train(m, "rtxn_mlp_train_backward");
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples, "rtxn_mlp_train_backward: n_samples = %ld out of [0, %ld]", n_samples, kMaxTrainSamples);
-  RTXN_DEVICE_OR_FAIL();
-  if (n_samples == 0) return RTXN_OK;
+  const int rc = check_entry(m, "rtxn_mlp_train_backward", n_samples, false);
+  if (rc != RTXN_OK || n_samples == 0) return rc;
   RTXN_REQUIRE(encT && output_half && dout_half4 && workspace && dparams, "rtxn_mlp_train_backward: NULL buffer");
-  return train_backward_impl(m, encT, output_half, dout_half4, n_samples, workspace, dparams, dencT, DevCount{nullptr, 0}, stream);
+  return train_backward_impl(m, encT, output_half, dout_half4, n_samples, workspace, dparams, dencT, kHostCount, stream);
 }
 
 // ---- lean path (128-wide models): forward with sign masks only, dgrad chain, weight gradient with recomputed activations ----
-// Workspace (halfs): dz [L][128][Sp] | dzL [16][Sp] | sign masks [L][Sp] x 16 B | one live flag per 256-sample tile.
+// (its workspace: TrainWs without acts)
 extern "C" int rtxn_mlp_train_lean_supported(const rtxn_mlp* m) {
   if (!m) return 0;
   return m->cfg.n_neurons == 128 && m->cfg.n_hidden_layers == 8 && m->enc_padded == 112;
@@ -3085,64 +3104,46 @@ extern "C" int rtxn_mlp_train_lean_supported(const rtxn_mlp* m) {
 
 extern "C" size_t rtxn_mlp_train_lean_workspace_bytes(const rtxn_mlp* m, long n_samples) {
   if (!rtxn_mlp_train_lean_supported(m) || n_samples < 0) return 0;
-  const long Sp = padded(n_samples), W = m->cfg.n_neurons, L = m->cfg.n_hidden_layers;
-  return (size_t)((L * W + 16 + 8 * L) * Sp) * sizeof(_Float16) + (size_t)((Sp / kTile + 15) / 16 * 16);
+  return TrainWs(m, n_samples, true).bytes;
 }
 
 // src != NULL: the weight gradient recomputes the ENCODING too (the reference's Composite-Frequency model); encT is not read
 static int train_backward_lean_impl(const rtxn_mlp* m, const void* encT, const void* output_half, const void* dout_half4,
                                     long n_samples, void* workspace, float* dparams, DevCount dc, rtxn_stream_t stream,
-                                    const int* live_list = nullptr, const int* live_count = nullptr, const SampleSrc* src = nullptr) {
-  const int W = 128, L = m->cfg.n_hidden_layers, E = m->enc_padded;
-  const long Sp = padded(n_samples);
-  _Float16* ws = static_cast<_Float16*>(workspace);
-  TrainArgs a;
-  memset(&a, 0, sizeof(a));
+                                    const SampleSrc* src, LiveRef live = LiveRef()) {
+  const TrainWs ws(m, n_samples, true);
+  TrainArgs a = train_args(m, n_samples, dc, live);
   a.packed = static_cast<const uint8_t*>(m->packed_t);
-  a.n_hidden = L;
-  a.out_act = m->cfg.output_activation;
-  a.E = E;
-  a.S = n_samples;
-  a.Sp = Sp;
-  a.dc = dc;
   a.encT = static_cast<const _Float16*>(encT);
-  a.dz = ws;
-  a.dzL = ws + (long)L * W * Sp;
-  a.masks = reinterpret_cast<unsigned long long*>(ws + ((long)L * W + 16) * Sp);
-  a.live_tiles = reinterpret_cast<uint8_t*>(ws + ((long)L * W + 16 + 8L * L) * Sp);
+  a.dz = TrainWs::at<_Float16>(workspace, ws.dz);
+  a.dzL = TrainWs::at<_Float16>(workspace, ws.dzL);
+  a.masks = TrainWs::at<unsigned long long>(workspace, ws.masks);
+  a.live_tiles = TrainWs::at<uint8_t>(workspace, ws.live_tiles);
   a.skip_last_dz = src ? 1 : 0;     // the folded weight-gradient kernel forms the last hidden layer's dZ itself
-  a.live_list = live_list;
-  a.live_count = live_count;
   a.out_half = const_cast<_Float16*>(static_cast<const _Float16*>(output_half));
   a.dout = static_cast<const _Float16*>(dout_half4);
-  const int RT = W / 32, KS = W / 16;
-  const size_t lds = (size_t)RT * KS * 1024;
   hipStream_t s = rtxn::as_stream(stream);
-  RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(mlp_bwd_kernel<128>), (int)lds));
-  hipLaunchKernelGGL(mlp_bwd_kernel<128>, dim3((unsigned)(Sp / kTile)), dim3(kThreads), lds, s, a);
-  RTXN_LAUNCH_CHECK("mlp_bwd_kernel");
+  int rc = launch_bwd_chain(m, a, s);
+  if (rc != RTXN_OK) return rc;
   LeanArgs la;
   memset(&la, 0, sizeof(la));
   la.packed_fwd = static_cast<const uint8_t*>(m->packed_train);
   la.out_act = a.out_act;
   la.S = n_samples;
-  la.Sp = Sp;
+  la.Sp = a.Sp;
   la.dc = dc;
-  la.n_tiles = (int)(Sp / kTile);
+  la.n_tiles = (int)(a.Sp / kTile);
   la.encT = a.encT;
   la.dz = a.dz;
   la.dzL = a.dzL;
   la.dparams = dparams;
   la.live_tiles = a.live_tiles;
-  la.live_list = live_list;
-  la.live_count = live_count;
+  la.live_list = live.list, la.live_count = live.count;
   la.det = det_ctx(dparams, m->n_params, g_det_mlp);
   if (src) la.src = *src;
   la.packed_bwd = static_cast<const uint8_t*>(m->packed_t);
-  int dev = 0, n_cu = 0;
-  RTXN_HIP(hipGetDevice(&dev));
-  RTXN_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (n_cu <= 0) n_cu = 256;
+  int n_cu = 0;
+  RTXN_HIP(rtxn::cu_count(&n_cu));
   const int grid = la.n_tiles < n_cu ? la.n_tiles : n_cu;   // persistent: one block per CU (registers and LDS)
   typedef void (*lean_fn)(LeanArgs);
   // Three passes: layers 0-2 | 3-5 | 6-7 + output -- 192 accumulator registers per wave, 1.9 forward passes of recompute.  (Two
@@ -3163,17 +3164,12 @@ static int train_backward_lean_impl(const rtxn_mlp* m, const void* encT, const v
   }
   const int slots = n_cu / 8;
   if (split[0] > 0 && split[0] < split[1] && split[1] < slots && la.n_tiles >= 4 * n_cu) {
-    if (src) {
-      RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(wgrad_recompute_all_kernel<7, true>), kLnLdsLaunch));
-      hipLaunchKernelGGL((wgrad_recompute_all_kernel<7, true>), dim3((unsigned)(slots * 8)), dim3(kThreads), kLnLdsLaunch, s, la, split[0] * slots / 32, split[1] * slots / 32);
-    } else {
-      RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(wgrad_recompute_all_kernel<7>), kLnLdsLaunch));
-      hipLaunchKernelGGL(wgrad_recompute_all_kernel<7>, dim3((unsigned)(slots * 8)), dim3(kThreads), kLnLdsLaunch, s, la, split[0] * slots / 32, split[1] * slots / 32);
-    }
+    typedef void (*lean_all_fn)(LeanArgs, int, int);
+    const lean_all_fn all = src ? wgrad_recompute_all_kernel<7, true> : wgrad_recompute_all_kernel<7>;
+    RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(all), kLnLdsLaunch));
+    hipLaunchKernelGGL(all, dim3((unsigned)(slots * 8)), dim3(kThreads), kLnLdsLaunch, s, la, split[0] * slots / 32, split[1] * slots / 32);
     RTXN_LAUNCH_CHECK("wgrad_recompute_all_kernel");
-    return det_fold(la.det.q, m->n_params, dparams, nullptr, 0, s);
-  }
-  for (int i = 0; i < n_pass; ++i) {
+  } else for (int i = 0; i < n_pass; ++i) {
     RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(pass[i]), kLnLdsLaunch));
     hipLaunchKernelGGL(pass[i], dim3((unsigned)grid), dim3(kThreads), kLnLdsLaunch, s, la);
     RTXN_LAUNCH_CHECK("wgrad_recompute_kernel");
@@ -3181,6 +3177,7 @@ static int train_backward_lean_impl(const rtxn_mlp* m, const void* encT, const v
   return det_fold(la.det.q, m->n_params, dparams, nullptr, 0, s);
 }
 
+// check_entry of the lean entries, less the device: the model must have the lean path (the text of the count check is the lean entries' own)
 static int check_lean(const rtxn_mlp* m, const char* who, long n_samples, bool whole_segments) {
   int rc = check_train(m, who);
   if (rc != RTXN_OK) return rc;
@@ -3202,7 +3199,9 @@ extern "C" int rtxn_mlp_train_forward_lean(const rtxn_mlp* m, const void* encT, 
   RTXN_DEVICE_OR_FAIL();
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(encT && workspace_lean && output_half, "rtxn_mlp_train_forward_lean: NULL buffer");
-  return train_forward_impl(m, encT, n_samples, workspace_lean, output_half, radiance, DevCount{nullptr, 0}, stream, nullptr, nullptr, true);
+  FwdOpts o;
+  o.save = kSaveMasks;
+  return train_forward_impl(m, encT, n_samples, workspace_lean, output_half, radiance, kHostCount, stream, o);
 }
 
 extern "C" int rtxn_mlp_train_forward_lean_fused_supported(const rtxn_mlp* m) {
@@ -3227,8 +3226,12 @@ extern "C" int rtxn_mlp_train_forward_lean_segments(const rtxn_mlp* m, const flo
   if (n_segments == 0) return RTXN_OK;
   RTXN_REQUIRE(workspace_lean && output_half, "rtxn_mlp_train_forward_lean_segments: NULL buffer");
   const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return train_forward_impl(m, nullptr, n_segments * 32, workspace_lean, output_half, radiance, DevCount{nullptr, 0}, stream, nullptr, nullptr, true, &src,
-                            t_vals, t_scale);
+  FwdOpts o;
+  o.save = kSaveMasks;
+  o.src = &src;
+  o.t_vals = t_vals;
+  o.t_scale = t_scale;
+  return train_forward_impl(m, nullptr, n_segments * 32, workspace_lean, output_half, radiance, kHostCount, stream, o);
 }
 
 #ifdef RTXN_LN_STAMPS
@@ -3249,8 +3252,7 @@ extern "C" int rtxn_mlp_train_backward_lean(const rtxn_mlp* m, const void* encT,
   RTXN_DEVICE_OR_FAIL();
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(encT && output_half && dout_half4 && workspace_lean && dparams, "rtxn_mlp_train_backward_lean: NULL buffer");
-  return train_backward_lean_impl(m, encT, output_half, dout_half4, n_samples, workspace_lean, dparams, DevCount{nullptr, 0}, stream,
-                                  live_ws ? live_list_of(live_ws) : nullptr, live_ws ? live_count_of(live_ws) : nullptr);
+  return train_backward_lean_impl(m, encT, output_half, dout_half4, n_samples, workspace_lean, dparams, kHostCount, stream, nullptr, LiveRef(live_ws));
 }
 
 extern "C" int rtxn_mlp_train_backward_lean_segments(const rtxn_mlp* m, const float* start_points, const float* end_points,
@@ -3270,8 +3272,7 @@ extern "C" int rtxn_mlp_train_backward_lean_segments(const rtxn_mlp* m, const fl
   if (n_segments == 0) return RTXN_OK;
   RTXN_REQUIRE(output_half && dout_half4 && workspace_lean && dparams, "rtxn_mlp_train_backward_lean_segments: NULL buffer");
   const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return train_backward_lean_impl(m, nullptr, output_half, dout_half4, n_segments * 32, workspace_lean, dparams, DevCount{nullptr, 0}, stream,
-                                  live_ws ? live_list_of(live_ws) : nullptr, live_ws ? live_count_of(live_ws) : nullptr, &src);
+  return train_backward_lean_impl(m, nullptr, output_half, dout_half4, n_segments * 32, workspace_lean, dparams, kHostCount, stream, &src, LiveRef(live_ws));
 }
 
 // ---- recompute path (64-wide models): forward without saved activations + fused backward ----
@@ -3282,18 +3283,17 @@ extern "C" int rtxn_mlp_train_recompute_supported(const rtxn_mlp* m) {
 
 extern "C" int rtxn_mlp_train_forward_outputs(const rtxn_mlp* m, const void* encT, long n_samples, void* output_half,
                                               float* radiance, rtxn_stream_t stream) {
-  int rc = check_train(m, "rtxn_mlp_train_forward_outputs");
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples, "rtxn_mlp_train_forward_outputs: n_samples = %ld out of [0, %ld]", n_samples, kMaxTrainSamples);
-  RTXN_DEVICE_OR_FAIL();
-  if (n_samples == 0) return RTXN_OK;
+  const int rc = check_entry(m, "rtxn_mlp_train_forward_outputs", n_samples, false);
+  if (rc != RTXN_OK || n_samples == 0) return rc;
   RTXN_REQUIRE(encT && output_half, "rtxn_mlp_train_forward_outputs: NULL buffer");
-  return train_forward_impl(m, encT, n_samples, nullptr, output_half, radiance, DevCount{nullptr, 0}, stream);
+  FwdOpts o;
+  o.save = kSaveNone;
+  return train_forward_impl(m, encT, n_samples, nullptr, output_half, radiance, kHostCount, stream, o);
 }
 
 static int train_backward_recompute_impl(const rtxn_mlp* m, const void* encT, const void* output_half, const void* dout_half4,
                                          long n_samples, float* dparams, void* dencT, DevCount dc, rtxn_stream_t stream,
-                                         const int* live_list = nullptr, const int* live_count = nullptr) {
+                                         LiveRef live = LiveRef()) {
   const int L = m->cfg.n_hidden_layers, E = m->enc_padded;
   FusedArgs a;
   memset(&a, 0, sizeof(a));
@@ -3312,16 +3312,13 @@ static int train_backward_recompute_impl(const rtxn_mlp* m, const void* encT, co
   a.dout = static_cast<const _Float16*>(dout_half4);
   a.dencT = static_cast<_Float16*>(dencT);
   a.dparams = dparams;
-  a.live_list = live_list;
-  a.live_count = live_count;
+  a.live_list = live.list, a.live_count = live.count;
   a.det = det_ctx(dparams, m->n_params, g_det_mlp);
   const int RT = 2, KS = 4;
   const size_t lds = (size_t)(a.KS0 * RT + (L - 1) * KS * RT) * 1024 + (size_t)(RT + (L - 1) * RT * KS + ((E + 31) / 32) * KS) * 1024 +
                      8 * (size_t)kImgBytes;
-  int dev = 0, n_cu = 0;
-  RTXN_HIP(hipGetDevice(&dev));
-  RTXN_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (n_cu <= 0) n_cu = 256;
+  int n_cu = 0;
+  RTXN_HIP(rtxn::cu_count(&n_cu));
   const int grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;   // persistent: one block per CU (LDS- and register-bound)
   typedef void (*fused_fn)(FusedArgs);
   static const fused_fn table[kFusedMaxL][4] = {
@@ -3330,7 +3327,7 @@ static int train_backward_recompute_impl(const rtxn_mlp* m, const void* encT, co
       {mlp_bwd_fused64_kernel<3, 1>, mlp_bwd_fused64_kernel<3, 2>, mlp_bwd_fused64_kernel<3, 3>, mlp_bwd_fused64_kernel<3, 4>},
       {mlp_bwd_fused64_kernel<4, 1>, mlp_bwd_fused64_kernel<4, 2>, mlp_bwd_fused64_kernel<4, 3>, mlp_bwd_fused64_kernel<4, 4>}};
   const fused_fn fn = table[L - 1][a.KS0 - 1];
-  RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(fn), (int)lds));
+  RTXN_HIP(set_lds_once(reinterpret_cast<const void*>(fn), lds));
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), lds, rtxn::as_stream(stream), a);
   RTXN_LAUNCH_CHECK("mlp_bwd_fused64_kernel");
   return det_fold(a.det.q, m->n_params, dparams, nullptr, 0, rtxn::as_stream(stream));
@@ -3347,11 +3344,12 @@ extern "C" int rtxn_mlp_train_backward_recompute(const rtxn_mlp* m, const void* 
                     kFusedMaxL, m->cfg.n_neurons, m->cfg.n_hidden_layers, m->enc_padded);
     return RTXN_ERR_UNSUPPORTED;
   }
-  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples, "rtxn_mlp_train_backward_recompute: n_samples = %ld out of [0, %ld]", n_samples, kMaxTrainSamples);
+  rc = check_n_samples("rtxn_mlp_train_backward_recompute", n_samples, false);
+  if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(encT && output_half && dout_half4 && dparams, "rtxn_mlp_train_backward_recompute: NULL buffer");
-  return train_backward_recompute_impl(m, encT, output_half, dout_half4, n_samples, dparams, dencT, DevCount{nullptr, 0}, stream);
+  return train_backward_recompute_impl(m, encT, output_half, dout_half4, n_samples, dparams, dencT, kHostCount, stream);
 }
 
 extern "C" int rtxn_hashgrid_create(const rtxn_hashgrid_config* cfg, rtxn_hashgrid** out) {
@@ -3651,7 +3649,7 @@ extern "C" int rtxn_hashgrid_encode(const rtxn_hashgrid* g, int n_dir_freqs, con
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(table_fp16 && input && encT, "rtxn_hashgrid_encode: NULL buffer");
   const SampleSrc src{input, nullptr, nullptr, nullptr, 0};
-  return hashgrid_encode_impl(g, n_dir_freqs, table_fp16, src, encT, nullptr, 1.0f, n_samples, DevCount{nullptr, 0}, stream);
+  return hashgrid_encode_impl(g, n_dir_freqs, table_fp16, src, encT, nullptr, 1.0f, n_samples, kHostCount, stream);
 }
 
 extern "C" int rtxn_hashgrid_encode_segments(const rtxn_hashgrid* g, int n_dir_freqs, const void* table_fp16,
@@ -3665,14 +3663,13 @@ extern "C" int rtxn_hashgrid_encode_segments(const rtxn_hashgrid* g, int n_dir_f
   if (n_segments == 0) return RTXN_OK;
   RTXN_REQUIRE(table_fp16 && encT, "rtxn_hashgrid_encode_segments: NULL buffer");
   const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return hashgrid_encode_impl(g, n_dir_freqs, table_fp16, src, encT, t_vals, t_scale, n_segments * 32, DevCount{nullptr, 0}, stream);
+  return hashgrid_encode_impl(g, n_dir_freqs, table_fp16, src, encT, t_vals, t_scale, n_segments * 32, kHostCount, stream);
 }
 
 // dtable_hashed_half == NULL: every level into the fp32 table.  Otherwise (n_features == 2): the hashed levels go to the fp16
 // buffer, which holds the parameters from the first hashed level on.
 static int hashgrid_backward_impl(const rtxn_hashgrid* g, const SampleSrc& input, const void* dencT, long n_samples,
-                                  float* dtable, void* dtable_hashed_half, DevCount dc, rtxn_stream_t stream,
-                                  const int* live_list = nullptr, const int* live_count = nullptr) {
+                                  float* dtable, void* dtable_hashed_half, DevCount dc, rtxn_stream_t stream, LiveRef live = LiveRef()) {
   const long Sp = padded(n_samples);
   const int NL = g->cfg.n_levels, F = g->cfg.n_features;
   int first_hashed = NL;
@@ -3688,18 +3685,18 @@ static int hashgrid_backward_impl(const rtxn_hashgrid* g, const SampleSrc& input
   if (det.q) {
     // deterministic: every level as fp32-shaped contributions into the fixed-point shadow, then one fold into dtable / dtable_h
     hashgrid_backward_kernel<false, true><<<dim3(sblocks, (unsigned)NL), kThreads, 0, st>>>(
-        lv, 0, input, de, n_samples, Sp, dtable, nullptr, 0, dc, live_list, live_count, det);
+        lv, 0, input, de, n_samples, Sp, dtable, nullptr, 0, dc, live.list, live.count, det);
     RTXN_LAUNCH_CHECK("hashgrid_backward_kernel<deterministic>");
     return det_fold(det.q, g->n_params, dtable, dtable_hashed_half, hashed_lo, st);
   }
   if (first_hashed > 0) {
     hashgrid_backward_kernel<false><<<dim3(sblocks, (unsigned)first_hashed), kThreads, 0, st>>>(
-        lv, 0, input, de, n_samples, Sp, dtable, nullptr, 0, dc, live_list, live_count);
+        lv, 0, input, de, n_samples, Sp, dtable, nullptr, 0, dc, live.list, live.count);
     RTXN_LAUNCH_CHECK("hashgrid_backward_kernel");
   }
   if (first_hashed < NL) {
     hashgrid_backward_kernel<true><<<dim3(sblocks, (unsigned)(NL - first_hashed)), kThreads, 0, st>>>(
-        lv, first_hashed, input, de, n_samples, Sp, dtable, static_cast<_Float16*>(dtable_hashed_half), hashed_lo, dc, live_list, live_count);
+        lv, first_hashed, input, de, n_samples, Sp, dtable, static_cast<_Float16*>(dtable_hashed_half), hashed_lo, dc, live.list, live.count);
     RTXN_LAUNCH_CHECK("hashgrid_backward_kernel<pk_f16>");
   }
   return RTXN_OK;
@@ -3712,7 +3709,7 @@ extern "C" int rtxn_hashgrid_backward(const rtxn_hashgrid* g, const float* input
   RTXN_DEVICE_OR_FAIL();
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(input && dencT && dtable, "rtxn_hashgrid_backward: NULL buffer");
-  return hashgrid_backward_impl(g, SampleSrc{input, nullptr, nullptr, nullptr, 0}, dencT, n_samples, dtable, nullptr, DevCount{nullptr, 0}, stream);
+  return hashgrid_backward_impl(g, SampleSrc{input, nullptr, nullptr, nullptr, 0}, dencT, n_samples, dtable, nullptr, kHostCount, stream);
 }
 
 extern "C" int rtxn_hashgrid_backward_mixed(const rtxn_hashgrid* g, const float* input, const void* dencT, long n_samples,
@@ -3724,21 +3721,29 @@ extern "C" int rtxn_hashgrid_backward_mixed(const rtxn_hashgrid* g, const float*
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(input && dencT && dtable && dtable_hashed_half, "rtxn_hashgrid_backward_mixed: NULL buffer");
   RTXN_REQUIRE(((uintptr_t)dtable_hashed_half & 3) == 0, "rtxn_hashgrid_backward_mixed: fp16 table must be 4-byte aligned");
-  return hashgrid_backward_impl(g, SampleSrc{input, nullptr, nullptr, nullptr, 0}, dencT, n_samples, dtable, dtable_hashed_half, DevCount{nullptr, 0}, stream);
+  return hashgrid_backward_impl(g, SampleSrc{input, nullptr, nullptr, nullptr, 0}, dencT, n_samples, dtable, dtable_hashed_half, kHostCount, stream);
+}
+
+// rtxn_hashgrid_backward_segments[_live]: with_live: over the live list of live_ws only
+static int hashgrid_backward_segments_entry(const char* who, const rtxn_hashgrid* g, const float* start_points, const float* end_points,
+                                            long n_segments, int sample_type, const void* dencT, bool with_live, const void* live_ws,
+                                            float* dtable, void* dtable_hashed_half, rtxn_stream_t stream) {
+  RTXN_REQUIRE(g, "%s: NULL grid", who);
+  int rc = check_segments(who, start_points, end_points, start_points, n_segments, sample_type);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(!dtable_hashed_half || g->cfg.n_features == 2, "%s: packed fp16 atomics need n_features == 2 (got %d)", who, g->cfg.n_features);
+  RTXN_DEVICE_OR_FAIL();
+  if (n_segments == 0) return RTXN_OK;
+  RTXN_REQUIRE(dencT && dtable && (live_ws || !with_live), "%s: NULL buffer", who);
+  const SampleSrc src{nullptr, start_points, end_points, nullptr, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
+  return hashgrid_backward_impl(g, src, dencT, n_segments * 32, dtable, dtable_hashed_half, kHostCount, stream, LiveRef(live_ws));
 }
 
 extern "C" int rtxn_hashgrid_backward_segments(const rtxn_hashgrid* g, const float* start_points, const float* end_points,
                                                long n_segments, int sample_type, const void* dencT, float* dtable,
                                                void* dtable_hashed_half, rtxn_stream_t stream) {
-  RTXN_REQUIRE(g, "rtxn_hashgrid_backward_segments: NULL grid");
-  int rc = check_segments("rtxn_hashgrid_backward_segments", start_points, end_points, start_points, n_segments, sample_type);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(!dtable_hashed_half || g->cfg.n_features == 2, "rtxn_hashgrid_backward_segments: packed fp16 atomics need n_features == 2 (got %d)", g->cfg.n_features);
-  RTXN_DEVICE_OR_FAIL();
-  if (n_segments == 0) return RTXN_OK;
-  RTXN_REQUIRE(dencT && dtable, "rtxn_hashgrid_backward_segments: NULL buffer");
-  const SampleSrc src{nullptr, start_points, end_points, nullptr, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return hashgrid_backward_impl(g, src, dencT, n_segments * 32, dtable, dtable_hashed_half, DevCount{nullptr, 0}, stream);
+  return hashgrid_backward_segments_entry("rtxn_hashgrid_backward_segments", g, start_points, end_points, n_segments, sample_type, dencT, false, nullptr,
+                                          dtable, dtable_hashed_half, stream);
 }
 
 extern "C" int rtxn_l2_loss(const float* pred, const float* target, long n, float loss_scale, float* values,
@@ -3769,13 +3774,9 @@ static int adam_impl(const char* who, long n, float* master, void* params_fp16, 
   hipStream_t st = rtxn::as_stream(stream);
   __half* p16 = static_cast<__half*>(params_fp16);
   const float ils = 1.0f / loss_scale;
-  if (grads_fp16) {
-    if (zero) adam_kernel<true, true><<<blocks, kThreads, 0, st>>>(n, master, p16, grads, m, v, lr_eff, beta1, beta2, eps, ils, lr_dev);
-    else adam_kernel<true, false><<<blocks, kThreads, 0, st>>>(n, master, p16, grads, m, v, lr_eff, beta1, beta2, eps, ils, lr_dev);
-  } else {
-    if (zero) adam_kernel<false, true><<<blocks, kThreads, 0, st>>>(n, master, p16, grads, m, v, lr_eff, beta1, beta2, eps, ils, lr_dev);
-    else adam_kernel<false, false><<<blocks, kThreads, 0, st>>>(n, master, p16, grads, m, v, lr_eff, beta1, beta2, eps, ils, lr_dev);
-  }
+  static decltype(&adam_kernel<false, false>) const table[2][2] = {{adam_kernel<false, false>, adam_kernel<false, true>},   // [HALF_GRADS][ZERO]
+                                                                   {adam_kernel<true, false>, adam_kernel<true, true>}};
+  table[grads_fp16 != 0][zero]<<<blocks, kThreads, 0, st>>>(n, master, p16, grads, m, v, lr_eff, beta1, beta2, eps, ils, lr_dev);
   RTXN_LAUNCH_CHECK("adam_kernel");
   return RTXN_OK;
 }
@@ -3825,10 +3826,9 @@ extern "C" int rtxn_adam_step_sparse(long n, float* master, void* params_fp16, v
   const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
   __half* p16 = static_cast<__half*>(params_fp16);
   const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  if (half && zero) adam_sparse_kernel<true, true><<<gridx, kThreads, 0, st>>>(n, master, p16, grads, m, v, param_steps, lr, beta1, beta2, eps, ils, l2b1, l2b2);
-  else if (half) adam_sparse_kernel<true, false><<<gridx, kThreads, 0, st>>>(n, master, p16, grads, m, v, param_steps, lr, beta1, beta2, eps, ils, l2b1, l2b2);
-  else if (zero) adam_sparse_kernel<false, true><<<gridx, kThreads, 0, st>>>(n, master, p16, grads, m, v, param_steps, lr, beta1, beta2, eps, ils, l2b1, l2b2);
-  else adam_sparse_kernel<false, false><<<gridx, kThreads, 0, st>>>(n, master, p16, grads, m, v, param_steps, lr, beta1, beta2, eps, ils, l2b1, l2b2);
+  static decltype(&adam_sparse_kernel<false, false>) const table[2][2] = {{adam_sparse_kernel<false, false>, adam_sparse_kernel<false, true>},   // [HALF_GRADS][ZERO]
+                                                                          {adam_sparse_kernel<true, false>, adam_sparse_kernel<true, true>}};
+  table[half][zero]<<<gridx, kThreads, 0, st>>>(n, master, p16, grads, m, v, param_steps, lr, beta1, beta2, eps, ils, l2b1, l2b2);
   RTXN_LAUNCH_CHECK("adam_sparse_kernel");
   return RTXN_OK;
 }
@@ -3840,13 +3840,12 @@ extern "C" size_t rtxn_live_segments_workspace_bytes(long segment_capacity) {
 }
 
 static int live_segments_impl(const void* dout_half4, long n_segments, long capacity, void* live_ws, DevCount dc, rtxn_stream_t stream) {
-  uint8_t* ws = static_cast<uint8_t*>(live_ws);
-  uint8_t* flags = ws + 16 + 4 * capacity;
+  uint8_t* flags = live_flags_of(live_ws, capacity);
   const long S = n_segments * 32;
   hipStream_t st = rtxn::as_stream(stream);
   live_flags_kernel<<<(unsigned)((S + kThreads - 1) / kThreads), kThreads, 0, st>>>(static_cast<const uint2*>(dout_half4), S, dc, flags);
   RTXN_LAUNCH_CHECK("live_flags_kernel");
-  live_compact_kernel<<<1, kCompactThreads, 0, st>>>(flags, S, dc, reinterpret_cast<int*>(ws + 16), reinterpret_cast<int*>(ws));
+  live_compact_kernel<<<1, kCompactThreads, 0, st>>>(flags, S, dc, const_cast<int*>(live_list_of(live_ws)), const_cast<int*>(live_count_of(live_ws)));
   RTXN_LAUNCH_CHECK("live_compact_kernel");
   return RTXN_OK;
 }
@@ -3862,7 +3861,7 @@ extern "C" int rtxn_live_segments(const void* radiance_gradients_half4, long n_s
     return RTXN_OK;
   }
   RTXN_REQUIRE(radiance_gradients_half4 && ((uintptr_t)radiance_gradients_half4 & 7) == 0, "rtxn_live_segments: gradients NULL or not 8-byte aligned");
-  return live_segments_impl(radiance_gradients_half4, n_segments, segment_capacity, live_ws, DevCount{nullptr, 0}, stream);
+  return live_segments_impl(radiance_gradients_half4, n_segments, segment_capacity, live_ws, kHostCount, stream);
 }
 
 extern "C" int rtxn_mlp_train_backward_recompute_live(const rtxn_mlp* m, const void* encT, const void* output_half,
@@ -3871,42 +3870,28 @@ extern "C" int rtxn_mlp_train_backward_recompute_live(const rtxn_mlp* m, const v
   int rc = check_train(m, "rtxn_mlp_train_backward_recompute_live");
   if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(rtxn_mlp_train_recompute_supported(m), "rtxn_mlp_train_backward_recompute_live: this model has no recompute path");
-  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples && n_samples % 32 == 0,
-               "rtxn_mlp_train_backward_recompute_live: n_samples = %ld must be whole segments in [0, %ld]", n_samples, kMaxTrainSamples);
+  rc = check_n_samples("rtxn_mlp_train_backward_recompute_live", n_samples, true);
+  if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
   if (n_samples == 0) return RTXN_OK;
   RTXN_REQUIRE(encT && output_half && dout_half4 && dparams && live_ws, "rtxn_mlp_train_backward_recompute_live: NULL buffer");
-  return train_backward_recompute_impl(m, encT, output_half, dout_half4, n_samples, dparams, dencT, DevCount{nullptr, 0}, stream,
-                                       live_list_of(live_ws), live_count_of(live_ws));
+  return train_backward_recompute_impl(m, encT, output_half, dout_half4, n_samples, dparams, dencT, kHostCount, stream, LiveRef(live_ws));
 }
 
 extern "C" int rtxn_mlp_train_backward_live(const rtxn_mlp* m, const void* encT, const void* output_half, const void* dout_half4,
                                             long n_samples, void* workspace, const void* live_ws, float* dparams, void* dencT,
                                             rtxn_stream_t stream) {
-  int rc = check_train(m, "rtxn_mlp_train_backward_live");
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(n_samples >= 0 && n_samples <= kMaxTrainSamples && n_samples % 32 == 0,
-               "rtxn_mlp_train_backward_live: n_samples = %ld must be whole segments in [0, %ld]", n_samples, kMaxTrainSamples);
-  RTXN_DEVICE_OR_FAIL();
-  if (n_samples == 0) return RTXN_OK;
+  const int rc = check_entry(m, "rtxn_mlp_train_backward_live", n_samples, true);
+  if (rc != RTXN_OK || n_samples == 0) return rc;
   RTXN_REQUIRE(encT && output_half && dout_half4 && workspace && dparams && live_ws, "rtxn_mlp_train_backward_live: NULL buffer");
-  return train_backward_impl(m, encT, output_half, dout_half4, n_samples, workspace, dparams, dencT, DevCount{nullptr, 0}, stream,
-                             live_list_of(live_ws), live_count_of(live_ws));
+  return train_backward_impl(m, encT, output_half, dout_half4, n_samples, workspace, dparams, dencT, kHostCount, stream, LiveRef(live_ws));
 }
 
 extern "C" int rtxn_hashgrid_backward_segments_live(const rtxn_hashgrid* g, const float* start_points, const float* end_points,
                                                     long n_segments, int sample_type, const void* dencT, const void* live_ws,
                                                     float* dtable, void* dtable_hashed_half, rtxn_stream_t stream) {
-  RTXN_REQUIRE(g, "rtxn_hashgrid_backward_segments_live: NULL grid");
-  int rc = check_segments("rtxn_hashgrid_backward_segments_live", start_points, end_points, start_points, n_segments, sample_type);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(!dtable_hashed_half || g->cfg.n_features == 2, "rtxn_hashgrid_backward_segments_live: packed fp16 atomics need n_features == 2 (got %d)", g->cfg.n_features);
-  RTXN_DEVICE_OR_FAIL();
-  if (n_segments == 0) return RTXN_OK;
-  RTXN_REQUIRE(dencT && dtable && live_ws, "rtxn_hashgrid_backward_segments_live: NULL buffer");
-  const SampleSrc src{nullptr, start_points, end_points, nullptr, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return hashgrid_backward_impl(g, src, dencT, n_segments * 32, dtable, dtable_hashed_half, DevCount{nullptr, 0}, stream,
-                                live_list_of(live_ws), live_count_of(live_ws));
+  return hashgrid_backward_segments_entry("rtxn_hashgrid_backward_segments_live", g, start_points, end_points, n_segments, sample_type, dencT, true,
+                                          live_ws, dtable, dtable_hashed_half, stream);
 }
 
 // ------------------------------------------------------------------------- a whole batch, segment count on the device
@@ -3949,7 +3934,7 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   const SampleSrc src{nullptr, b->start_points, b->end_points, b->seg_view, b->sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
   // The reference's own model on the lean path: sampler AND encoder folded into the forward and into the weight gradient (encT is
   // never written; RTXN_TRAIN_LEAN_FUSED=0: the staged encoder, for the A/B -- the same values bit for bit)
-  const char* fused_env = getenv("RTXN_TRAIN_LEAN_FUSED");       // (read per call: a test switches it between trainers)
+  const char* fused_env = getenv("RTXN_TRAIN_LEAN_FUSED");
   const bool fused_off = fused_env && atoi(fused_env) == 0;
   const bool fused = lean && !fused_off && rtxn_mlp_train_forward_lean_fused_supported(m);
   // launchSampler + encoding (main.cu:703,721)
@@ -3962,8 +3947,14 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   // behind the first surface): outputs only here, the activations of the live segments are saved after the compositor.
   // (lean: the forward saves 16 bytes of sign masks per sample and layer for EVERY sample -- cheap enough that no second pass is needed)
   const bool two_pass = !recompute && !lean && b->live_ws != nullptr && b->vr_mode == RTXN_VR_NERF;
-  rc = fused ? train_forward_impl(m, nullptr, cap_samples, b->workspace, b->output_half, b->radiance, dc, stream, nullptr, nullptr, true, &src, b->t_vals, b->t_scale)
-             : train_forward_impl(m, b->encT, cap_samples, two_pass ? nullptr : b->workspace, b->output_half, b->radiance, dc, stream, nullptr, nullptr, lean);
+  FwdOpts fwd;
+  fwd.save = recompute || two_pass ? kSaveNone : lean ? kSaveMasks : kSaveAll;
+  if (fused) {
+    fwd.src = &src;
+    fwd.t_vals = b->t_vals;
+    fwd.t_scale = b->t_scale;
+  }
+  rc = train_forward_impl(m, fused ? nullptr : b->encT, cap_samples, b->workspace, b->output_half, b->radiance, dc, stream, fwd);
   if (rc != RTXN_OK) return rc;
   // launch_volrender_cuda, loss->evaluate, launch_volrender_backward_cuda (main.cu:737-767): per ray, no sample count needed
   if (b->vr_mode == RTXN_VR_NERF) {
@@ -3982,27 +3973,27 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
     if (rc != RTXN_OK) return rc;
   }
   // network->backward (main.cu:781); with live_ws only over the segments that carry a loss gradient
-  const bool use_live = b->live_ws != nullptr;
-  if (use_live) {
+  if (b->live_ws) {
     RTXN_REQUIRE(((uintptr_t)b->live_ws & 15) == 0, "rtxn_train_gradients: live_ws not 16-byte aligned");
     rc = live_segments_impl(b->radiance_gradients, b->segment_capacity, b->segment_capacity, b->live_ws, dc, stream);
     if (rc != RTXN_OK) return rc;
   }
-  const int* ll = use_live ? live_list_of(b->live_ws) : nullptr;
-  const int* lc = use_live ? live_count_of(b->live_ws) : nullptr;
+  const LiveRef live(b->live_ws);
   if (two_pass) {
-    rc = train_forward_impl(m, b->encT, cap_samples, b->workspace, nullptr, nullptr, dc, stream, ll, lc);
+    FwdOpts save;
+    save.live = live;
+    rc = train_forward_impl(m, b->encT, cap_samples, b->workspace, nullptr, nullptr, dc, stream, save);
     if (rc != RTXN_OK) return rc;
   }
-  rc = lean      ? train_backward_lean_impl(m, b->encT, b->output_half, b->radiance_gradients, cap_samples, b->workspace, b->dparams, dc, stream, ll, lc,
-                                            fused ? &src : nullptr)
-     : recompute ? train_backward_recompute_impl(m, b->encT, b->output_half, b->radiance_gradients, cap_samples, b->dparams, b->dencT, dc, stream, ll, lc)
+  rc = lean      ? train_backward_lean_impl(m, b->encT, b->output_half, b->radiance_gradients, cap_samples, b->workspace, b->dparams, dc, stream,
+                                            fused ? &src : nullptr, live)
+     : recompute ? train_backward_recompute_impl(m, b->encT, b->output_half, b->radiance_gradients, cap_samples, b->dparams, b->dencT, dc, stream, live)
                  : train_backward_impl(m, b->encT, b->output_half, b->radiance_gradients, cap_samples, b->workspace, b->dparams,
-                                       hash ? b->dencT : nullptr, dc, stream, ll, lc);
+                                       hash ? b->dencT : nullptr, dc, stream, live);
   if (rc != RTXN_OK) return rc;
   if (hash && !b->skip_table_backward) {
     const SampleSrc bsrc{nullptr, b->start_points, b->end_points, nullptr, b->sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-    rc = hashgrid_backward_impl(b->grid, bsrc, b->dencT, cap_samples, b->dtable, b->dtable_hashed_half, dc, stream, ll, lc);
+    rc = hashgrid_backward_impl(b->grid, bsrc, b->dencT, cap_samples, b->dtable, b->dtable_hashed_half, dc, stream, live);
   }
   return rc;
 }
