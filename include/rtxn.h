@@ -57,7 +57,10 @@ enum rtxn_sampling_type {
   RTXN_SAMPLING_UNIFORM = 2,
   /* not in the reference: sample i at the MIDPOINT t = (i+0.5)/32 of its sub-interval, and t_vals = the
    * sub-interval's world-space length |end-start|/32 -- the inputs RTXN_VR_NERF expects */
-  RTXN_SAMPLING_MIDPOINT_WORLD = 3
+  RTXN_SAMPLING_MIDPOINT_WORLD = 3,
+  /* not in the reference: MIDPOINT_WORLD with a fresh position inside each sub-interval per training step -- see "sample
+   * jitter" below (rtxn_sample_jitter); training entry points only, and only those that take the struct */
+  RTXN_SAMPLING_JITTER_WORLD = 4
 };
 
 /* ---- traversal ------------------------------------------------------------ */
@@ -792,7 +795,7 @@ typedef struct rtxn_train_batch {
   const int* total_segments;        /* DEVICE int: segments of this batch (rtxn_scan_hits' total) */
   long segment_capacity;
   int n_rays;
-  int sample_type;                  /* RTXN_SAMPLING_REGULAR | RTXN_SAMPLING_MIDPOINT_WORLD */
+  int sample_type;                  /* RTXN_SAMPLING_REGULAR | RTXN_SAMPLING_MIDPOINT_WORLD (| RTXN_SAMPLING_JITTER_WORLD: the _jitter forms) */
   float t_scale;                    /* MIDPOINT_WORLD: factor on the step lengths written to t_vals */
   int vr_mode;                      /* RTXN_VR_COMPAT | RTXN_VR_NERF */
   const float* targets;             /* float[n_rays][3] */
@@ -891,6 +894,67 @@ int rtxn_mlp_train_forward_live(const rtxn_mlp* m, const void* encT, long n_samp
 int rtxn_hashgrid_backward_segments_live(const rtxn_hashgrid* g, const float* start_points, const float* end_points,
                                          long n_segments, int sample_type, const void* dencT, const void* live_ws,
                                          float* dtable, void* dtable_hashed_half, rtxn_stream_t stream);
+
+/* ---- sample jitter (training only) ----------------------------------------------------------------------------------
+ * RTXN_SAMPLING_JITTER_WORLD: stratified per-step jitter of the 32 samples of a segment (not in the reference, whose two random
+ * modes replay one minstd_rand stream for every ray and step; NeRF's perturb / instant-ngp's per-step offsets).  Sample i of
+ * packed segment g of the batch, s = 32 g + i:
+ *   step = (uint32)*jitter.step (NULL: 0)
+ *   h0   = fmix32((seed ^ 0x5BD1E995u) + 0x9E3779B9u * step)      (uint32 wrap-around; fmix32: see RTXN_BG_RANDOM)
+ *   u    = (float)(fmix32(h0 ^ (uint32)s) >> 8) * 2^-24           (24 hash bits, exact, in [0, 1))
+ *   t    = ((float)i + u) * (1/32)                                in [i/32, (i + 1)/32): inside its stratum and its cell
+ *   pos  = fmaf(t, end - start, start),  (theta, phi) = the segment's
+ *   t_vals[s] = |end - start| / 32 * t_scale                      exactly MIDPOINT_WORLD's
+ * The offset is a pure function of (seed, step, s) and is never stored: the encoders, the lean forward and weight gradient and
+ * the hash scatter (also over a live list) each form the same position from the same s, so the backward differentiates the
+ * samples the forward shaded.  `step` is read on the device: a captured graph draws new offsets on every replay once the
+ * counter moves, the same step number gives the same offsets on every path, and a resumed run continues the sequence.  The
+ * step LENGTH stays the stratum's, so the compositor and its backward are untouched and remain exact.
+ * Every entry point that reads packed segments for training has a `_jitter` form with the struct as its last argument before
+ * the stream; the plain name is that form called with NULL.  Rules (RTXN_ERR_INVALID with a message, before any device is
+ * touched): RTXN_SAMPLING_JITTER_WORLD needs the struct; the struct needs RTXN_SAMPLING_JITTER_WORLD; not with RTXN_VR_COMPAT
+ * (rtxn_train_gradients_jitter / rtxn_train_step_jitter), whose t_vals are not step lengths.  Rendering and the occupancy
+ * refresh stay deterministic: rtxn_render_*, rtxn_hashmlp_forward_segments, rtxn_volrender_fwd_aux and rtxn_sample refuse
+ * type 4. */
+typedef struct rtxn_sample_jitter {
+  unsigned seed;
+  const int* step;                  /* DEVICE int hashed with the seed; NULL = 0 (rtxn_train_step_jitter: NULL = opt.step before
+                                       its increment) */
+} rtxn_sample_jitter;
+/* rtxn_sample with room for the jitter: the same positions and t_vals as float[S][5] / float[S] (s = the sample's index in the
+ * packed batch).  sample_type 0..3 with jitter == NULL: rtxn_sample. */
+int rtxn_sample_ex(const float* start_points, const float* end_points, const float* view_dirs,
+                   float* t_vals, float* sampled_points, int batch_size, int grid_res,
+                   const int* num_hits, const int* indices, int sample_type, const rtxn_sample_jitter* jitter,
+                   rtxn_stream_t stream);
+int rtxn_encode_frequency_segments_jitter(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                          const float* seg_view, long n_segments, int sample_type, float t_scale,
+                                          void* encT, float* t_vals, const rtxn_sample_jitter* jitter, rtxn_stream_t stream);
+int rtxn_hashgrid_encode_segments_jitter(const rtxn_hashgrid* g, int n_dir_freqs, const void* table_fp16,
+                                         const float* start_points, const float* end_points, const float* seg_view,
+                                         long n_segments, int sample_type, float t_scale, void* encT, float* t_vals,
+                                         const rtxn_sample_jitter* jitter, rtxn_stream_t stream);
+int rtxn_mlp_train_forward_lean_segments_jitter(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                                const float* seg_view, long n_segments, int sample_type, float t_scale,
+                                                float* t_vals, void* workspace_lean, void* output_half, float* radiance,
+                                                const rtxn_sample_jitter* jitter, rtxn_stream_t stream);
+int rtxn_mlp_train_backward_lean_segments_jitter(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                                 const float* seg_view, long n_segments, int sample_type, const void* output_half,
+                                                 const void* dout_half4, void* workspace_lean, const void* live_ws, float* dparams,
+                                                 const rtxn_sample_jitter* jitter, rtxn_stream_t stream);
+int rtxn_hashgrid_backward_segments_jitter(const rtxn_hashgrid* g, const float* start_points, const float* end_points,
+                                           long n_segments, int sample_type, const void* dencT, float* dtable,
+                                           void* dtable_hashed_half, const rtxn_sample_jitter* jitter, rtxn_stream_t stream);
+int rtxn_hashgrid_backward_segments_live_jitter(const rtxn_hashgrid* g, const float* start_points, const float* end_points,
+                                                long n_segments, int sample_type, const void* dencT, const void* live_ws,
+                                                float* dtable, void* dtable_hashed_half, const rtxn_sample_jitter* jitter,
+                                                rtxn_stream_t stream);
+/* rtxn_train_gradients_ex / rtxn_train_step_ex with the jitter beside the background; either may be NULL.  The step form: a
+ * NULL jitter->step is opt.step as it is BEFORE the call increments it, by the background's rule. */
+int rtxn_train_gradients_jitter(const rtxn_train_batch* batch, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                rtxn_stream_t stream);
+int rtxn_train_step_jitter(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                           rtxn_stream_t stream);
 
 /* fp32 <-> fp16 copies of a gradient block on the device (no counterpart in the reference, which is single-GPU): the
  * data-parallel exchange sends the hashed levels' gradient in fp16 -- tiny-cuda-nn holds that gradient in fp16 throughout. */

@@ -115,6 +115,11 @@ class TrainBackground(C.Structure):
     _fields_ = [("mode", C.c_int), ("color", C.c_float * 3), ("seed", C.c_uint), ("step", C.c_void_p), ("target_channels", C.c_int)]
 
 
+class SampleJitter(C.Structure):
+    """struct rtxn_sample_jitter (include/rtxn.h)."""
+    _fields_ = [("seed", C.c_uint), ("step", C.c_void_p)]
+
+
 class RenderConfig(C.Structure):
     """struct rtxn_render_config (include/rtxn.h)."""
     _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("table_fp16", C.c_void_p), ("n_dir_freqs", C.c_int),
@@ -263,6 +268,15 @@ SYMBOLS = {
     "rtxn_mlp_train_backward_live": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P, _P]),
     "rtxn_mlp_train_forward_live": (_I, [_P, _P, _L, _P, _P, _P]),
     "rtxn_hashgrid_backward_segments_live": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, _P, _P]),
+    "rtxn_sample_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(SampleJitter), _P]),
+    "rtxn_encode_frequency_segments_jitter": (_I, [_P, _P, _P, _P, _L, _I, _F, _P, _P, C.POINTER(SampleJitter), _P]),
+    "rtxn_hashgrid_encode_segments_jitter": (_I, [_P, _I, _P, _P, _P, _P, _L, _I, _F, _P, _P, C.POINTER(SampleJitter), _P]),
+    "rtxn_mlp_train_forward_lean_segments_jitter": (_I, [_P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, C.POINTER(SampleJitter), _P]),
+    "rtxn_mlp_train_backward_lean_segments_jitter": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, C.POINTER(SampleJitter), _P]),
+    "rtxn_hashgrid_backward_segments_jitter": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, C.POINTER(SampleJitter), _P]),
+    "rtxn_hashgrid_backward_segments_live_jitter": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, _P, C.POINTER(SampleJitter), _P]),
+    "rtxn_train_gradients_jitter": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), _P]),
+    "rtxn_train_step_jitter": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),
     "rtxn_load_llff": (_I, [C.c_char_p, _I, _I, C.POINTER(ImageDataset), C.POINTER(C.POINTER(C.c_float))]),

@@ -19,6 +19,7 @@ SAMPLING_REGULAR = 0                   # sampler/sampler.h:5-9
 SAMPLING_STRATIFIED_JITTERING = 1
 SAMPLING_UNIFORM = 2
 SAMPLING_MIDPOINT_WORLD = 3               # this build: midpoints + world step lengths (for VR_NERF)
+SAMPLING_JITTER_WORLD = 4                 # this build: MIDPOINT_WORLD with a per-step offset inside each stratum (sample_jitter())
 TRACE_COMPAT, TRACE_DDA = 0, 1
 VR_COMPAT, VR_NERF = 0, 1
 ACT_NONE, ACT_SIGMOID = 0, 1
@@ -211,9 +212,32 @@ def scan_hits(num_hits, indices=None, total=None, workspace=None):
 
 
 # --------------------------------------------------------------------------- sampler
+def sample_jitter(seed=0, step=None):
+    """struct rtxn_sample_jitter (include/rtxn.h) for SAMPLING_JITTER_WORLD: the offsets are hashed from `seed`, the device int32
+    tensor `step` (None: 0, or opt.step for train_step) and the sample's index.  The tensor must outlive the calls."""
+    j = _lib.SampleJitter()
+    j.seed = int(seed) & 0xFFFFFFFF
+    j.step = _ptr(step, torch.int32, "step")
+    return j
+
+
+def _jit(jitter):
+    return C.byref(jitter) if jitter is not None else None
+
+
 def launchSampler(d_start_points, d_end_points, d_view_dirs, d_t_vals, d_sampled_points, batch_size,
-                  grid_res, d_num_hits, d_indices, sample_type=SAMPLING_REGULAR):
-    """sampler/sampler.h:19-30 (the stream argument is torch's current stream)."""
+                  grid_res, d_num_hits, d_indices, sample_type=SAMPLING_REGULAR, jitter=None):
+    """sampler/sampler.h:19-30 (the stream argument is torch's current stream).  jitter: sample_jitter(...) -> rtxn_sample_ex."""
+    if jitter is not None:
+        check(_lib.lib().rtxn_sample_ex(_ptr(d_start_points, torch.float32, "d_start_points"),
+                                        _ptr(d_end_points, torch.float32, "d_end_points"),
+                                        _ptr(d_view_dirs, torch.float32, "d_view_dirs"),
+                                        _ptr(d_t_vals, torch.float32, "d_t_vals"),
+                                        _ptr(d_sampled_points, torch.float32, "d_sampled_points"),
+                                        batch_size, grid_res, _ptr(d_num_hits, torch.int32, "d_num_hits"),
+                                        _ptr(d_indices, torch.int32, "d_indices"), sample_type, _jit(jitter), _stream()),
+              "rtxn_sample_ex")
+        return
     check(_lib.lib().rtxn_sample(_ptr(d_start_points, torch.float32, "d_start_points"),
                                  _ptr(d_end_points, torch.float32, "d_end_points"),
                                  _ptr(d_view_dirs, torch.float32, "d_view_dirs"),
@@ -509,30 +533,31 @@ class HashGrid:
                                               n, _stream()), "rtxn_hashgrid_encode")
         return encT
 
-    def encode_segments(self, table_fp16, start_points, end_points, seg_view, n_segments, sample_type, encT, t_vals=None, t_scale=1.0):
-        """launchSampler + encode in one pass over the packed segments (the float[S][5] samples are never written)."""
-        check(_lib.lib().rtxn_hashgrid_encode_segments(self._h, self.n_dir_freqs, _ptr(table_fp16, torch.float16, "table"),
-                                                       _ptr(start_points, torch.float32, "start_points"), _ptr(end_points, torch.float32, "end_points"),
-                                                       _ptr(seg_view, torch.float32, "seg_view"), n_segments, sample_type, t_scale,
-                                                       _ptr(encT, torch.float16, "encT"), _ptr(t_vals, torch.float32, "t_vals"), _stream()),
-              "rtxn_hashgrid_encode_segments")
+    def encode_segments(self, table_fp16, start_points, end_points, seg_view, n_segments, sample_type, encT, t_vals=None, t_scale=1.0,
+                        jitter=None):
+        """launchSampler + encode in one pass over the packed segments (the float[S][5] samples are never written).
+        jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> the _jitter entry point (here and in every method that takes it)."""
+        args = (self._h, self.n_dir_freqs, _ptr(table_fp16, torch.float16, "table"),
+                _ptr(start_points, torch.float32, "start_points"), _ptr(end_points, torch.float32, "end_points"),
+                _ptr(seg_view, torch.float32, "seg_view"), n_segments, sample_type, t_scale,
+                _ptr(encT, torch.float16, "encT"), _ptr(t_vals, torch.float32, "t_vals"))
+        if jitter is not None:
+            check(_lib.lib().rtxn_hashgrid_encode_segments_jitter(*args, _jit(jitter), _stream()), "rtxn_hashgrid_encode_segments_jitter")
+        else:
+            check(_lib.lib().rtxn_hashgrid_encode_segments(*args, _stream()), "rtxn_hashgrid_encode_segments")
         return encT
 
-    def backward_segments(self, start_points, end_points, n_segments, sample_type, dencT, dtable, dtable_hashed_half=None, live_ws=None):
+    def backward_segments(self, start_points, end_points, n_segments, sample_type, dencT, dtable, dtable_hashed_half=None, live_ws=None,
+                          jitter=None):
         """live_ws (from live_segments): visit only the segments that carry a loss gradient."""
+        head = (self._h, _ptr(start_points, torch.float32, "start_points"), _ptr(end_points, torch.float32, "end_points"), n_segments,
+                sample_type, _ptr(dencT, torch.float16, "dencT"))
+        tail = (_ptr(dtable, torch.float32, "dtable"), _ptr(dtable_hashed_half, torch.float16, "dtable_hashed_half"))
+        tail += (_jit(jitter), _stream()) if jitter is not None else (_stream(),)
+        name = "rtxn_hashgrid_backward_segments" + ("_live" if live_ws is not None else "") + ("_jitter" if jitter is not None else "")
         if live_ws is not None:
-            check(_lib.lib().rtxn_hashgrid_backward_segments_live(self._h, _ptr(start_points, torch.float32, "start_points"),
-                                                                  _ptr(end_points, torch.float32, "end_points"), n_segments, sample_type,
-                                                                  _ptr(dencT, torch.float16, "dencT"), _ptr(live_ws, None, "live_ws"),
-                                                                  _ptr(dtable, torch.float32, "dtable"),
-                                                                  _ptr(dtable_hashed_half, torch.float16, "dtable_hashed_half"), _stream()),
-                  "rtxn_hashgrid_backward_segments_live")
-            return dtable
-        check(_lib.lib().rtxn_hashgrid_backward_segments(self._h, _ptr(start_points, torch.float32, "start_points"),
-                                                         _ptr(end_points, torch.float32, "end_points"), n_segments, sample_type,
-                                                         _ptr(dencT, torch.float16, "dencT"), _ptr(dtable, torch.float32, "dtable"),
-                                                         _ptr(dtable_hashed_half, torch.float16, "dtable_hashed_half"), _stream()),
-              "rtxn_hashgrid_backward_segments")
+            head += (_ptr(live_ws, None, "live_ws"),)
+        check(getattr(_lib.lib(), name)(*head, *tail), name)
         return dtable
 
     def backward_mixed(self, inputs, dencT, dtable, dtable_hashed_half):
@@ -562,12 +587,16 @@ def _net_encode_frequency(self, inputs, encT=None):
     return encT
 
 
-def _net_encode_frequency_segments(self, start_points, end_points, seg_view, n_segments, sample_type, encT, t_vals=None, t_scale=1.0):
+def _net_encode_frequency_segments(self, start_points, end_points, seg_view, n_segments, sample_type, encT, t_vals=None, t_scale=1.0,
+                                   jitter=None):
     """launchSampler + Composite-Frequency encoding in one pass over the packed segments."""
-    check(_lib.lib().rtxn_encode_frequency_segments(self._h, _ptr(start_points, torch.float32, "start_points"),
-                                                    _ptr(end_points, torch.float32, "end_points"), _ptr(seg_view, torch.float32, "seg_view"),
-                                                    n_segments, sample_type, t_scale, _ptr(encT, torch.float16, "encT"),
-                                                    _ptr(t_vals, torch.float32, "t_vals"), _stream()), "rtxn_encode_frequency_segments")
+    args = (self._h, _ptr(start_points, torch.float32, "start_points"), _ptr(end_points, torch.float32, "end_points"),
+            _ptr(seg_view, torch.float32, "seg_view"), n_segments, sample_type, t_scale, _ptr(encT, torch.float16, "encT"),
+            _ptr(t_vals, torch.float32, "t_vals"))
+    if jitter is not None:
+        check(_lib.lib().rtxn_encode_frequency_segments_jitter(*args, _jit(jitter), _stream()), "rtxn_encode_frequency_segments_jitter")
+    else:
+        check(_lib.lib().rtxn_encode_frequency_segments(*args, _stream()), "rtxn_encode_frequency_segments")
     return encT
 
 
@@ -673,27 +702,31 @@ def _net_lean_fused_supported(self):
 
 
 def _net_train_forward_lean_segments(self, start_points, end_points, seg_view, n_segments, sample_type, workspace, output, radiance=None,
-                                     t_vals=None, t_scale=1.0):
+                                     t_vals=None, t_scale=1.0, jitter=None):
     """The lean forward with sampler and encoder folded in (rtxn_mlp_train_forward_lean_segments): encT is not read; t_vals as the
     standalone encoder writes them."""
-    check(_lib.lib().rtxn_mlp_train_forward_lean_segments(self._h, _ptr(start_points, torch.float32, "start_points"),
-                                                          _ptr(end_points, torch.float32, "end_points"), _ptr(seg_view, torch.float32, "seg_view"),
-                                                          n_segments, sample_type, t_scale, _ptr(t_vals, torch.float32, "t_vals"),
-                                                          _ptr(workspace, torch.float16, "workspace"), _ptr(output, torch.float16),
-                                                          _ptr(radiance, torch.float32, "radiance"), _stream()),
-          "rtxn_mlp_train_forward_lean_segments")
+    args = (self._h, _ptr(start_points, torch.float32, "start_points"), _ptr(end_points, torch.float32, "end_points"),
+            _ptr(seg_view, torch.float32, "seg_view"), n_segments, sample_type, t_scale, _ptr(t_vals, torch.float32, "t_vals"),
+            _ptr(workspace, torch.float16, "workspace"), _ptr(output, torch.float16), _ptr(radiance, torch.float32, "radiance"))
+    if jitter is not None:
+        check(_lib.lib().rtxn_mlp_train_forward_lean_segments_jitter(*args, _jit(jitter), _stream()),
+              "rtxn_mlp_train_forward_lean_segments_jitter")
+    else:
+        check(_lib.lib().rtxn_mlp_train_forward_lean_segments(*args, _stream()), "rtxn_mlp_train_forward_lean_segments")
     return output
 
 
 def _net_train_backward_lean_segments(self, start_points, end_points, seg_view, n_segments, sample_type, output, dout, workspace, dparams,
-                                      live_ws=None):
+                                      live_ws=None, jitter=None):
     """The lean backward whose weight gradient recomputes the encoding as well (rtxn_mlp_train_backward_lean_segments): no encT."""
-    check(_lib.lib().rtxn_mlp_train_backward_lean_segments(self._h, _ptr(start_points, torch.float32, "start_points"),
-                                                           _ptr(end_points, torch.float32, "end_points"), _ptr(seg_view, torch.float32, "seg_view"),
-                                                           n_segments, sample_type, _ptr(output, torch.float16), _ptr(dout, torch.float16),
-                                                           _ptr(workspace, torch.float16, "workspace"), _ptr(live_ws, None, "live_ws"),
-                                                           _ptr(dparams, torch.float32), _stream()),
-          "rtxn_mlp_train_backward_lean_segments")
+    args = (self._h, _ptr(start_points, torch.float32, "start_points"), _ptr(end_points, torch.float32, "end_points"),
+            _ptr(seg_view, torch.float32, "seg_view"), n_segments, sample_type, _ptr(output, torch.float16), _ptr(dout, torch.float16),
+            _ptr(workspace, torch.float16, "workspace"), _ptr(live_ws, None, "live_ws"), _ptr(dparams, torch.float32))
+    if jitter is not None:
+        check(_lib.lib().rtxn_mlp_train_backward_lean_segments_jitter(*args, _jit(jitter), _stream()),
+              "rtxn_mlp_train_backward_lean_segments_jitter")
+    else:
+        check(_lib.lib().rtxn_mlp_train_backward_lean_segments(*args, _stream()), "rtxn_mlp_train_backward_lean_segments")
     return dparams
 
 
@@ -811,11 +844,16 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
                     total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                     encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                     loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                    workspace_lean=False, background=None):
+                    workspace_lean=False, background=None, jitter=None):
     """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781).
-    background: train_background(...) -> rtxn_train_gradients_ex (targets float[n_rays][background.target_channels])."""
-    kw = {k: v for k, v in locals().items() if k != "background"}
-    if background is None:
+    background: train_background(...) -> rtxn_train_gradients_ex (targets float[n_rays][background.target_channels]);
+    jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> rtxn_train_gradients_jitter (with or without a background)."""
+    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter")}
+    if jitter is not None:
+        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
+        check(_lib.lib().rtxn_train_gradients_jitter(C.byref(b), C.byref(background) if background is not None else None, _jit(jitter),
+                                                     _stream()), "rtxn_train_gradients_jitter")
+    elif background is None:
         b = train_batch(**kw)
         check(_lib.lib().rtxn_train_gradients(C.byref(b), _stream()), "rtxn_train_gradients")
     else:
@@ -864,10 +902,14 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None):
+def train_step(args, background=None, jitter=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
-    background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment)."""
-    if background is None:
+    background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
+    jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule)."""
+    if jitter is not None:
+        check(_lib.lib().rtxn_train_step_jitter(C.byref(args), C.byref(background) if background is not None else None, _jit(jitter),
+                                                _stream()), "rtxn_train_step_jitter")
+    elif background is None:
         check(_lib.lib().rtxn_train_step(C.byref(args), _stream()), "rtxn_train_step")
     else:
         check(_lib.lib().rtxn_train_step_ex(C.byref(args), C.byref(background), _stream()), "rtxn_train_step_ex")

@@ -44,9 +44,22 @@ __host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {
   return h;
 }
 
+// RTXN_SAMPLING_JITTER_WORLD (include/rtxn.h states it bit for bit): the offset of sample s of the batch inside its stratum is a
+// pure function of (seed, step, s), formed wherever a kernel forms the sample's position and never stored.  h0 is uniform over a
+// launch (one scalar load and three scalar multiplies per wave); the per-sample part is one fmix32.
+__device__ __forceinline__ unsigned jitter_h0(unsigned seed, const int* step) {
+  const unsigned t = step ? (unsigned)*step : 0u;
+  return fmix32((seed ^ 0x5BD1E995u) + 0x9E3779B9u * t);
+}
+__device__ __forceinline__ float jitter_u(unsigned h0, unsigned s) { return (float)(fmix32(h0 ^ s) >> 8) * 0x1p-24f; }
+
+// The rules of a sample jitter (rtxn_sample_jitter, include/rtxn.h), host only: type 4 needs the struct, the struct needs type 4,
+// and type 4's t_vals are step lengths, which RTXN_VR_COMPAT does not take (vr_mode < 0: the entry point has no compositor).
+int check_sample_jitter(const char* who, int sample_type, const rtxn_sample_jitter* jitter, int vr_mode);
+
 }  // namespace rtxn
 
-#define RTXN_HIP(expr)                                           \
+#define RTXN_HIP(expr)                                          \
   do {                                                           \
     hipError_t e_ = (expr);                                      \
     if (e_ != hipSuccess) return ::rtxn::fail_hip(e_, #expr);    \

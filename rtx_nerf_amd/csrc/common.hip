@@ -74,6 +74,15 @@ hipError_t set_lds_once(const void* fn, size_t bytes) {
   return e;
 }
 
+int check_sample_jitter(const char* who, int sample_type, const rtxn_sample_jitter* jitter, int vr_mode) {
+  RTXN_REQUIRE(sample_type != RTXN_SAMPLING_JITTER_WORLD || jitter, "%s: RTXN_SAMPLING_JITTER_WORLD needs a jitter struct (seed, step)", who);
+  RTXN_REQUIRE(!jitter || sample_type == RTXN_SAMPLING_JITTER_WORLD,
+               "%s: a jitter struct with sample_type %d (it goes with RTXN_SAMPLING_JITTER_WORLD only; pass NULL otherwise)", who, sample_type);
+  RTXN_REQUIRE(!jitter || vr_mode != RTXN_VR_COMPAT,
+               "%s: RTXN_SAMPLING_JITTER_WORLD with RTXN_VR_COMPAT (its t_vals are step lengths, which that compositor does not take)", who);
+  return RTXN_OK;
+}
+
 }  // namespace rtxn
 
 extern "C" int rtxn_version(void) { return RTXN_VERSION; }

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ s
                                                      const float* __restrict__ view_dirs,
                                                      float* __restrict__ t_vals, float* __restrict__ samples,
                                                      int batch_size, const int* __restrict__ num_hits,
-                                                     const int* __restrict__ indices) {
+                                                     const int* __restrict__ indices, rtxn_sample_jitter jitter) {
   __shared__ __attribute__((aligned(16))) float strips[4][64 * 5];
   const int lane = threadIdx.x & 63;
   float* strip = strips[threadIdx.x >> 6];
@@ -75,8 +75,13 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ s
     if (TYPE == RTXN_SAMPLING_REGULAR) {
       t = (float)i * inc;  // i repeated additions of 2^-5 are exact
       tv = (float)(i + 1) * inc;
-    } else if (TYPE == RTXN_SAMPLING_MIDPOINT_WORLD) {
-      t = ((float)i + 0.5f) * inc;
+    } else if (TYPE == RTXN_SAMPLING_MIDPOINT_WORLD || TYPE == RTXN_SAMPLING_JITTER_WORLD) {
+      // JITTER_WORLD: the midpoint's 0.5 becomes u(seed, step, s), s the sample's index in the packed batch -- what the folded
+      // consumers of train.hip form from the same s (include/rtxn.h); t_vals are MIDPOINT_WORLD's
+      const float u = TYPE == RTXN_SAMPLING_JITTER_WORLD
+                          ? rtxn::jitter_u(rtxn::jitter_h0(jitter.seed, jitter.step), (unsigned)((seg0 + (lane >> 5)) * K + i))
+                          : 0.5f;
+      t = ((float)i + u) * inc;
       const long g = (seg0 + min(lane >> 5, nseg - 1)) * 3;
       const float dx = end_points[g] - start_points[g], dy = end_points[g + 1] - start_points[g + 1],
                   dz = end_points[g + 2] - start_points[g + 2];
@@ -125,36 +130,60 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ s
 
 }  // namespace
 
-extern "C" int rtxn_sample(const float* start_points, const float* end_points, const float* view_dirs,
-                           float* t_vals, float* sampled_points, int batch_size, int grid_res,
-                           const int* num_hits, const int* indices, int sample_type, rtxn_stream_t stream) {
-  (void)grid_res;
-  RTXN_REQUIRE(batch_size >= 0, "rtxn_sample: batch_size = %d < 0", batch_size);
-  RTXN_REQUIRE(sample_type >= 0 && sample_type <= 3, "rtxn_sample: unknown sample_type %d", sample_type);
+// rtxn_sample (jitter == NULL: types 0..3) and rtxn_sample_ex (RTXN_SAMPLING_JITTER_WORLD with its struct as well)
+static int sample_entry(const char* who, const float* start_points, const float* end_points, const float* view_dirs, float* t_vals,
+                        float* sampled_points, int batch_size, const int* num_hits, const int* indices, int sample_type,
+                        const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  RTXN_REQUIRE(batch_size >= 0, "%s: batch_size = %d < 0", who, batch_size);
+  RTXN_REQUIRE(sample_type >= 0 && sample_type <= (jitter ? RTXN_SAMPLING_JITTER_WORLD : RTXN_SAMPLING_MIDPOINT_WORLD),
+               "%s: unknown sample_type %d", who, sample_type);
   RTXN_DEVICE_OR_FAIL();
   if (batch_size == 0) return RTXN_OK;
-  RTXN_REQUIRE(start_points && end_points && view_dirs && t_vals && sampled_points && num_hits && indices,
-               "rtxn_sample: NULL buffer");
+  RTXN_REQUIRE(start_points && end_points && view_dirs && t_vals && sampled_points && num_hits && indices, "%s: NULL buffer", who);
   hipStream_t s = rtxn::as_stream(stream);
   dim3 grid((batch_size + 3) / 4), block(256);
+  const rtxn_sample_jitter none{0u, nullptr};
   switch (sample_type) {
     case RTXN_SAMPLING_REGULAR:
       sample_kernel<RTXN_SAMPLING_REGULAR><<<grid, block, 0, s>>>(start_points, end_points, view_dirs, t_vals,
-                                                                   sampled_points, batch_size, num_hits, indices);
+                                                                   sampled_points, batch_size, num_hits, indices, none);
       break;
     case RTXN_SAMPLING_STRATIFIED_JITTERING:
       sample_kernel<RTXN_SAMPLING_STRATIFIED_JITTERING><<<grid, block, 0, s>>>(
-          start_points, end_points, view_dirs, t_vals, sampled_points, batch_size, num_hits, indices);
+          start_points, end_points, view_dirs, t_vals, sampled_points, batch_size, num_hits, indices, none);
       break;
     case RTXN_SAMPLING_UNIFORM:
       sample_kernel<RTXN_SAMPLING_UNIFORM><<<grid, block, 0, s>>>(start_points, end_points, view_dirs, t_vals,
-                                                                   sampled_points, batch_size, num_hits, indices);
+                                                                   sampled_points, batch_size, num_hits, indices, none);
+      break;
+    case RTXN_SAMPLING_JITTER_WORLD:
+      sample_kernel<RTXN_SAMPLING_JITTER_WORLD><<<grid, block, 0, s>>>(start_points, end_points, view_dirs, t_vals,
+                                                                        sampled_points, batch_size, num_hits, indices, *jitter);
       break;
     default:
       sample_kernel<RTXN_SAMPLING_MIDPOINT_WORLD><<<grid, block, 0, s>>>(start_points, end_points, view_dirs, t_vals,
-                                                                          sampled_points, batch_size, num_hits, indices);
+                                                                          sampled_points, batch_size, num_hits, indices, none);
       break;
   }
   RTXN_LAUNCH_CHECK("sample_kernel");
   return RTXN_OK;
+}
+
+extern "C" int rtxn_sample(const float* start_points, const float* end_points, const float* view_dirs,
+                           float* t_vals, float* sampled_points, int batch_size, int grid_res,
+                           const int* num_hits, const int* indices, int sample_type, rtxn_stream_t stream) {
+  (void)grid_res;
+  return sample_entry("rtxn_sample", start_points, end_points, view_dirs, t_vals, sampled_points, batch_size, num_hits, indices, sample_type,
+                      nullptr, stream);
+}
+
+extern "C" int rtxn_sample_ex(const float* start_points, const float* end_points, const float* view_dirs,
+                              float* t_vals, float* sampled_points, int batch_size, int grid_res,
+                              const int* num_hits, const int* indices, int sample_type, const rtxn_sample_jitter* jitter,
+                              rtxn_stream_t stream) {
+  (void)grid_res;
+  const int rc = rtxn::check_sample_jitter("rtxn_sample_ex", sample_type, jitter, -1);
+  if (rc != RTXN_OK) return rc;
+  return sample_entry("rtxn_sample_ex", start_points, end_points, view_dirs, t_vals, sampled_points, batch_size, num_hits, indices, sample_type,
+                      jitter, stream);
 }

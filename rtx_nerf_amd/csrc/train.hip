@@ -105,20 +105,31 @@ __device__ __forceinline__ void grad_add(float* addr, float v, const DetCtx& det
 // packed segments themselves -- sample (segment g, i) is then formed here exactly as sample_kernel forms it (REGULAR: t = i/32;
 // MIDPOINT_WORLD: t = (i + 0.5)/32; position = fma(t, end - start, start); (theta, phi) = the segment's), so the 20-byte
 // samples never exist in memory: launchSampler folded into its consumers.
+// JITTER_WORLD: MIDPOINT_WORLD with the 0.5 replaced by u(seed, step, s) in [0, 1) (rtxn::jitter_u): the same t_vals, and every
+// consumer -- forward, weight gradient, scatter -- forms the same position from the same s.  The switch is a wave-uniform branch on
+// the kernarg `jitter`: with it off, t is the expression it was and the hash is never issued.
 struct SampleSrc {
   const float* in;        // [S][5], or NULL: segments
   const float* start;     // [P][3]
   const float* end;       // [P][3]
   const float* seg_view;  // [P][2]
-  int midpoint;           // RTXN_SAMPLING_MIDPOINT_WORLD (1) / RTXN_SAMPLING_REGULAR (0)
+  int midpoint;           // RTXN_SAMPLING_MIDPOINT_WORLD, RTXN_SAMPLING_JITTER_WORLD (1) / RTXN_SAMPLING_REGULAR (0)
+  int jitter;             // RTXN_SAMPLING_JITTER_WORLD
+  unsigned seed;          // jitter: rtxn_sample_jitter's
+  const int* step;        // jitter: DEVICE int, NULL = 0
 };
+// where sample s sits inside its stratum [i/32, (i + 1)/32), in strata
+__device__ __forceinline__ float sample_offset(const SampleSrc& src, long s) {
+  if (src.jitter) return rtxn::jitter_u(rtxn::jitter_h0(src.seed, src.step), (unsigned)s);
+  return src.midpoint ? 0.5f : 0.0f;
+}
 __device__ __forceinline__ void sample_pos(const SampleSrc& src, long s, bool ok, float (&x)[3]) {
   if (src.in) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) x[a] = ok ? src.in[5 * s + a] : 0.0f;
   } else {
     const long g = ok ? (s >> 5) * 3 : 0;
-    const float t = ((float)(int)(s & 31) + (src.midpoint ? 0.5f : 0.0f)) * (1.0f / 32);
+    const float t = ((float)(int)(s & 31) + sample_offset(src, s)) * (1.0f / 32);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const float og = src.start[g + a];
@@ -133,7 +144,7 @@ __device__ __forceinline__ void sample_pos_unmasked(const SampleSrc& src, long s
   const long g = (s >> 5) * 3;
   const float* p0 = src.in ? src.in + 5 * s : src.start + g;
   const float* p1 = src.in ? p0 : src.end + g;
-  const float t = src.in ? 0.0f : ((float)(int)(s & 31) + (src.midpoint ? 0.5f : 0.0f)) * (1.0f / 32);
+  const float t = src.in ? 0.0f : ((float)(int)(s & 31) + sample_offset(src, s)) * (1.0f / 32);
   float og[3], en[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) og[a] = p0[a], en[a] = p1[a];
@@ -2175,9 +2186,11 @@ __device__ __forceinline__ void wgrad_recompute_pass(LeanArgs a, const int sub_b
       // the four dZ stages of the tile's first gradient layer: the whole ring is free, and they travel while the encoding is computed
 #pragma unroll
       for (int v = 0; v < 4; ++v) issue_stage(v, L0, (long)tile * kTile + 64 * v);
-      const float tpar = ((float)col + (a.src.midpoint ? 0.5f : 0.0f)) * (1.0f / 32);      // as sample_pos: sample i of its segment
+      const float tmid = ((float)col + (a.src.midpoint ? 0.5f : 0.0f)) * (1.0f / 32);      // as sample_pos: sample i of its segment
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) {
+        // jitter: sample col of the segment at col0[ct] is sample col0[ct] + col of the batch, with or without the live list
+        const float tpar = a.src.jitter ? ((float)col + sample_offset(a.src, col0[ct] + col)) * (1.0f / 32) : tmid;
         float x[5];
 #pragma unroll
         for (int c = 0; c < 3; ++c) x[c] = fmaf(tpar, seg[ct][3 + c] - seg[ct][c], seg[ct][c]);
@@ -2910,27 +2923,55 @@ extern "C" int rtxn_encode_frequency(const rtxn_mlp* m, const float* input, void
   return encode_frequency_impl(m, src, encT, nullptr, 1.0f, n_samples, kHostCount, stream);
 }
 
+// jitter: the entry point's rtxn_sample_jitter (NULL: none); its rules come first, before anything else is looked at
 static int check_segments(const char* who, const float* start_points, const float* end_points, const float* seg_view,
-                          long n_segments, int sample_type) {
+                          long n_segments, int sample_type, const rtxn_sample_jitter* jitter = nullptr, int vr_mode = -1) {
+  const int rc = rtxn::check_sample_jitter(who, sample_type, jitter, vr_mode);
+  if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(n_segments >= 0 && n_segments <= kMaxTrainSamples / 32, "%s: n_segments = %ld", who, n_segments);
-  RTXN_REQUIRE(sample_type == RTXN_SAMPLING_REGULAR || sample_type == RTXN_SAMPLING_MIDPOINT_WORLD,
+  RTXN_REQUIRE(sample_type == RTXN_SAMPLING_REGULAR || sample_type == RTXN_SAMPLING_MIDPOINT_WORLD || jitter,
                "%s: sample_type %d (the deterministic modes only: REGULAR, MIDPOINT_WORLD)", who, sample_type);
   RTXN_REQUIRE(n_segments == 0 || (start_points && end_points && seg_view), "%s: NULL segment buffer", who);
   return RTXN_OK;
+}
+// the packed segments of a checked entry point as a sample source
+static SampleSrc segment_src(const float* start_points, const float* end_points, const float* seg_view, int sample_type,
+                             const rtxn_sample_jitter* jitter) {
+  SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type != RTXN_SAMPLING_REGULAR, 0, 0u, nullptr};
+  if (jitter) src.jitter = 1, src.seed = jitter->seed, src.step = jitter->step;
+  return src;
+}
+
+// Every segment-reading entry point below exists twice: the plain name and the same with a trailing rtxn_sample_jitter
+// (`_jitter`), which the plain one calls with NULL.  `who` is the name the caller used.
+static int encode_frequency_segments_entry(const char* who, const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                           const float* seg_view, long n_segments, int sample_type, float t_scale, void* encT,
+                                           float* t_vals, const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  int rc = rtxn::check_sample_jitter(who, sample_type, jitter, -1);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(m && m->cfg.encoding == RTXN_ENC_FREQUENCY, "%s: model has no frequency encoding", who);
+  RTXN_REQUIRE(m->cfg.n_pos_dims == 3 && m->cfg.n_dir_dims == 2, "%s: needs 3 + 2 input dimensions", who);
+  rc = check_segments(who, start_points, end_points, seg_view, n_segments, sample_type, jitter);
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  if (n_segments == 0) return RTXN_OK;
+  RTXN_REQUIRE(encT, "%s: NULL buffer", who);
+  const SampleSrc src = segment_src(start_points, end_points, seg_view, sample_type, jitter);
+  return encode_frequency_impl(m, src, encT, t_vals, t_scale, n_segments * 32, kHostCount, stream);
 }
 
 extern "C" int rtxn_encode_frequency_segments(const rtxn_mlp* m, const float* start_points, const float* end_points,
                                               const float* seg_view, long n_segments, int sample_type, float t_scale,
                                               void* encT, float* t_vals, rtxn_stream_t stream) {
-  RTXN_REQUIRE(m && m->cfg.encoding == RTXN_ENC_FREQUENCY, "rtxn_encode_frequency_segments: model has no frequency encoding");
-  RTXN_REQUIRE(m->cfg.n_pos_dims == 3 && m->cfg.n_dir_dims == 2, "rtxn_encode_frequency_segments: needs 3 + 2 input dimensions");
-  int rc = check_segments("rtxn_encode_frequency_segments", start_points, end_points, seg_view, n_segments, sample_type);
-  if (rc != RTXN_OK) return rc;
-  RTXN_DEVICE_OR_FAIL();
-  if (n_segments == 0) return RTXN_OK;
-  RTXN_REQUIRE(encT, "rtxn_encode_frequency_segments: NULL buffer");
-  const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return encode_frequency_impl(m, src, encT, t_vals, t_scale, n_segments * 32, kHostCount, stream);
+  return encode_frequency_segments_entry("rtxn_encode_frequency_segments", m, start_points, end_points, seg_view, n_segments, sample_type, t_scale,
+                                         encT, t_vals, nullptr, stream);
+}
+
+extern "C" int rtxn_encode_frequency_segments_jitter(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                                     const float* seg_view, long n_segments, int sample_type, float t_scale,
+                                                     void* encT, float* t_vals, const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  return encode_frequency_segments_entry("rtxn_encode_frequency_segments_jitter", m, start_points, end_points, seg_view, n_segments, sample_type,
+                                         t_scale, encT, t_vals, jitter, stream);
 }
 
 using rtxn::set_lds_once;
@@ -3209,29 +3250,47 @@ extern "C" int rtxn_mlp_train_forward_lean_fused_supported(const rtxn_mlp* m) {
          m->cfg.n_dir_dims == 2 && m->cfg.n_dir_freqs == 12;
 }
 
-extern "C" int rtxn_mlp_train_forward_lean_segments(const rtxn_mlp* m, const float* start_points, const float* end_points,
-                                                    const float* seg_view, long n_segments, int sample_type, float t_scale, float* t_vals,
-                                                    void* workspace_lean, void* output_half, float* radiance, rtxn_stream_t stream) {
-  int rc = check_lean(m, "rtxn_mlp_train_forward_lean_segments", n_segments * 32, true);
+static int train_forward_lean_segments_entry(const char* who, const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                             const float* seg_view, long n_segments, int sample_type, float t_scale, float* t_vals,
+                                             void* workspace_lean, void* output_half, float* radiance, const rtxn_sample_jitter* jitter,
+                                             rtxn_stream_t stream) {
+  int rc = rtxn::check_sample_jitter(who, sample_type, jitter, -1);
+  if (rc != RTXN_OK) return rc;
+  rc = check_lean(m, who, n_segments * 32, true);
   if (rc != RTXN_OK) return rc;
   if (!rtxn_mlp_train_forward_lean_fused_supported(m)) {
-    rtxn::set_error("rtxn_mlp_train_forward_lean_segments: the fused encoder is the reference's Composite-Frequency(3 x 10, 2 x 12); this model: "
-                    "%d x %d, %d x %d -- use rtxn_encode_frequency_segments + rtxn_mlp_train_forward_lean", m->cfg.n_pos_dims, m->cfg.n_pos_freqs,
+    rtxn::set_error("%s: the fused encoder is the reference's Composite-Frequency(3 x 10, 2 x 12); this model: "
+                    "%d x %d, %d x %d -- use rtxn_encode_frequency_segments + rtxn_mlp_train_forward_lean", who, m->cfg.n_pos_dims, m->cfg.n_pos_freqs,
                     m->cfg.n_dir_dims, m->cfg.n_dir_freqs);
     return RTXN_ERR_UNSUPPORTED;
   }
-  rc = check_segments("rtxn_mlp_train_forward_lean_segments", start_points, end_points, seg_view, n_segments, sample_type);
+  rc = check_segments(who, start_points, end_points, seg_view, n_segments, sample_type, jitter);
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
   if (n_segments == 0) return RTXN_OK;
-  RTXN_REQUIRE(workspace_lean && output_half, "rtxn_mlp_train_forward_lean_segments: NULL buffer");
-  const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
+  RTXN_REQUIRE(workspace_lean && output_half, "%s: NULL buffer", who);
+  const SampleSrc src = segment_src(start_points, end_points, seg_view, sample_type, jitter);
   FwdOpts o;
   o.save = kSaveMasks;
   o.src = &src;
   o.t_vals = t_vals;
   o.t_scale = t_scale;
   return train_forward_impl(m, nullptr, n_segments * 32, workspace_lean, output_half, radiance, kHostCount, stream, o);
+}
+
+extern "C" int rtxn_mlp_train_forward_lean_segments(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                                    const float* seg_view, long n_segments, int sample_type, float t_scale, float* t_vals,
+                                                    void* workspace_lean, void* output_half, float* radiance, rtxn_stream_t stream) {
+  return train_forward_lean_segments_entry("rtxn_mlp_train_forward_lean_segments", m, start_points, end_points, seg_view, n_segments, sample_type,
+                                           t_scale, t_vals, workspace_lean, output_half, radiance, nullptr, stream);
+}
+
+extern "C" int rtxn_mlp_train_forward_lean_segments_jitter(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                                           const float* seg_view, long n_segments, int sample_type, float t_scale,
+                                                           float* t_vals, void* workspace_lean, void* output_half, float* radiance,
+                                                           const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  return train_forward_lean_segments_entry("rtxn_mlp_train_forward_lean_segments_jitter", m, start_points, end_points, seg_view, n_segments,
+                                           sample_type, t_scale, t_vals, workspace_lean, output_half, radiance, jitter, stream);
 }
 
 #ifdef RTXN_LN_STAMPS
@@ -3255,24 +3314,42 @@ extern "C" int rtxn_mlp_train_backward_lean(const rtxn_mlp* m, const void* encT,
   return train_backward_lean_impl(m, encT, output_half, dout_half4, n_samples, workspace_lean, dparams, kHostCount, stream, nullptr, LiveRef(live_ws));
 }
 
+static int train_backward_lean_segments_entry(const char* who, const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                              const float* seg_view, long n_segments, int sample_type, const void* output_half,
+                                              const void* dout_half4, void* workspace_lean, const void* live_ws, float* dparams,
+                                              const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  int rc = rtxn::check_sample_jitter(who, sample_type, jitter, -1);
+  if (rc != RTXN_OK) return rc;
+  rc = check_lean(m, who, n_segments * 32, true);
+  if (rc != RTXN_OK) return rc;
+  if (!rtxn_mlp_train_forward_lean_fused_supported(m)) {
+    rtxn::set_error("%s: the fused encoder is the reference's Composite-Frequency(3 x 10, 2 x 12); use "
+                    "rtxn_mlp_train_backward_lean with encT", who);
+    return RTXN_ERR_UNSUPPORTED;
+  }
+  rc = check_segments(who, start_points, end_points, seg_view, n_segments, sample_type, jitter);
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  if (n_segments == 0) return RTXN_OK;
+  RTXN_REQUIRE(output_half && dout_half4 && workspace_lean && dparams, "%s: NULL buffer", who);
+  const SampleSrc src = segment_src(start_points, end_points, seg_view, sample_type, jitter);
+  return train_backward_lean_impl(m, nullptr, output_half, dout_half4, n_segments * 32, workspace_lean, dparams, kHostCount, stream, &src, LiveRef(live_ws));
+}
+
 extern "C" int rtxn_mlp_train_backward_lean_segments(const rtxn_mlp* m, const float* start_points, const float* end_points,
                                                      const float* seg_view, long n_segments, int sample_type, const void* output_half,
                                                      const void* dout_half4, void* workspace_lean, const void* live_ws, float* dparams,
                                                      rtxn_stream_t stream) {
-  int rc = check_lean(m, "rtxn_mlp_train_backward_lean_segments", n_segments * 32, true);
-  if (rc != RTXN_OK) return rc;
-  if (!rtxn_mlp_train_forward_lean_fused_supported(m)) {
-    rtxn::set_error("rtxn_mlp_train_backward_lean_segments: the fused encoder is the reference's Composite-Frequency(3 x 10, 2 x 12); use "
-                    "rtxn_mlp_train_backward_lean with encT");
-    return RTXN_ERR_UNSUPPORTED;
-  }
-  rc = check_segments("rtxn_mlp_train_backward_lean_segments", start_points, end_points, seg_view, n_segments, sample_type);
-  if (rc != RTXN_OK) return rc;
-  RTXN_DEVICE_OR_FAIL();
-  if (n_segments == 0) return RTXN_OK;
-  RTXN_REQUIRE(output_half && dout_half4 && workspace_lean && dparams, "rtxn_mlp_train_backward_lean_segments: NULL buffer");
-  const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return train_backward_lean_impl(m, nullptr, output_half, dout_half4, n_segments * 32, workspace_lean, dparams, kHostCount, stream, &src, LiveRef(live_ws));
+  return train_backward_lean_segments_entry("rtxn_mlp_train_backward_lean_segments", m, start_points, end_points, seg_view, n_segments, sample_type,
+                                            output_half, dout_half4, workspace_lean, live_ws, dparams, nullptr, stream);
+}
+
+extern "C" int rtxn_mlp_train_backward_lean_segments_jitter(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                                            const float* seg_view, long n_segments, int sample_type, const void* output_half,
+                                                            const void* dout_half4, void* workspace_lean, const void* live_ws, float* dparams,
+                                                            const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  return train_backward_lean_segments_entry("rtxn_mlp_train_backward_lean_segments_jitter", m, start_points, end_points, seg_view, n_segments,
+                                            sample_type, output_half, dout_half4, workspace_lean, live_ws, dparams, jitter, stream);
 }
 
 // ---- recompute path (64-wide models): forward without saved activations + fused backward ----
@@ -3652,18 +3729,36 @@ extern "C" int rtxn_hashgrid_encode(const rtxn_hashgrid* g, int n_dir_freqs, con
   return hashgrid_encode_impl(g, n_dir_freqs, table_fp16, src, encT, nullptr, 1.0f, n_samples, kHostCount, stream);
 }
 
+static int hashgrid_encode_segments_entry(const char* who, const rtxn_hashgrid* g, int n_dir_freqs, const void* table_fp16,
+                                          const float* start_points, const float* end_points, const float* seg_view, long n_segments,
+                                          int sample_type, float t_scale, void* encT, float* t_vals, const rtxn_sample_jitter* jitter,
+                                          rtxn_stream_t stream) {
+  int rc = rtxn::check_sample_jitter(who, sample_type, jitter, -1);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(g && n_dir_freqs >= 0 && n_dir_freqs <= 16, "%s: bad argument", who);
+  rc = check_segments(who, start_points, end_points, seg_view, n_segments, sample_type, jitter);
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  if (n_segments == 0) return RTXN_OK;
+  RTXN_REQUIRE(table_fp16 && encT, "%s: NULL buffer", who);
+  const SampleSrc src = segment_src(start_points, end_points, seg_view, sample_type, jitter);
+  return hashgrid_encode_impl(g, n_dir_freqs, table_fp16, src, encT, t_vals, t_scale, n_segments * 32, kHostCount, stream);
+}
+
 extern "C" int rtxn_hashgrid_encode_segments(const rtxn_hashgrid* g, int n_dir_freqs, const void* table_fp16,
                                              const float* start_points, const float* end_points, const float* seg_view,
                                              long n_segments, int sample_type, float t_scale, void* encT, float* t_vals,
                                              rtxn_stream_t stream) {
-  RTXN_REQUIRE(g && n_dir_freqs >= 0 && n_dir_freqs <= 16, "rtxn_hashgrid_encode_segments: bad argument");
-  int rc = check_segments("rtxn_hashgrid_encode_segments", start_points, end_points, seg_view, n_segments, sample_type);
-  if (rc != RTXN_OK) return rc;
-  RTXN_DEVICE_OR_FAIL();
-  if (n_segments == 0) return RTXN_OK;
-  RTXN_REQUIRE(table_fp16 && encT, "rtxn_hashgrid_encode_segments: NULL buffer");
-  const SampleSrc src{nullptr, start_points, end_points, seg_view, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
-  return hashgrid_encode_impl(g, n_dir_freqs, table_fp16, src, encT, t_vals, t_scale, n_segments * 32, kHostCount, stream);
+  return hashgrid_encode_segments_entry("rtxn_hashgrid_encode_segments", g, n_dir_freqs, table_fp16, start_points, end_points, seg_view, n_segments,
+                                        sample_type, t_scale, encT, t_vals, nullptr, stream);
+}
+
+extern "C" int rtxn_hashgrid_encode_segments_jitter(const rtxn_hashgrid* g, int n_dir_freqs, const void* table_fp16,
+                                                    const float* start_points, const float* end_points, const float* seg_view,
+                                                    long n_segments, int sample_type, float t_scale, void* encT, float* t_vals,
+                                                    const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  return hashgrid_encode_segments_entry("rtxn_hashgrid_encode_segments_jitter", g, n_dir_freqs, table_fp16, start_points, end_points, seg_view,
+                                        n_segments, sample_type, t_scale, encT, t_vals, jitter, stream);
 }
 
 // dtable_hashed_half == NULL: every level into the fp32 table.  Otherwise (n_features == 2): the hashed levels go to the fp16
@@ -3727,15 +3822,17 @@ extern "C" int rtxn_hashgrid_backward_mixed(const rtxn_hashgrid* g, const float*
 // rtxn_hashgrid_backward_segments[_live]: with_live: over the live list of live_ws only
 static int hashgrid_backward_segments_entry(const char* who, const rtxn_hashgrid* g, const float* start_points, const float* end_points,
                                             long n_segments, int sample_type, const void* dencT, bool with_live, const void* live_ws,
-                                            float* dtable, void* dtable_hashed_half, rtxn_stream_t stream) {
+                                            float* dtable, void* dtable_hashed_half, const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  int rc = rtxn::check_sample_jitter(who, sample_type, jitter, -1);
+  if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(g, "%s: NULL grid", who);
-  int rc = check_segments(who, start_points, end_points, start_points, n_segments, sample_type);
+  rc = check_segments(who, start_points, end_points, start_points, n_segments, sample_type, jitter);
   if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(!dtable_hashed_half || g->cfg.n_features == 2, "%s: packed fp16 atomics need n_features == 2 (got %d)", who, g->cfg.n_features);
   RTXN_DEVICE_OR_FAIL();
   if (n_segments == 0) return RTXN_OK;
   RTXN_REQUIRE(dencT && dtable && (live_ws || !with_live), "%s: NULL buffer", who);
-  const SampleSrc src{nullptr, start_points, end_points, nullptr, sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
+  const SampleSrc src = segment_src(start_points, end_points, nullptr, sample_type, jitter);
   return hashgrid_backward_impl(g, src, dencT, n_segments * 32, dtable, dtable_hashed_half, kHostCount, stream, LiveRef(live_ws));
 }
 
@@ -3743,7 +3840,14 @@ extern "C" int rtxn_hashgrid_backward_segments(const rtxn_hashgrid* g, const flo
                                                long n_segments, int sample_type, const void* dencT, float* dtable,
                                                void* dtable_hashed_half, rtxn_stream_t stream) {
   return hashgrid_backward_segments_entry("rtxn_hashgrid_backward_segments", g, start_points, end_points, n_segments, sample_type, dencT, false, nullptr,
-                                          dtable, dtable_hashed_half, stream);
+                                          dtable, dtable_hashed_half, nullptr, stream);
+}
+
+extern "C" int rtxn_hashgrid_backward_segments_jitter(const rtxn_hashgrid* g, const float* start_points, const float* end_points,
+                                                      long n_segments, int sample_type, const void* dencT, float* dtable,
+                                                      void* dtable_hashed_half, const rtxn_sample_jitter* jitter, rtxn_stream_t stream) {
+  return hashgrid_backward_segments_entry("rtxn_hashgrid_backward_segments_jitter", g, start_points, end_points, n_segments, sample_type, dencT, false,
+                                          nullptr, dtable, dtable_hashed_half, jitter, stream);
 }
 
 extern "C" int rtxn_l2_loss(const float* pred, const float* target, long n, float loss_scale, float* values,
@@ -3891,11 +3995,20 @@ extern "C" int rtxn_hashgrid_backward_segments_live(const rtxn_hashgrid* g, cons
                                                     long n_segments, int sample_type, const void* dencT, const void* live_ws,
                                                     float* dtable, void* dtable_hashed_half, rtxn_stream_t stream) {
   return hashgrid_backward_segments_entry("rtxn_hashgrid_backward_segments_live", g, start_points, end_points, n_segments, sample_type, dencT, true,
-                                          live_ws, dtable, dtable_hashed_half, stream);
+                                          live_ws, dtable, dtable_hashed_half, nullptr, stream);
+}
+
+extern "C" int rtxn_hashgrid_backward_segments_live_jitter(const rtxn_hashgrid* g, const float* start_points, const float* end_points,
+                                                           long n_segments, int sample_type, const void* dencT, const void* live_ws,
+                                                           float* dtable, void* dtable_hashed_half, const rtxn_sample_jitter* jitter,
+                                                           rtxn_stream_t stream) {
+  return hashgrid_backward_segments_entry("rtxn_hashgrid_backward_segments_live_jitter", g, start_points, end_points, n_segments, sample_type, dencT,
+                                          true, live_ws, dtable, dtable_hashed_half, jitter, stream);
 }
 
 // ------------------------------------------------------------------------- a whole batch, segment count on the device
-static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
+static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                rtxn_stream_t stream) {
   RTXN_REQUIRE(b && b->mlp, "rtxn_train_gradients: NULL batch or model");
   const rtxn_mlp* m = b->mlp;
   int rc = check_train(m, "rtxn_train_gradients");
@@ -3903,7 +4016,8 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   RTXN_REQUIRE(b->n_rays > 0, "rtxn_train_gradients: n_rays = %d", b->n_rays);
   RTXN_REQUIRE(b->segment_capacity > 0 && b->segment_capacity <= kMaxTrainSamples / 32 && b->segment_capacity <= 0x7fffffffL,
                "rtxn_train_gradients: segment_capacity = %ld", b->segment_capacity);
-  rc = check_segments("rtxn_train_gradients", b->start_points, b->end_points, b->seg_view, b->segment_capacity, b->sample_type);
+  rc = check_segments("rtxn_train_gradients", b->start_points, b->end_points, b->seg_view, b->segment_capacity, b->sample_type, jitter,
+                      b->vr_mode);
   if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(b->total_segments && b->num_stored && b->indices, "rtxn_train_gradients: NULL total_segments / num_stored / indices");
   RTXN_REQUIRE(b->vr_mode == RTXN_VR_COMPAT || b->vr_mode == RTXN_VR_NERF, "rtxn_train_gradients: vr_mode %d", b->vr_mode);
@@ -3931,7 +4045,7 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   RTXN_DEVICE_OR_FAIL();
   const DevCount dc{b->total_segments, (int)b->segment_capacity};
   const long cap_samples = b->segment_capacity * 32;
-  const SampleSrc src{nullptr, b->start_points, b->end_points, b->seg_view, b->sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
+  const SampleSrc src = segment_src(b->start_points, b->end_points, b->seg_view, b->sample_type, jitter);
   // The reference's own model on the lean path: sampler AND encoder folded into the forward and into the weight gradient (encT is
   // never written; RTXN_TRAIN_LEAN_FUSED=0: the staged encoder, for the A/B -- the same values bit for bit)
   const char* fused_env = getenv("RTXN_TRAIN_LEAN_FUSED");
@@ -3992,13 +4106,13 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
                                        hash ? b->dencT : nullptr, dc, stream, live);
   if (rc != RTXN_OK) return rc;
   if (hash && !b->skip_table_backward) {
-    const SampleSrc bsrc{nullptr, b->start_points, b->end_points, nullptr, b->sample_type == RTXN_SAMPLING_MIDPOINT_WORLD};
+    const SampleSrc bsrc = segment_src(b->start_points, b->end_points, nullptr, b->sample_type, jitter);    // the forward's samples
     rc = hashgrid_backward_impl(b->grid, bsrc, b->dencT, cap_samples, b->dtable, b->dtable_hashed_half, dc, stream, live);
   }
   return rc;
 }
 
-extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, stream); }
+extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, nullptr, stream); }
 
 // over a background: the one difference is the compositor (rtxn_volrender_l2_train_ex); NULL / NONE + 3 channels: the plain call
 extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
@@ -4006,5 +4120,17 @@ extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_tra
   bool active = false;
   const int rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_ex", &active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, stream);
+  return train_gradients_impl(b, active ? bg : nullptr, nullptr, stream);
+}
+
+// ... and with the sampler's jitter (RTXN_SAMPLING_JITTER_WORLD): both optional, NULL + NULL is rtxn_train_gradients
+extern "C" int rtxn_train_gradients_jitter(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                           rtxn_stream_t stream) {
+  RTXN_REQUIRE(b, "rtxn_train_gradients_jitter: NULL batch");
+  int rc = rtxn::check_sample_jitter("rtxn_train_gradients_jitter", b->sample_type, jitter, b->vr_mode);
+  if (rc != RTXN_OK) return rc;
+  bool active = false;
+  rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_jitter", &active);
+  if (rc != RTXN_OK) return rc;
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, stream);
 }

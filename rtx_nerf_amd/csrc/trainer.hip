@@ -9,16 +9,22 @@
 namespace {
 
 // t = ++*step;  *lr_eff = lr sqrt(1 - beta2^t) / (1 - beta1^t)  -- the same single-precision expression rtxn_adam_effective_lr
-// evaluates on the host (powf on the device library: within an ulp or two of glibc's; it multiplies a learning rate)
+// evaluates on the host.  The two powers are formed in double and rounded once: the device library's powf is an ulp or two off
+// glibc's, which is correctly rounded but for rare ties, so a step through this call used to leave the eager step's parameters
+// by 1e-8 from the third step on; like this the rate is the host's bit for bit (beta 0.9 / 0.999, t = 1 .. 70000: all but t = 3606,
+// where glibc's own powf is the one that misrounds) and the eager, captured and one-call steps stay bit-identical in
+// deterministic mode (tests/test_gpu_sample_jitter.py).  sqrtf and the division are correctly rounded on both sides.
 __global__ void advance_step_kernel(int* step, float lr, float beta1, float beta2, float* lr_eff) {
   const int t = *step + 1;
   *step = t;
-  *lr_eff = lr * sqrtf(1.0f - powf(beta2, (float)t)) / (1.0f - powf(beta1, (float)t));
+  const float p2 = (float)pow((double)beta2, (double)t), p1 = (float)pow((double)beta1, (double)t);
+  *lr_eff = lr * sqrtf(1.0f - p2) / (1.0f - p1);
 }
 
 }  // namespace
 
-static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
+static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                           rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
@@ -60,7 +66,7 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   if (rc != RTXN_OK) return rc;
 
   // ---- sampler ... backward (main.cu:703-781), segment count read on the device ----
-  rc = bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
+  rc = jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
   if (rc != RTXN_OK) return rc;
 
   // ---- optimizer->step (main.cu:787): every gradient is cleared as it is consumed ----
@@ -93,16 +99,38 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   return RTXN_OK;
 }
 
-extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, stream); }
+extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, stream); }
 
 extern "C" int rtxn_train_step_ex(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step_ex: NULL arguments");
   bool active = false;
   const int rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_ex", &active);
   if (rc != RTXN_OK) return rc;
-  if (!active) return train_step_impl(a, nullptr, stream);
+  if (!active) return train_step_impl(a, nullptr, nullptr, stream);
   // RANDOM without a counter of its own: the optimizer's, read by the compositor before advance_step_kernel increments it
   rtxn_train_background own = *bg;
   if (own.mode == RTXN_BG_RANDOM && !own.step) own.step = a->opt.step;
-  return train_step_impl(a, &own, stream);
+  return train_step_impl(a, &own, nullptr, stream);
+}
+
+// ... and with the sampler's jitter; a NULL jitter->step is the optimizer's counter too, by the same rule
+extern "C" int rtxn_train_step_jitter(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                      rtxn_stream_t stream) {
+  RTXN_REQUIRE(a, "rtxn_train_step_jitter: NULL arguments");
+  int rc = rtxn::check_sample_jitter("rtxn_train_step_jitter", a->batch.sample_type, jitter, a->batch.vr_mode);
+  if (rc != RTXN_OK) return rc;
+  bool active = false;
+  rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_jitter", &active);
+  if (rc != RTXN_OK) return rc;
+  rtxn_train_background own_bg;
+  if (active) {
+    own_bg = *bg;
+    if (own_bg.mode == RTXN_BG_RANDOM && !own_bg.step) own_bg.step = a->opt.step;
+  }
+  rtxn_sample_jitter own_jitter;
+  if (jitter) {
+    own_jitter = *jitter;
+    if (!own_jitter.step) own_jitter.step = a->opt.step;
+  }
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, stream);
 }

@@ -58,8 +58,11 @@ class Trainer:
     def __init__(self, grid_res, occupancy=None, encoding="hash", n_neurons=64, n_hidden_layers=4,
                  hashgrid=None, n_dir_freqs=4, batch_rays=4096, max_segments=None, lr=1e-3, loss_scale=128.0,
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
-                 target_channels=None):
-        """background: None (black, the reference's compositor), (r, g, b) -- train over that constant colour -- or "random":
+                 target_channels=None, sample_jitter=False, jitter_seed=0):
+        """sample_jitter: draw the 32 samples of every segment at fresh positions inside their strata on every training step
+        (SAMPLING_JITTER_WORLD; mode "nerf" only) instead of at the midpoints; rendering and the occupancy refresh stay
+        at the midpoints.  jitter_seed: its seed (the rank is mixed in when data parallel).
+        background: None (black, the reference's compositor), (r, g, b) -- train over that constant colour -- or "random":
         a fresh colour per ray and step (librtxn: rtxn_volrender_l2_train_ex / rtxn_train_gradients_ex /
         rtxn_train_step_ex).  Targets are [n, 3] or straight RGBA [n, 4] (composited over the ray's background in the kernel);
         "random" needs RGBA.  target_channels: the width of graph_targets for the captured / one-call steps (default 4 with
@@ -79,6 +82,7 @@ class Trainer:
         self._occ_seed = seed
         self._stage_ev = None     # list of (stage, start event, end event) while time_stages() is collecting
         self._init_background(background, background_seed, target_channels)      # refused before anything is allocated
+        self._init_jitter(sample_jitter, jitter_seed)
         d = self.dev
         # ---- model -------------------------------------------------------------------------------
         self.encoding = encoding
@@ -229,6 +233,25 @@ class Trainer:
         self._bg_step = torch.zeros(1, dtype=torch.int32, device=self.dev) if random else None
         self._bg_step_host = 0
 
+    def _init_jitter(self, sample_jitter, seed):
+        if sample_jitter and self.mode != "nerf":
+            raise ValueError("Trainer: sample_jitter needs mode='nerf': the jittered sampler writes step lengths (MIDPOINT_WORLD's "
+                             "t_vals), which the compat compositor does not take")
+        self.sample_jitter, self.jitter_seed = bool(sample_jitter), int(seed)
+        # the step number is hashed from a DEVICE int, kept as the background's is: this one for step(), the captured counter for
+        # step_captured(), the optimizer's own for step_entry() -- the same step number draws the same offsets on all three paths
+        self._jit_step = torch.zeros(1, dtype=torch.int32, device=self.dev) if self.sample_jitter else None
+        self._jit_step_host = 0
+
+    def _jitter(self, step):
+        """api.sample_jitter for this trainer, `step` the device int32 counter (None: 0 / opt.step); None when jitter is off."""
+        if not self.sample_jitter:
+            return None
+        seed = self.jitter_seed
+        if _world() > 1:                        # every rank draws its own offsets
+            seed = (seed + 0x632BE5AB * dist.get_rank()) & 0xFFFFFFFF
+        return api.sample_jitter(seed=seed, step=step)
+
     def _bg(self, step, n_channels):
         """api.train_background for this trainer's background, `step` the device int32 counter (None: 0 / opt.step)."""
         if self.background is None:
@@ -274,42 +297,49 @@ class Trainer:
             P = self.max_segments
         return P
 
-    def _stype(self):
+    def _stype(self, jitter=None):
+        """The sampling type of a launch: with a jitter struct (training launches of a sample_jitter trainer) JITTER_WORLD."""
+        if jitter is not None:
+            return api.SAMPLING_JITTER_WORLD
         return api.SAMPLING_MIDPOINT_WORLD if self.mode == "nerf" else api.SAMPLING_REGULAR
 
-    def _sample(self, n, P):
+    def _sample(self, n, P, jitter=None):
         """The standalone sampler (sampler/sampler.h:19-30): float[S][5] samples + t_vals."""
         with _Stage(self, "sampler"):
             api.launchSampler(self.start, self.end, self.view_dirs, self.t_vals, self.samples, n, self.R, self.num_stored,
-                              self.indices, self._stype())
+                              self.indices, self._stype(jitter), jitter=jitter)
             if self.mode == "nerf" and self.density_scale != 1.0:
                 self.t_vals[:P * api.NUM_SAMPLES_PER_SEGMENT].mul_(self.density_scale)
 
-    def materialize_samples(self, n):
+    def materialize_samples(self, n, jitter="last"):
         """Tests / inspection: run the standalone sampler over the current batch's segments (fills self.samples; t_vals are
-        rewritten with the same values the folded path produced)."""
-        self._sample(n, min(int(self.total.item()), self.max_segments))
+        rewritten with the same values the folded path produced).  A sample_jitter trainer draws the offsets of the step its last
+        gradients() ran at ("last"); jitter: an api.sample_jitter(...) of the caller's, or None for the midpoints."""
+        if isinstance(jitter, str):
+            jitter = self._jitter(self._jit_step)
+        self._sample(n, min(int(self.total.item()), self.max_segments), jitter)
 
-    def _forward(self, S, from_samples=False, save=True):
+    def _forward(self, S, from_samples=False, save=True, jitter=None):
         """encoding + network->forward over the batch's S samples; save=False: outputs only (rendering; the first pass of the
-        two-pass step)."""
+        two-pass step).  jitter: the step's sample jitter -- a TRAINING forward, whatever `save` says; None: the midpoints."""
         P = S // api.NUM_SAMPLES_PER_SEGMENT
         t_scale = self.density_scale if self.mode == "nerf" else 1.0
+        stype = self._stype(jitter)
         if self.lean_fused and not from_samples and save:
             with _Stage(self, "mlp_fwd"):       # sampler + encoder + forward: one kernel, t_vals beside the outputs
-                self.net.train_forward_lean_segments(self.start, self.end, self.seg_view, P, self._stype(), self.ws, self.out, self.radiance,
-                                                     t_vals=self.t_vals, t_scale=t_scale)
+                self.net.train_forward_lean_segments(self.start, self.end, self.seg_view, P, stype, self.ws, self.out, self.radiance,
+                                                     t_vals=self.t_vals, t_scale=t_scale, jitter=jitter)
             self._fused_batch = True
             return
         self._fused_batch = False
         with _Stage(self, "encode"):
             if self.fold_sampler and not from_samples:      # sampler + encoder in one pass over the segments; writes t_vals too
                 if self.encoding == "hash":
-                    self.hg.encode_segments(self.table, self.start, self.end, self.seg_view, P, self._stype(), self.encT,
-                                            self.t_vals, t_scale)
+                    self.hg.encode_segments(self.table, self.start, self.end, self.seg_view, P, stype, self.encT,
+                                            self.t_vals, t_scale, jitter=jitter)
                 else:
-                    self.net.encode_frequency_segments(self.start, self.end, self.seg_view, P, self._stype(), self.encT,
-                                                       self.t_vals, t_scale)
+                    self.net.encode_frequency_segments(self.start, self.end, self.seg_view, P, stype, self.encT,
+                                                       self.t_vals, t_scale, jitter=jitter)
             elif self.encoding == "hash":
                 self.hg.encode(self.table, self.samples[:S], self.encT)
             else:
@@ -382,6 +412,10 @@ class Trainer:
         if self._bg_step is not None and self._bg_step_host != self.step_count:
             self._bg_step.fill_(self.step_count)
             self._bg_step_host = self.step_count
+        jit = self._jitter(self._jit_step)
+        if self._jit_step is not None and self._jit_step_host != self.step_count:
+            self._jit_step.fill_(self.step_count)
+            self._jit_step_host = self.step_count
         self._det_select()
         P = self._segments(rays_o, rays_d, n)
         S = P * K
@@ -403,8 +437,8 @@ class Trainer:
                 self.loss.zero_()
             return 0
         if not self.fold_sampler:
-            self._sample(n, P)
-        self._forward(S, save=not self.two_pass)
+            self._sample(n, P, jit)
+        self._forward(S, save=not self.two_pass, jitter=jit)
         if self.mode == "nerf" and self.fuse_compositor:
             with _Stage(self, "composite_fwd+l2+bwd"):   # one launch: the backward's first sweep IS the forward
                 if bg is not None:
@@ -430,8 +464,8 @@ class Trainer:
                 self.net.train_forward_live(self.encT, S, self.ws, self.live_ws)
         with _Stage(self, "mlp_bwd+wgrad"):
             if self.lean and getattr(self, "_fused_batch", False):
-                self.net.train_backward_lean_segments(self.start, self.end, self.seg_view, P, self._stype(), self.out, self.dout, self.ws,
-                                                      self.dparams, live_ws=self.live_ws if self.live_segments else None)
+                self.net.train_backward_lean_segments(self.start, self.end, self.seg_view, P, self._stype(jit), self.out, self.dout, self.ws,
+                                                      self.dparams, live_ws=self.live_ws if self.live_segments else None, jitter=jit)
             elif self.lean:
                 self.net.train_backward_lean(self.encT, self.out, self.dout, S, self.ws, self.dparams,
                                              live_ws=self.live_ws if self.live_segments else None)
@@ -448,8 +482,9 @@ class Trainer:
         if self.encoding == "hash":
             with _Stage(self, "hash_bwd"):
                 if self.fold_sampler:
-                    self.hg.backward_segments(self.start, self.end, P, self._stype(), self.dencT, self.dtable,
-                                              self.dtable_h if self.hash_fp16 else None, live_ws=self.live_ws if self.live_segments else None)
+                    self.hg.backward_segments(self.start, self.end, P, self._stype(jit), self.dencT, self.dtable,
+                                              self.dtable_h if self.hash_fp16 else None, live_ws=self.live_ws if self.live_segments else None,
+                                              jitter=jit)
                 elif self.hash_fp16:
                     self.hg.backward_mixed(self.samples[:S], self.dencT, self.dtable, self.dtable_h)
                 else:
@@ -707,6 +742,7 @@ class Trainer:
         self._g_step = torch.full((1,), self.step_count, dtype=torch.int64, device=d)
         # RANDOM hashes the low 32-bit word of that counter (little endian), which _captured_apply advances after the gradients
         self._g_bg = self._bg(self._g_step.view(torch.int32)[:1], self.target_channels)
+        self._g_jit = self._jitter(self._g_step.view(torch.int32)[:1])       # applied by the gradient kernels, not by the traversal
         self._g_idx = torch.zeros(1, dtype=torch.int64, device=d)
         self._g_lr = torch.zeros((1, 2), device=d)
         world = _world()
@@ -821,7 +857,8 @@ class Trainer:
         a.batch = api.train_batch(self.net, grid=self.hg if hash_ else None, n_dir_freqs=self.hg.n_dir_freqs if hash_ else 0,
                                   table=self.table if hash_ else None, start_points=self.start, end_points=self.end, seg_view=self.seg_view,
                                   num_stored=self.num_stored, indices=self.indices, total_segments=self.total, segment_capacity=cap,
-                                  n_rays=n, sample_type=self._stype(), t_scale=self.density_scale if self.mode == "nerf" else 1.0,
+                                  n_rays=n, sample_type=self._stype(self._jitter(None)),
+                                  t_scale=self.density_scale if self.mode == "nerf" else 1.0,
                                   vr_mode=api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT, targets=self.graph_targets,
                                   loss_scale=self.loss_scale, encT=self.encT, dencT=self.dencT, workspace=self.ws,
                                   output_half=self.out, radiance=self.radiance, t_vals=self.t_vals, radiance_gradients=self.dout,
@@ -832,6 +869,7 @@ class Trainer:
                                   target_channels=self.graph_targets.shape[1])
         # RANDOM: step NULL = the call's own counter (entry_step) before its increment
         self._entry_bg = self._bg(None, self.graph_targets.shape[1])
+        self._entry_jit = self._jitter(None)        # step NULL: likewise
         o = a.opt
         o.mlp_master, o.mlp_params_fp16 = self.master.data_ptr(), self.params.data_ptr()
         o.mlp_m, o.mlp_v = self.adam_m.data_ptr(), self.adam_v.data_ptr()
@@ -860,7 +898,7 @@ class Trainer:
             self._clear_grads()
         if int(self.step_count) != getattr(self, "_entry_step_host", self.step_count):
             self.entry_step.fill_(self.step_count)
-        api.train_step(self._entry_args, self._entry_bg)
+        api.train_step(self._entry_args, self._entry_bg, self._entry_jit)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -894,20 +932,20 @@ class Trainer:
         api.train_gradients(self.net, grid=self.hg if hash_ else None, n_dir_freqs=self.hg.n_dir_freqs if hash_ else 0,
                             table=self.table if hash_ else None, start_points=st["start"], end_points=st["end"], seg_view=st["seg_view"],
                             num_stored=st["num_stored"], indices=st["indices"], total_segments=st["total"], segment_capacity=cap,
-                            n_rays=n, sample_type=self._stype(), t_scale=self.density_scale if self.mode == "nerf" else 1.0,
+                            n_rays=n, sample_type=self._stype(self._g_jit), t_scale=self.density_scale if self.mode == "nerf" else 1.0,
                             vr_mode=api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT, targets=st["targets"],
                             loss_scale=self.loss_scale, encT=self.encT, dencT=self.dencT, workspace=self.ws,
                             output_half=self.out, radiance=self.radiance, t_vals=self.t_vals, radiance_gradients=self.dout,
                             pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss, dparams=self.dparams,
                             dtable=self.dtable if hash_ else None, dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
                             live_ws=self.live_ws if self.live_segments else None, skip_table_backward=self._g_split,
-                            workspace_lean=self.lean, background=self._g_bg)
+                            workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit)
 
     def _captured_table_bwd(self, k):
         """the hash scatter of set k's batch over the live list the gradient graph left (its count is on the device)"""
         st = self._g_sets[k]
-        self.hg.backward_segments(st["start"], st["end"], self._g_cap, self._stype(), self.dencT, self.dtable,
-                                  self.dtable_h if self.hash_fp16 else None, live_ws=self.live_ws)
+        self.hg.backward_segments(st["start"], st["end"], self._g_cap, self._stype(self._g_jit), self.dencT, self.dtable,
+                                  self.dtable_h if self.hash_fp16 else None, live_ws=self.live_ws, jitter=self._g_jit)
 
     def _captured_apply(self, grad_divisor):
         self._g_step.add_(1)
