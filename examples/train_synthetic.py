@@ -6,6 +6,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
 
   python examples/train_synthetic.py --data /path/to/lego [--steps 2000] [--encoding hash]
   python examples/train_synthetic.py --make-demo /tmp/demo_scene --data /tmp/demo_scene --steps 400
+  python examples/train_synthetic.py --data /path/to/lego --device-batches     (frames resident as RGBA8/RGB8, batches drawn on the device)
 """
 import argparse
 import json
@@ -18,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 
-from rtx_nerf_amd import loader, scenes
+from rtx_nerf_amd import api, loader, scenes
 from rtx_nerf_amd.train import RayDataset, Trainer, camera_rays, psnr
 
 
@@ -51,6 +52,9 @@ def main():
     ap.add_argument("--grid", type=int, default=32)
     ap.add_argument("--encoding", default="hash")
     ap.add_argument("--out", default="train_synthetic_view.png")
+    ap.add_argument("--device-batches", action="store_true",
+                    help="keep the frames on the device as uint8 (api.ImageSet) and draw every batch there (Trainer.step_images) "
+                         "instead of gathering it from a per-ray dataset")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.make_demo:
@@ -62,22 +66,33 @@ def main():
         sys.exit("no frames loaded")
     n_hold = max(1, ds.images.shape[0] // 8)
     train_ds = loader.ImageDataset(ds.images[:-n_hold], ds.poses[:-n_hold], ds.focal, ds.image_width, ds.image_height, 3, ds.camera_angle_x)
-    rays, focal = RayDataset.from_images(train_ds, origin_scale=0.1)
+    if a.device_batches:
+        # flags=2 frames are k/255: one byte per channel holds them exactly
+        images, focal = api.ImageSet.from_dataset(train_ds, storage="u8")
+        n_rays, held = images.n_images * images.width * images.height, images.nbytes()
+    else:
+        rays, focal = RayDataset.from_images(train_ds, origin_scale=0.1)
+        n_rays, held = rays.n, sum(t.numel() * t.element_size() for t in (rays.rays_o, rays.rays_d, rays.pixels))
     R = a.grid
     tr = Trainer(R, None, encoding=a.encoding, n_neurons=64, n_hidden_layers=2 if a.encoding == "hash" else 4,
                  hashgrid=dict(n_levels=8, n_features=2, log2_hashmap_size=15, base_resolution=8, per_level_scale=1.5),
                  batch_rays=max(a.batch, ds.image_width * ds.image_height), max_segments=max(a.batch, ds.image_width * ds.image_height) * (3 * R),
                  lr=1e-2 if a.encoding == "hash" else 2e-3, density_scale=150.0)
+    if a.device_batches:
+        tr.attach_images(images)
     g = torch.Generator(device="cuda").manual_seed(0)
     W, H = ds.image_width, ds.image_height
     o_t, d_t = camera_rays(ds.poses[-1], focal, W, H, origin_scale=0.1)
     gt = torch.from_numpy(ds.images[-1].reshape(-1, 3)).cuda()
-    print(f"{rays.n} training rays from {train_ds.images.shape[0]} frames ({W}x{H}); held-out PSNR before: {psnr(tr.render_rays(o_t, d_t), gt):.2f} dB")
+    print(f"{n_rays} training rays from {train_ds.images.shape[0]} frames ({W}x{H}), {held / 1e6:.2f} MB on the device "
+          f"({'image set, batches drawn on the device' if a.device_batches else 'ray dataset'}); held-out PSNR before: {psnr(tr.render_rays(o_t, d_t), gt):.2f} dB")
     for it in range(a.steps):
-        loss = tr.step(*rays.sample_batch(a.batch, g))
+        loss = tr.step_images(a.batch) if a.device_batches else tr.step(*rays.sample_batch(a.batch, g))
         if (it + 1) % 100 == 0:
             frac = tr.update_occupancy(threshold=0.01) if it + 1 >= 200 else 1.0
             print(f"step {it + 1:5d} loss {float(loss.item()):.6f} occupied {100 * frac:.1f}% held-out PSNR {psnr(tr.render_rays(o_t, d_t), gt):.2f} dB", flush=True)
+    print(f"final held-out PSNR after {a.steps} steps ({'device batches' if a.device_batches else 'ray dataset'}): "
+          f"{psnr(tr.render_rays(o_t, d_t), gt):.2f} dB")
     img = tr.render_rays(o_t, d_t).reshape(H, W, 3).cpu().numpy()
     loader.write_png(a.out, img)
     print("wrote", a.out)

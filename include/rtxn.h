@@ -760,7 +760,10 @@ int rtxn_adam_step_sparse(long n, float* master, void* params_fp16, void* grads,
  *   table_shadow: rtxn_deterministic_workspace_bytes(rtxn_hashgrid_n_params) bytes, zeroed once, or NULL (no hash grid).
  * Process-wide and read when a backward / scatter entry point is CALLED (so: baked into a captured graph); (NULL, NULL)
  * restores the default.  The folds leave the shadows zero.  Costs: 8-byte atomics in the scatter (about 2x its time) and one
- * sweep over each shadow per call.  Not covered: the reported loss sum (a float atomic; it feeds nothing back).
+ * sweep over each shadow per call.  The loss scalar of rtxn_volrender_l2_train[_ex] (and of rtxn_train_gradients* /
+ * rtxn_train_step*, which call them) is covered too: with a shadow registered it is summed behind the compositor in a fixed
+ * order (groups of four rays, ascending) from the pixels and targets, one small launch more, instead of by the compositor's
+ * float atomics (one per block of four rays, or one per ray for odd K or misaligned buffers).  Not covered: rtxn_l2_loss's sum (the three-launch compositor path; a float atomic, it feeds nothing back).
  * Range: a single contribution that is NaN, +-Inf or of magnitude >= 2^22 marks its element (a bitmap behind the sums, part of
  * the workspace size) and the fold writes a quiet NaN there -- as the float atomics would propagate NaN / Inf.  What is NOT
  * caught: in-range contributions whose running sum passes +-2^23 wrap around in the 64-bit integer and fold to a finite, wrong
@@ -1010,6 +1013,47 @@ int rtxn_load_llff(const char* basedir, int factor, int flags, rtxn_image_datase
 void rtxn_free_llff_bounds(float* bounds);
 /* stb_image_write's role (included, never called, main.cu:19-21): 8-bit RGB PNG of a rendered frame. */
 int rtxn_write_png_rgb8(const char* path, const unsigned char* rgb, int width, int height);
+
+/* ---- training batches drawn on the device --------------------------------------------------------------------------
+ * Replaces the reference's host batch build (a random shuffle + gather, main.cu:612-629) and the per-ray dataset it
+ * gathers from: the training frames stay resident as they were loaded (float, or one byte per channel) beside their poses,
+ * and ONE kernel draws a batch -- picks (image, pixel) per ray, generates the pixel's pinhole ray and copies its colour --
+ * on `stream`, without an allocation or a synchronisation, so the call is hipGraph-capturable in front of a traversal.
+ * Batch number `step` (uint32 wrap-around throughout; fmix32: see RTXN_BG_RANDOM) draws, for ray r of n_rays:
+ *   h0    = fmix32((seed ^ 0x2C1B3C6Du) + 0x9E3779B9u * (uint32)step)                 step = *step, NULL: 0
+ *   image = (uint64(fmix32(h0 ^ (2r)))     * n_images)       >> 32
+ *   pixel = (uint64(fmix32(h0 ^ (2r + 1))) * (width*height)) >> 32                    px = pixel % width, py = pixel / width
+ * (with replacement; width*height <= 2^24 keeps the multiply-shift's bias at or below 2^-8 relative).
+ * Ray: the pinhole ray rtxn_trace_grid generates for launch pixel (px, py) of a width x height launch with
+ * look_at = poses[image] and the set's focal_length / aspect_ratio -- the same function, operation for operation:
+ *   u = (float)((2 (px + 0.5) / width - 1) * aspect_ratio), v = (float)(2 (py + 0.5) / height - 1)   (formed in double),
+ *   d = normalise(fmaf(-la[2+4k], focal, fmaf(la[4k], u, la[4k+1] v)))_k=0..2,   o_k = la[4k+3] / 10;
+ * rays_o gets o, rays_d the normalised d: explicit rays that walk the grid exactly as the pinhole launch's ray does.
+ * Target: the `channels` stored values of images[image][py][px]; RTXN_IMAGE_F32 copied, RTXN_IMAGE_U8 (float)v / 255.0f
+ * (IEEE division), alpha included.  drawn (optional) records (image, pixel) per ray.
+ * Rules (RTXN_ERR_INVALID with a message, before any device is touched): no NULL among images, poses, rays_o, rays_d,
+ * targets; n_images >= 1; n_rays >= 1; width, height >= 1 and width*height <= 1 << 24; channels 3 | 4; format F32 | U8. */
+enum rtxn_image_format { RTXN_IMAGE_F32 = 0, RTXN_IMAGE_U8 = 1 };
+typedef struct rtxn_image_set {
+  const void* images;    /* DEVICE: [n_images][height][width][channels], float or uint8_t */
+  const float* poses;    /* DEVICE: float[n_images][16], row-major look_at as rtxn_trace_params.look_at */
+  int n_images;
+  uint32_t width, height;
+  int channels;          /* 3 | 4 */
+  int format;            /* enum rtxn_image_format */
+  float focal_length, aspect_ratio;      /* as rtxn_trace_params */
+} rtxn_image_set;
+typedef struct rtxn_draw_batch_args {
+  rtxn_image_set set;
+  int n_rays;
+  unsigned seed;
+  const int* step;       /* DEVICE int: index of this batch in the sequence; NULL = 0 */
+  float* rays_o;         /* float[n_rays][3] */
+  float* rays_d;         /* float[n_rays][3] */
+  float* targets;        /* float[n_rays][channels] */
+  uint32_t* drawn;       /* optional uint32[n_rays][2]: (image, y*width + x) */
+} rtxn_draw_batch_args;
+int rtxn_draw_batch(const rtxn_draw_batch_args* a, rtxn_stream_t stream);
 
 #ifdef __cplusplus
 }

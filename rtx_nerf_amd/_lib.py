@@ -120,6 +120,18 @@ class SampleJitter(C.Structure):
     _fields_ = [("seed", C.c_uint), ("step", C.c_void_p)]
 
 
+class ImageSet(C.Structure):
+    """struct rtxn_image_set (include/rtxn.h)."""
+    _fields_ = [("images", C.c_void_p), ("poses", C.c_void_p), ("n_images", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("channels", C.c_int), ("format", C.c_int), ("focal_length", C.c_float), ("aspect_ratio", C.c_float)]
+
+
+class DrawBatchArgs(C.Structure):
+    """struct rtxn_draw_batch_args (include/rtxn.h)."""
+    _fields_ = [("set", ImageSet), ("n_rays", C.c_int), ("seed", C.c_uint), ("step", C.c_void_p), ("rays_o", C.c_void_p),
+                ("rays_d", C.c_void_p), ("targets", C.c_void_p), ("drawn", C.c_void_p)]
+
+
 class RenderConfig(C.Structure):
     """struct rtxn_render_config (include/rtxn.h)."""
     _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("table_fp16", C.c_void_p), ("n_dir_freqs", C.c_int),
@@ -277,6 +289,7 @@ SYMBOLS = {
     "rtxn_hashgrid_backward_segments_live_jitter": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, _P, C.POINTER(SampleJitter), _P]),
     "rtxn_train_gradients_jitter": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), _P]),
     "rtxn_train_step_jitter": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), _P]),
+    "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),
     "rtxn_load_llff": (_I, [C.c_char_p, _I, _I, C.POINTER(ImageDataset), C.POINTER(C.POINTER(C.c_float))]),

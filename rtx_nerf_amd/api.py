@@ -976,3 +976,93 @@ def convert_f32_to_f16(src, dst):
 def convert_f16_to_f32(src, dst):
     check(_lib.lib().rtxn_convert_f16_to_f32(_ptr(src, torch.float16, "src"), _ptr(dst, torch.float32, "dst"), src.numel(), _stream()),
           "rtxn_convert_f16_to_f32")
+
+
+# --------------------------------------------------------------------------- device batches
+IMAGE_F32, IMAGE_U8 = 0, 1                 # enum rtxn_image_format
+
+
+class ImageSet:
+    """struct rtxn_image_set (include/rtxn.h) over resident training frames: `images` a device tensor [N, H, W, C] (C = 3 or 4),
+    float32 or uint8 (v / 255 on read), `poses` [N, 16] or [N, 4, 4] float32 on the same device, one pinhole camera
+    (focal_length and aspect_ratio as rtxn_trace_params; aspect_ratio defaults to W / H) for all of them.  A thin holder: it keeps the two tensors
+    alive and hands draw_batch() their pointers."""
+
+    def __init__(self, images, poses, focal_length, aspect_ratio=None):
+        if images.dim() != 4 or images.shape[-1] not in (3, 4) or images.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"ImageSet: images of shape {tuple(images.shape)} / {images.dtype}: [N, H, W, 3 | 4], float32 or uint8")
+        n, h, w, c = (int(v) for v in images.shape)
+        if n < 1 or h < 1 or w < 1 or w * h > 1 << 24:
+            raise ValueError(f"ImageSet: {n} frames of {w} x {h}: at least one frame, width * height <= 1 << 24")
+        if poses.dtype != torch.float32 or poses.numel() != 16 * n or tuple(poses.shape[1:]) not in ((16,), (4, 4)):
+            raise ValueError(f"ImageSet: poses of shape {tuple(poses.shape)} / {poses.dtype}: float32 [{n}, 16] or [{n}, 4, 4]")
+        if poses.device != images.device:
+            raise ValueError(f"ImageSet: images on {images.device}, poses on {poses.device}")
+        self.images, self.poses = images.contiguous(), poses.reshape(n, 16).contiguous()
+        self.n_images, self.height, self.width, self.channels = n, h, w, c
+        self.format = IMAGE_U8 if images.dtype == torch.uint8 else IMAGE_F32
+        self.focal_length = float(focal_length)
+        self.aspect_ratio = float(aspect_ratio) if aspect_ratio is not None else w / h
+
+    @classmethod
+    def from_dataset(cls, dataset, corrected_focal=True, storage="u8", device="cuda"):
+        """dataset: rtx_nerf_amd.loader.ImageDataset; the focal rule is RayDataset.from_images' (corrected_focal:
+        1/tan(camera_angle_x/2) instead of the reference's 1/tan(0.5*focal_px), quirk Q1).  storage "f32" keeps the loader's
+        floats; "u8" quantises them ONCE on the host with round(v * 255) -- a quarter of the memory, and exact (the drawn
+        v / 255 is the loader's float, bit for bit) for datasets loaded with flags bit 1 (v / 255, no gamma), whose values are
+        k / 255 already; gamma-linearised frames (flags 0) are rounded to the nearest 1/255.  Returns (image_set, focal)."""
+        import math
+        import numpy as np
+        if storage not in ("u8", "f32"):
+            raise ValueError(f"ImageSet.from_dataset: storage {storage!r} (u8 | f32)")
+        if corrected_focal:
+            focal = 1.0 / math.tan(0.5 * dataset.camera_angle_x)
+        else:
+            focal = float(np.float32(1.0) / np.tan(np.float32(0.5) * np.float32(dataset.focal)))
+        W, H = int(dataset.image_width), int(dataset.image_height)
+        ch = int(dataset.image_channels) or 3
+        img = np.ascontiguousarray(dataset.images, dtype=np.float32).reshape(-1, H, W, ch)
+        if storage == "u8":
+            img = np.clip(np.rint(img * np.float32(255.0)), 0, 255).astype(np.uint8)
+        poses = np.ascontiguousarray(dataset.poses, dtype=np.float32).reshape(-1, 16)
+        return cls(torch.from_numpy(img).to(device), torch.from_numpy(poses).to(device), focal), focal
+
+    def nbytes(self):
+        """bytes held on the device"""
+        return self.images.numel() * self.images.element_size() + self.poses.numel() * 4
+
+    def c_struct(self):
+        s = _lib.ImageSet()
+        s.images, s.poses = _ptr(self.images, name="images"), _ptr(self.poses, torch.float32, "poses")
+        s.n_images, s.width, s.height, s.channels, s.format = self.n_images, self.width, self.height, self.channels, self.format
+        s.focal_length, s.aspect_ratio = self.focal_length, self.aspect_ratio
+        return s
+
+
+def draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None):
+    """struct rtxn_draw_batch_args over the given tensors (which the caller keeps alive): rays_o, rays_d float32 [>= n, 3],
+    targets float32 [>= n, channels], drawn int32 [>= n, 2] or None, step a device int32 tensor or None (0)."""
+    n, C_ = int(n), image_set.channels
+    for t, w, nm in ((rays_o, 3, "rays_o"), (rays_d, 3, "rays_d"), (targets, C_, "targets"), (drawn, 2, "drawn")):
+        if t is not None and (t.dim() != 2 or t.shape[1] != w or t.shape[0] < n):
+            raise _lib.RtxnError(f"draw_batch: {nm} of shape {tuple(t.shape)}: [>= {n}, {w}]")
+    a = _lib.DrawBatchArgs()
+    a.set = image_set.c_struct()
+    a.n_rays, a.seed = n, int(seed) & 0xFFFFFFFF
+    a.step = _ptr(step, torch.int32, "step")
+    a.rays_o, a.rays_d = _ptr(rays_o, torch.float32, "rays_o"), _ptr(rays_d, torch.float32, "rays_d")
+    a.targets = _ptr(targets, torch.float32, "targets")
+    a.drawn = _ptr(drawn, torch.int32, "drawn")
+    return a
+
+
+def draw_batch(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None):
+    """rtxn_draw_batch: batch number `step` (device int32 tensor, None: 0) of the sequence `seed` keys, n rays drawn from
+    image_set into rays_o / rays_d / targets on the current stream; drawn (int32 [n, 2], optional) receives (image, y*W + x)."""
+    a = draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn)
+    check(_lib.lib().rtxn_draw_batch(C.byref(a), _stream()), "rtxn_draw_batch")
+
+
+def draw_batch_launch(args):
+    """rtxn_draw_batch over a struct draw_batch_args() built earlier (its tensors still alive), on the current stream."""
+    check(_lib.lib().rtxn_draw_batch(C.byref(args), _stream()), "rtxn_draw_batch")

@@ -29,6 +29,15 @@ __attribute__((visibility("hidden"))) hipError_t cu_count(int* n_cu);
 // of every launch, and never inside a stream capture after the first, un-captured, call.
 __attribute__((visibility("hidden"))) hipError_t set_lds_once(const void* fn, size_t bytes);
 
+// Deterministic mode (rtxn_set_deterministic_workspace, train.hip): whether a fixed-point shadow is registered right now.
+__attribute__((visibility("hidden"))) bool deterministic_mode();
+// ... in which the training compositor's loss scalar is summed in a fixed order behind the compositor instead of by its float
+// atomics (loss.hip): *loss_sum = the L2 loss of pixels float[n_rays][3] against target float[n_rays][target_channels], a
+// 4-channel target composited over the ray's background (bg_mode rtxn_train_background_mode, bg_color host float[3] or NULL).
+__attribute__((visibility("hidden"))) int l2_loss_fixed_order(const float* pixels, const float* target, int n_rays, int bg_mode,
+                                                              const float* bg_color, unsigned bg_seed, const int* bg_step,
+                                                              int target_channels, float* loss_sum, hipStream_t stream);
+
 // The rules of a training background (rtxn_train_background, include/rtxn.h), host only: RTXN_ERR_INVALID with a message, or
 // RTXN_OK with *active = whether a background is composited at all.
 int check_train_background(const rtxn_train_background* bg, int vr_mode, const char* who, bool* active);

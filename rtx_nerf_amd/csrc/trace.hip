@@ -23,6 +23,7 @@
 // read only by the depth output of the compositor (RTXN_RENDER_AUX), optional +8).  The occupancy bitfield
 // (R^3/8 bytes: 256 KiB at 128^3, 2 MiB at 256^3) is L2-resident.
 #include "common.h"
+#include "ray_internal.h"
 
 namespace {
 
@@ -64,27 +65,7 @@ __device__ __forceinline__ bool occ_test(const uint32_t* __restrict__ occ, int R
   return (occ[idx >> 5] >> (idx & 31)) & 1u;
 }
 
-// a2: optixPrograms.cu:43-82
-__device__ __forceinline__ void make_ray(const float* __restrict__ la, float focal_length, float aspect_ratio,
-                                         unsigned width, unsigned height, unsigned px, unsigned py, float (&o)[3],
-                                         float (&d)[3], float (&v)[2]) {
-  const float u = (float)((2 * (px + 0.5) / width - 1) * aspect_ratio);
-  const float vv = (float)(2 * (py + 0.5) / height - 1);
-  const float nf0 = la[2] * -1.0f, nf1 = la[6] * -1.0f, nf2 = la[10] * -1.0f;
-  float xd = fmaf(nf0, focal_length, fmaf(la[0], u, la[1] * vv));
-  float yd = fmaf(nf1, focal_length, fmaf(la[4], u, la[5] * vv));
-  float zd = fmaf(nf2, focal_length, fmaf(la[8], u, la[9] * vv));
-  const float norm = sqrtf(fmaf(zd, zd, fmaf(xd, xd, yd * yd)));
-  xd /= norm;
-  yd /= norm;
-  zd /= norm;
-  v[0] = atan2f(sqrtf(fmaf(xd, xd, yd * yd)), zd);
-  v[1] = atan2f(yd, xd);
-  d[0] = xd; d[1] = yd; d[2] = zd;
-  o[0] = la[3] / 10;
-  o[1] = la[7] / 10;
-  o[2] = la[11] / 10;
-}
+using rtxn::make_ray;   // a2: optixPrograms.cu:43-82, shared with the batch draw (ray_internal.h)
 
 __device__ __forceinline__ bool grid_entry(const float (&o)[3], const float (&d)[3], int R, float L, int (&cell)[3],
                                            float& t_enter) {

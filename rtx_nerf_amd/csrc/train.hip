@@ -2807,6 +2807,10 @@ int det_fold(long long* q, long n, float* dst, void* dst_half, long hashed_lo, h
 
 }  // namespace
 
+bool rtxn::deterministic_mode() {
+  return g_det_mlp.load(std::memory_order_relaxed) != nullptr || g_det_table.load(std::memory_order_relaxed) != nullptr;
+}
+
 // ============================================================================ C ABI
 // n_params fixed-point sums, then one bit per element: the out-of-range / non-finite marks (DetCtx)
 extern "C" size_t rtxn_deterministic_workspace_bytes(long n_params) {

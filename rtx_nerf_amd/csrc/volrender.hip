@@ -21,6 +21,7 @@
 // holds each sample's world-space step length) with its exact gradient.
 #include <type_traits>
 
+#include "background_internal.h"
 #include "common.h"
 
 namespace {
@@ -810,39 +811,7 @@ __global__ __launch_bounds__(256) void volrender_aux_pair_kernel(const float4* _
 // A = sum w.  Written as bg + sum w_k (c_k - bg) it is the plain compositor with colours c_k - bg: dL/dc_i is unchanged, the
 // optical-depth gradient dots g with c_k - bg, and the second sweep's total is S' = g . (sum w c) - (g . bg) A.  Separate
 // kernels beside the plain ones (copies with the additions written in: a shared inlined body changes the plain kernels' bytes).
-struct BgArgs {
-  int mode;              // RTXN_BG_CONSTANT | RTXN_BG_RANDOM
-  float color[3];        // CONSTANT
-  unsigned seed;         // RANDOM
-  const int* step;       // RANDOM: device int hashed with the seed, or NULL (0)
-  int target_channels;   // 3 | 4 (straight RGBA, composited over the ray's background)
-};
-
-using rtxn::fmix32;
-
-// the ray's background and its (composited) target: wave-uniform values
-__device__ __forceinline__ void ray_background(const BgArgs& bg, const float* __restrict__ target, int ray, float (&b)[3],
-                                               float (&t)[3]) {
-  if (bg.mode == RTXN_BG_RANDOM) {
-    const unsigned step = bg.step ? (unsigned)*bg.step : 0u;
-    const unsigned h0 = fmix32(bg.seed + 0x9E3779B9u * step);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) b[c] = (float)(fmix32(h0 ^ (3u * (unsigned)ray + (unsigned)c)) >> 8) * 0x1p-24f;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) b[c] = bg.color[c];
-  }
-  if (bg.target_channels == 4) {
-    const float* p = target + 4 * (long)ray;
-    const float a = p[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) t[c] = a * p[c] + (1.0f - a) * b[c];
-  } else {
-    const float* p = target + 3 * (long)ray;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) t[c] = p[c];
-  }
-}
+// BgArgs and ray_background (the ray's background and composited target): background_internal.h, shared with loss.hip.
 
 // one ray per wave, 64 samples per step: the form for odd K or misaligned buffers (volrender_l2_fused_kernel's arithmetic)
 __global__ __launch_bounds__(256) void volrender_l2_bg_kernel(const float4* __restrict__ radiance, const float* __restrict__ step_len,
@@ -1230,9 +1199,13 @@ int l2_train(const char* who, const float* network_outputs, const float* ray_hit
   RTXN_REQUIRE(num_samples_per_hit > 0, "%s: num_samples_per_hit = %d", who, num_samples_per_hit);
   RTXN_DEVICE_OR_FAIL();
   hipStream_t s = rtxn::as_stream(stream);
-  if (loss_sum) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
+  // deterministic mode: the kernels get no loss pointer (their sum is float atomics, per block or per ray); loss.hip sums behind them
+  const bool det_loss = loss_sum && batch_size > 0 && rtxn::deterministic_mode();
+  if (loss_sum && !det_loss) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
   if (batch_size == 0) return RTXN_OK;
   RTXN_REQUIRE(network_outputs && ray_hit && num_hits && indices && target && pixels && radiance_gradients, "%s: NULL buffer", who);
+  float* const loss_out = loss_sum;
+  if (det_loss) loss_sum = nullptr;
   RTXN_REQUIRE(((uintptr_t)network_outputs & 15) == 0 && ((uintptr_t)radiance_gradients & 7) == 0,
                "%s: radiance must be 16-byte and gradients 8-byte aligned", who);
   // 512 samples per step, two per lane: an even K, 8-byte-aligned step lengths and 16-byte-aligned gradients
@@ -1251,6 +1224,9 @@ int l2_train(const char* who, const float* network_outputs, const float* ray_hit
     else volrender_l2_fused_kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out);
     RTXN_LAUNCH_CHECK("volrender_l2_fused_kernel");
   }
+  if (det_loss)
+    return rtxn::l2_loss_fixed_order(pixels, target, batch_size, bg ? bg->mode : RTXN_BG_NONE, bg ? bg->color : nullptr, bg ? bg->seed : 0u,
+                                     bg ? bg->step : nullptr, bg ? bg->target_channels : 3, loss_out, s);
   return RTXN_OK;
 }
 

@@ -83,6 +83,9 @@ class Trainer:
         self._stage_ev = None     # list of (stage, start event, end event) while time_stages() is collecting
         self._init_background(background, background_seed, target_channels)      # refused before anything is allocated
         self._init_jitter(sample_jitter, jitter_seed)
+        self.image_set = None      # attach_images(): batches drawn on the device
+        self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
+        self._draw_step = None
         d = self.dev
         # ---- model -------------------------------------------------------------------------------
         self.encoding = encoding
@@ -260,6 +263,58 @@ class Trainer:
         if _world() > 1:                        # every rank draws its own backgrounds
             seed = (seed + 0x632BE5AB * dist.get_rank()) & 0xFFFFFFFF
         return api.train_background(self.background, seed=seed, step=step, target_channels=n_channels)
+
+    # ------------------------------------------------------------------------------------------ device batches
+    def attach_images(self, image_set, draw_seed=0):
+        """Draw this trainer's batches on the device from the resident frames of an api.ImageSet (librtxn: rtxn_draw_batch,
+        DESIGN 5.10): step_images(), capture_step(draw=True) and entry_args(draw=True) then need no rays or targets from the
+        caller.  The set's channel count must be the trainer's target width (3, or 4 = straight RGBA over its background).
+        Batch k of the sequence is a pure function of (draw_seed, k) -- the rank is mixed into the seed when data parallel --
+        and k is a DEVICE int32 counter of the batches drawn so far, advanced stream-ordered by one behind every draw: it is
+        not the optimizer's step, so batch k is the same batch on all three stepping paths, with or without prefetch.
+        self.draw_count mirrors it on the host (checkpoints keep it); self.drawn holds (image, y*W + x) of the last draw.
+        A graph captured with draw=True and the struct of entry_args(draw=True) hold the counter's, the frames' and the
+        poses' addresses, so once either exists another set cannot be attached: build a new Trainer for it."""
+        if getattr(self, "_g_draw", False) or getattr(self, "_entry_draw", None) is not None:
+            raise RuntimeError("Trainer.attach_images: a captured graph or an entry struct of this trainer already draws from the attached "
+                               "set (capture_step(draw=True) / entry_args(draw=True) keep its addresses); build a new Trainer")
+        c = int(image_set.channels)
+        if c != self.target_channels:           # refused before anything is allocated
+            raise ValueError(f"Trainer.attach_images: a {c}-channel image set for a trainer that takes {self.target_channels}-channel targets" +
+                             (" (RGBA frames need a background and target_channels=4)" if c == 4 else
+                              " (this trainer composites straight RGBA targets over its background: load the frames with their alpha)"))
+        if not image_set.images.is_cuda:
+            raise api._lib.RtxnError("Trainer.attach_images: the image set must live on the device (librtxn has no CPU path)")
+        d = self.dev
+        self.image_set, self.draw_seed = image_set, int(draw_seed)
+        self._draw_step = torch.full((1,), self.draw_count, dtype=torch.int32, device=d)
+        self.draw_rays_o = torch.empty((self.B, 3), device=d)
+        self.draw_rays_d = torch.empty((self.B, 3), device=d)
+        self.draw_targets = torch.empty((self.B, c), device=d)
+        self.drawn = torch.zeros((self.B, 2), dtype=torch.int32, device=d)
+        return self
+
+    def _draw_seed(self):
+        seed = self.draw_seed
+        if _world() > 1:                        # every rank draws its own rays
+            seed = (seed + 0x632BE5AB * dist.get_rank()) & 0xFFFFFFFF
+        return seed
+
+    def _draw(self, n, rays_o, rays_d, targets):
+        """enqueue: the next batch of the sequence into the given buffers, then the device counter + 1 (the host's is the caller's)"""
+        api.draw_batch(self.image_set, n, self._draw_seed(), self._draw_step, rays_o, rays_d, targets, self.drawn)
+        self._draw_step.add_(1)
+
+    def step_images(self, n=None):
+        """step() on the next batch of n rays (default batch_rays) drawn from the attached image set; returns the loss scalar."""
+        if self.image_set is None:
+            raise RuntimeError("step_images: call attach_images() first")
+        n = self.B if n is None else int(n)
+        if n < 1 or n > self.B:
+            raise ValueError(f"step_images: n = {n} outside [1, batch_rays = {self.B}]")
+        self._draw(n, self.draw_rays_o, self.draw_rays_d, self.draw_targets)
+        self.draw_count += 1
+        return self.step(self.draw_rays_o[:n], self.draw_rays_d[:n], self.draw_targets[:n])
 
     def _target_width(self, targets, n):
         tc = int(targets.shape[-1]) if targets.dim() == 2 and targets.shape[0] >= n else -1
@@ -627,9 +682,12 @@ class Trainer:
         return arrs
 
     def save_checkpoint(self, path):
+        """The header's "draw_count" is the number of batches DRAWN (attach_images): the loaded trainer draws batch draw_count
+        next.  With capture_step(prefetch=True, draw=True) one batch is drawn ahead of the step that trains on it, so a
+        checkpoint saved between replays resumes one batch further on: the pending batch is skipped, none is repeated."""
         arrs = {k: v.detach().cpu().numpy() for k, v in self.state_arrays().items()}
         cfg = self.net.cfg
-        header = {"step": self.step_count, "encoding": self.encoding, "grid_res": self.R, "mode": self.mode,
+        header = {"step": self.step_count, "draw_count": self.draw_count, "encoding": self.encoding, "grid_res": self.R, "mode": self.mode,
                   "mlp": {f: getattr(cfg, f) for f, _ in cfg._fields_},
                   "hashgrid": None if self.hg is None else {**{f: getattr(self.hg.cfg, f) for f, _ in self.hg.cfg._fields_},
                                                             "n_dir_freqs": self.hg.n_dir_freqs},
@@ -673,13 +731,16 @@ class Trainer:
                     raise ValueError(f"{path}: {ent['name']} has shape {ent['shape']}, model needs {list(t.shape)}")
                 t.copy_(torch.from_numpy(a.reshape(ent["shape"]).copy()))
         self.step_count = header["step"]
+        self.draw_count = int(header.get("draw_count", 0))       # files from before device batches: the sequence starts over
+        if self._draw_step is not None:
+            self._draw_step.fill_(self.draw_count)
         self.net.set_params(self.params)
         return header
 
     # ------------------------------------------------------------------------------------------ captured step (hipGraph)
     _LR_TABLE = 1 << 16     # beyond ~2^16 steps the bias correction is exactly 1.0f for beta2 <= 0.999
 
-    def capture_step(self, n_rays, launch_segments=None, prefetch=False):
+    def capture_step(self, n_rays, launch_segments=None, prefetch=False, draw=False):
         """Capture the whole optimisation step for batches of exactly `n_rays` rays as a hipGraph: traversal (count, scan,
         write) -> rtxn_train_gradients (sampler ... backward with the segment count read ON THE DEVICE) -> Adam -> weight
         re-pack, with no host round trip anywhere (the reference synchronises for the segment count, main.cu:632, and so
@@ -698,7 +759,13 @@ class Trainer:
         and flush_captured() trains on the last batch submitted.  Two segment-buffer sets alternate.  An occupancy grid
         updated between two calls takes effect one batch later.
 
+        draw=True (attach_images() first): the batch is drawn inside the graph -- rtxn_draw_batch is the first node, in front of
+        the traversal (with prefetch: in the traversal's forked branch, into that buffer set's own rays and targets) -- and
+        step_captured() needs nothing filled in.  Default False: everything as described above.
+
         Data parallel: gradients and optimizer are captured as two graphs with the all-reduces between them."""
+        if draw and self.image_set is None:
+            raise RuntimeError("capture_step(draw=True): call attach_images() first")
         if not self.fold_sampler:
             raise RuntimeError("capture_step needs the folded sampler (RTXN_TRAIN_FOLD_SAMPLER=0 is set)")
         n = int(n_rays)
@@ -712,7 +779,7 @@ class Trainer:
         self.graph_rays_d = torch.zeros((n, 3), device=d)
         self.graph_rays_d[:, 2] = 1.0
         self.graph_targets = torch.zeros((n, self.target_channels), device=d)
-        self._g_n, self._g_cap, self._g_prefetch = n, cap, bool(prefetch)
+        self._g_n, self._g_cap, self._g_prefetch, self._g_draw = n, cap, bool(prefetch), bool(draw)
         # the traversal's outputs, once per buffer set (set 0 = the trainer's own buffers)
         names = ("view_dirs", "num_hits", "indices", "num_stored", "sub_hits", "total", "start", "end", "seg_view")
         set0 = {k: getattr(self, k) for k in names}
@@ -725,6 +792,10 @@ class Trainer:
         for st in sets:
             st["targets"] = torch.zeros((n, self.target_channels), device=d)
             st["total_host"] = torch.zeros(1, dtype=torch.int32).pin_memory()
+        if draw:                                # the rays each set's draw writes and its traversal reads (set 0: graph_rays_*)
+            for k, st in enumerate(sets):
+                st["rays_o"] = self.graph_rays_o if k == 0 else torch.zeros_like(self.graph_rays_o)
+                st["rays_d"] = self.graph_rays_d if k == 0 else self.graph_rays_d.clone()
         self._g_sets = sets
         self._g_pending = None          # prefetch: the set that holds a traversed, not yet trained batch
         self._g_next = 0
@@ -779,6 +850,8 @@ class Trainer:
         self.net.set_params_training(self.params)
         self._g_step.fill_(self.step_count)
         self._g_step_host = self.step_count     # host mirror of the device counter (see _sync_device_step)
+        if draw:
+            self._draw_step.fill_(self.draw_count)      # the warm-up's draws are not batches of the sequence
         clear_grads()
         torch.cuda.synchronize()
         for st in sets:
@@ -826,11 +899,15 @@ class Trainer:
         return self
 
     # ------------------------------------------------------------------------------------------ the step as ONE C call
-    def entry_args(self, n_rays, launch_segments=None):
+    def entry_args(self, n_rays, launch_segments=None, draw=False):
         """struct rtxn_train_step_args over this trainer's buffers: what a C++ host passes to rtxn_train_step (include/rtxn.h)
         -- traversal, rtxn_train_gradients, optimizer and weight re-pack of one batch in one call.  Inputs are read from
         graph_rays_o / graph_rays_d / graph_targets (created here if capture_step() has not).  The step counter the call
-        advances lives on the device (entry_step)."""
+        advances lives on the device (entry_step).  draw=True (attach_images() first): returns (args, draw_args), draw_args the
+        struct rtxn_draw_batch_args that fills those three inputs from the image set -- what the host passes to rtxn_draw_batch in
+        front of rtxn_train_step, as step_entry() then does."""
+        if draw and self.image_set is None:
+            raise RuntimeError("entry_args(draw=True): call attach_images() first")
         if _world() > 1:
             raise RuntimeError("entry_args: rtxn_train_step steps the optimizer inside the call; data-parallel training exchanges the "
                                "gradients between rtxn_train_gradients and the optimizer (step() / capture_step())")
@@ -883,6 +960,11 @@ class Trainer:
         self._entry_step_host = self.step_count      # what the device counter holds now (an eager step() in between is noticed by step_entry)
         self._entry_inputs = (self.graph_rays_o.data_ptr(), self.graph_rays_d.data_ptr(), self.graph_targets.data_ptr())
         self._clear_grads()            # the call's optimizer clears what it consumes; it must start from zeros
+        self._entry_draw = None
+        if draw:
+            self._entry_draw = api.draw_batch_args(self.image_set, n, self._draw_seed(), self._draw_step, self.graph_rays_o,
+                                                   self.graph_rays_d, self.graph_targets, self.drawn)
+            return a, self._entry_draw
         return a
 
     def step_entry(self):
@@ -898,6 +980,10 @@ class Trainer:
             self._clear_grads()
         if int(self.step_count) != getattr(self, "_entry_step_host", self.step_count):
             self.entry_step.fill_(self.step_count)
+        if getattr(self, "_entry_draw", None) is not None:      # the next batch of the sequence, in front of the step
+            api.draw_batch_launch(self._entry_draw)
+            self._draw_step.add_(1)
+            self.draw_count += 1
         api.train_step(self._entry_args, self._entry_bg, self._entry_jit)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
@@ -914,11 +1000,16 @@ class Trainer:
 
     def _captured_traverse(self, k):
         st, n, cap = self._g_sets[k], self._g_n, self._g_cap
-        kw = dict(grid_res=self.R, rays_o=self.graph_rays_o, rays_d=self.graph_rays_d, width=n, height=1, ray_begin=0, ray_count=n,
+        if self._g_draw:                        # the batch is drawn here, straight into this set's rays and targets
+            rays_o, rays_d = st["rays_o"], st["rays_d"]
+            self._draw(n, rays_o, rays_d, st["targets"])
+        else:
+            rays_o, rays_d = self.graph_rays_o, self.graph_rays_d
+            st["targets"].copy_(self.graph_targets)
+        kw = dict(grid_res=self.R, rays_o=rays_o, rays_d=rays_d, width=n, height=1, ray_begin=0, ray_count=n,
                   occupancy=self.occ, occupancy_coarse=self.coarse, occupancy_bricks=self.bricks, occupancy_super=self.super_mip,
                   mode=api.TRACE_DDA, viewing_direction=st["view_dirs"], num_hits=st["num_hits"], sub_rays=api.auto_sub_rays(n),
                   sub_hits=st["sub_hits"])
-        st["targets"].copy_(self.graph_targets)
         api.trace_grid(None, **kw)
         api.scan_hits(st["num_hits"][:n], st["indices"][:n], st["total"], self.scan_ws)
         api.trace_grid(None, indices=st["indices"], start_points=st["start"], end_points=st["end"], seg_view=st["seg_view"],
@@ -1002,7 +1093,8 @@ class Trainer:
         self._graphs["apply"].replay()
 
     def step_captured(self):
-        """Replay the captured step on graph_rays_o / graph_rays_d / graph_targets; returns the (device) loss scalar -- with
+        """Replay the captured step on graph_rays_o / graph_rays_d / graph_targets (capture_step(draw=True): on the next batch the
+        graph draws itself); returns the (device) loss scalar -- with
         prefetch, of the batch submitted by the previous call (None on the first).  Unlike step() it never looks at the
         segment count on the host: a batch without any sample still runs Adam (on a zero gradient), and a truncated batch
         is noticed a call later (truncated_steps)."""
@@ -1016,6 +1108,7 @@ class Trainer:
             self._check_truncation(0)
             self.step_count += 1
             self._g_step_host += 1
+            self.draw_count += self._g_draw
             self._graphs["step"][0].replay()
             if self._g_world > 1:
                 self._g_split_table = 0 if self._g_split else None
@@ -1026,10 +1119,12 @@ class Trainer:
         if self._g_pending is None:                     # nothing traversed yet: this call only traverses
             self._graphs["prime"][k].replay()
             self._g_pending = k
+            self.draw_count += self._g_draw
             return None
         self._check_truncation(self._g_pending)
         self.step_count += 1
         self._g_step_host += 1
+        self.draw_count += self._g_draw
         self._graphs["step"][k].replay()                # traverse into set k || train on set 1-k (the pending one)
         self._g_pending = k
         if self._g_world > 1:

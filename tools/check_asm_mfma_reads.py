@@ -60,7 +60,7 @@ def check(path):
         dst_ops = [] if (is_store or op.startswith(("s_", "v_cmp", "v_cmpx"))) else ops[:1]
         src_ops = ops if (is_store or op.startswith("v_cmp")) else ops[1:]
         if not in_asm and not op.startswith("s_"):
-            for r in {r for o in src_ops for r in regs(o)}:
+            for r in sorted({r for o in src_ops for r in regs(o)}):     # sorted: the register named does not follow the hash seed
                 if r in pending and pending[r] < NEED:
                     findings.append(f"{path}:{n}: {kernel[:70]}: `{line}` reads {r[0]}{r[1]} {pending[r]} wait states after an asm MFMA wrote it")
                     break
