@@ -7,6 +7,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego [--steps 2000] [--encoding hash]
   python examples/train_synthetic.py --make-demo /tmp/demo_scene --data /tmp/demo_scene --steps 400
   python examples/train_synthetic.py --data /path/to/lego --device-batches     (frames resident as RGBA8/RGB8, batches drawn on the device)
+  python examples/train_synthetic.py --data /path/to/lego --loss huber --opacity-weight 0.1     (Huber, and the frames' alpha fitted)
 """
 import argparse
 import json
@@ -55,17 +56,24 @@ def main():
     ap.add_argument("--device-batches", action="store_true",
                     help="keep the frames on the device as uint8 (api.ImageSet) and draw every batch there (Trainer.step_images) "
                          "instead of gathering it from a per-ray dataset")
+    ap.add_argument("--loss", default="l2", choices=sorted(api.LOSS_KINDS), help="the training loss (Trainer(loss=...))")
+    ap.add_argument("--opacity-weight", type=float, default=0.0,
+                    help="> 0: load the frames with their alpha (RGBA, trained over white) and fit the rays' opacity to it with this weight")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.make_demo:
         make_demo(a.make_demo)
     # flags=2: keep the PNGs' sRGB values (the reference's stbi_loadf applies a 2.2 gamma, Q11); corrected focal (Q1);
     # origin/10 as in the reference (Q2) so that Blender's radius-4 cameras sit just outside the unit grid
-    ds = loader.load_images_json(a.data, "train", flags=2)
+    rgba = a.opacity_weight > 0.0
+    C = 4 if rgba else 3
+    ds = loader.load_images_json(a.data, "train", flags=2 | (4 if rgba else 0))      # 4: RTXN_LOAD_RGBA
     if ds.images.shape[0] == 0:
         sys.exit("no frames loaded")
+    if rgba and float(ds.images[..., 3].min()) == 1.0:
+        sys.exit("--opacity-weight: these frames carry no alpha (every pixel is opaque): there is no mask to fit")
     n_hold = max(1, ds.images.shape[0] // 8)
-    train_ds = loader.ImageDataset(ds.images[:-n_hold], ds.poses[:-n_hold], ds.focal, ds.image_width, ds.image_height, 3, ds.camera_angle_x)
+    train_ds = loader.ImageDataset(ds.images[:-n_hold], ds.poses[:-n_hold], ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
     if a.device_batches:
         # flags=2 frames are k/255: one byte per channel holds them exactly
         images, focal = api.ImageSet.from_dataset(train_ds, storage="u8")
@@ -77,23 +85,31 @@ def main():
     tr = Trainer(R, None, encoding=a.encoding, n_neurons=64, n_hidden_layers=2 if a.encoding == "hash" else 4,
                  hashgrid=dict(n_levels=8, n_features=2, log2_hashmap_size=15, base_resolution=8, per_level_scale=1.5),
                  batch_rays=max(a.batch, ds.image_width * ds.image_height), max_segments=max(a.batch, ds.image_width * ds.image_height) * (3 * R),
-                 lr=1e-2 if a.encoding == "hash" else 2e-3, density_scale=150.0)
+                 lr=1e-2 if a.encoding == "hash" else 2e-3, density_scale=150.0, loss=a.loss, opacity_weight=a.opacity_weight,
+                 background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C)
+    white = (1.0, 1.0, 1.0) if rgba else None
+
+    def render():
+        return tr.render_rays(o_t, d_t, background=white)
+
     if a.device_batches:
         tr.attach_images(images)
     g = torch.Generator(device="cuda").manual_seed(0)
     W, H = ds.image_width, ds.image_height
     o_t, d_t = camera_rays(ds.poses[-1], focal, W, H, origin_scale=0.1)
-    gt = torch.from_numpy(ds.images[-1].reshape(-1, 3)).cuda()
+    gt = torch.from_numpy(ds.images[-1].reshape(-1, C)).cuda()
+    if rgba:                                    # the held-out frame over white, as the model is rendered
+        gt = gt[:, 3:4] * gt[:, :3] + (1.0 - gt[:, 3:4])
     print(f"{n_rays} training rays from {train_ds.images.shape[0]} frames ({W}x{H}), {held / 1e6:.2f} MB on the device "
-          f"({'image set, batches drawn on the device' if a.device_batches else 'ray dataset'}); held-out PSNR before: {psnr(tr.render_rays(o_t, d_t), gt):.2f} dB")
+          f"({'image set, batches drawn on the device' if a.device_batches else 'ray dataset'}); held-out PSNR before: {psnr(render(), gt):.2f} dB")
     for it in range(a.steps):
         loss = tr.step_images(a.batch) if a.device_batches else tr.step(*rays.sample_batch(a.batch, g))
         if (it + 1) % 100 == 0:
             frac = tr.update_occupancy(threshold=0.01) if it + 1 >= 200 else 1.0
-            print(f"step {it + 1:5d} loss {float(loss.item()):.6f} occupied {100 * frac:.1f}% held-out PSNR {psnr(tr.render_rays(o_t, d_t), gt):.2f} dB", flush=True)
+            print(f"step {it + 1:5d} loss {float(loss.item()):.6f} occupied {100 * frac:.1f}% held-out PSNR {psnr(render(), gt):.2f} dB", flush=True)
     print(f"final held-out PSNR after {a.steps} steps ({'device batches' if a.device_batches else 'ray dataset'}): "
-          f"{psnr(tr.render_rays(o_t, d_t), gt):.2f} dB")
-    img = tr.render_rays(o_t, d_t).reshape(H, W, 3).cpu().numpy()
+          f"{psnr(render(), gt):.2f} dB")
+    img = render().reshape(H, W, 3).cpu().numpy()
     loader.write_png(a.out, img)
     print("wrote", a.out)
 

@@ -959,6 +959,62 @@ int rtxn_train_gradients_jitter(const rtxn_train_batch* batch, const rtxn_train_
 int rtxn_train_step_jitter(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                            rtxn_stream_t stream);
 
+/* ---- training losses beyond L2 (not in the reference, whose loss is tcnn "L2", main.cu:36-38) ---------------------------
+ * Per ray r:
+ *   pixel  p_c = sum_k w_k c_kc + (1 - A) b_c, with A = sum_k w_k;
+ *   target t_c is the ray's target, RGBA composited over the ray's background (as rtxn_volrender_l2_train_ex does);
+ *   e_c = p_c - t_c;
+ *   N = 3 n_rays.
+ *
+ *   kind                                      | per-channel term l(e)                              | dl/dp
+ *   RTXN_LOSS_L2 = 0                          | e^2                                                | 2e
+ *   RTXN_LOSS_L1 = 1                          | abs(e)                                             | sign(e), 0 at e == 0
+ *   RTXN_LOSS_HUBER = 2 (param = delta > 0)   | e^2 / 2 if abs(e) <= delta,                        | clamp(e, -delta, delta)
+ *                                             | else delta (abs(e) - delta / 2)                    |
+ *   RTXN_LOSS_RELATIVE_L2 = 3 (param = eps>0) | e^2 / (p^2 + eps)                                  | 2e / (p^2 + eps)
+ *
+ * For relative L2 the denominator is a constant to the gradient, as in tiny-cuda-nn.  The division is IEEE.
+ * Alpha term, weight lambda = opacity_weight >= 0: lambda (A - alpha_r)^2 per ray, where alpha_r is the target's fourth
+ * channel.  So lambda > 0 needs 4-channel targets and the RTXN_VR_NERF compositor.
+ * The loss scalar written to loss_sum, unscaled:
+ *   (1/N) sum l(e) + (lambda / n_rays) sum (A - alpha)^2
+ * The gradients handed on, each rounded to fp16 exactly as the L2 path rounds its own and used in that rounded form:
+ *   g_c = half(loss_scale l'(e_c) / N)
+ *   g_A = half(loss_scale lambda 2 (A - alpha) / n_rays)
+ * Sweep 2 is the background kernels' sweep with one more constant:
+ *   dL/dw_k = g.c_k - g.b + g_A, so gc = (g.c_k) - gbg + g_A;
+ *   S = g.(sum w c) - gbg A + g_A A;
+ *   with no background, b = 0 and gbg = 0.
+ * Rules (RTXN_ERR_INVALID with a message naming the field, before any device is touched): a known kind; HUBER and
+ * RELATIVE_L2 need a finite param > 0; opacity_weight >= 0; opacity_weight > 0 needs 4-channel targets (a CONSTANT or RANDOM
+ * background) and not RTXN_VR_COMPAT.  In deterministic mode (rtxn_set_deterministic_workspace) the scalar is summed in a
+ * fixed order behind the compositor from pixels, targets and, with opacity_weight > 0, the opacities: `opacity` must then be
+ * given.  loss == NULL, or kind L2 with opacity_weight == 0 and opacity == NULL: exactly the call without the struct -- the
+ * same kernels, the same bits. */
+enum rtxn_loss_kind { RTXN_LOSS_L2 = 0, RTXN_LOSS_L1 = 1, RTXN_LOSS_HUBER = 2, RTXN_LOSS_RELATIVE_L2 = 3 };
+typedef struct rtxn_train_loss {
+  int kind;               /* rtxn_loss_kind */
+  float param;            /* HUBER: delta; RELATIVE_L2: epsilon; otherwise ignored */
+  float opacity_weight;   /* lambda */
+  float* opacity;         /* optional DEVICE float[n_rays]: A of every ray, written by the compositor; NULL: not written */
+} rtxn_train_loss;
+/* rtxn_volrender_l2_train_ex with the loss chosen by `loss` (bg may be NULL: black, 3-channel targets) */
+int rtxn_volrender_loss_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                              int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
+                              void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                              const rtxn_train_background* bg, const rtxn_train_loss* loss, rtxn_stream_t stream);
+/* rtxn_l2_loss for the four kinds, elementwise with N = n: values[i] = l(e_i) / n, grads[i] = half(loss_scale l'(e_i) / n),
+ * *loss_sum = sum of values (a float atomic per block).  What the RTXN_VR_COMPAT three-launch route of rtxn_train_gradients_loss
+ * uses.  opacity_weight must be 0 and opacity NULL: there is no compositor here. */
+int rtxn_loss(const float* pred, const float* target, long n, const rtxn_train_loss* loss, float loss_scale, float* values,
+              void* grads_half, float* loss_sum, rtxn_stream_t stream);
+/* rtxn_train_gradients_jitter / rtxn_train_step_jitter with the loss beside the background and the jitter; each may be NULL.
+ * The step form: a NULL bg->step or jitter->step is opt.step as it is BEFORE the call increments it. */
+int rtxn_train_gradients_loss(const rtxn_train_batch* batch, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                              const rtxn_train_loss* loss, rtxn_stream_t stream);
+int rtxn_train_step_loss(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                         const rtxn_train_loss* loss, rtxn_stream_t stream);
+
 /* fp32 <-> fp16 copies of a gradient block on the device (no counterpart in the reference, which is single-GPU): the
  * data-parallel exchange sends the hashed levels' gradient in fp16 -- tiny-cuda-nn holds that gradient in fp16 throughout. */
 int rtxn_convert_f32_to_f16(const float* src, void* dst_half, long n, rtxn_stream_t stream);

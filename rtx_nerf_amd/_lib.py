@@ -120,6 +120,11 @@ class SampleJitter(C.Structure):
     _fields_ = [("seed", C.c_uint), ("step", C.c_void_p)]
 
 
+class TrainLoss(C.Structure):
+    """struct rtxn_train_loss (include/rtxn.h)."""
+    _fields_ = [("kind", C.c_int), ("param", C.c_float), ("opacity_weight", C.c_float), ("opacity", C.c_void_p)]
+
+
 class ImageSet(C.Structure):
     """struct rtxn_image_set (include/rtxn.h)."""
     _fields_ = [("images", C.c_void_p), ("poses", C.c_void_p), ("n_images", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32),
@@ -289,6 +294,10 @@ SYMBOLS = {
     "rtxn_hashgrid_backward_segments_live_jitter": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, _P, C.POINTER(SampleJitter), _P]),
     "rtxn_train_gradients_jitter": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), _P]),
     "rtxn_train_step_jitter": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), _P]),
+    "rtxn_volrender_loss_train": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(TrainBackground), C.POINTER(TrainLoss), _P]),
+    "rtxn_loss": (_I, [_P, _P, _L, C.POINTER(TrainLoss), _F, _P, _P, _P, _P]),
+    "rtxn_train_gradients_loss": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss), _P]),
+    "rtxn_train_step_loss": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss), _P]),
     "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),

@@ -320,6 +320,43 @@ def volrender_l2_train_ex(network_outputs, ray_hit, num_hits, indices, batch_siz
           "rtxn_volrender_l2_train_ex")
 
 
+LOSS_L2, LOSS_L1, LOSS_HUBER, LOSS_RELATIVE_L2 = 0, 1, 2, 3   # enum rtxn_loss_kind
+LOSS_KINDS = {"l2": LOSS_L2, "l1": LOSS_L1, "huber": LOSS_HUBER, "relative_l2": LOSS_RELATIVE_L2}
+LOSS_DEFAULT_PARAM = {LOSS_HUBER: 0.1, LOSS_RELATIVE_L2: 1e-2}      # delta (instant-ngp's); epsilon (tiny-cuda-nn's)
+
+
+def train_loss(kind="l2", param=None, opacity_weight=0.0, opacity=None):
+    """struct rtxn_train_loss (include/rtxn.h): kind "l2" | "l1" | "huber" | "relative_l2"; param: Huber's delta (default 0.1) or
+    relative L2's epsilon (default 1e-2); opacity_weight: lambda of the alpha term lambda (A - alpha)^2 (needs RGBA targets);
+    opacity: optional device float32[n_rays] the compositor writes every ray's A into (kept referenced by the struct)."""
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"loss {kind!r}: one of {sorted(LOSS_KINDS)}")
+    s = _lib.TrainLoss()
+    s.kind = LOSS_KINDS[kind]
+    s.param = float(param) if param is not None else LOSS_DEFAULT_PARAM.get(s.kind, 0.0)
+    s.opacity_weight = float(opacity_weight)
+    s.opacity = _ptr(opacity, torch.float32, "opacity")
+    s._opacity_tensor = opacity
+    return s
+
+
+def _byref(s):
+    return C.byref(s) if s is not None else None
+
+
+def volrender_loss_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
+                         loss_gradients, loss_sum, radiance_gradients, background=None, loss=None):
+    """volrender_l2_train_ex with the loss of train_loss(...) (None, or plain "l2": that very call): the loss compositor."""
+    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
+        raise _lib.RtxnError(f"volrender_loss_train: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
+    check(_lib.lib().rtxn_volrender_loss_train(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
+                                               _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
+                                               num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
+                                               _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
+                                               _ptr(loss_sum, torch.float32, "loss_sum"), _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
+                                               _byref(background), _byref(loss), _stream()), "rtxn_volrender_loss_train")
+
+
 # --------------------------------------------------------------------------- MLP
 class Network:
     """tcnn::create_from_config(n_input_dims=5, n_output_dims=4, config) (main.cu:35-69,325)."""
@@ -762,6 +799,13 @@ def l2_loss(pred, target, loss_scale=1.0, values=None, grads=None, loss_sum=None
                                   _ptr(loss_sum, torch.float32, "loss_sum"), _stream()), "rtxn_l2_loss")
 
 
+def loss(pred, target, spec, loss_scale=1.0, values=None, grads=None, loss_sum=None):
+    """l2_loss for the four kinds (spec: train_loss(...) without an alpha term): rtxn_loss, elementwise over pred.numel() values."""
+    check(_lib.lib().rtxn_loss(_ptr(pred, torch.float32, "pred"), _ptr(target, torch.float32, "target"), pred.numel(), _byref(spec),
+                               loss_scale, _ptr(values, torch.float32, "values"), _ptr(grads, torch.float16, "grads"),
+                               _ptr(loss_sum, torch.float32, "loss_sum"), _stream()), "rtxn_loss")
+
+
 def adam_step(master, params_fp16, grads, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, loss_scale=1.0):
     """optimizer->step(stream, loss_scale, params_fp32, params, gradients) (main.cu:787)."""
     check(_lib.lib().rtxn_adam_step(master.numel(), _ptr(master, torch.float32, "master"),
@@ -844,12 +888,17 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
                     total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                     encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                     loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                    workspace_lean=False, background=None, jitter=None):
+                    workspace_lean=False, background=None, jitter=None, loss=None):
     """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781).
     background: train_background(...) -> rtxn_train_gradients_ex (targets float[n_rays][background.target_channels]);
-    jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> rtxn_train_gradients_jitter (with or without a background)."""
+    jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> rtxn_train_gradients_jitter (with or without a background);
+    loss: train_loss(...) -> rtxn_train_gradients_loss (with or without either)."""
     kw = {k: v for k, v in locals().items() if k not in ("background", "jitter")}
-    if jitter is not None:
+    if loss is not None:
+        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
+        check(_lib.lib().rtxn_train_gradients_loss(C.byref(b), _byref(background), _jit(jitter), C.byref(loss), _stream()),
+              "rtxn_train_gradients_loss")
+    elif jitter is not None:
         b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
         check(_lib.lib().rtxn_train_gradients_jitter(C.byref(b), C.byref(background) if background is not None else None, _jit(jitter),
                                                      _stream()), "rtxn_train_gradients_jitter")
@@ -865,9 +914,12 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
                 total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                 encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                 loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                workspace_lean=False, target_channels=3):
+                workspace_lean=False, target_channels=3, loss=None):
     """struct rtxn_train_batch over the given tensors (which the caller keeps alive), sizes checked against the capacity
-    (targets: target_channels floats per ray)."""
+    (targets: target_channels floats per ray).  loss: the train_loss(...) the batch will be stepped with -- not part of the
+    struct, its opacity buffer is sized against n_rays here."""
+    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < int(n_rays):
+        raise _lib.RtxnError(f"train_gradients: loss.opacity holds {loss._opacity_tensor.numel()} elements, {n_rays} rays")
     b = _lib.TrainBatch()
     b.mlp, b.grid = net._h, (grid._h if grid is not None else None)
     b.n_dir_freqs = int(n_dir_freqs)
@@ -902,11 +954,15 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None, jitter=None):
+def train_step(args, background=None, jitter=None, loss=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
-    jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule)."""
-    if jitter is not None:
+    jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
+    loss: train_loss(...) -> rtxn_train_step_loss (with or without either)."""
+    if loss is not None:
+        check(_lib.lib().rtxn_train_step_loss(C.byref(args), _byref(background), _jit(jitter), C.byref(loss), _stream()),
+              "rtxn_train_step_loss")
+    elif jitter is not None:
         check(_lib.lib().rtxn_train_step_jitter(C.byref(args), C.byref(background) if background is not None else None, _jit(jitter),
                                                 _stream()), "rtxn_train_step_jitter")
     elif background is None:

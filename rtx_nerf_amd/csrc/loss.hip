@@ -13,8 +13,10 @@
 // The value differs from the atomics' sum by float rounding of the order only (tests/test_gpu_deterministic_loss.py holds it
 // to a float64 restatement from pixels and targets).  One block: a 4096-ray batch is one group per thread.  Default mode
 // never comes here.
+// Also here: the same fixed-order sum and the stand-alone elementwise kernel (rtxn_loss) for the losses of rtxn_train_loss.
 #include "background_internal.h"
 #include "common.h"
+#include "loss_internal.h"
 
 namespace {
 
@@ -50,9 +52,94 @@ __global__ __launch_bounds__(kLossThreads) void l2_loss_fixed_order_kernel(const
   if (threadIdx.x == 0) *loss_sum = red[0];
 }
 
+// The same sum for the losses of rtxn_train_loss (composite_loss.hip's kernels; include/rtxn.h): the per-ray term is
+// loss_internal.h's ray_loss_term, the function the compositor evaluates, on the pixels it stored and -- with lambda > 0 -- on
+// the opacities it stored; grouping and order are l2_loss_fixed_order_kernel's.
+__global__ __launch_bounds__(kLossThreads) void loss_fixed_order_kernel(const float* __restrict__ pixels, const float* __restrict__ target,
+                                                                        int n_rays, BgArgs bg, LossArgs la, float* __restrict__ loss_sum) {
+  __shared__ float red[kLossThreads];
+  const float inv_n = 1.0f / (float)(3L * n_rays), inv_rays = 1.0f / (float)n_rays;
+  const int groups = (n_rays + 3) / 4;
+  float acc = 0.0f;
+  for (int g = threadIdx.x; g < groups; g += kLossThreads) {
+    float e[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int ray = 4 * g + k;
+      e[k] = 0.0f;
+      if (ray < n_rays) {
+        float b[3], t[3], dl[3], dA;
+        ray_background(bg, target, ray, b, t);
+        const float p[3] = {pixels[3 * (long)ray], pixels[3 * (long)ray + 1], pixels[3 * (long)ray + 2]};
+        const bool alpha_term = la.opacity_weight > 0.0f;
+        e[k] = ray_loss_term(la, p, t, alpha_term ? la.opacity[ray] : 0.0f, alpha_term ? target[4 * (long)ray + 3] : 0.0f, inv_n, inv_rays,
+                             dl, dA);
+      }
+    }
+    acc += (e[0] + e[1]) + (e[2] + e[3]);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = kLossThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss_sum = red[0];
+}
+
+// rtxn_loss: loss->evaluate for the four kinds, elementwise (l2_loss_kernel's role, train.hip), N = n
+constexpr int kElemThreads = 256;
+__global__ __launch_bounds__(kElemThreads) void loss_kernel(const float* __restrict__ pred, const float* __restrict__ target, long n,
+                                                            float scale, int kind, float param, float* __restrict__ values,
+                                                            __half* __restrict__ grads, float* __restrict__ loss_sum) {
+  __shared__ float red[kElemThreads / 64];
+  const float inv_n = 1.0f / (float)n;
+  float local = 0.0f;
+  for (long i = (long)blockIdx.x * kElemThreads + threadIdx.x; i < n; i += (long)gridDim.x * kElemThreads) {
+    const float p = pred[i];
+    float dl;
+    const float v = loss_term(kind, param, p, p - target[i], dl) * inv_n;
+    if (values) values[i] = v;
+    if (grads) grads[i] = loss_grad_half(scale, dl, inv_n);
+    local += v;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
+  __syncthreads();
+  if (threadIdx.x == 0 && loss_sum) {
+    float t = 0.0f;
+    for (int w = 0; w < kElemThreads / 64; ++w) t += red[w];
+    atomicAdd(loss_sum, t);
+  }
+}
+
 }  // namespace
 
 namespace rtxn {
+
+int loss_fixed_order(const float* pixels, const float* target, int n_rays, const rtxn_train_background* bg, const rtxn_train_loss* loss,
+                     float* loss_sum, hipStream_t stream) {
+  BgArgs a{};
+  a.mode = RTXN_BG_NONE;
+  a.target_channels = 3;
+  if (bg) {
+    a.mode = bg->mode;
+    for (int c = 0; c < 3; ++c) a.color[c] = bg->color[c];
+    a.seed = bg->seed;
+    a.step = bg->step;
+    a.target_channels = bg->target_channels;
+  }
+  LossArgs la{};
+  la.kind = loss->kind;
+  la.param = loss->param;
+  la.opacity_weight = loss->opacity_weight;
+  la.has_background = bg ? 1 : 0;
+  la.opacity = loss->opacity;
+  loss_fixed_order_kernel<<<1, kLossThreads, 0, stream>>>(pixels, target, n_rays, a, la, loss_sum);
+  RTXN_LAUNCH_CHECK("loss_fixed_order_kernel");
+  return RTXN_OK;
+}
 
 int l2_loss_fixed_order(const float* pixels, const float* target, int n_rays, int bg_mode, const float* bg_color, unsigned bg_seed,
                         const int* bg_step, int target_channels, float* loss_sum, hipStream_t stream) {
@@ -68,3 +155,22 @@ int l2_loss_fixed_order(const float* pixels, const float* target, int n_rays, in
 }
 
 }  // namespace rtxn
+
+extern "C" int rtxn_loss(const float* pred, const float* target, long n, const rtxn_train_loss* loss, float loss_scale, float* values,
+                         void* grads_half, float* loss_sum, rtxn_stream_t stream) {
+  bool active = false;
+  const int rc = rtxn::check_train_loss(loss, 3, -1, "rtxn_loss", &active);
+  if (rc != RTXN_OK) return rc;
+  if (!active) return rtxn_l2_loss(pred, target, n, loss_scale, values, grads_half, loss_sum, stream);      // NULL or L2: the L2 kernel itself
+  RTXN_REQUIRE(n >= 0, "rtxn_loss: n = %ld < 0", n);
+  RTXN_DEVICE_OR_FAIL();
+  hipStream_t s = rtxn::as_stream(stream);
+  if (loss_sum) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(pred && target, "rtxn_loss: NULL buffer");
+  const long want = (n + kElemThreads - 1) / kElemThreads;
+  loss_kernel<<<(unsigned)(want < 1024 ? want : 1024), kElemThreads, 0, s>>>(pred, target, n, loss_scale, loss->kind, loss->param, values,
+                                                                             static_cast<__half*>(grads_half), loss_sum);
+  RTXN_LAUNCH_CHECK("loss_kernel");
+  return RTXN_OK;
+}

@@ -24,7 +24,7 @@ __global__ void advance_step_kernel(int* step, float lr, float beta1, float beta
 }  // namespace
 
 static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                           rtxn_stream_t stream) {
+                           const rtxn_train_loss* loss, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
@@ -66,7 +66,8 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   if (rc != RTXN_OK) return rc;
 
   // ---- sampler ... backward (main.cu:703-781), segment count read on the device ----
-  rc = jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
+  rc = loss   ? rtxn_train_gradients_loss(&b, bg, jitter, loss, stream)
+     : jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
   if (rc != RTXN_OK) return rc;
 
   // ---- optimizer->step (main.cu:787): every gradient is cleared as it is consumed ----
@@ -99,18 +100,18 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   return RTXN_OK;
 }
 
-extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, stream); }
+extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, stream); }
 
 extern "C" int rtxn_train_step_ex(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step_ex: NULL arguments");
   bool active = false;
   const int rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_ex", &active);
   if (rc != RTXN_OK) return rc;
-  if (!active) return train_step_impl(a, nullptr, nullptr, stream);
+  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, stream);
   // RANDOM without a counter of its own: the optimizer's, read by the compositor before advance_step_kernel increments it
   rtxn_train_background own = *bg;
   if (own.mode == RTXN_BG_RANDOM && !own.step) own.step = a->opt.step;
-  return train_step_impl(a, &own, nullptr, stream);
+  return train_step_impl(a, &own, nullptr, nullptr, stream);
 }
 
 // ... and with the sampler's jitter; a NULL jitter->step is the optimizer's counter too, by the same rule
@@ -132,5 +133,29 @@ extern "C" int rtxn_train_step_jitter(const rtxn_train_step_args* a, const rtxn_
     own_jitter = *jitter;
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, stream);
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, stream);
+}
+
+// ... and with the loss of rtxn_train_loss (rtxn_train_gradients_loss); NULL, or plain L2: rtxn_train_step_jitter
+extern "C" int rtxn_train_step_loss(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                    const rtxn_train_loss* loss, rtxn_stream_t stream) {
+  RTXN_REQUIRE(a, "rtxn_train_step_loss: NULL arguments");
+  int rc = rtxn::check_sample_jitter("rtxn_train_step_loss", a->batch.sample_type, jitter, a->batch.vr_mode);
+  if (rc != RTXN_OK) return rc;
+  bool active = false, loss_active = false;
+  rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_loss", &active);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, a->batch.vr_mode, "rtxn_train_step_loss", &loss_active);
+  if (rc != RTXN_OK) return rc;
+  rtxn_train_background own_bg;
+  if (active) {
+    own_bg = *bg;
+    if (own_bg.mode == RTXN_BG_RANDOM && !own_bg.step) own_bg.step = a->opt.step;
+  }
+  rtxn_sample_jitter own_jitter;
+  if (jitter) {
+    own_jitter = *jitter;
+    if (!own_jitter.step) own_jitter.step = a->opt.step;
+  }
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, stream);
 }

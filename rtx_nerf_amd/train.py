@@ -58,8 +58,12 @@ class Trainer:
     def __init__(self, grid_res, occupancy=None, encoding="hash", n_neurons=64, n_hidden_layers=4,
                  hashgrid=None, n_dir_freqs=4, batch_rays=4096, max_segments=None, lr=1e-3, loss_scale=128.0,
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
-                 target_channels=None, sample_jitter=False, jitter_seed=0):
-        """sample_jitter: draw the 32 samples of every segment at fresh positions inside their strata on every training step
+                 target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0):
+        """loss: "l2" (the reference's; every code path as without the argument), "l1", "huber" (loss_param: delta, default 0.1) or
+        "relative_l2" (loss_param: epsilon, default 1e-2); opacity_weight: lambda of the alpha term lambda (A - alpha)^2, which fits
+        the ray's opacity to the fourth channel of RGBA targets (librtxn: rtxn_volrender_loss_train /
+        rtxn_train_gradients_loss / rtxn_train_step_loss).  Configuration, not state: checkpoints do not hold it.
+        sample_jitter: draw the 32 samples of every segment at fresh positions inside their strata on every training step
         (SAMPLING_JITTER_WORLD; mode "nerf" only) instead of at the midpoints; rendering and the occupancy refresh stay
         at the midpoints.  jitter_seed: its seed (the rank is mixed in when data parallel).
         background: None (black, the reference's compositor), (r, g, b) -- train over that constant colour -- or "random":
@@ -83,6 +87,7 @@ class Trainer:
         self._stage_ev = None     # list of (stage, start event, end event) while time_stages() is collecting
         self._init_background(background, background_seed, target_channels)      # refused before anything is allocated
         self._init_jitter(sample_jitter, jitter_seed)
+        self._init_loss(loss, loss_param, opacity_weight)
         self.image_set = None      # attach_images(): batches drawn on the device
         self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
         self._draw_step = None
@@ -192,6 +197,10 @@ class Trainer:
         self.pixels = torch.empty((B, 3), device=d)
         self.loss_grads = torch.empty((B, 3), dtype=torch.float16, device=d)
         self.loss = torch.zeros(1, device=d)
+        # the alpha term's per-ray opacities, written by the loss compositor (deterministic mode sums the loss from them)
+        self.opacity = torch.zeros(B, device=d) if self.opacity_weight > 0.0 else None
+        self._loss = (api.train_loss(self.loss_kind, self.loss_param, self.opacity_weight, self.opacity)
+                      if (self.loss_kind != "l2" or self.opacity_weight > 0.0) else None)
         # data parallel (world > 1): the MLP gradient's all-reduce is issued from inside gradients(), right behind the MLP
         # backward, and runs beside the hash scatter; the hashed levels go through dp.Half2GradExchange (lists where a level
         # is sparse, RTXN_DP_SPARSE=0: always the dense fp16 level)
@@ -235,6 +244,19 @@ class Trainer:
         # the optimizer's own for step_entry() -- the same step number draws the same backgrounds on all three paths
         self._bg_step = torch.zeros(1, dtype=torch.int32, device=self.dev) if random else None
         self._bg_step_host = 0
+
+    def _init_loss(self, kind, param, opacity_weight):
+        if kind not in api.LOSS_KINDS:
+            raise ValueError(f"Trainer: loss {kind!r}: one of {sorted(api.LOSS_KINDS)}")
+        lam = float(opacity_weight)
+        if param is not None and kind in ("huber", "relative_l2") and not (float(param) > 0.0 and np.isfinite(float(param))):
+            raise ValueError(f"Trainer: loss_param = {param!r}: {kind} needs a finite value > 0")
+        if not (lam >= 0.0 and np.isfinite(lam)):
+            raise ValueError(f"Trainer: opacity_weight = {opacity_weight!r} (finite, >= 0)")
+        if lam > 0.0 and self.target_channels != 4:
+            raise ValueError("Trainer: opacity_weight > 0 fits the opacity to the alpha of RGBA targets: it needs a background and "
+                             "target_channels=4 (mode='nerf')")
+        self.loss_kind, self.loss_param, self.opacity_weight = kind, (float(param) if param is not None else None), lam
 
     def _init_jitter(self, sample_jitter, seed):
         if sample_jitter and self.mode != "nerf":
@@ -464,6 +486,8 @@ class Trainer:
         K = api.NUM_SAMPLES_PER_SEGMENT
         vr = api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT
         bg = self._bg(self._bg_step, self._target_width(targets, n))
+        if self.opacity_weight > 0.0 and targets.shape[-1] != 4:
+            raise ValueError(f"Trainer: opacity_weight > 0 needs [n, 4] (straight RGBA) targets, got {tuple(targets.shape)}")
         if self._bg_step is not None and self._bg_step_host != self.step_count:
             self._bg_step.fill_(self.step_count)
             self._bg_step_host = self.step_count
@@ -485,7 +509,10 @@ class Trainer:
                     self.dtable.zero_()
         self._dp_pending = None
         if S == 0:
-            if bg is not None:            # every pixel is its background: loss and pixels, no radiance to differentiate
+            if self._loss is not None and self.mode == "nerf" and self.fuse_compositor:
+                api.volrender_loss_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
+                                         self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss)
+            elif bg is not None:          # every pixel is its background: loss and pixels, no radiance to differentiate
                 api.volrender_l2_train_ex(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
                                           self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg)
             else:
@@ -496,7 +523,10 @@ class Trainer:
         self._forward(S, save=not self.two_pass, jitter=jit)
         if self.mode == "nerf" and self.fuse_compositor:
             with _Stage(self, "composite_fwd+l2+bwd"):   # one launch: the backward's first sweep IS the forward
-                if bg is not None:
+                if self._loss is not None:
+                    api.volrender_loss_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
+                                             self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss)
+                elif bg is not None:
                     api.volrender_l2_train_ex(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
                                               self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg)
                 else:
@@ -507,7 +537,10 @@ class Trainer:
                 api.launch_volrender_cuda(None, self.radiance, self.num_stored, self.indices, self.t_vals, n, K,
                                           self.pixels[:n], mode=vr)
             with _Stage(self, "l2_loss"):
-                api.l2_loss(self.pixels[:n], targets, self.loss_scale, None, self.loss_grads[:n], self.loss)
+                if self._loss is not None:
+                    api.loss(self.pixels[:n], targets, self._loss, self.loss_scale, None, self.loss_grads[:n], self.loss)
+                else:
+                    api.l2_loss(self.pixels[:n], targets, self.loss_scale, None, self.loss_grads[:n], self.loss)
             with _Stage(self, "composite_bwd"):
                 api.launch_volrender_backward_cuda(None, self.loss_grads, self.radiance, self.t_vals, self.num_stored,
                                                    self.indices, n, K, self.dout, mode=vr)
@@ -984,7 +1017,7 @@ class Trainer:
             api.draw_batch_launch(self._entry_draw)
             self._draw_step.add_(1)
             self.draw_count += 1
-        api.train_step(self._entry_args, self._entry_bg, self._entry_jit)
+        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -1030,7 +1063,7 @@ class Trainer:
                             pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss, dparams=self.dparams,
                             dtable=self.dtable if hash_ else None, dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
                             live_ws=self.live_ws if self.live_segments else None, skip_table_backward=self._g_split,
-                            workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit)
+                            workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit, loss=self._loss)
 
     def _captured_table_bwd(self, k):
         """the hash scatter of set k's batch over the live list the gradient graph left (its count is on the device)"""
