@@ -8,6 +8,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --make-demo /tmp/demo_scene --data /tmp/demo_scene --steps 400
   python examples/train_synthetic.py --data /path/to/lego --device-batches     (frames resident as RGBA8/RGB8, batches drawn on the device)
   python examples/train_synthetic.py --data /path/to/lego --loss huber --opacity-weight 0.1     (Huber, and the frames' alpha fitted)
+  python examples/train_synthetic.py --data /path/to/lego --distortion-weight 0.01 --loss-scale 4096     (mip-NeRF 360's distortion loss)
 """
 import argparse
 import json
@@ -59,6 +60,11 @@ def main():
     ap.add_argument("--loss", default="l2", choices=sorted(api.LOSS_KINDS), help="the training loss (Trainer(loss=...))")
     ap.add_argument("--opacity-weight", type=float, default=0.0,
                     help="> 0: load the frames with their alpha (RGBA, trained over white) and fit the rays' opacity to it with this weight")
+    ap.add_argument("--distortion-weight", type=float, default=0.0,
+                    help="> 0: mip-NeRF 360's distortion regulariser with this weight, for world distances along the ray (a weight quoted "
+                         "for distances normalised to [0, 1] is divided by 2 sqrt(3)); raise --loss-scale with it")
+    ap.add_argument("--loss-scale", type=float, default=128.0,
+                    help="the fp16 gradients' loss scale: the regulariser's gradient is largely rounded away at the default (DESIGN 5.12)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.make_demo:
@@ -86,7 +92,8 @@ def main():
                  hashgrid=dict(n_levels=8, n_features=2, log2_hashmap_size=15, base_resolution=8, per_level_scale=1.5),
                  batch_rays=max(a.batch, ds.image_width * ds.image_height), max_segments=max(a.batch, ds.image_width * ds.image_height) * (3 * R),
                  lr=1e-2 if a.encoding == "hash" else 2e-3, density_scale=150.0, loss=a.loss, opacity_weight=a.opacity_weight,
-                 background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C)
+                 background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C, distortion_weight=a.distortion_weight,
+                 loss_scale=a.loss_scale)
     white = (1.0, 1.0, 1.0) if rgba else None
 
     def render():

@@ -1015,6 +1015,56 @@ int rtxn_train_gradients_loss(const rtxn_train_batch* batch, const rtxn_train_ba
 int rtxn_train_step_loss(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                          const rtxn_train_loss* loss, rtxn_stream_t stream);
 
+/* ---- distortion regulariser (mip-NeRF 360; not in the reference) -----------------------------------------------------------
+ * Per ray r, over its n = num_samples_per_hit * num_stored samples in storage order (a ray's segments are stored in ascending,
+ * disjoint t):
+ *   w_i     the RTXN_VR_NERF compositor's weights, exactly those the pixel uses;
+ *   delta_i = (t_end_j - t_start_j) * (1 / K), the width of sub-interval k of segment j: the step length the compositor reads
+ *           (ray_hit / t_vals) wherever that is a distance -- rtxn_train_batch.t_scale is a factor on sigma that the step lengths
+ *           of a batch carry, and no part of delta_i;
+ *   m_i     = fmaf((k + 0.5) * (1 / K), t_end_j - t_start_j, t_start_j), the midpoint of sub-interval k of segment j (K samples
+ *           per segment) -- the depth expression of rtxn_volrender_fwd_aux with u0 = 0.5.  With RTXN_SAMPLING_JITTER_WORLD m_i
+ *           stays the stratum's midpoint and delta_i its width: w_i is taken as the weight of the interval, not of the
+ *           jittered point, so the compositor needs no jitter state.
+ *   L_r   = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i
+ *         = 2 sum_i w_i (m_i W_<i - M_<i) + (1/3) sum_i w_i^2 delta_i,    W_<i = sum_{j<i} w_j,  M_<i = sum_{j<i} w_j m_j
+ *   q_i   = dL_r/dw_i = 2 [m_i (W_<i - W_>i) - (M_<i - M_>i)] + (2/3) w_i delta_i
+ *   loss += (lambda_d / n_rays) sum_r L_r                                  (lambda_d = distortion_weight)
+ * Distances are world units along the normalised ray; the cube [-1, 1]^3 has diagonal 2 sqrt(3), so a lambda quoted for
+ * distances normalised to [0, 1] is divided by that.
+ * The term enters sweep 2 (see the losses above) as one more addend of gc, with k = loss_scale lambda_d / n_rays in fp32 -- no
+ * fp16 hand-off for this term:
+ *   dL/dw_i = g.c_i - g.b + g_A + k q_i;     S gains 2 k L_r   (sum_i w_i q_i = 2 L_r: L_r is homogeneous of degree 2 in w).
+ * The radiance gradients are fp16: with loss_scale 128, 4096 rays and lambda_d = 0.01 the term is ~1e-7 per sample, one or two
+ * fp16 subnormal steps, and is largely rounded away on its own; it needs a larger loss_scale to act where the colour gradient
+ * has vanished.
+ * Rules (RTXN_ERR_INVALID with a message naming the field, before any device is touched): distortion_weight finite and >= 0;
+ * a weight > 0, or either output pointer, needs t_start and t_end, the RTXN_VR_NERF compositor and sample_type
+ * RTXN_SAMPLING_MIDPOINT_WORLD or RTXN_SAMPLING_JITTER_WORLD.  In deterministic mode the scalar is summed in a fixed order
+ * behind the compositor; with distortion_weight > 0 that sum reads `distortion`, which must then be given (the rule `opacity`
+ * follows).  reg == NULL, or weight 0 with both outputs NULL: exactly the corresponding _loss call -- the same kernels, the same
+ * bits. */
+typedef struct rtxn_train_regularizer {
+  float distortion_weight;   /* lambda_d >= 0, finite */
+  const float* t_start;      /* DEVICE float per packed segment slot, as rtxn_trace_grid writes them (RTXN_TRACE_DDA) */
+  const float* t_end;
+  float* distortion;         /* optional DEVICE float[n_rays]: L_r of every ray */
+  float* depth;              /* optional DEVICE float[n_rays]: sum w_i m_i (rtxn_volrender_fwd_aux's depth for MIDPOINT_WORLD) */
+} rtxn_train_regularizer;
+/* rtxn_volrender_loss_train with the regulariser (bg and loss may be NULL) */
+int rtxn_volrender_reg_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                             int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
+                             void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                             const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
+                             rtxn_stream_t stream);
+/* rtxn_train_gradients_loss / rtxn_train_step_loss with the regulariser beside the other three; each may be NULL.  The step
+ * form traces in RTXN_TRACE_DDA (RTXN_TRACE_COMPAT is refused when the regulariser is active) and its write pass stores the
+ * segments' t_start / t_end into the struct's buffers, which must hold batch.segment_capacity floats each. */
+int rtxn_train_gradients_reg(const rtxn_train_batch* batch, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                             const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream);
+int rtxn_train_step_reg(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                        const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream);
+
 /* fp32 <-> fp16 copies of a gradient block on the device (no counterpart in the reference, which is single-GPU): the
  * data-parallel exchange sends the hashed levels' gradient in fp16 -- tiny-cuda-nn holds that gradient in fp16 throughout. */
 int rtxn_convert_f32_to_f16(const float* src, void* dst_half, long n, rtxn_stream_t stream);

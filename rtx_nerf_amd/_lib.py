@@ -125,6 +125,12 @@ class TrainLoss(C.Structure):
     _fields_ = [("kind", C.c_int), ("param", C.c_float), ("opacity_weight", C.c_float), ("opacity", C.c_void_p)]
 
 
+class TrainRegularizer(C.Structure):
+    """struct rtxn_train_regularizer (include/rtxn.h)."""
+    _fields_ = [("distortion_weight", C.c_float), ("t_start", C.c_void_p), ("t_end", C.c_void_p), ("distortion", C.c_void_p),
+                ("depth", C.c_void_p)]
+
+
 class ImageSet(C.Structure):
     """struct rtxn_image_set (include/rtxn.h)."""
     _fields_ = [("images", C.c_void_p), ("poses", C.c_void_p), ("n_images", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32),
@@ -298,6 +304,12 @@ SYMBOLS = {
     "rtxn_loss": (_I, [_P, _P, _L, C.POINTER(TrainLoss), _F, _P, _P, _P, _P]),
     "rtxn_train_gradients_loss": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss), _P]),
     "rtxn_train_step_loss": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss), _P]),
+    "rtxn_volrender_reg_train": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(TrainBackground), C.POINTER(TrainLoss),
+                                      C.POINTER(TrainRegularizer), _P]),
+    "rtxn_train_gradients_reg": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                      C.POINTER(TrainRegularizer), _P]),
+    "rtxn_train_step_reg": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                 C.POINTER(TrainRegularizer), _P]),
     "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),

@@ -357,6 +357,49 @@ def volrender_loss_train(network_outputs, ray_hit, num_hits, indices, batch_size
                                                _byref(background), _byref(loss), _stream()), "rtxn_volrender_loss_train")
 
 
+def train_regularizer(distortion_weight=0.0, t_start=None, t_end=None, distortion=None, depth=None):
+    """struct rtxn_train_regularizer (include/rtxn.h): the distortion regulariser of mip-NeRF 360 in the training compositor.
+    distortion_weight: lambda_d >= 0, for world distances (a lambda quoted for distances normalised to [0, 1] is divided by the
+    cube's diagonal 2 sqrt(3)); t_start, t_end: device float32 per packed segment slot, as trace_grid writes them (TRACE_DDA);
+    distortion, depth: optional device float32[n_rays] outputs, L_r and sum w m of every ray.  The tensors stay referenced by the
+    struct."""
+    s = _lib.TrainRegularizer()
+    s.distortion_weight = float(distortion_weight)
+    s.t_start, s.t_end = _ptr(t_start, torch.float32, "t_start"), _ptr(t_end, torch.float32, "t_end")
+    s.distortion, s.depth = _ptr(distortion, torch.float32, "distortion"), _ptr(depth, torch.float32, "depth")
+    s._tensors = {"t_start": t_start, "t_end": t_end, "distortion": distortion, "depth": depth}
+    return s
+
+
+def _check_regularizer(who, reg, n_rays, n_segments=None):
+    tensors = getattr(reg, "_tensors", None)       # a _lib.TrainRegularizer filled by hand: nothing to size, the library checks the rest
+    if reg is None or tensors is None:
+        return
+    for nm in ("distortion", "depth"):
+        t = tensors[nm]
+        if t is not None and t.numel() < int(n_rays):
+            raise _lib.RtxnError(f"{who}: regularizer.{nm} holds {t.numel()} elements, {n_rays} rays")
+    if n_segments is not None:
+        for nm in ("t_start", "t_end"):
+            t = tensors[nm]
+            if t is not None and t.numel() < int(n_segments):
+                raise _lib.RtxnError(f"{who}: regularizer.{nm} holds {t.numel()} elements, {n_segments} segment slots")
+
+
+def volrender_reg_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
+                        loss_gradients, loss_sum, radiance_gradients, background=None, loss=None, regularizer=None):
+    """volrender_loss_train with the regulariser of train_regularizer(...) (None, or weight 0 without outputs: that very call)."""
+    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
+        raise _lib.RtxnError(f"volrender_reg_train: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
+    _check_regularizer("volrender_reg_train", regularizer, batch_size, ray_hit.numel() // int(num_samples_per_hit))
+    check(_lib.lib().rtxn_volrender_reg_train(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
+                                              _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
+                                              num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
+                                              _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
+                                              _ptr(loss_sum, torch.float32, "loss_sum"), _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
+                                              _byref(background), _byref(loss), _byref(regularizer), _stream()), "rtxn_volrender_reg_train")
+
+
 # --------------------------------------------------------------------------- MLP
 class Network:
     """tcnn::create_from_config(n_input_dims=5, n_output_dims=4, config) (main.cu:35-69,325)."""
@@ -888,13 +931,19 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
                     total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                     encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                     loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                    workspace_lean=False, background=None, jitter=None, loss=None):
+                    workspace_lean=False, background=None, jitter=None, loss=None, regularizer=None):
     """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781).
     background: train_background(...) -> rtxn_train_gradients_ex (targets float[n_rays][background.target_channels]);
     jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> rtxn_train_gradients_jitter (with or without a background);
-    loss: train_loss(...) -> rtxn_train_gradients_loss (with or without either)."""
-    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter")}
-    if loss is not None:
+    loss: train_loss(...) -> rtxn_train_gradients_loss (with or without either);
+    regularizer: train_regularizer(...) -> rtxn_train_gradients_reg (with or without any of the three)."""
+    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer")}
+    if regularizer is not None:
+        _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
+        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
+        check(_lib.lib().rtxn_train_gradients_reg(C.byref(b), _byref(background), _jit(jitter), _byref(loss), C.byref(regularizer), _stream()),
+              "rtxn_train_gradients_reg")
+    elif loss is not None:
         b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
         check(_lib.lib().rtxn_train_gradients_loss(C.byref(b), _byref(background), _jit(jitter), C.byref(loss), _stream()),
               "rtxn_train_gradients_loss")
@@ -954,12 +1003,18 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None, jitter=None, loss=None):
+def train_step(args, background=None, jitter=None, loss=None, regularizer=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
     jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
-    loss: train_loss(...) -> rtxn_train_step_loss (with or without either)."""
-    if loss is not None:
+    loss: train_loss(...) -> rtxn_train_step_loss (with or without either);
+    regularizer: train_regularizer(...) -> rtxn_train_step_reg (with or without any of the three): the write pass of the traversal
+    stores the segments' t_start / t_end into the regulariser's buffers."""
+    if regularizer is not None:
+        _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
+        check(_lib.lib().rtxn_train_step_reg(C.byref(args), _byref(background), _jit(jitter), _byref(loss), C.byref(regularizer), _stream()),
+              "rtxn_train_step_reg")
+    elif loss is not None:
         check(_lib.lib().rtxn_train_step_loss(C.byref(args), _byref(background), _jit(jitter), C.byref(loss), _stream()),
               "rtxn_train_step_loss")
     elif jitter is not None:

@@ -53,6 +53,11 @@ __attribute__((visibility("hidden"))) int loss_fixed_order(const float* pixels, 
                                                            const rtxn_train_background* bg, const rtxn_train_loss* loss,
                                                            float* loss_sum, hipStream_t stream);
 
+// The rules of the distortion regulariser (rtxn_train_regularizer, include/rtxn.h), host only, composite_reg.hip:
+// RTXN_ERR_INVALID with a message naming the field, or RTXN_OK with *active = whether the regularised compositor runs at all
+// (NULL, or weight 0 with no output: the entry point makes exactly the _loss call).  sample_type < 0: the entry point has none.
+int check_train_regularizer(const rtxn_train_regularizer* reg, int vr_mode, int sample_type, const char* who, bool* active);
+
 // MurmurHash3's 32-bit finaliser: the integer hash behind RTXN_BG_RANDOM and the occupancy refresh's jitter (include/rtxn.h
 // states both uses bit for bit)
 __host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {

@@ -4012,7 +4012,7 @@ extern "C" int rtxn_hashgrid_backward_segments_live_jitter(const rtxn_hashgrid* 
 
 // ------------------------------------------------------------------------- a whole batch, segment count on the device
 static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                                const rtxn_train_loss* loss, rtxn_stream_t stream) {
+                                const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
   RTXN_REQUIRE(b && b->mlp, "rtxn_train_gradients: NULL batch or model");
   const rtxn_mlp* m = b->mlp;
   int rc = check_train(m, "rtxn_train_gradients");
@@ -4076,7 +4076,9 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   if (rc != RTXN_OK) return rc;
   // launch_volrender_cuda, loss->evaluate, launch_volrender_backward_cuda (main.cu:737-767): per ray, no sample count needed
   if (b->vr_mode == RTXN_VR_NERF) {
-    rc = loss ? rtxn_volrender_loss_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
+    rc = reg  ? rtxn_volrender_reg_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
+                                         b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, loss, reg, stream)
+       : loss ? rtxn_volrender_loss_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
                                           b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, loss, stream)
          : bg ? rtxn_volrender_l2_train_ex(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
                                          b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, stream)
@@ -4119,7 +4121,7 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   return rc;
 }
 
-extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, nullptr, nullptr, stream); }
+extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, nullptr, nullptr, nullptr, stream); }
 
 // over a background: the one difference is the compositor (rtxn_volrender_l2_train_ex); NULL / NONE + 3 channels: the plain call
 extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
@@ -4127,7 +4129,7 @@ extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_tra
   bool active = false;
   const int rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_ex", &active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, nullptr, nullptr, stream);
+  return train_gradients_impl(b, active ? bg : nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the sampler's jitter (RTXN_SAMPLING_JITTER_WORLD): both optional, NULL + NULL is rtxn_train_gradients
@@ -4139,7 +4141,7 @@ extern "C" int rtxn_train_gradients_jitter(const rtxn_train_batch* b, const rtxn
   bool active = false;
   rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_jitter", &active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, nullptr, stream);
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, nullptr, nullptr, stream);
 }
 
 // ... and with the loss of rtxn_train_loss: the compositor (RTXN_VR_NERF: rtxn_volrender_loss_train) or the loss launch between
@@ -4154,5 +4156,22 @@ extern "C" int rtxn_train_gradients_loss(const rtxn_train_batch* b, const rtxn_t
   if (rc != RTXN_OK) return rc;
   rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, b->vr_mode, "rtxn_train_gradients_loss", &loss_active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, stream);
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, nullptr, stream);
+}
+
+// ... and with the distortion regulariser (rtxn_train_regularizer): the compositor (rtxn_volrender_reg_train) is the one
+// difference; NULL, or weight 0 without outputs: rtxn_train_gradients_loss
+extern "C" int rtxn_train_gradients_reg(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                        const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
+  RTXN_REQUIRE(b, "rtxn_train_gradients_reg: NULL batch");
+  int rc = rtxn::check_sample_jitter("rtxn_train_gradients_reg", b->sample_type, jitter, b->vr_mode);
+  if (rc != RTXN_OK) return rc;
+  bool active = false, loss_active = false, reg_active = false;
+  rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_reg", &active);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, b->vr_mode, "rtxn_train_gradients_reg", &loss_active);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn::check_train_regularizer(reg, b->vr_mode, b->sample_type, "rtxn_train_gradients_reg", &reg_active);
+  if (rc != RTXN_OK) return rc;
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, reg_active ? reg : nullptr, stream);
 }

@@ -24,7 +24,7 @@ __global__ void advance_step_kernel(int* step, float lr, float beta1, float beta
 }  // namespace
 
 static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                           const rtxn_train_loss* loss, rtxn_stream_t stream) {
+                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
@@ -62,11 +62,16 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   t.seg_view = const_cast<float*>(b.seg_view);
   t.num_stored = const_cast<int*>(b.num_stored);
   t.segment_capacity = b.segment_capacity;
+  if (reg) {                                                  // the regulariser's distances, written beside the segments
+    t.t_start = const_cast<float*>(reg->t_start);
+    t.t_end = const_cast<float*>(reg->t_end);
+  }
   rc = rtxn_trace_grid(&t, stream);
   if (rc != RTXN_OK) return rc;
 
   // ---- sampler ... backward (main.cu:703-781), segment count read on the device ----
-  rc = loss   ? rtxn_train_gradients_loss(&b, bg, jitter, loss, stream)
+  rc = reg    ? rtxn_train_gradients_reg(&b, bg, jitter, loss, reg, stream)
+     : loss   ? rtxn_train_gradients_loss(&b, bg, jitter, loss, stream)
      : jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
   if (rc != RTXN_OK) return rc;
 
@@ -100,18 +105,18 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   return RTXN_OK;
 }
 
-extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, stream); }
+extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, stream); }
 
 extern "C" int rtxn_train_step_ex(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step_ex: NULL arguments");
   bool active = false;
   const int rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_ex", &active);
   if (rc != RTXN_OK) return rc;
-  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, stream);
+  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, stream);
   // RANDOM without a counter of its own: the optimizer's, read by the compositor before advance_step_kernel increments it
   rtxn_train_background own = *bg;
   if (own.mode == RTXN_BG_RANDOM && !own.step) own.step = a->opt.step;
-  return train_step_impl(a, &own, nullptr, nullptr, stream);
+  return train_step_impl(a, &own, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the sampler's jitter; a NULL jitter->step is the optimizer's counter too, by the same rule
@@ -133,7 +138,7 @@ extern "C" int rtxn_train_step_jitter(const rtxn_train_step_args* a, const rtxn_
     own_jitter = *jitter;
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, stream);
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the loss of rtxn_train_loss (rtxn_train_gradients_loss); NULL, or plain L2: rtxn_train_step_jitter
@@ -157,5 +162,36 @@ extern "C" int rtxn_train_step_loss(const rtxn_train_step_args* a, const rtxn_tr
     own_jitter = *jitter;
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, stream);
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, nullptr, stream);
+}
+
+// ... and with the distortion regulariser (rtxn_train_gradients_reg): the write pass of the traversal stores t_start / t_end
+// into the struct's buffers; NULL, or weight 0 without outputs: rtxn_train_step_loss
+extern "C" int rtxn_train_step_reg(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                   const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
+  RTXN_REQUIRE(a, "rtxn_train_step_reg: NULL arguments");
+  int rc = rtxn::check_sample_jitter("rtxn_train_step_reg", a->batch.sample_type, jitter, a->batch.vr_mode);
+  if (rc != RTXN_OK) return rc;
+  bool active = false, loss_active = false, reg_active = false;
+  rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_reg", &active);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, a->batch.vr_mode, "rtxn_train_step_reg", &loss_active);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn::check_train_regularizer(reg, a->batch.vr_mode, a->batch.sample_type, "rtxn_train_step_reg", &reg_active);
+  if (rc != RTXN_OK) return rc;
+  if (reg_active)
+    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "rtxn_train_step_reg: trace.mode = %d: the regulariser's t_start / t_end are written by the "
+                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", a->trace.mode);
+  rtxn_train_background own_bg;
+  if (active) {
+    own_bg = *bg;
+    if (own_bg.mode == RTXN_BG_RANDOM && !own_bg.step) own_bg.step = a->opt.step;
+  }
+  rtxn_sample_jitter own_jitter;
+  if (jitter) {
+    own_jitter = *jitter;
+    if (!own_jitter.step) own_jitter.step = a->opt.step;
+  }
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, reg_active ? reg : nullptr,
+                         stream);
 }

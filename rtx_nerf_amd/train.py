@@ -58,8 +58,15 @@ class Trainer:
     def __init__(self, grid_res, occupancy=None, encoding="hash", n_neurons=64, n_hidden_layers=4,
                  hashgrid=None, n_dir_freqs=4, batch_rays=4096, max_segments=None, lr=1e-3, loss_scale=128.0,
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
-                 target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0):
-        """loss: "l2" (the reference's; every code path as without the argument), "l1", "huber" (loss_param: delta, default 0.1) or
+                 target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0,
+                 distortion_weight=0.0):
+        """distortion_weight: lambda_d of mip-NeRF 360's distortion regulariser (librtxn: rtxn_volrender_reg_train /
+        rtxn_train_gradients_reg / rtxn_train_step_reg), in world distances along the ray (a lambda quoted for distances normalised to
+        [0, 1] is divided by the cube's diagonal 2 sqrt(3)); mode "nerf" and the fused compositor only.  Its gradient is ~1e-7 per
+        sample at lambda_d = 0.01, loss_scale 128 and 4096 rays, at the edge of the fp16 radiance gradients: raise loss_scale with it.
+        Trainer.distortion holds L_r of every ray of the last batch.  0.0: nothing is allocated and every call is the one made
+        without the argument.  Configuration, not state, as loss is.
+        loss: "l2" (the reference's; every code path as without the argument), "l1", "huber" (loss_param: delta, default 0.1) or
         "relative_l2" (loss_param: epsilon, default 1e-2); opacity_weight: lambda of the alpha term lambda (A - alpha)^2, which fits
         the ray's opacity to the fourth channel of RGBA targets (librtxn: rtxn_volrender_loss_train /
         rtxn_train_gradients_loss / rtxn_train_step_loss).  Configuration, not state: checkpoints do not hold it.
@@ -88,6 +95,7 @@ class Trainer:
         self._init_background(background, background_seed, target_channels)      # refused before anything is allocated
         self._init_jitter(sample_jitter, jitter_seed)
         self._init_loss(loss, loss_param, opacity_weight)
+        self._init_regularizer(distortion_weight)
         self.image_set = None      # attach_images(): batches drawn on the device
         self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
         self._draw_step = None
@@ -201,6 +209,12 @@ class Trainer:
         self.opacity = torch.zeros(B, device=d) if self.opacity_weight > 0.0 else None
         self._loss = (api.train_loss(self.loss_kind, self.loss_param, self.opacity_weight, self.opacity)
                       if (self.loss_kind != "l2" or self.opacity_weight > 0.0) else None)
+        # the distortion regulariser: the segments' entry / exit distances, written by the traversal's write pass, and L_r per ray
+        self.t_start = self.t_end = self.distortion = self._reg = None
+        if self.distortion_weight > 0.0:
+            self.t_start, self.t_end = torch.zeros(M, device=d), torch.zeros(M, device=d)
+            self.distortion = torch.zeros(B, device=d)
+            self._reg = api.train_regularizer(self.distortion_weight, self.t_start, self.t_end, self.distortion)
         # data parallel (world > 1): the MLP gradient's all-reduce is issued from inside gradients(), right behind the MLP
         # backward, and runs beside the hash scatter; the hashed levels go through dp.Half2GradExchange (lists where a level
         # is sparse, RTXN_DP_SPARSE=0: always the dense fp16 level)
@@ -257,6 +271,24 @@ class Trainer:
             raise ValueError("Trainer: opacity_weight > 0 fits the opacity to the alpha of RGBA targets: it needs a background and "
                              "target_channels=4 (mode='nerf')")
         self.loss_kind, self.loss_param, self.opacity_weight = kind, (float(param) if param is not None else None), lam
+
+    def _init_regularizer(self, distortion_weight):
+        lam = float(distortion_weight)
+        if not (lam >= 0.0 and np.isfinite(lam)):
+            raise ValueError(f"Trainer: distortion_weight = {distortion_weight!r} (finite, >= 0)")
+        if lam > 0.0 and self.mode != "nerf":
+            raise ValueError("Trainer: distortion_weight > 0 needs mode='nerf': the regulariser lives in the fused NeRF compositor "
+                             "and measures world distances, which mode='compat' does not sample")
+        if lam > 0.0 and os.environ.get("RTXN_TRAIN_FUSE_COMPOSITOR", "1") == "0":
+            raise ValueError("Trainer: distortion_weight > 0 needs the fused training compositor (RTXN_TRAIN_FUSE_COMPOSITOR=0 selects "
+                             "the three-launch compositor, which has no regulariser)")
+        self.distortion_weight = lam
+
+    def _reg_t(self, st=None):
+        """the write pass's t_start / t_end arguments: the regulariser's buffers (of buffer set st), or nothing"""
+        if self._reg is None:
+            return {}
+        return dict(t_start=self.t_start if st is None else st["t_start"], t_end=self.t_end if st is None else st["t_end"])
 
     def _init_jitter(self, sample_jitter, seed):
         if sample_jitter and self.mode != "nerf":
@@ -360,7 +392,7 @@ class Trainer:
             api.scan_hits(self.num_hits[:n], self.indices[:n], self.total, self.scan_ws)
         with _Stage(self, "trace_write"):
             api.trace_grid(None, indices=self.indices, start_points=self.start, end_points=self.end, seg_view=self.seg_view,
-                           num_stored=self.num_stored, segment_capacity=self.max_segments, **kw)
+                           num_stored=self.num_stored, segment_capacity=self.max_segments, **self._reg_t(), **kw)
         P = int(self.total.item())            # the reference synchronises here too (thrust::reduce, main.cu:632)
         if P > self.max_segments:
             # Rays whose segments do not fit are cut off ON THE DEVICE (num_stored < num_hits, never out of bounds) and
@@ -509,7 +541,10 @@ class Trainer:
                     self.dtable.zero_()
         self._dp_pending = None
         if S == 0:
-            if self._loss is not None and self.mode == "nerf" and self.fuse_compositor:
+            if self._reg is not None:
+                api.volrender_reg_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
+                                        self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
+            elif self._loss is not None and self.mode == "nerf" and self.fuse_compositor:
                 api.volrender_loss_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
                                          self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss)
             elif bg is not None:          # every pixel is its background: loss and pixels, no radiance to differentiate
@@ -523,7 +558,10 @@ class Trainer:
         self._forward(S, save=not self.two_pass, jitter=jit)
         if self.mode == "nerf" and self.fuse_compositor:
             with _Stage(self, "composite_fwd+l2+bwd"):   # one launch: the backward's first sweep IS the forward
-                if self._loss is not None:
+                if self._reg is not None:
+                    api.volrender_reg_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
+                                            self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
+                elif self._loss is not None:
                     api.volrender_loss_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
                                              self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss)
                 elif bg is not None:
@@ -815,6 +853,8 @@ class Trainer:
         self._g_n, self._g_cap, self._g_prefetch, self._g_draw = n, cap, bool(prefetch), bool(draw)
         # the traversal's outputs, once per buffer set (set 0 = the trainer's own buffers)
         names = ("view_dirs", "num_hits", "indices", "num_stored", "sub_hits", "total", "start", "end", "seg_view")
+        if self._reg is not None:
+            names += ("t_start", "t_end")
         set0 = {k: getattr(self, k) for k in names}
         sets = [set0]
         if prefetch:
@@ -822,6 +862,9 @@ class Trainer:
             for k in ("start", "end", "seg_view"):       # only the launch capacity is ever written
                 s1[k] = torch.zeros((cap,) + tuple(set0[k].shape[1:]), device=d)
             sets.append(s1)
+        for k, st in enumerate(sets):           # the regulariser reads the t_start / t_end of the set it trains on
+            st["reg"] = (None if self._reg is None else self._reg if k == 0 else
+                         api.train_regularizer(self.distortion_weight, st["t_start"], st["t_end"], self.distortion))
         for st in sets:
             st["targets"] = torch.zeros((n, self.target_channels), device=d)
             st["total_host"] = torch.zeros(1, dtype=torch.int32).pin_memory()
@@ -1017,7 +1060,7 @@ class Trainer:
             api.draw_batch_launch(self._entry_draw)
             self._draw_step.add_(1)
             self.draw_count += 1
-        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss)
+        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -1046,7 +1089,7 @@ class Trainer:
         api.trace_grid(None, **kw)
         api.scan_hits(st["num_hits"][:n], st["indices"][:n], st["total"], self.scan_ws)
         api.trace_grid(None, indices=st["indices"], start_points=st["start"], end_points=st["end"], seg_view=st["seg_view"],
-                       num_stored=st["num_stored"], segment_capacity=cap, **kw)
+                       num_stored=st["num_stored"], segment_capacity=cap, **self._reg_t(st), **kw)
         st["total_host"].copy_(st["total"], non_blocking=True)      # 4 bytes for a later call's truncation check
 
     def _captured_gradients(self, k):
@@ -1063,7 +1106,8 @@ class Trainer:
                             pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss, dparams=self.dparams,
                             dtable=self.dtable if hash_ else None, dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
                             live_ws=self.live_ws if self.live_segments else None, skip_table_backward=self._g_split,
-                            workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit, loss=self._loss)
+                            workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit, loss=self._loss,
+                            regularizer=st["reg"])
 
     def _captured_table_bwd(self, k):
         """the hash scatter of set k's batch over the live list the gradient graph left (its count is on the device)"""

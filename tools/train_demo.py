@@ -21,13 +21,14 @@ teacher_field = scenes.teacher_field   # kept under this name for the tests that
 
 def run(steps=300, encoding="hash", grid=32, res=64, batch=4096, n_poses=12, seed=0, verbose=True, neurons=64, layers=2,
         hash_levels=8, hash_log2=15, hash_base=8, background=None, rgba=False, loss="l2", loss_param=None, opacity_weight=0.0,
-        probe=None):
+        probe=None, distortion_weight=0.0, loss_scale=128.0):
     """Returns (PSNR before, PSNR after, losses) on the held-out pose.  background=None, rgba=False: the teacher over black,
     trained over black.  background=(r, g, b): the training targets are the teacher composited over that colour, or with
     rgba=True its straight RGBA (colour / opacity, opacity); "random" (needs rgba): RGBA targets over a fresh background per
     ray and step.  With a background both PSNRs are dicts {"white": dB, "black": dB}: the model against the teacher, both
-    composited over white / over black.  loss / loss_param / opacity_weight: the Trainer's.  probe: called as
-    probe(trainer, rays_o, rays_d, targets, when) with the whole training set, when = "before" and "after" the steps."""
+    composited over white / over black.  loss / loss_param / opacity_weight: the Trainer's; distortion_weight /
+    loss_scale likewise.  probe: called as probe(trainer, rays_o, rays_d, targets, when) with the whole training
+    set, when = "before" and "after" the steps."""
     if background == "random" and not rgba:
         raise ValueError("train_demo.run: background='random' trains on RGBA targets (rgba=True)")
     torch.cuda.set_device(0)
@@ -37,8 +38,9 @@ def run(steps=300, encoding="hash", grid=32, res=64, batch=4096, n_poses=12, see
                     per_level_scale=1.5)
     tr = Trainer(grid, occ, encoding=encoding, n_neurons=neurons, n_hidden_layers=layers, hashgrid=hashgrid,
                  batch_rays=max(batch, res * res), max_segments=max(batch, res * res) * 40, lr=1e-2 if encoding == "hash" else 2e-3,
-                 loss_scale=128.0, density_scale=150.0, mode="nerf", seed=seed, background=background,
-                 target_channels=4 if rgba else None, loss=loss, loss_param=loss_param, opacity_weight=opacity_weight)
+                 loss_scale=loss_scale, density_scale=150.0, mode="nerf", seed=seed, background=background,
+                 target_channels=4 if rgba else None, loss=loss, loss_param=loss_param, opacity_weight=opacity_weight,
+                 distortion_weight=distortion_weight)
 
     def teacher(o, d):
         """the training target of these rays"""
