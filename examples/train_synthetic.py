@@ -9,6 +9,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego --device-batches     (frames resident as RGBA8/RGB8, batches drawn on the device)
   python examples/train_synthetic.py --data /path/to/lego --loss huber --opacity-weight 0.1     (Huber, and the frames' alpha fitted)
   python examples/train_synthetic.py --data /path/to/lego --distortion-weight 0.01 --loss-scale 4096     (mip-NeRF 360's distortion loss)
+  python examples/train_synthetic.py --data /path/to/lego --steps 20000 --lr-schedule cosine:20000 --weight-decay 1e-6 --skip-nonfinite
 """
 import argparse
 import json
@@ -65,7 +66,16 @@ def main():
                          "for distances normalised to [0, 1] is divided by 2 sqrt(3)); raise --loss-scale with it")
     ap.add_argument("--loss-scale", type=float, default=128.0,
                     help="the fp16 gradients' loss scale: the regulariser's gradient is largely rounded away at the default (DESIGN 5.12)")
+    ap.add_argument("--lr-schedule", default=None, metavar="nerf|instant_ngp|cosine:N",
+                    help="decay the learning rates on the device (Trainer(lr_schedule=...)): NeRF's x0.1 per 250k steps, instant-ngp's x0.33 "
+                         "every 10k steps after 20k, or a cosine to 0.01 of the rate over N steps")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="AdamW's decoupled weight decay on the MLP")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="skip a step whose gradients hold an Inf or a NaN instead of stepping Adam on them; the number skipped is printed")
     a = ap.parse_args()
+    schedule = a.lr_schedule
+    if schedule and schedule.startswith("cosine:"):
+        schedule = dict(kind="cosine", decay_steps=int(schedule.split(":", 1)[1]), ratio=0.01)
     torch.cuda.set_device(0)
     if a.make_demo:
         make_demo(a.make_demo)
@@ -93,7 +103,7 @@ def main():
                  batch_rays=max(a.batch, ds.image_width * ds.image_height), max_segments=max(a.batch, ds.image_width * ds.image_height) * (3 * R),
                  lr=1e-2 if a.encoding == "hash" else 2e-3, density_scale=150.0, loss=a.loss, opacity_weight=a.opacity_weight,
                  background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C, distortion_weight=a.distortion_weight,
-                 loss_scale=a.loss_scale)
+                 loss_scale=a.loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite)
     white = (1.0, 1.0, 1.0) if rgba else None
 
     def render():
@@ -113,9 +123,12 @@ def main():
         loss = tr.step_images(a.batch) if a.device_batches else tr.step(*rays.sample_batch(a.batch, g))
         if (it + 1) % 100 == 0:
             frac = tr.update_occupancy(threshold=0.01) if it + 1 >= 200 else 1.0
-            print(f"step {it + 1:5d} loss {float(loss.item()):.6f} occupied {100 * frac:.1f}% held-out PSNR {psnr(render(), gt):.2f} dB", flush=True)
+            print(f"step {it + 1:5d} loss {float(loss.item()):.6f} lr {tr.current_lr():.3e} occupied {100 * frac:.1f}% held-out PSNR "
+                  f"{psnr(render(), gt):.2f} dB", flush=True)
     print(f"final held-out PSNR after {a.steps} steps ({'device batches' if a.device_batches else 'ray dataset'}): "
           f"{psnr(render(), gt):.2f} dB")
+    if tr.skipped_steps is not None and a.skip_nonfinite:
+        print(f"steps skipped for non-finite gradients: {int(tr.skipped_steps.item())} (many: lower --loss-scale)")
     img = render().reshape(H, W, 3).cpu().numpy()
     loader.write_png(a.out, img)
     print("wrote", a.out)

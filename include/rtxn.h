@@ -1065,6 +1065,90 @@ int rtxn_train_gradients_reg(const rtxn_train_batch* batch, const rtxn_train_bac
 int rtxn_train_step_reg(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                         const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream);
 
+/* ---- optimizer options: learning-rate schedule, decoupled weight decay, non-finite guard -------------------------------
+ * Not in the reference, whose configuration only says what it wanted (main.cu:39, "adam optimizer decays from 5e-4 to 5e-5").
+ * Everything is evaluated ON THE DEVICE from the step counter, so a captured step needs nothing refreshed from the host.
+ * With t the 1-based number of the update (the device step counter AFTER this step's increment; rtxn_adam_step's `step`):
+ *   warm(t) = warmup_steps > 0 ? min(1, t / warmup_steps) : 1
+ *   x(t)    = max(0, t - decay_start) / decay_steps                  (staircase: floor(x))
+ *   RTXN_LR_CONSTANT:     dec = 1
+ *   RTXN_LR_EXPONENTIAL:  dec = ratio^x                              (unbounded)
+ *   RTXN_LR_COSINE:       dec = ratio + (1 - ratio) (1 + cos(pi min(x, 1))) / 2     (ratio: the final factor)
+ *   factor(t) = (float)(warm dec)     -- all of it in double ((double)ratio), rounded to float once
+ *   lr_t = lr factor(t),  table_lr_t = table_lr factor(t)            (float products)
+ * The MLP's bias-corrected rate is rtxn_adam_effective_lr's expression with lr_t for lr; the table's sparse Adam uses table_lr_t
+ * for its lr.  RTXN_LR_CONSTANT without warm-up is exactly 1.0f.
+ * weight_decay (AdamW, decoupled): after the Adam update of an element, w -= lr_t weight_decay w, with lr_t the scheduled rate
+ * WITHOUT bias correction.  The step entry point applies it to the MLP only (tiny-cuda-nn regularises matrix parameters only).
+ * skip_nonfinite: rtxn_check_gradients ORs guard[0] if any element of the gradient buffers the optimizer is about to consume is
+ * Inf or NaN; rtxn_optimizer_rate moves that into the skip word guard[2], clears guard[0] and counts guard[1] up; the _opt Adam
+ * kernels read the skip word before any store to the state: master weights, fp16 parameters, both moments and the table's
+ * per-entry counts keep their bits, the gradient is still cleared (RTXN_ADAM_ZERO_GRADS).  The step counter advances all the
+ * same -- it keys the sample jitter, the random background and this schedule -- so Adam's global bias-correction step counts
+ * ATTEMPTED steps.  The loss scale is a by-value argument of every compositor entry point and is not adapted: guard[1], the
+ * number of skipped steps, is what tells the caller to lower it.
+ * Rules (RTXN_ERR_INVALID with a message, before any device is touched): kind is one of the three; ratio in (0, 1];
+ * decay_steps >= 1 unless the kind is CONSTANT; warmup_steps >= 0 and decay_start >= 0; staircase only with EXPONENTIAL;
+ * weight_decay finite and >= 0; when anything is switched on, lr_factor, and with skip_nonfinite guard, must not be NULL.
+ * "Switched on": a schedule other than CONSTANT without warm-up, weight_decay > 0 or skip_nonfinite != 0.  With NULL options,
+ * or nothing switched on, every _opt entry point makes exactly the call that existed before it. */
+enum rtxn_lr_schedule_kind { RTXN_LR_CONSTANT = 0, RTXN_LR_EXPONENTIAL = 1, RTXN_LR_COSINE = 2 };
+typedef struct rtxn_lr_schedule {
+  int kind;                         /* rtxn_lr_schedule_kind */
+  int warmup_steps;                 /* linear warm-up over the first warmup_steps updates; 0: none */
+  int decay_start;                  /* the decay's x is 0 up to this update */
+  int decay_steps;                  /* updates per unit of x */
+  float ratio;                      /* EXPONENTIAL: factor per decay_steps; COSINE: the final factor */
+  int staircase;                    /* EXPONENTIAL only: x = floor(x) */
+} rtxn_lr_schedule;
+typedef struct rtxn_optimizer_options {
+  rtxn_lr_schedule schedule;
+  float weight_decay;
+  int skip_nonfinite;
+  float* lr_factor;                 /* DEVICE float scratch: factor(t) of this step, written by rtxn_optimizer_rate */
+  unsigned* guard;                  /* DEVICE unsigned[4], zero-initialised: [0] the non-finite flag, [1] skipped steps so far,
+                                       [2] this step's skip word, [3] unused; may be NULL without skip_nonfinite */
+} rtxn_optimizer_options;
+/* factor(t) on the host: the definition above (step < 1, or a schedule that breaks the rules: -1 and a message;
+ * a factor is never negative). */
+float rtxn_lr_schedule_factor(const rtxn_lr_schedule* schedule, int step);
+/* The rules above without the two pointers (what a caller checks before it allocates anything); NULL is valid. */
+int rtxn_optimizer_options_check(const rtxn_optimizer_options* opt);
+/* The one-thread rate kernel every stepping path shares: t = *step (+ 1, written back, if advance != 0);
+ * *opt->lr_factor = factor(t); *effective_lr = lr_t sqrt(1 - beta2^t) / (1 - beta1^t); *table_effective_lr (may be NULL): the
+ * same with table_lr_t, for a table stepped by the dense rule; with skip_nonfinite the guard words move as described above.
+ * The powers, the cosine and warm dec are formed in double and rounded once, so the device's value is the host's to an ulp. */
+int rtxn_optimizer_rate(const rtxn_optimizer_options* opt, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
+                        float* effective_lr, float* table_effective_lr, rtxn_stream_t stream);
+/* ORs *flag (device unsigned, opt->guard) with 1 if any element of up to RTXN_MAX_GRAD_BUFFERS gradient buffers is Inf or NaN:
+ * one launch, 16 bytes per lane, the exponent bits tested on the raw words, at most one atomic per wave.  An OR is order-free:
+ * deterministic mode stays deterministic.  Buffers with count 0 are skipped. */
+enum { RTXN_MAX_GRAD_BUFFERS = 4 };
+typedef struct rtxn_grad_buffer {
+  const void* data;                 /* DEVICE float[count] or half[count] */
+  long count;
+  int is_fp16;
+} rtxn_grad_buffer;
+int rtxn_check_gradients(const rtxn_grad_buffer* buffers, int n_buffers, unsigned* flag, rtxn_stream_t stream);
+/* rtxn_adam_step_captured / rtxn_adam_step_sparse under the options: the rate is *effective_lr (dense; rtxn_optimizer_rate
+ * wrote it) or lr * *opt->lr_factor (sparse), the decay term uses lr * *opt->lr_factor, and with skip_nonfinite the skip word
+ * is honoured.  grad_flags: as rtxn_adam_step_captured, and RTXN_ADAM_NO_WEIGHT_DECAY: opt->weight_decay is not applied by
+ * this call (the hash table).  The sparse form decays the entries it updates.  opt == NULL or nothing switched on: the call
+ * without _opt (the dense one ignores `lr` then). */
+enum { RTXN_ADAM_NO_WEIGHT_DECAY = 4 };
+int rtxn_adam_step_opt(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                       const float* effective_lr, float lr, float beta1, float beta2, float eps, float loss_scale,
+                       const rtxn_optimizer_options* opt, rtxn_stream_t stream);
+int rtxn_adam_step_sparse_opt(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                              unsigned* param_steps, float lr, float beta1, float beta2, float eps, float loss_scale,
+                              const rtxn_optimizer_options* opt, rtxn_stream_t stream);
+/* rtxn_train_step_reg under the options (each of the four other structs may be NULL): behind the gradients, rtxn_check_gradients
+ * over dparams, dtable[:hashed_lo] and dtable_hashed_half (or the whole fp32 dtable) with skip_nonfinite, then rtxn_optimizer_rate
+ * advancing args->opt.step, then the _opt Adam calls -- weight decay on the MLP only. */
+int rtxn_train_step_opt(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                        const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                        rtxn_stream_t stream);
+
 /* fp32 <-> fp16 copies of a gradient block on the device (no counterpart in the reference, which is single-GPU): the
  * data-parallel exchange sends the hashed levels' gradient in fp16 -- tiny-cuda-nn holds that gradient in fp16 throughout. */
 int rtxn_convert_f32_to_f16(const float* src, void* dst_half, long n, rtxn_stream_t stream);

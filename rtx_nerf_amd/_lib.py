@@ -131,6 +131,23 @@ class TrainRegularizer(C.Structure):
                 ("depth", C.c_void_p)]
 
 
+class LrSchedule(C.Structure):
+    """struct rtxn_lr_schedule (include/rtxn.h)."""
+    _fields_ = [("kind", C.c_int), ("warmup_steps", C.c_int), ("decay_start", C.c_int), ("decay_steps", C.c_int), ("ratio", C.c_float),
+                ("staircase", C.c_int)]
+
+
+class OptimizerOptions(C.Structure):
+    """struct rtxn_optimizer_options (include/rtxn.h)."""
+    _fields_ = [("schedule", LrSchedule), ("weight_decay", C.c_float), ("skip_nonfinite", C.c_int), ("lr_factor", C.c_void_p),
+                ("guard", C.c_void_p)]
+
+
+class GradBuffer(C.Structure):
+    """struct rtxn_grad_buffer (include/rtxn.h)."""
+    _fields_ = [("data", C.c_void_p), ("count", C.c_long), ("is_fp16", C.c_int)]
+
+
 class ImageSet(C.Structure):
     """struct rtxn_image_set (include/rtxn.h)."""
     _fields_ = [("images", C.c_void_p), ("poses", C.c_void_p), ("n_images", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32),
@@ -310,6 +327,14 @@ SYMBOLS = {
                                       C.POINTER(TrainRegularizer), _P]),
     "rtxn_train_step_reg": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                  C.POINTER(TrainRegularizer), _P]),
+    "rtxn_lr_schedule_factor": (_F, [C.POINTER(LrSchedule), _I]),
+    "rtxn_optimizer_options_check": (_I, [C.POINTER(OptimizerOptions)]),
+    "rtxn_optimizer_rate": (_I, [C.POINTER(OptimizerOptions), _P, _I, _F, _F, _F, _F, _P, _P, _P]),
+    "rtxn_check_gradients": (_I, [C.POINTER(GradBuffer), _I, _P, _P]),
+    "rtxn_adam_step_opt": (_I, [_L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, C.POINTER(OptimizerOptions), _P]),
+    "rtxn_adam_step_sparse_opt": (_I, [_L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, C.POINTER(OptimizerOptions), _P]),
+    "rtxn_train_step_opt": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                 C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), _P]),
     "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),

@@ -900,6 +900,114 @@ def adam_step_sparse(master, params_fp16, grads, m, v, param_steps, lr=1e-3, bet
                                            _stream()), "rtxn_adam_step_sparse")
 
 
+# --------------------------------------------------------------------------- optimizer options
+LR_CONSTANT, LR_EXPONENTIAL, LR_COSINE = 0, 1, 2
+_LR_KINDS = {"constant": LR_CONSTANT, "exponential": LR_EXPONENTIAL, "cosine": LR_COSINE}
+# "nerf": x0.1 per 250k steps (the reference's own comment, main.cu:39, is this decay from 5e-4 to 5e-5);
+# "instant_ngp": x0.33 every 10k steps after the first 20k
+LR_PRESETS = {"nerf": dict(kind="exponential", decay_steps=250000, ratio=0.1),
+              "instant_ngp": dict(kind="exponential", decay_start=20000, decay_steps=10000, ratio=0.33, staircase=True)}
+ADAM_NO_WEIGHT_DECAY = 4
+
+
+def lr_schedule(kind="constant", warmup_steps=0, decay_start=0, decay_steps=0, ratio=1.0, staircase=False):
+    """struct rtxn_lr_schedule (include/rtxn.h): factor(t) = warm(t) dec(t) on the learning rates of update t (1-based), evaluated
+    on the device from the step counter.  kind: "constant", "exponential" (ratio^x, x = max(0, t - decay_start) / decay_steps;
+    staircase: floor(x)) or "cosine" (from 1 to ratio over decay_steps), or one of LR_PRESETS ("nerf", "instant_ngp") with the
+    other arguments overriding it; warmup_steps: linear warm-up.  Accepts a dict of these arguments, or a struct, as well."""
+    if isinstance(kind, _lib.LrSchedule):
+        return kind
+    if isinstance(kind, dict):
+        return lr_schedule(**kind)
+    kw = dict(warmup_steps=warmup_steps, decay_start=decay_start, decay_steps=decay_steps, ratio=ratio, staircase=staircase)
+    if kind in LR_PRESETS:
+        preset = dict(LR_PRESETS[kind])
+        defaults = dict(warmup_steps=0, decay_start=0, decay_steps=0, ratio=1.0, staircase=False)
+        kw = {**defaults, **preset, **{k: v for k, v in kw.items() if v != defaults[k]}}
+        kind = kw.pop("kind")
+    if isinstance(kind, str):
+        if kind not in _LR_KINDS:
+            raise ValueError(f"lr_schedule: kind {kind!r}: one of {sorted(_LR_KINDS) + sorted(LR_PRESETS)}")
+        kind = _LR_KINDS[kind]
+    s = _lib.LrSchedule()
+    s.kind, s.warmup_steps, s.decay_start, s.decay_steps = int(kind), int(kw["warmup_steps"]), int(kw["decay_start"]), int(kw["decay_steps"])
+    s.ratio, s.staircase = float(kw["ratio"]), int(bool(kw["staircase"]))
+    return s
+
+
+def lr_schedule_factor(schedule, step):
+    """rtxn_lr_schedule_factor: factor(step) on the host, the definition the device restates (for logging)."""
+    sch = lr_schedule(schedule)
+    f = _lib.lib().rtxn_lr_schedule_factor(C.byref(sch), int(step))
+    if f < 0.0:               # a schedule that breaks the rules, or step < 1: the message is the library's
+        check(1, "rtxn_lr_schedule_factor")
+    return float(f)
+
+
+def optimizer_options(schedule=None, weight_decay=0.0, skip_nonfinite=False, lr_factor=None, guard=None):
+    """struct rtxn_optimizer_options (include/rtxn.h).  lr_factor: device float32[1] scratch; guard: device int32[4], zeroed:
+    [0] the non-finite flag, [1] skipped steps, [2] this step's skip word.  The tensors stay referenced by the struct."""
+    o = _lib.OptimizerOptions()
+    o.schedule = lr_schedule(schedule) if schedule is not None else lr_schedule()
+    o.weight_decay, o.skip_nonfinite = float(weight_decay), int(bool(skip_nonfinite))
+    o.lr_factor, o.guard = _ptr(lr_factor, torch.float32, "lr_factor"), _ptr(guard, torch.int32, "guard")
+    if guard is not None and guard.numel() < 4:
+        raise _lib.RtxnError(f"optimizer_options: guard holds {guard.numel()} words, 4 are needed")
+    o._tensors = (lr_factor, guard)
+    return o
+
+
+def optimizer_options_check(opt):
+    """rtxn_optimizer_options_check: the struct's rules without its two pointers; needs no device."""
+    check(_lib.lib().rtxn_optimizer_options_check(_byref(opt)), "rtxn_optimizer_options_check")
+
+
+def optimizer_rate(opt, step, effective_lr, lr=1e-3, table_lr=0.0, table_effective_lr=None, advance=True, beta1=0.9, beta2=0.999):
+    """rtxn_optimizer_rate: the one-thread kernel that (advances and) reads the device int32 `step`, writes factor(t) to the
+    options' lr_factor, the bias-corrected rate(s) to effective_lr (and table_effective_lr) and moves the guard words."""
+    check(_lib.lib().rtxn_optimizer_rate(C.byref(opt), _ptr(step, torch.int32, "step"), int(bool(advance)), lr, table_lr, beta1, beta2,
+                                         _ptr(effective_lr, torch.float32, "effective_lr"),
+                                         _ptr(table_effective_lr, torch.float32, "table_effective_lr"), _stream()), "rtxn_optimizer_rate")
+
+
+def check_gradients(buffers, flag):
+    """rtxn_check_gradients: OR the device int32 `flag` (an options' guard) if any element of the fp32 / fp16 tensors in `buffers`
+    (at most 4; None and empty ones are skipped) is Inf or NaN."""
+    bufs = [b for b in buffers if b is not None and b.numel()]
+    arr = (_lib.GradBuffer * max(1, len(bufs)))()
+    for k, b in enumerate(bufs):
+        half = b.dtype == torch.float16
+        arr[k].data, arr[k].count, arr[k].is_fp16 = _ptr(b, torch.float16 if half else torch.float32, "buffers[%d]" % k), b.numel(), int(half)
+    check(_lib.lib().rtxn_check_gradients(arr, len(bufs), _ptr(flag, torch.int32, "flag"), _stream()), "rtxn_check_gradients")
+
+
+def adam_step_opt(master, params_fp16, grads, m, v, effective_lr, opt, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, loss_scale=1.0,
+                  zero_grads=False, weight_decay=True):
+    """rtxn_adam_step_opt: adam_step_captured under optimizer_options(...) -- the decay term uses lr * factor, the skip word is
+    honoured.  weight_decay=False: this call does not decay (the hash table)."""
+    half = grads.dtype == torch.float16
+    flags = (ADAM_GRADS_FP16 if half else 0) | (ADAM_ZERO_GRADS if zero_grads else 0) | (0 if weight_decay else ADAM_NO_WEIGHT_DECAY)
+    check(_lib.lib().rtxn_adam_step_opt(master.numel(), _ptr(master, torch.float32, "master"), _ptr(params_fp16, torch.float16, "params"),
+                                        _ptr(grads, torch.float16 if half else torch.float32, "grads"), flags,
+                                        _ptr(m, torch.float32, "m"), _ptr(v, torch.float32, "v"),
+                                        _ptr(effective_lr, torch.float32, "effective_lr"), lr, beta1, beta2, eps, loss_scale,
+                                        _byref(opt), _stream()), "rtxn_adam_step_opt")
+
+
+def adam_step_sparse_opt(master, params_fp16, grads, m, v, param_steps, opt, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, loss_scale=1.0,
+                         zero_grads=False, weight_decay=True):
+    """rtxn_adam_step_sparse_opt: adam_step_sparse under optimizer_options(...): lr * factor, the skip word, and the decay term
+    on the entries it updates (weight_decay=False: none)."""
+    half = grads.dtype == torch.float16
+    flags = (ADAM_GRADS_FP16 if half else 0) | (ADAM_ZERO_GRADS if zero_grads else 0) | (0 if weight_decay else ADAM_NO_WEIGHT_DECAY)
+    check(_lib.lib().rtxn_adam_step_sparse_opt(master.numel(), _ptr(master, torch.float32, "master"),
+                                               _ptr(params_fp16, torch.float16, "params"),
+                                               _ptr(grads, torch.float16 if half else torch.float32, "grads"), flags,
+                                               _ptr(m, torch.float32, "m"), _ptr(v, torch.float32, "v"),
+                                               _ptr(param_steps, torch.int32, "param_steps"), lr, beta1, beta2, eps, loss_scale,
+                                               _byref(opt), _stream()), "rtxn_adam_step_sparse_opt")
+
+
 def deterministic_shadow(n_params, device="cuda"):
     """A zeroed 64-bit fixed-point shadow for a gradient buffer of n_params floats (rtxn_deterministic_workspace_bytes)."""
     nbytes = _lib.lib().rtxn_deterministic_workspace_bytes(int(n_params))
@@ -1003,14 +1111,20 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None, jitter=None, loss=None, regularizer=None):
+def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
     jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
     loss: train_loss(...) -> rtxn_train_step_loss (with or without either);
     regularizer: train_regularizer(...) -> rtxn_train_step_reg (with or without any of the three): the write pass of the traversal
-    stores the segments' t_start / t_end into the regulariser's buffers."""
-    if regularizer is not None:
+    stores the segments' t_start / t_end into the regulariser's buffers;
+    optimizer: optimizer_options(...) -> rtxn_train_step_opt (with or without any of the four)."""
+    if optimizer is not None:
+        if regularizer is not None:
+            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
+        check(_lib.lib().rtxn_train_step_opt(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
+                                             C.byref(optimizer), _stream()), "rtxn_train_step_opt")
+    elif regularizer is not None:
         _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
         check(_lib.lib().rtxn_train_step_reg(C.byref(args), _byref(background), _jit(jitter), _byref(loss), C.byref(regularizer), _stream()),
               "rtxn_train_step_reg")

@@ -58,6 +58,12 @@ __attribute__((visibility("hidden"))) int loss_fixed_order(const float* pixels, 
 // (NULL, or weight 0 with no output: the entry point makes exactly the _loss call).  sample_type < 0: the entry point has none.
 int check_train_regularizer(const rtxn_train_regularizer* reg, int vr_mode, int sample_type, const char* who, bool* active);
 
+// The rules of the optimizer options (rtxn_optimizer_options, include/rtxn.h), host only, optimizer.hip: RTXN_ERR_INVALID with a
+// message naming the field, or RTXN_OK with *active = whether anything is switched on (NULL, or a CONSTANT schedule without
+// warm-up, no decay and no guard: the entry point makes exactly the call it made before the struct existed).  need_buffers:
+// an active struct must also carry lr_factor and, with skip_nonfinite, guard.
+int check_optimizer_options(const rtxn_optimizer_options* opt, const char* who, bool need_buffers, bool* active);
+
 // MurmurHash3's 32-bit finaliser: the integer hash behind RTXN_BG_RANDOM and the occupancy refresh's jitter (include/rtxn.h
 // states both uses bit for bit)
 __host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {

@@ -1,0 +1,418 @@
+// Optimizer options (include/rtxn.h, rtxn_optimizer_options): a learning-rate schedule evaluated on the device from
+// the step counter, decoupled weight decay and a guard that skips a step whose gradients are not finite.
+//   optimizer_rate_kernel     one thread: step counter, factor(t), the bias-corrected rate(s), the guard words
+//   check_gradients_kernel    Inf / NaN anywhere in up to four gradient buffers -> one flag
+//   adam_opt_kernel, adam_sparse_opt_kernel    train.hip's adam_kernel / adam_sparse_kernel reading the rate, the factor and the
+//                             skip word from device memory; siblings, so that the kernels a step without options launches are
+//                             the ones it always launched
+#include "common.h"
+#include "mlp_internal.h"
+#include "adam_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr double kPi = 3.14159265358979323846;
+
+// factor(t) of include/rtxn.h, the one restatement host and device share: everything in double, rounded to float once.  (The
+// file is built with -ffp-contract=off: no product below is fused on either side.)
+__host__ __device__ inline float schedule_factor(const rtxn_lr_schedule& s, int t) {
+  const double warm = s.warmup_steps > 0 ? fmin(1.0, (double)t / (double)s.warmup_steps) : 1.0;
+  double dec = 1.0;
+  if (s.kind != RTXN_LR_CONSTANT) {
+    const int past = t > s.decay_start ? t - s.decay_start : 0;
+    double x = (double)past / (double)s.decay_steps;
+    if (s.staircase) x = floor(x);
+    const double r = (double)s.ratio;
+    dec = s.kind == RTXN_LR_EXPONENTIAL ? pow(r, x) : r + (1.0 - r) * (1.0 + cos(kPi * fmin(x, 1.0))) / 2.0;
+  }
+  return (float)(warm * dec);
+}
+
+// t = *step (+ 1, stored, if advance); factor(t); the rates as advance_step_kernel (trainer.hip) forms them -- powers in double,
+// rounded once, sqrtf and the division correctly rounded -- with lr_t = lr factor in place of lr; then the guard: the flag the
+// check kernel ORed becomes this step's skip word, is cleared for the next step and counted.  One thread: every stepping path
+// launches this one kernel, so their rates are the same bits by construction.
+__global__ void optimizer_rate_kernel(int* step, int advance, rtxn_lr_schedule s, float lr, float table_lr, float beta1, float beta2,
+                                      float* lr_eff, float* table_lr_eff, float* factor_out, unsigned* guard) {
+  int t = *step;
+  if (advance) {
+    t += 1;
+    *step = t;
+  }
+  const float factor = schedule_factor(s, t);
+  *factor_out = factor;
+  const float p2 = (float)pow((double)beta2, (double)t), p1 = (float)pow((double)beta1, (double)t);
+  *lr_eff = (lr * factor) * sqrtf(1.0f - p2) / (1.0f - p1);
+  if (table_lr_eff) *table_lr_eff = (table_lr * factor) * sqrtf(1.0f - p2) / (1.0f - p1);
+  if (guard) {
+    const unsigned bad = guard[0] != 0u ? 1u : 0u;
+    guard[0] = 0u;
+    guard[1] += bad;
+    guard[2] = bad;
+  }
+}
+
+struct GradList {
+  const void* data[RTXN_MAX_GRAD_BUFFERS];
+  long count[RTXN_MAX_GRAD_BUFFERS];
+  int is_fp16[RTXN_MAX_GRAD_BUFFERS];
+};
+
+// exponent all ones: Inf or NaN, on the raw words (two halves per word)
+__device__ __forceinline__ bool nonfinite_f32(unsigned w) { return (w & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ bool nonfinite_h2(unsigned w) { return (w & 0x7c00u) == 0x7c00u || (w & 0x7c000000u) == 0x7c000000u; }
+
+// the body of a buffer: four independent 16-byte loads per lane and trip (one load in flight per lane left the kernel at half the
+// HBM rate on the 25 MB table gradient), then one by one
+template <typename Test>
+__device__ __forceinline__ bool any_word(const uint4* __restrict__ q, long body, long gid, long stride, Test nonfinite) {
+  bool bad = false;
+  long k = gid;
+  for (; k + 3 * stride < body; k += 4 * stride) {
+    const uint4 a = q[k], b = q[k + stride], c = q[k + 2 * stride], d = q[k + 3 * stride];
+    bad |= nonfinite(a.x) || nonfinite(a.y) || nonfinite(a.z) || nonfinite(a.w) || nonfinite(b.x) || nonfinite(b.y) || nonfinite(b.z) ||
+           nonfinite(b.w) || nonfinite(c.x) || nonfinite(c.y) || nonfinite(c.z) || nonfinite(c.w) || nonfinite(d.x) || nonfinite(d.y) ||
+           nonfinite(d.z) || nonfinite(d.w);
+  }
+  for (; k < body; k += stride) {
+    const uint4 w = q[k];
+    bad |= nonfinite(w.x) || nonfinite(w.y) || nonfinite(w.z) || nonfinite(w.w);
+  }
+  return bad;
+}
+
+// blockIdx.y: the buffer.  Elements in front of the first 16-byte boundary and behind the last whole 16 bytes go one by one, the
+// body as uint4 per lane; a wave that saw anything issues ONE atomic OR.  No lane leaves early: the ballot is over whole waves.
+__global__ __launch_bounds__(kThreads) void check_gradients_kernel(GradList L, unsigned* __restrict__ flag) {
+  const int b = blockIdx.y;
+  const long n = L.count[b];
+  const long gid = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
+  const uintptr_t base = (uintptr_t)L.data[b];
+  const int esize = L.is_fp16[b] ? 2 : 4, per16 = 16 / esize;
+  long head = (long)(((16u - (unsigned)(base & 15u)) & 15u) / (unsigned)esize);
+  if (head > n) head = n;
+  const long body = (n - head) / per16, tail = head + body * per16;
+  bool bad = false;
+  if (L.is_fp16[b]) {
+    const unsigned short* h = reinterpret_cast<const unsigned short*>(base);
+    for (long i = gid; i < head; i += stride) bad |= (h[i] & 0x7c00u) == 0x7c00u;
+    bad |= any_word(reinterpret_cast<const uint4*>(h + head), body, gid, stride, nonfinite_h2);
+    for (long i = tail + gid; i < n; i += stride) bad |= (h[i] & 0x7c00u) == 0x7c00u;
+  } else {
+    const unsigned* f = reinterpret_cast<const unsigned*>(base);
+    for (long i = gid; i < head; i += stride) bad |= nonfinite_f32(f[i]);
+    bad |= any_word(reinterpret_cast<const uint4*>(f + head), body, gid, stride, nonfinite_f32);
+    for (long i = tail + gid; i < n; i += stride) bad |= nonfinite_f32(f[i]);
+  }
+  const bool any = __ballot(bad) != 0;
+  if (any && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
+// adam_kernel (train.hip) under the options.  lr_dev: the bias-corrected rate; factor_dev: factor(t), for the decay term
+// lr_t weight_decay w with lr_t = lr factor (no bias correction); skip (may be NULL): this step's skip word -- set, nothing of
+// the state is stored, and ZERO still clears the gradient.
+template <bool HALF_GRADS, bool ZERO>
+__global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                            void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                            const float* __restrict__ lr_dev, const float* __restrict__ factor_dev, float lr,
+                                                            float weight_decay, const unsigned* __restrict__ skip, float beta1, float beta2,
+                                                            float eps, float inv_loss_scale) {
+  float* gf = static_cast<float*>(grads_v);
+  __half* gh = static_cast<__half*>(grads_v);
+  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
+  const long n4 = vec ? n / 4 : 0;
+  const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
+  if (skip && *skip != 0u) {
+    if (ZERO) {
+      for (long q = first; q < n4; q += stride) {
+        if (HALF_GRADS) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+        else reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      for (long i = 4 * n4 + first; i < n; i += stride) {
+        if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f;
+      }
+    }
+    return;
+  }
+  const float lr_eff = *lr_dev;
+  const float decay = (lr * *factor_dev) * weight_decay;          // w -= lr_t weight_decay w
+  auto one = [&](float g, float& mi, float& vi, float& w) {
+    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
+    if (decay != 0.0f) w = w - decay * w;
+  };
+  for (long q = first; q < n4; q += stride) {
+    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
+    float g[4];
+    if (HALF_GRADS) {
+      const half4v h = reinterpret_cast<const half4v*>(gh)[q];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
+      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+    } else {
+      const float4 f = reinterpret_cast<const float4*>(gf)[q];
+      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
+      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    one(g[0], m4.x, v4.x, w4.x);
+    one(g[1], m4.y, v4.y, w4.y);
+    one(g[2], m4.z, v4.z, w4.z);
+    one(g[3], m4.w, v4.w, w4.w);
+    reinterpret_cast<float4*>(master)[q] = w4;
+    reinterpret_cast<float4*>(m)[q] = m4;
+    reinterpret_cast<float4*>(v)[q] = v4;
+    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
+    reinterpret_cast<half4v*>(params)[q] = o;
+  }
+  for (long i = 4 * n4 + first; i < n; i += stride) {
+    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
+    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
+    float mi = m[i], vi = v[i], w = master[i];
+    one(g, mi, vi, w);
+    m[i] = mi;
+    v[i] = vi;
+    master[i] = w;
+    params[i] = __float2half(w);
+  }
+}
+
+// adam_sparse_kernel (train.hip) under the options: lr_t = lr factor in the entry's own bias correction, the decay term on the
+// entries it updates, and the skip word -- set, the update counts keep their bits with the rest of the state, and ZERO clears
+// every non-zero gradient word (also a NaN, which is not == 0).
+template <bool HALF_GRADS, bool ZERO>
+__global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                                   void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                                   unsigned* __restrict__ steps, const float* __restrict__ factor_dev, float lr,
+                                                                   float weight_decay, const unsigned* __restrict__ skip, float beta1,
+                                                                   float beta2, float eps, float inv_loss_scale, float log2_beta1,
+                                                                   float log2_beta2) {
+  float* gf = static_cast<float*>(grads_v);
+  __half* gh = static_cast<__half*>(grads_v);
+  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)steps | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
+  const long n4 = vec ? n / 4 : 0;
+  const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
+  if (skip && *skip != 0u) {
+    if (ZERO) {
+      for (long q = first; q < n4; q += stride) {
+        if (HALF_GRADS) {
+          const uint2 raw = reinterpret_cast<const uint2*>(gh)[q];
+          if ((raw.x | raw.y) != 0u) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+        } else {
+          const uint4 raw = reinterpret_cast<const uint4*>(gf)[q];
+          if ((raw.x | raw.y | raw.z | raw.w) != 0u) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      for (long i = 4 * n4 + first; i < n; i += stride) {
+        if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f;
+      }
+    }
+    return;
+  }
+  const float lr_t = lr * *factor_dev;
+  const float decay = lr_t * weight_decay;
+  auto one = [&](float g, float& mi, float& vi, float& w, unsigned& st) {
+    if (g == 0.0f) return;
+    st += 1u;
+    const float t = (float)st;
+    // beta^t = 2^(t log2 beta), as adam_sparse_kernel
+    const float lr_eff = lr_t * sqrtf(1.0f - __builtin_amdgcn_exp2f(t * log2_beta2)) / (1.0f - __builtin_amdgcn_exp2f(t * log2_beta1));
+    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
+    if (decay != 0.0f) w = w - decay * w;
+  };
+  for (long q = first; q < n4; q += stride) {
+    float g[4];
+    if (HALF_GRADS) {
+      const uint2 raw = reinterpret_cast<const uint2*>(gh)[q];
+      if (((raw.x | raw.y) & 0x7fff7fffu) == 0u) continue;
+      const half4v h = __builtin_bit_cast(half4v, raw);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
+      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+    } else {
+      const float4 f = reinterpret_cast<const float4*>(gf)[q];
+      if (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f && f.w == 0.0f) continue;
+      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
+      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
+    uint4 s4 = reinterpret_cast<uint4*>(steps)[q];
+    one(g[0], m4.x, v4.x, w4.x, s4.x);
+    one(g[1], m4.y, v4.y, w4.y, s4.y);
+    one(g[2], m4.z, v4.z, w4.z, s4.z);
+    one(g[3], m4.w, v4.w, w4.w, s4.w);
+    reinterpret_cast<float4*>(master)[q] = w4;
+    reinterpret_cast<float4*>(m)[q] = m4;
+    reinterpret_cast<float4*>(v)[q] = v4;
+    reinterpret_cast<uint4*>(steps)[q] = s4;
+    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
+    reinterpret_cast<half4v*>(params)[q] = o;
+  }
+  for (long i = 4 * n4 + first; i < n; i += stride) {
+    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
+    if (g == 0.0f) continue;
+    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
+    float mi = m[i], vi = v[i], w = master[i];
+    unsigned st = steps[i];
+    one(g, mi, vi, w, st);
+    m[i] = mi;
+    v[i] = vi;
+    master[i] = w;
+    steps[i] = st;
+    params[i] = __float2half(w);
+  }
+}
+
+int check_schedule(const rtxn_lr_schedule& s, const char* who) {
+  RTXN_REQUIRE(s.kind == RTXN_LR_CONSTANT || s.kind == RTXN_LR_EXPONENTIAL || s.kind == RTXN_LR_COSINE,
+               "%s: schedule.kind = %d (RTXN_LR_CONSTANT, _EXPONENTIAL or _COSINE)", who, s.kind);
+  RTXN_REQUIRE(s.ratio > 0.0f && s.ratio <= 1.0f, "%s: schedule.ratio = %g outside (0, 1]", who, (double)s.ratio);
+  RTXN_REQUIRE(s.kind == RTXN_LR_CONSTANT || s.decay_steps >= 1, "%s: schedule.decay_steps = %d (>= 1 unless the kind is RTXN_LR_CONSTANT)", who,
+               s.decay_steps);
+  RTXN_REQUIRE(s.warmup_steps >= 0, "%s: schedule.warmup_steps = %d < 0", who, s.warmup_steps);
+  RTXN_REQUIRE(s.decay_start >= 0, "%s: schedule.decay_start = %d < 0", who, s.decay_start);
+  RTXN_REQUIRE(!s.staircase || s.kind == RTXN_LR_EXPONENTIAL, "%s: schedule.staircase is set with kind %d: RTXN_LR_EXPONENTIAL only", who, s.kind);
+  return RTXN_OK;
+}
+
+}  // namespace
+
+int rtxn::check_optimizer_options(const rtxn_optimizer_options* opt, const char* who, bool need_buffers, bool* active) {
+  *active = false;
+  if (!opt) return RTXN_OK;
+  const int rc = check_schedule(opt->schedule, who);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(std::isfinite(opt->weight_decay) && opt->weight_decay >= 0.0f, "%s: opt->weight_decay = %g (finite, >= 0)", who,
+               (double)opt->weight_decay);
+  const bool scheduled = opt->schedule.kind != RTXN_LR_CONSTANT || opt->schedule.warmup_steps > 0;
+  if (!(scheduled || opt->weight_decay > 0.0f || opt->skip_nonfinite)) return RTXN_OK;
+  if (need_buffers) {
+    RTXN_REQUIRE(opt->lr_factor, "%s: opt->lr_factor is NULL: the schedule's factor is handed from the rate kernel to the optimizer through it", who);
+    RTXN_REQUIRE(!opt->skip_nonfinite || opt->guard, "%s: opt->guard is NULL with opt->skip_nonfinite set", who);
+  }
+  *active = true;
+  return RTXN_OK;
+}
+
+extern "C" float rtxn_lr_schedule_factor(const rtxn_lr_schedule* schedule, int step) {
+  if (!schedule || step < 1) {
+    rtxn::set_error("rtxn_lr_schedule_factor: schedule = %p, step = %d", (const void*)schedule, step);
+    return -1.0f;
+  }
+  if (check_schedule(*schedule, "rtxn_lr_schedule_factor") != RTXN_OK) return -1.0f;
+  return schedule_factor(*schedule, step);
+}
+
+extern "C" int rtxn_optimizer_options_check(const rtxn_optimizer_options* opt) {
+  bool active = false;
+  return rtxn::check_optimizer_options(opt, "rtxn_optimizer_options_check", false, &active);
+}
+
+extern "C" int rtxn_optimizer_rate(const rtxn_optimizer_options* opt, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
+                                   float* effective_lr, float* table_effective_lr, rtxn_stream_t stream) {
+  const char* who = "rtxn_optimizer_rate";
+  RTXN_REQUIRE(opt, "%s: NULL options", who);
+  bool active = false;
+  const int rc = rtxn::check_optimizer_options(opt, who, false, &active);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(opt->lr_factor && (!opt->skip_nonfinite || opt->guard), "%s: opt->lr_factor = %p, opt->guard = %p", who, (void*)opt->lr_factor,
+               (void*)opt->guard);
+  RTXN_REQUIRE(step && effective_lr, "%s: step = %p, effective_lr = %p", who, (void*)step, (void*)effective_lr);
+  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
+               (double)beta2);
+  RTXN_DEVICE_OR_FAIL();
+  optimizer_rate_kernel<<<1, 1, 0, rtxn::as_stream(stream)>>>(step, advance, opt->schedule, lr, table_lr, beta1, beta2, effective_lr,
+                                                              table_effective_lr, opt->lr_factor, opt->skip_nonfinite ? opt->guard : nullptr);
+  RTXN_LAUNCH_CHECK("optimizer_rate_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_check_gradients(const rtxn_grad_buffer* buffers, int n_buffers, unsigned* flag, rtxn_stream_t stream) {
+  const char* who = "rtxn_check_gradients";
+  RTXN_REQUIRE(n_buffers >= 0 && n_buffers <= RTXN_MAX_GRAD_BUFFERS && (buffers || n_buffers == 0), "%s: n_buffers = %d (0 .. %d), buffers = %p", who,
+               n_buffers, (int)RTXN_MAX_GRAD_BUFFERS, (const void*)buffers);
+  RTXN_REQUIRE(flag, "%s: NULL flag", who);
+  GradList L = {};
+  int k = 0;
+  long most = 0;                                                // 16-byte words of the largest buffer
+  for (int i = 0; i < n_buffers; ++i) {
+    const rtxn_grad_buffer& b = buffers[i];
+    RTXN_REQUIRE(b.count >= 0, "%s: buffers[%d].count = %ld", who, i, b.count);
+    if (b.count == 0) continue;
+    const int esize = b.is_fp16 ? 2 : 4;
+    RTXN_REQUIRE(b.data && ((uintptr_t)b.data & (uintptr_t)(esize - 1)) == 0, "%s: buffers[%d].data = %p (NULL, or not aligned to its element)", who,
+                 i, b.data);
+    L.data[k] = b.data;
+    L.count[k] = b.count;
+    L.is_fp16[k] = b.is_fp16 != 0;
+    const long words = (b.count * esize + 15) / 16;
+    most = words > most ? words : most;
+    ++k;
+  }
+  RTXN_DEVICE_OR_FAIL();
+  if (k == 0) return RTXN_OK;
+  const long blocks = (most + 4 * kThreads - 1) / (4 * kThreads);          // four 16-byte words per lane and trip
+  const dim3 grid((unsigned)(blocks > 2048 ? 2048 : blocks), (unsigned)k);
+  check_gradients_kernel<<<grid, kThreads, 0, rtxn::as_stream(stream)>>>(L, flag);
+  RTXN_LAUNCH_CHECK("check_gradients_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_adam_step_opt(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                  const float* effective_lr, float lr, float beta1, float beta2, float eps, float loss_scale,
+                                  const rtxn_optimizer_options* opt, rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_opt";
+  bool active = false;
+  const int rc = rtxn::check_optimizer_options(opt, who, true, &active);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  if (!active) return rtxn_adam_step_captured(n, master, params_fp16, grads, grad_flags & 3, m, v, effective_lr, beta1, beta2, eps, loss_scale, stream);
+  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
+  RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v, "%s: NULL buffer", who);
+  const long work = (n + 3) / 4;
+  const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
+  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  static decltype(&adam_opt_kernel<false, false>) const table[2][2] = {{adam_opt_kernel<false, false>, adam_opt_kernel<false, true>},   // [HALF_GRADS][ZERO]
+                                                                       {adam_opt_kernel<true, false>, adam_opt_kernel<true, true>}};
+  table[half][zero]<<<blocks, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, effective_lr,
+                                                                      opt->lr_factor, lr, wd, opt->skip_nonfinite ? opt->guard + 2 : nullptr, beta1,
+                                                                      beta2, eps, 1.0f / loss_scale);
+  RTXN_LAUNCH_CHECK("adam_opt_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_adam_step_sparse_opt(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                         unsigned* param_steps, float lr, float beta1, float beta2, float eps, float loss_scale,
+                                         const rtxn_optimizer_options* opt, rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_sparse_opt";
+  bool active = false;
+  const int rc = rtxn::check_optimizer_options(opt, who, true, &active);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  if (!active) return rtxn_adam_step_sparse(n, master, params_fp16, grads, grad_flags & 3, m, v, param_steps, lr, beta1, beta2, eps, loss_scale, stream);
+  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+  RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
+  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
+               (double)beta2);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps, "%s: NULL buffer", who);
+  const long blocks = (n / 4 + kThreads - 1) / kThreads;
+  const unsigned gridx = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
+  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
+  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  static decltype(&adam_sparse_opt_kernel<false, false>) const table[2][2] = {
+      {adam_sparse_opt_kernel<false, false>, adam_sparse_opt_kernel<false, true>},   // [HALF_GRADS][ZERO]
+      {adam_sparse_opt_kernel<true, false>, adam_sparse_opt_kernel<true, true>}};
+  table[half][zero]<<<gridx, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, param_steps,
+                                                                     opt->lr_factor, lr, wd, opt->skip_nonfinite ? opt->guard + 2 : nullptr, beta1,
+                                                                     beta2, eps, 1.0f / loss_scale, l2b1, l2b2);
+  RTXN_LAUNCH_CHECK("adam_sparse_opt_kernel");
+  return RTXN_OK;
+}

@@ -25,6 +25,7 @@
 //   l2_loss_kernel, adam_kernel
 #include "mlp_internal.h"
 #include "hashgrid_internal.h"
+#include "adam_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2613,12 +2614,7 @@ __global__ __launch_bounds__(kThreads) void l2_loss_kernel(const float* __restri
   }
 }
 
-// One Adam update (tcnn "Adam": no weight decay, bias correction folded into lr_eff on the host / lr_dev).
-__device__ __forceinline__ void adam_one(float g, float& mi, float& vi, float& w, float lr_eff, float beta1, float beta2, float eps) {
-  mi = beta1 * mi + (1.0f - beta1) * g;
-  vi = beta2 * vi + (1.0f - beta2) * g * g;
-  w = w - lr_eff * mi / (sqrtf(vi) + eps);
-}
+// adam_one: adam_internal.h
 // HBM-bound (22-28 B per parameter): four parameters per thread, 16-byte accesses
 // ZERO: the gradient is cleared as it is consumed (the next step accumulates into zeros without a separate fill pass)
 template <bool HALF_GRADS, bool ZERO>

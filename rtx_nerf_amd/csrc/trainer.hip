@@ -23,8 +23,59 @@ __global__ void advance_step_kernel(int* step, float lr, float beta1, float beta
 
 }  // namespace
 
+// the table parameters whose gradient is in the fp32 buffer: those before the first hashed level, or all of them
+static long fp32_gradient_params(const rtxn_train_batch& b) {
+  const long n = rtxn_hashgrid_n_params(b.grid);
+  if (!b.dtable_hashed_half) return n;
+  for (int l = 0; rtxn_hashgrid_level_offset(b.grid, l) < n; ++l)
+    if (rtxn_hashgrid_level_is_hashed(b.grid, l) == 1) return rtxn_hashgrid_level_offset(b.grid, l);
+  return n;
+}
+
+// optimizer->step under ACTIVE options (include/rtxn.h, rtxn_optimizer_options): the gradients are complete -- one pass looks
+// for Inf / NaN in every buffer the optimizer is about to consume, the rate kernel advances the step, evaluates the schedule and
+// turns the flag into the skip word, and the _opt Adam kernels read rate, factor and skip word from the device.  Weight decay:
+// the MLP only.
+static int optimizer_step_opt(const rtxn_train_step_args* a, const rtxn_optimizer_options* opt, rtxn_stream_t stream) {
+  const rtxn_train_batch& b = a->batch;
+  const rtxn_train_state& o = a->opt;
+  const bool hash = b.grid != nullptr;
+  const long n_mlp = rtxn_mlp_n_params(b.mlp), n = hash ? rtxn_hashgrid_n_params(b.grid) : 0, lo = hash ? fp32_gradient_params(b) : 0;
+  int rc;
+  if (opt->skip_nonfinite) {
+    const rtxn_grad_buffer bufs[3] = {{b.dparams, n_mlp, 0}, {b.dtable, lo, 0}, {b.dtable_hashed_half, n - lo, 1}};
+    rc = rtxn_check_gradients(bufs, 3, opt->guard, stream);
+    if (rc != RTXN_OK) return rc;
+  }
+  rc = rtxn_optimizer_rate(opt, o.step, 1, o.lr, o.table_lr, o.beta1, o.beta2, o.effective_lr, nullptr, stream);
+  if (rc != RTXN_OK) return rc;
+  const float ls = b.loss_scale * o.loss_scale_divisor;
+  rc = rtxn_adam_step_opt(n_mlp, o.mlp_master, o.mlp_params_fp16, b.dparams, RTXN_ADAM_ZERO_GRADS, o.mlp_m, o.mlp_v, o.effective_lr, o.lr, o.beta1,
+                          o.beta2, o.eps, ls, opt, stream);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn_mlp_set_params_training(const_cast<rtxn_mlp*>(b.mlp), o.mlp_params_fp16, stream);
+  if (rc != RTXN_OK) return rc;
+  if (hash) {
+    __half* p16 = static_cast<__half*>(o.table_params_fp16);
+    const int flags = RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY;
+    if (lo > 0) {
+      rc = rtxn_adam_step_sparse_opt(lo, o.table_master, p16, b.dtable, flags, o.table_m, o.table_v, o.table_steps, o.table_lr, o.beta1, o.beta2,
+                                     o.table_eps, ls, opt, stream);
+      if (rc != RTXN_OK) return rc;
+    }
+    if (lo < n) {
+      rc = rtxn_adam_step_sparse_opt(n - lo, o.table_master + lo, p16 + lo, b.dtable_hashed_half, flags | RTXN_ADAM_GRADS_FP16, o.table_m + lo,
+                                     o.table_v + lo, o.table_steps + lo, o.table_lr, o.beta1, o.beta2, o.table_eps, ls, opt, stream);
+      if (rc != RTXN_OK) return rc;
+    }
+  }
+  return RTXN_OK;
+}
+
+// opt: ACTIVE optimizer options (rtxn_train_step_opt, optimizer.hip) or NULL
 static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
+                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                           rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
@@ -75,6 +126,7 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
      : jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
   if (rc != RTXN_OK) return rc;
 
+  if (opt) return optimizer_step_opt(a, opt, stream);
   // ---- optimizer->step (main.cu:787): every gradient is cleared as it is consumed ----
   advance_step_kernel<<<1, 1, 0, rtxn::as_stream(stream)>>>(o.step, o.lr, o.beta1, o.beta2, o.effective_lr);
   RTXN_LAUNCH_CHECK("advance_step_kernel");
@@ -85,11 +137,7 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   rc = rtxn_mlp_set_params_training(const_cast<rtxn_mlp*>(b.mlp), o.mlp_params_fp16, stream);
   if (rc != RTXN_OK) return rc;
   if (hash) {
-    const long n = rtxn_hashgrid_n_params(b.grid);
-    long lo = n;                                              // parameters before the first hashed level
-    for (int l = 0; rtxn_hashgrid_level_offset(b.grid, l) < n; ++l)
-      if (rtxn_hashgrid_level_is_hashed(b.grid, l) == 1) { lo = rtxn_hashgrid_level_offset(b.grid, l); break; }
-    if (!b.dtable_hashed_half) lo = n;                        // everything in the fp32 gradient
+    const long n = rtxn_hashgrid_n_params(b.grid), lo = fp32_gradient_params(b);
     __half* p16 = static_cast<__half*>(o.table_params_fp16);
     if (lo > 0) {
       rc = rtxn_adam_step_sparse(lo, o.table_master, p16, b.dtable, RTXN_ADAM_ZERO_GRADS, o.table_m, o.table_v, o.table_steps, o.table_lr, o.beta1,
@@ -105,18 +153,18 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   return RTXN_OK;
 }
 
-extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, stream); }
+extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, stream); }
 
 extern "C" int rtxn_train_step_ex(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step_ex: NULL arguments");
   bool active = false;
   const int rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_ex", &active);
   if (rc != RTXN_OK) return rc;
-  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, stream);
+  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
   // RANDOM without a counter of its own: the optimizer's, read by the compositor before advance_step_kernel increments it
   rtxn_train_background own = *bg;
   if (own.mode == RTXN_BG_RANDOM && !own.step) own.step = a->opt.step;
-  return train_step_impl(a, &own, nullptr, nullptr, nullptr, stream);
+  return train_step_impl(a, &own, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the sampler's jitter; a NULL jitter->step is the optimizer's counter too, by the same rule
@@ -138,7 +186,7 @@ extern "C" int rtxn_train_step_jitter(const rtxn_train_step_args* a, const rtxn_
     own_jitter = *jitter;
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, nullptr, stream);
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the loss of rtxn_train_loss (rtxn_train_gradients_loss); NULL, or plain L2: rtxn_train_step_jitter
@@ -162,26 +210,26 @@ extern "C" int rtxn_train_step_loss(const rtxn_train_step_args* a, const rtxn_tr
     own_jitter = *jitter;
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, nullptr, stream);
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the distortion regulariser (rtxn_train_gradients_reg): the write pass of the traversal stores t_start / t_end
 // into the struct's buffers; NULL, or weight 0 without outputs: rtxn_train_step_loss
-extern "C" int rtxn_train_step_reg(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                                   const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
-  RTXN_REQUIRE(a, "rtxn_train_step_reg: NULL arguments");
-  int rc = rtxn::check_sample_jitter("rtxn_train_step_reg", a->batch.sample_type, jitter, a->batch.vr_mode);
+static int train_step_reg(const char* who, const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                          const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt, rtxn_stream_t stream) {
+  RTXN_REQUIRE(a, "%s: NULL arguments", who);
+  int rc = rtxn::check_sample_jitter(who, a->batch.sample_type, jitter, a->batch.vr_mode);
   if (rc != RTXN_OK) return rc;
   bool active = false, loss_active = false, reg_active = false;
-  rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_reg", &active);
+  rc = rtxn::check_train_background(bg, a->batch.vr_mode, who, &active);
   if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, a->batch.vr_mode, "rtxn_train_step_reg", &loss_active);
+  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, a->batch.vr_mode, who, &loss_active);
   if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_regularizer(reg, a->batch.vr_mode, a->batch.sample_type, "rtxn_train_step_reg", &reg_active);
+  rc = rtxn::check_train_regularizer(reg, a->batch.vr_mode, a->batch.sample_type, who, &reg_active);
   if (rc != RTXN_OK) return rc;
   if (reg_active)
-    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "rtxn_train_step_reg: trace.mode = %d: the regulariser's t_start / t_end are written by the "
-                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", a->trace.mode);
+    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the regulariser's t_start / t_end are written by the "
+                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
   rtxn_train_background own_bg;
   if (active) {
     own_bg = *bg;
@@ -193,5 +241,21 @@ extern "C" int rtxn_train_step_reg(const rtxn_train_step_args* a, const rtxn_tra
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
   return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, reg_active ? reg : nullptr,
-                         stream);
+                         opt, stream);
+}
+
+extern "C" int rtxn_train_step_reg(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                   const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
+  return train_step_reg("rtxn_train_step_reg", a, bg, jitter, loss, reg, nullptr, stream);
+}
+
+// ... and under the optimizer options (optimizer.hip); NULL, or nothing switched on: rtxn_train_step_reg
+extern "C" int rtxn_train_step_opt(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                   const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                                   rtxn_stream_t stream) {
+  bool opt_active = false;
+  const int rc = rtxn::check_optimizer_options(opt, "rtxn_train_step_opt", true, &opt_active);
+  if (rc != RTXN_OK) return rc;
+  if (!opt_active) return rtxn_train_step_reg(a, bg, jitter, loss, reg, stream);
+  return train_step_reg("rtxn_train_step_opt", a, bg, jitter, loss, reg, opt, stream);
 }

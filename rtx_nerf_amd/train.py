@@ -59,8 +59,17 @@ class Trainer:
                  hashgrid=None, n_dir_freqs=4, batch_rays=4096, max_segments=None, lr=1e-3, loss_scale=128.0,
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
                  target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0,
-                 distortion_weight=0.0):
-        """distortion_weight: lambda_d of mip-NeRF 360's distortion regulariser (librtxn: rtxn_volrender_reg_train /
+                 distortion_weight=0.0, lr_schedule=None, weight_decay=0.0, skip_nonfinite=False):
+        """lr_schedule: None, or api.lr_schedule(...) / a dict of its arguments / a preset name ("nerf": x0.1 per 250k steps;
+        "instant_ngp": x0.33 every 10k steps after 20k): the factor on lr and on the table's 10 lr, evaluated on the device from the
+        step counter (librtxn: rtxn_optimizer_options, rtxn_optimizer_rate); current_lr() is its host restatement.
+        weight_decay: AdamW's decoupled decay w -= lr_t weight_decay w, on the MLP only.  skip_nonfinite: a step whose gradients hold
+        an Inf or a NaN leaves weights, moments and update counts as they are, clears the gradients and counts one up in
+        skipped_steps (a device tensor, never read by the stepping methods); step_count advances all the same, so Adam's bias
+        correction counts attempted steps.  The loss scale is not adapted: a growing skipped_steps says to lower it.  All three at
+        their defaults (or a constant schedule without warm-up): nothing is allocated and every call is the one made without the
+        arguments.  Configuration, not state, as loss is; checkpoints hold only the skipped count.
+        distortion_weight: lambda_d of mip-NeRF 360's distortion regulariser (librtxn: rtxn_volrender_reg_train /
         rtxn_train_gradients_reg / rtxn_train_step_reg), in world distances along the ray (a lambda quoted for distances normalised to
         [0, 1] is divided by the cube's diagonal 2 sqrt(3)); mode "nerf" and the fused compositor only.  Its gradient is ~1e-7 per
         sample at lambda_d = 0.01, loss_scale 128 and 4096 rays, at the edge of the fp16 radiance gradients: raise loss_scale with it.
@@ -96,6 +105,7 @@ class Trainer:
         self._init_jitter(sample_jitter, jitter_seed)
         self._init_loss(loss, loss_param, opacity_weight)
         self._init_regularizer(distortion_weight)
+        self._init_optimizer(lr_schedule, weight_decay, skip_nonfinite)
         self.image_set = None      # attach_images(): batches drawn on the device
         self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
         self._draw_step = None
@@ -138,6 +148,16 @@ class Trainer:
         self.adam_v = torch.zeros_like(self.master)
         self.dparams = torch.zeros_like(self.master)
         self.net.set_params(self.params)
+        # optimizer options: the schedule's factor, the guard words, and the eager step's device counter and rates (the captured
+        # and the one-call step have their own counters); nothing without options
+        self._opt = self._opt_guard = self._opt_step = self._opt_lr = None
+        if self._opt_active:
+            self._opt_factor = torch.ones(1, device=d)
+            self._opt_guard = torch.zeros(4, dtype=torch.int32, device=d)
+            self._opt = api.optimizer_options(self._schedule, self.weight_decay, self.skip_nonfinite, self._opt_factor, self._opt_guard)
+            self._opt_step = torch.zeros(1, dtype=torch.int32, device=d)
+            self._opt_step_host = 0
+            self._opt_lr = torch.zeros(2, device=d)
         # 64-wide models (configs[2]): forward without saved activations + ONE fused backward kernel that recomputes them and
         # keeps every weight gradient on the chip (librtxn: mlp_bwd_fused64_kernel).  RTXN_TRAIN_RECOMPUTE=0 selects the
         # three-kernel path (saved activations, dgrad chain, weight-gradient GEMM) for A/B runs.
@@ -283,6 +303,31 @@ class Trainer:
             raise ValueError("Trainer: distortion_weight > 0 needs the fused training compositor (RTXN_TRAIN_FUSE_COMPOSITOR=0 selects "
                              "the three-launch compositor, which has no regulariser)")
         self.distortion_weight = lam
+
+    def _init_optimizer(self, lr_schedule, weight_decay, skip_nonfinite):
+        """the library's own rules (rtxn_optimizer_options_check), before anything is allocated"""
+        try:
+            self._schedule = api.lr_schedule(lr_schedule) if lr_schedule is not None else None
+            self.weight_decay, self.skip_nonfinite = float(weight_decay), bool(skip_nonfinite)
+            api.optimizer_options_check(api.optimizer_options(self._schedule, self.weight_decay, self.skip_nonfinite))
+        except (api._lib.RtxnError, TypeError, ValueError) as e:
+            raise ValueError(f"Trainer: lr_schedule = {lr_schedule!r}, weight_decay = {weight_decay!r}: {e}") from None
+        sch = self._schedule
+        scheduled = sch is not None and (sch.kind != api.LR_CONSTANT or sch.warmup_steps > 0)
+        self._opt_active = scheduled or self.weight_decay > 0.0 or self.skip_nonfinite
+        if not scheduled:
+            self._schedule = None
+
+    @property
+    def skipped_steps(self):
+        """device int32[1]: steps the non-finite guard skipped so far (None without optimizer options)"""
+        return None if self._opt_guard is None else self._opt_guard[1:2]
+
+    def current_lr(self):
+        """The MLP's scheduled rate lr_t of the NEXT update (the table's is 10 x): lr times the host restatement of the schedule
+        (rtxn_lr_schedule_factor) at step_count + 1, without Adam's bias correction."""
+        f = 1.0 if self._schedule is None else api.lr_schedule_factor(self._schedule, self.step_count + 1)
+        return float(np.float32(self.lr) * np.float32(f))
 
     def _reg_t(self, st=None):
         """the write pass's t_start / t_end arguments: the regulariser's buffers (of buffer set st), or nothing"""
@@ -619,6 +664,15 @@ class Trainer:
 
     def apply_gradients(self, grad_divisor=1.0):
         """optimizer->step (main.cu:787) on self.dparams / self.dtable; grad_divisor: ranks summed into them."""
+        if self._opt is not None:              # the rate comes from the device kernel the other two paths launch as well
+            if self._opt_step_host != self.step_count:
+                self._opt_step.fill_(self.step_count)
+            with _Stage(self, "adam"):
+                self._apply_opt(self._opt_step, self._opt_lr, self.loss_scale * grad_divisor)
+            self.step_count += 1
+            self._opt_step_host = self.step_count
+            self._grads_clean = True           # cleared as they were consumed, skipped step or not
+            return
         self.step_count += 1
         with _Stage(self, "adam"):
             api.adam_step(self.master, self.params, self.dparams, self.adam_m, self.adam_v, self.step_count, lr=self.lr,
@@ -637,6 +691,32 @@ class Trainer:
                                              self.table_v[lo:], self.step_count, **kw)
                 else:
                     api.adam_step(self.table_master, self.table, self.dtable, self.table_m, self.table_v, self.step_count, **kw)
+
+    def _apply_opt(self, step, rates, ls):
+        """The optimizer under rtxn_optimizer_options, as rtxn_train_step_opt sequences it: the gradients are complete (data
+        parallel: summed), so one pass looks for Inf / NaN, the rate kernel advances the device int32 `step`, writes the factor,
+        the two bias-corrected rates (`rates`: MLP, dense table) and the skip word, and the _opt Adam kernels read them.  Every
+        gradient is cleared as it is consumed.  Capturable; nothing is read on the host."""
+        hash_ = self.encoding == "hash"
+        lo = self.hashed_lo if hash_ else 0
+        parts = []
+        if hash_:
+            parts = [(slice(0, lo), self.dtable[:lo]), (slice(lo, None), self.dtable_h)] if self.hash_fp16 else [(slice(None), self.dtable)]
+        if self.skip_nonfinite:
+            api.check_gradients([self.dparams] + [g for _, g in parts], self._opt_guard)
+        api.optimizer_rate(self._opt, step, rates[0:1], lr=self.lr, table_lr=self.lr * 10.0, table_effective_lr=rates[1:2])
+        api.adam_step_opt(self.master, self.params, self.dparams, self.adam_m, self.adam_v, rates[0:1], self._opt, lr=self.lr, loss_scale=ls,
+                          zero_grads=True)
+        self.net.set_params_training(self.params)
+        for sl, g in parts:
+            if not g.numel():
+                continue
+            if self.table_adam_sparse:
+                api.adam_step_sparse_opt(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], self.table_steps[sl],
+                                         self._opt, lr=self.lr * 10.0, eps=1e-15, loss_scale=ls, zero_grads=True, weight_decay=False)
+            else:
+                api.adam_step_opt(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], rates[1:2], self._opt,
+                                  lr=self.lr * 10.0, eps=1e-15, loss_scale=ls, zero_grads=True, weight_decay=False)
 
     def _table_adam_sparse(self, **kw):
         """rtxn_adam_step_sparse over the table: the densely stored levels from the fp32 gradient, the hashed ones from the fp16 one"""
@@ -758,7 +838,9 @@ class Trainer:
         checkpoint saved between replays resumes one batch further on: the pending batch is skipped, none is repeated."""
         arrs = {k: v.detach().cpu().numpy() for k, v in self.state_arrays().items()}
         cfg = self.net.cfg
-        header = {"step": self.step_count, "draw_count": self.draw_count, "encoding": self.encoding, "grid_res": self.R, "mode": self.mode,
+        header = {"step": self.step_count, "draw_count": self.draw_count,
+                  "skipped_steps": 0 if self._opt_guard is None else int(self._opt_guard[1].item()),
+                  "encoding": self.encoding, "grid_res": self.R, "mode": self.mode,
                   "mlp": {f: getattr(cfg, f) for f, _ in cfg._fields_},
                   "hashgrid": None if self.hg is None else {**{f: getattr(self.hg.cfg, f) for f, _ in self.hg.cfg._fields_},
                                                             "n_dir_freqs": self.hg.n_dir_freqs},
@@ -805,6 +887,9 @@ class Trainer:
         self.draw_count = int(header.get("draw_count", 0))       # files from before device batches: the sequence starts over
         if self._draw_step is not None:
             self._draw_step.fill_(self.draw_count)
+        if self._opt_guard is not None:                          # the schedule itself has no state: it continues from `step`
+            self._opt_guard.zero_()
+            self._opt_guard[1] = int(header.get("skipped_steps", 0))
         self.net.set_params(self.params)
         return header
 
@@ -906,6 +991,7 @@ class Trainer:
         state = (self.master.clone(), self.params.clone(), self.adam_m.clone(), self.adam_v.clone())
         tstate = (self.table_master.clone(), self.table.clone(), self.table_m.clone(), self.table_v.clone(),
                   self.table_steps.clone()) if self.encoding == "hash" else None
+        guard = None if self._opt_guard is None else self._opt_guard.clone()
         clear_grads = self._clear_grads
         with torch.cuda.stream(side):
             clear_grads()
@@ -923,6 +1009,8 @@ class Trainer:
         if tstate is not None:
             for dst, src in zip((self.table_master, self.table, self.table_m, self.table_v, self.table_steps), tstate):
                 dst.copy_(src)
+        if guard is not None:
+            self._opt_guard.copy_(guard)            # a warm-up pass over non-finite inputs is not a skipped step
         self.net.set_params_training(self.params)
         self._g_step.fill_(self.step_count)
         self._g_step_host = self.step_count     # host mirror of the device counter (see _sync_device_step)
@@ -1060,7 +1148,7 @@ class Trainer:
             api.draw_batch_launch(self._entry_draw)
             self._draw_step.add_(1)
             self.draw_count += 1
-        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg)
+        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -1116,6 +1204,11 @@ class Trainer:
                                   self.dtable_h if self.hash_fp16 else None, live_ws=self.live_ws, jitter=self._g_jit)
 
     def _captured_apply(self, grad_divisor):
+        if self._opt is not None:
+            # the rate kernel advances the counter's low word itself and evaluates schedule and bias correction from it: no table
+            # lookup, so the schedule keeps running past _LR_TABLE steps
+            self._apply_opt(self._g_step.view(torch.int32)[:1], self._g_lr[0], self.loss_scale * grad_divisor)
+            return
         self._g_step.add_(1)
         torch.clamp(self._g_step, max=self._LR_TABLE - 1, out=self._g_idx)
         torch.index_select(self._g_lr_table, 0, self._g_idx, out=self._g_lr)
