@@ -12,14 +12,14 @@ all: rtx_nerf_amd/librtxn.so oracle examples/render_host examples/render_host_mg
 # weight-gradient accumulators in AGPRs by hand (asm "+a"); left to its heuristic, hipcc put the destination of EVERY MFMA of
 # that kernel in AGPRs and copied each chain accumulator back for the fp16 conversion (816 v_accvgpr_read per tile).
 build/train.o: EXTRA := -mllvm -amdgpu-mfma-vgpr-form
-build/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/mlp_internal.h $(CSRC)/hashgrid_internal.h $(CSRC)/terminate_internal.h $(CSRC)/ray_internal.h $(CSRC)/background_internal.h $(CSRC)/loss_internal.h $(CSRC)/reg_internal.h $(CSRC)/adam_internal.h include/rtxn.h
+build/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/rtxn.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c $< -o $@
 
 # ISA text of the files that hold asm MFMAs, and the static check that no compiler-generated instruction reads an asm MFMA's
 # result inside its wait states (tools/check_asm_mfma_reads.py; the round-3 hoisted-conversion bug)
 build/train.s: EXTRA := -mllvm -amdgpu-mfma-vgpr-form
-build/%.s: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/mlp_internal.h $(CSRC)/hashgrid_internal.h $(CSRC)/terminate_internal.h $(CSRC)/ray_internal.h $(CSRC)/background_internal.h $(CSRC)/loss_internal.h $(CSRC)/reg_internal.h $(CSRC)/adam_internal.h include/rtxn.h
+build/%.s: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/rtxn.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -S --cuda-device-only $< -o $@
 check-isa: build/train.s build/mlp.s build/hashmlp.s

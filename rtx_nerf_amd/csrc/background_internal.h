@@ -1,5 +1,5 @@
 // A training ray's background and the target it is fitted to (include/rtxn.h, rtxn_volrender_l2_train_ex), shared
-// by the training compositor (volrender.hip) and the fixed-order loss sum (loss.hip) so that the loss is formed from the
+// by the training compositors (volrender.hip, composite_train.hip) and the fixed-order loss sum (loss.hip) so that the loss is formed from the
 // target the compositor fitted, bit for bit.  Internal to librtxn.so.  The struct stays in an anonymous namespace: the
 // compositor's kernels take it by value and their symbols, pinned by tests/test_compositor_isa.py, carry its name.
 #pragma once
@@ -14,6 +14,21 @@ struct BgArgs {
   const int* step;       // RANDOM: device int hashed with the seed, or NULL (0)
   int target_channels;   // 3 | 4 (straight RGBA, composited over the ray's background)
 };
+
+// the kernels' argument from the caller's struct; bg: an ACTIVE background, or NULL for plain 3-channel targets
+inline BgArgs make_bg_args(const rtxn_train_background* bg) {
+  BgArgs a{};
+  a.mode = RTXN_BG_NONE;
+  a.target_channels = 3;
+  if (bg) {
+    a.mode = bg->mode;
+    for (int c = 0; c < 3; ++c) a.color[c] = bg->color[c];
+    a.seed = bg->seed;
+    a.step = bg->step;
+    a.target_channels = bg->target_channels;
+  }
+  return a;
+}
 
 // the ray's background and its (composited) target: wave-uniform values
 __device__ __forceinline__ void ray_background(const BgArgs& bg, const float* __restrict__ target, int ray, float (&b)[3],

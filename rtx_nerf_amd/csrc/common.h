@@ -42,18 +42,19 @@ __attribute__((visibility("hidden"))) int l2_loss_fixed_order(const float* pixel
 // RTXN_OK with *active = whether a background is composited at all.
 int check_train_background(const rtxn_train_background* bg, int vr_mode, const char* who, bool* active);
 
-// The rules of a training loss (rtxn_train_loss, include/rtxn.h), host only, composite_loss.hip: RTXN_ERR_INVALID with a
-// message naming the field, or RTXN_OK with *active = whether the loss kernels run at all (NULL, or L2 with no alpha term and
+// The rules of a training loss (rtxn_train_loss, include/rtxn.h), host only, composite_train.hip: RTXN_ERR_INVALID with
+// a message naming the field, or RTXN_OK with *active = whether the loss kernels run at all (NULL, or L2 with no alpha term and
 // no opacity output: the entry point makes exactly the call it made before the struct existed).  target_channels: of the
 // batch's targets (3 without an active background); vr_mode < 0: the entry point has no compositor (rtxn_loss).
 int check_train_loss(const rtxn_train_loss* loss, int target_channels, int vr_mode, const char* who, bool* active);
 // ... and its scalar in deterministic mode (loss.hip, beside l2_loss_fixed_order, same grouping and order): the sum of
-// include/rtxn.h from pixels, targets and, with opacity_weight > 0, loss->opacity.  bg: an ACTIVE background or NULL.
+// include/rtxn.h from pixels, targets and, with opacity_weight > 0, loss->opacity; with reg, the regulariser's share is added
+// per ray from reg->distortion.  bg, loss, reg: an ACTIVE struct or NULL (loss: L2).
 __attribute__((visibility("hidden"))) int loss_fixed_order(const float* pixels, const float* target, int n_rays,
                                                            const rtxn_train_background* bg, const rtxn_train_loss* loss,
-                                                           float* loss_sum, hipStream_t stream);
+                                                           const rtxn_train_regularizer* reg, float* loss_sum, hipStream_t stream);
 
-// The rules of the distortion regulariser (rtxn_train_regularizer, include/rtxn.h), host only, composite_reg.hip:
+// The rules of the distortion regulariser (rtxn_train_regularizer, include/rtxn.h), host only, composite_train.hip:
 // RTXN_ERR_INVALID with a message naming the field, or RTXN_OK with *active = whether the regularised compositor runs at all
 // (NULL, or weight 0 with no output: the entry point makes exactly the _loss call).  sample_type < 0: the entry point has none.
 int check_train_regularizer(const rtxn_train_regularizer* reg, int vr_mode, int sample_type, const char* who, bool* active);

@@ -17,6 +17,7 @@
 #include "background_internal.h"
 #include "common.h"
 #include "loss_internal.h"
+#include "reg_internal.h"
 
 namespace {
 
@@ -52,11 +53,14 @@ __global__ __launch_bounds__(kLossThreads) void l2_loss_fixed_order_kernel(const
   if (threadIdx.x == 0) *loss_sum = red[0];
 }
 
-// The same sum for the losses of rtxn_train_loss (composite_loss.hip's kernels; include/rtxn.h): the per-ray term is
+// The same sum for the losses of rtxn_train_loss (composite_train.hip's kernels; include/rtxn.h): the per-ray term is
 // loss_internal.h's ray_loss_term, the function the compositor evaluates, on the pixels it stored and -- with lambda > 0 -- on
-// the opacities it stored; grouping and order are l2_loss_fixed_order_kernel's.
+// the opacities it stored; grouping and order are l2_loss_fixed_order_kernel's.  REG: the regulariser's share is added per ray
+// from the L_r the compositor stored, by the expression the compositor itself adds (reg_internal.h).
+template <bool REG>
 __global__ __launch_bounds__(kLossThreads) void loss_fixed_order_kernel(const float* __restrict__ pixels, const float* __restrict__ target,
-                                                                        int n_rays, BgArgs bg, LossArgs la, float* __restrict__ loss_sum) {
+                                                                        int n_rays, BgArgs bg, LossArgs la, float* __restrict__ loss_sum,
+                                                                        RegArgs ra) {
   __shared__ float red[kLossThreads];
   const float inv_n = 1.0f / (float)(3L * n_rays), inv_rays = 1.0f / (float)n_rays;
   const int groups = (n_rays + 3) / 4;
@@ -74,6 +78,9 @@ __global__ __launch_bounds__(kLossThreads) void loss_fixed_order_kernel(const fl
         const bool alpha_term = la.opacity_weight > 0.0f;
         e[k] = ray_loss_term(la, p, t, alpha_term ? la.opacity[ray] : 0.0f, alpha_term ? target[4 * (long)ray + 3] : 0.0f, inv_n, inv_rays,
                              dl, dA);
+        if constexpr (REG) {
+          if (ra.weight > 0.0f) e[k] += reg_loss_share(ra.weight, ra.distortion[ray], inv_rays);
+        }
       }
     }
     acc += (e[0] + e[1]) + (e[2] + e[3]);
@@ -119,24 +126,12 @@ __global__ __launch_bounds__(kElemThreads) void loss_kernel(const float* __restr
 namespace rtxn {
 
 int loss_fixed_order(const float* pixels, const float* target, int n_rays, const rtxn_train_background* bg, const rtxn_train_loss* loss,
-                     float* loss_sum, hipStream_t stream) {
-  BgArgs a{};
-  a.mode = RTXN_BG_NONE;
-  a.target_channels = 3;
-  if (bg) {
-    a.mode = bg->mode;
-    for (int c = 0; c < 3; ++c) a.color[c] = bg->color[c];
-    a.seed = bg->seed;
-    a.step = bg->step;
-    a.target_channels = bg->target_channels;
-  }
-  LossArgs la{};
-  la.kind = loss->kind;
-  la.param = loss->param;
-  la.opacity_weight = loss->opacity_weight;
-  la.has_background = bg ? 1 : 0;
-  la.opacity = loss->opacity;
-  loss_fixed_order_kernel<<<1, kLossThreads, 0, stream>>>(pixels, target, n_rays, a, la, loss_sum);
+                     const rtxn_train_regularizer* reg, float* loss_sum, hipStream_t stream) {
+  const BgArgs a = make_bg_args(bg);
+  const LossArgs la = make_loss_args(loss, bg != nullptr);
+  const RegArgs ra = make_reg_args(reg, 1.0f, n_rays);      // the loss scale enters sweep 2's factor only: not read here
+  auto* const kernel = reg ? loss_fixed_order_kernel<true> : loss_fixed_order_kernel<false>;
+  kernel<<<1, kLossThreads, 0, stream>>>(pixels, target, n_rays, a, la, loss_sum, ra);
   RTXN_LAUNCH_CHECK("loss_fixed_order_kernel");
   return RTXN_OK;
 }

@@ -1,5 +1,5 @@
 // The training losses of rtxn_train_loss (include/rtxn.h): the per-channel term l(e) with its derivative dl/dp,
-// and the per-ray alpha term, shared by the loss compositor (composite_loss.hip), the fixed-order loss sum and the stand-alone
+// and the per-ray alpha term, shared by the loss compositor (composite_train.hip), the fixed-order loss sum and the stand-alone
 // loss kernel (loss.hip) so that all three form a scalar from the same operations, bit for bit (-ffp-contract=off on every
 // side).  Internal to librtxn.so.  The struct stays in an anonymous namespace, as BgArgs does: kernels take it by value.
 #pragma once
@@ -14,6 +14,20 @@ struct LossArgs {
   int has_background;     // the compositor adds (1 - A) b to the pixel
   float* opacity;         // compositor: A of every ray is written here (may be NULL); the loss sums read it when lambda > 0
 };
+
+// the kernels' argument from the caller's struct; loss: an ACTIVE loss, or NULL for L2 with no alpha term and no opacity output
+inline LossArgs make_loss_args(const rtxn_train_loss* loss, bool has_background) {
+  LossArgs la{};
+  la.kind = RTXN_LOSS_L2;
+  if (loss) {
+    la.kind = loss->kind;
+    la.param = loss->param;
+    la.opacity_weight = loss->opacity_weight;
+    la.opacity = loss->opacity;
+  }
+  la.has_background = has_background ? 1 : 0;
+  return la;
+}
 
 // l(e) of one channel, e = p - t; dl = dl/dp (relative L2: the denominator is a constant to the gradient; IEEE division)
 __device__ __forceinline__ float loss_term(int kind, float param, float p, float e, float& dl) {

@@ -1,5 +1,5 @@
 // The distortion regulariser of rtxn_train_regularizer (include/rtxn.h): what the regularised compositor
-// (composite_reg.hip) and the fixed-order loss sum behind it share, so that both form a ray's share of the scalar from the same
+// (composite_train.hip) and the fixed-order loss sum behind it (loss.hip) share, so that both form a ray's share of the scalar from the same
 // operations, bit for bit (-ffp-contract=off on every side).  Internal to librtxn.so; anonymous namespace, as LossArgs is.
 #pragma once
 #include "common.h"
@@ -14,6 +14,20 @@ struct RegArgs {
   float* distortion;       // L_r of every ray (may be NULL); the fixed-order sum reads it when lambda_d > 0
   float* depth;            // sum w m of every ray (may be NULL)
 };
+
+// the kernels' argument from the caller's struct; reg: an ACTIVE regulariser, or NULL (all zero: nothing reads it)
+inline RegArgs make_reg_args(const rtxn_train_regularizer* reg, float loss_scale, int n_rays) {
+  RegArgs ra{};
+  if (reg) {
+    ra.weight = reg->distortion_weight;
+    ra.k = loss_scale * reg->distortion_weight / (float)n_rays;
+    ra.t_start = reg->t_start;
+    ra.t_end = reg->t_end;
+    ra.distortion = reg->distortion;
+    ra.depth = reg->depth;
+  }
+  return ra;
+}
 
 // midpoint of sub-interval k of a segment (volrender_aux_kernel's depth expression with u0 = 0.5)
 __device__ __forceinline__ float reg_midpoint(int k, float rK, float ts, float te) { return fmaf(((float)k + 0.5f) * rK, te - ts, ts); }

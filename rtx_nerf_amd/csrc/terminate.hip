@@ -18,38 +18,17 @@
 //
 // The compositing arithmetic is that of volrender.hip's one-sample forward body (fwd_body<MODE, COMPACT = true, AUX = true>),
 // restated here rather than shared: that file's kernels are pinned by their machine code (tests/test_compositor_isa.py), and
-// a body inlined into one more kernel is optimised once more.  Sums are reduced over the wave at every round boundary instead
+// a body inlined into one more kernel is optimised once more.  The wave scan helpers and half4 are shared
+// (wave_scan_internal.h): they are inlined everywhere and leave every kernel's code as it was.  Sums are reduced over the wave at every round boundary instead
 // of once per ray, so against the plain compositors the results agree to fp32 summation order, not bit for bit.
 #include "terminate_internal.h"
+#include "wave_scan_internal.h"
 
 namespace {
 
 constexpr int K = RTXN_NUM_SAMPLES_PER_SEGMENT;   // 32: a 64-lane step is two whole segments
 static_assert(K == 32, "the resume kernel's index arithmetic assumes 32 samples per segment");
 
-// Inclusive prefix sum over the 64 lanes in six DPP adds (volrender.hip has the lane pattern's description).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_term(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
-}
-__device__ __forceinline__ float wave_incl_scan_f(float v) {
-  v += dpp_term<0x111, 0xf>(v);
-  v += dpp_term<0x112, 0xf>(v);
-  v += dpp_term<0x114, 0xf>(v);
-  v += dpp_term<0x118, 0xf>(v);
-  v += dpp_term<0x142, 0xa>(v);
-  v += dpp_term<0x143, 0xc>(v);
-  return v;
-}
-__device__ __forceinline__ float lane63(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ float wave_sum(float v) { return lane63(wave_incl_scan_f(v)); }
-__device__ __forceinline__ float lane_below(float v) { return dpp_term<0x138, 0xf>(v); }
-
-struct alignas(8) half4 {
-  __half x, y, z, w;
-};
 struct F3 {       // a float3 record: 12 bytes, 4-byte aligned, moved as one global_load/store_dwordx3
   float x, y, z;
 };

@@ -23,39 +23,9 @@
 
 #include "background_internal.h"
 #include "common.h"
+#include "wave_scan_internal.h"
 
 namespace {
-
-// Inclusive prefix sum over the 64 lanes in six DPP adds (row_shr 1/2/4/8 inside each row of 16, then row_bcast:15 into rows
-// 1 and 3 and row_bcast:31 into rows 2 and 3): no LDS crossbar round trips -- the __shfl_up form (six dependent
-// ds_bpermute_b32) was most of a compositor step's latency (tools/probe/dpp_scan_probe.hip checks the lane pattern).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_term(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
-}
-__device__ __forceinline__ float wave_incl_scan_f(float v) {
-  v += dpp_term<0x111, 0xf>(v);
-  v += dpp_term<0x112, 0xf>(v);
-  v += dpp_term<0x114, 0xf>(v);
-  v += dpp_term<0x118, 0xf>(v);
-  v += dpp_term<0x142, 0xa>(v);
-  v += dpp_term<0x143, 0xc>(v);
-  return v;
-}
-__device__ __forceinline__ float lane63(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
-// Sum over the wave, returned in every lane: the DPP inclusive scan above leaves the total in lane 63, read back as a scalar
-// (six VALU adds + v_readlane; the __shfl_xor butterfly was six dependent ds_swizzle / ds_bpermute round trips, three times
-// per ray in the compositors).
-__device__ __forceinline__ float wave_sum(float v) { return lane63(wave_incl_scan_f(v)); }
-// lane - 1's value (lane 0: 0): DPP wave_shr:1
-__device__ __forceinline__ float lane_below(float v) { return dpp_term<0x138, 0xf>(v); }
-
-struct alignas(8) half4 {
-  __half x, y, z, w;
-};
 
 // Colour, opacity A = sum w_i and expected depth sum w_i d_i in one pass (rtxn_volrender_fwd_aux): the forward kernels with two
 // more accumulators.  One-sample schedule: ONE body, fwd_body<MODE, COMPACT, AUX>, instantiated by volrender_fwd_kernel
@@ -1247,14 +1217,7 @@ extern "C" int rtxn_volrender_l2_train_ex(const float* network_outputs, const fl
   bool active = false;
   const int rc = rtxn::check_train_background(bg, RTXN_VR_NERF, "rtxn_volrender_l2_train_ex", &active);
   if (rc != RTXN_OK) return rc;
-  BgArgs a;
-  if (active) {
-    a.mode = bg->mode;
-    for (int c = 0; c < 3; ++c) a.color[c] = bg->color[c];
-    a.seed = bg->seed;
-    a.step = bg->step;
-    a.target_channels = bg->target_channels;
-  }
+  const BgArgs a = make_bg_args(active ? bg : nullptr);
   // NULL, or NONE with 3-channel targets: exactly what the plain entry point runs, under its name
   return l2_train(active ? "rtxn_volrender_l2_train_ex" : "rtxn_volrender_l2_train", network_outputs, ray_hit, num_hits, indices, batch_size,
                   num_samples_per_hit, target, loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, active ? &a : nullptr,

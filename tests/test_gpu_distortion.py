@@ -1,5 +1,5 @@
 """The distortion regulariser on the GPU (include/rtxn.h, rtxn_train_regularizer): the regularised compositor
-(composite_reg.hip) against float64 autograd of the pairwise double sum; weight 0 is the existing call bit for bit; the
+(composite_train.hip, REG = true) against float64 autograd of the pairwise double sum; weight 0 is the existing call bit for bit; the
 traversal's t_start / t_end as the trainer plumbs them; agreement of the eager / captured / one-call steps; the fixed-order loss
 sum of deterministic mode; and end-to-end training on the sphere teacher.
 
@@ -154,10 +154,14 @@ def _structs(torch, api, case, weight, B, P, dev, outputs=True, opacity=True):
     return bg, spec, reg, opa, dist, dep
 
 
-def _run(torch, api, K, case, weight=LAMBDA_D, t_scale=1.0, **kw):
+def _run(torch, api, K, case, weight=LAMBDA_D, t_scale=1.0, misaligned=False, **kw):
+    """misaligned: the step lengths are handed over as a view that starts 4 bytes into its allocation"""
     nh, idx, P, rad, step, ts, te, tgt, bg_np = case_inputs(K, case, t_scale)
     B = B_RAYS
     dev = _to_dev(torch, rad=rad, step=step, nh=nh, idx=idx, tgt=tgt, ts=ts, te=te)
+    if misaligned:
+        dev["step"] = torch.cat([torch.zeros(1, device="cuda"), dev["step"]])[1:]
+        assert dev["step"].data_ptr() % 8 == 4 and dev["step"].is_contiguous()
     bg, spec, reg, opa, dist, dep = _structs(torch, api, case, weight, B, P, dev, **kw)
     pix = torch.zeros((B, 3), device="cuda")
     lg = torch.zeros((B, 3), dtype=torch.float16, device="cuda")
@@ -173,7 +177,7 @@ def _run(torch, api, K, case, weight=LAMBDA_D, t_scale=1.0, **kw):
 @pytest.mark.parametrize("K", [32, 7])
 @pytest.mark.parametrize("case", list(CASES))
 def test_reg_compositor_against_float64_autograd(gpu, case, K):
-    """K = 32: composite_reg_multi_kernel<4>; K = 7: composite_reg_kernel.  lambda_d = 10, loss scale 128.  Pixels and A keep the
+    """K = 32: composite_train_multi_kernel<true, 4>; K = 7: composite_train_kernel<true>.  lambda_d = 10, loss scale 128.  Pixels and A keep the
     loss test's bars; depth within 3e-6 max(m) of sum w m (max over the ray's own samples, which asks no less than the batch's);
     L_r within 2e-5 of the largest L_r; the loss scalar within 1e-5 relative; radiance gradients rtol 1.5e-3, atol 2e-5 against
     autograd of pixels.g + A.g_A + k sum_r L_r (g, g_A: the kernel's own fp16 values; k = loss_scale lambda_d / n_rays in fp32).
@@ -182,12 +186,14 @@ def test_reg_compositor_against_float64_autograd(gpu, case, K):
     _check_compositor(gpu, case, K, 1.0)
 
 
-def _check_compositor(torch, case, K, t_scale):
+def _check_compositor(torch, case, K, t_scale, misaligned=False, results=None):
     from rtx_nerf_amd import api
     nh, idx, P, rad, step, ts, te, tgt, bg_np = case_inputs(K, case, t_scale)
     kind, color, lam = CASES[case]
     B = B_RAYS
-    got = _run(torch, api, K, case, t_scale=t_scale)
+    got = _run(torch, api, K, case, t_scale=t_scale, misaligned=misaligned)
+    if results is not None:
+        results.append(got)
     c, w, ref_pix_t, ref_A_t, ref_depth, ref_L, q, m = reference(torch, K, case, t_scale)
     ref_pix, ref_A = ref_pix_t.detach().numpy(), ref_A_t.detach().numpy()
     e = ref_pix - _composited(bg_np, tgt)
@@ -218,7 +224,7 @@ def _check_compositor(torch, case, K, t_scale):
     ratio = np.abs(have - want) / bar
     nz = want[:, 3] != 0.0
     moved = (np.abs(dist_part[:, 3]) > bar[:, 3])[nz].mean()
-    print(f"\n[{case} K={K} t_scale={t_scale}] pixels max|err| {pix_err:.2e}  opacity max|err| {A_err:.2e}  depth max err / (3e-6 max m) {depth_ratio:.3f}  "
+    print(f"\n[{case} K={K} t_scale={t_scale}{' misaligned' if misaligned else ''}] pixels max|err| {pix_err:.2e}  opacity max|err| {A_err:.2e}  depth max err / (3e-6 max m) {depth_ratio:.3f}  "
           f"L_r max|err| / max L_r {L_err:.2e} (max L_r {ref_L.max():.3f})  loss {ref_loss:.5f} (distortion part "
           f"{LAMBDA_D / B * ref_L.sum():.5f}) rel {loss_err:.2e}  radiance grads max|err| {np.abs(have - want).max():.2e}, "
           f"max err / (1.5e-3 |want| + 2e-5) {ratio.max():.3f}  distortion part of the sigma-gradient: max {np.abs(dist_part[:, 3]).max():.3e}, "
@@ -235,6 +241,34 @@ def _check_compositor(torch, case, K, t_scale):
     assert np.abs(dist_part[:, 3]).max() > 1e-3 and np.all(dist_part[:, :3] == 0.0)
     assert moved >= 0.5
     return w.detach().numpy(), step, ref_L, got["dist"]
+
+
+def test_misaligned_step_lengths_take_the_one_ray_kernel_at_an_even_K(gpu):
+    """K = 32 with the step lengths 4 bytes off an 8-byte boundary: the pair schedule reads them two at a time, so the call
+    must run composite_train_kernel<true>, the one-ray form, which the other tests reach at an odd K only.  Every bar of
+    test_reg_compositor_against_float64_autograd holds for it against the same float64 reference, and its pixels and fp16 loss
+    gradients are the aligned call's within the pixels' bar and one fp16 ulp.  Huber over a constant background, RGBA targets,
+    the alpha term, lambda_d = 10.  Measured on an MI355X (profiles/r12/compositor_merge_ab.txt): against float64 pixels
+    1.90e-7, opacities 2.92e-7, depth 0.060 of its bar, L_r 4.0e-7 of the largest, loss 2.1e-8 relative, radiance gradients
+    0.299 of their bar (aligned: the same but L_r 4.4e-7 and loss 2.0e-7); aligned against misaligned pixels within 2.4e-7,
+    all 2331 fp16 loss gradients equal.  No bar needed widening."""
+    case, K = "huber_constant4", 32
+    res = []
+    _check_compositor(gpu, case, K, 1.0, results=res)
+    _check_compositor(gpu, case, K, 1.0, misaligned=True, results=res)
+    a, b = res
+    pix_diff = np.abs(a["pix"] - b["pix"]).max()
+    ulps = np.abs(_half_order(a["lg"]) - _half_order(b["lg"]))
+    print(f"[{case} K={K}] aligned against misaligned: pixels max|diff| {pix_diff:.2e}  fp16 loss gradients: {int((ulps != 0).sum())} of "
+          f"{ulps.size} differ, max {int(ulps.max())} ulp")
+    np.testing.assert_allclose(a["pix"], b["pix"], rtol=0, atol=3e-6)
+    assert ulps.max() <= 1
+
+
+def _half_order(x):
+    """fp16 values as integers ordered like the values: differences are distances in units of the last place"""
+    i = x.view(np.int16).astype(np.int32)
+    return np.where(i < 0, -(i & 0x7FFF), i)
 
 
 @pytest.mark.parametrize("case,K", [("huber_constant4", 32), ("l2_none3", 7)])

@@ -1,4 +1,4 @@
-"""Training losses beyond L2 on the GPU: the loss compositor (composite_loss.hip) for L2 / L1 / Huber / relative
+"""Training losses beyond L2 on the GPU: the loss compositor (composite_train.hip, REG = false) for L2 / L1 / Huber / relative
 L2 with and without the alpha term against a float64 torch restatement and autograd; plain L2 through the new entry points is
 the existing call bit for bit; the fixed-order loss sum of deterministic mode; agreement of the eager / captured / one-call
 steps; the stand-alone rtxn_loss; and end-to-end training on the sphere teacher.
@@ -170,9 +170,13 @@ def _to_dev(torch, **arrays):
 @pytest.mark.parametrize("case", ["none3", "constant4", "random4"])
 @pytest.mark.parametrize("kind", KINDS)
 def test_loss_compositor_against_float64_autograd(gpu, kind, case, K):
+    _check_compositor(gpu, kind, case, K)
+
+
+def _check_compositor(gpu, kind, case, K, misaligned=False):
     """Every kind; no background with RGB targets (lambda = 0), constant and random backgrounds with RGBA targets and
     lambda = 0.5.  An opacity buffer is always given, so kind "l2" without an alpha term runs the new kernels too.
-    K = 32: composite_loss_multi_kernel<4>; K = 7: composite_loss_kernel.  Measured on an MI355X
+    K = 32: composite_train_multi_kernel<false, 4>; K = 7: composite_train_kernel<false>.  Measured on an MI355X
     (profiles/r08/train_loss_tests.txt): pixels and opacities within 2.6e-7, loss within 7e-7 relative, radiance gradients within
     0.18 of their bar, fp16 loss gradients never more than one ulp off; see LG_EQUAL_BAR for the share of equal ones."""
     torch = gpu
@@ -182,6 +186,9 @@ def test_loss_compositor_against_float64_autograd(gpu, kind, case, K):
     lam = 0.0 if case == "none3" else LAMBDA
     bg, _keep = _bg_struct(torch, api, case)
     dev = _to_dev(torch, rad=rad, step=step, nh=nh, idx=idx, tgt=tgt)
+    if misaligned:                                         # a view that starts 4 bytes into its allocation
+        dev["step"] = torch.cat([torch.zeros(1, device="cuda"), dev["step"]])[1:]
+        assert dev["step"].data_ptr() % 8 == 4 and dev["step"].is_contiguous()
     pix = torch.zeros((B, 3), device="cuda")
     lg = torch.zeros((B, 3), dtype=torch.float16, device="cuda")
     loss = torch.full((1,), 9.0, device="cuda")           # a stale value: the call must replace it
@@ -220,7 +227,7 @@ def test_loss_compositor_against_float64_autograd(gpu, kind, case, K):
     want = c.grad.numpy().copy()
     got = out.cpu().numpy().astype(np.float64)
     ratio = np.abs(got - want) / (1.5e-3 * np.abs(want) + 2e-5)
-    print(f"\n[{kind} {case} K={K}] pixels max|err| {pix_err:.2e}  opacity max|err| {A_err:.2e}  loss rel {loss_err:.2e}  "
+    print(f"\n[{kind} {case} K={K}{' misaligned' if misaligned else ''}] pixels max|err| {pix_err:.2e}  opacity max|err| {A_err:.2e}  loss rel {loss_err:.2e}  "
           f"fp16 loss grads: equal {lg_match:.5f} ({int((ulps != 0).sum())} of {ulps.size} differ), max {int(ulps.max())} ulp, "
           f"left out at kinks {left_out:.5f}  radiance grads max|err| {np.abs(got - want).max():.2e}, "
           f"max err / (1.5e-3 |want| + 2e-5) {ratio.max():.3f}")
@@ -236,6 +243,25 @@ def test_loss_compositor_against_float64_autograd(gpu, kind, case, K):
     assert np.abs(want[:, 3]).max() > 1e-3 and np.abs(want[:, :3]).max() > 1e-3
     if lam > 0.0:
         assert np.abs(gA.astype(np.float64)).max() > 1e-3        # the alpha term took part
+    return got_pix, lg_np
+
+
+def test_misaligned_step_lengths_take_the_one_ray_kernel_at_an_even_K(gpu):
+    """K = 32 with the step lengths 4 bytes off an 8-byte boundary: the pair schedule reads them two at a time, so the call
+    must run composite_train_kernel<false>, the one-ray form, which the other tests reach at an odd K only.  Every bar of
+    test_loss_compositor_against_float64_autograd holds for it against the same float64 reference, and its pixels and fp16
+    loss gradients are the aligned call's within the pixels' bar, one fp16 ulp and LG_EQUAL_BAR.  Measured on an MI355X
+    (profiles/r12/compositor_merge_ab.txt): against float64 pixels 1.91e-7, opacities 2.37e-7, loss 4.4e-7 relative, radiance
+    gradients 0.064 of their bar, no fp16 loss gradient off (aligned: 1.98e-7, 2.21e-7, 3.3e-7, 0.064, none); aligned against
+    misaligned pixels within 2.4e-7, all 2331 fp16 loss gradients equal.  No bar needed widening."""
+    kind, case, K = "huber", "constant4", 32
+    pix_a, lg_a = _check_compositor(gpu, kind, case, K)
+    pix_m, lg_m = _check_compositor(gpu, kind, case, K, misaligned=True)
+    ulps = half_ulps(lg_a, lg_m)
+    print(f"[{kind} {case} K={K}] aligned against misaligned: pixels max|diff| {np.abs(pix_a - pix_m).max():.2e}  fp16 loss gradients: "
+          f"{int((ulps != 0).sum())} of {ulps.size} differ, max {int(ulps.max())} ulp")
+    np.testing.assert_allclose(pix_a, pix_m, rtol=0, atol=3e-6)
+    assert ulps.max() <= 1 and (ulps == 0).mean() > LG_EQUAL_BAR[kind]
 
 
 # Share of bit-equal fp16 loss gradients demanded per kind: the existing L2 test's 0.999, i.e. at most 2 of the 2331 elements
