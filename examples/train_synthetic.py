@@ -64,8 +64,13 @@ def main():
     ap.add_argument("--distortion-weight", type=float, default=0.0,
                     help="> 0: mip-NeRF 360's distortion regulariser with this weight, for world distances along the ray (a weight quoted "
                          "for distances normalised to [0, 1] is divided by 2 sqrt(3)); raise --loss-scale with it")
-    ap.add_argument("--loss-scale", type=float, default=128.0,
-                    help="the fp16 gradients' loss scale: the regulariser's gradient is largely rounded away at the default (DESIGN 5.12)")
+    ap.add_argument("--loss-scale", default="128", metavar="S|dynamic",
+                    help="the fp16 gradients' loss scale: the regulariser's gradient is largely rounded away at the default (DESIGN 5.12); "
+                         "'dynamic': kept on the device, halved when a step's gradients are not finite and doubled after "
+                         "--growth-interval clean steps (DESIGN 5.14)")
+    ap.add_argument("--growth-interval", type=int, default=2000, help="--loss-scale dynamic: clean steps between two doublings")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the total gradient norm to X (Trainer(max_grad_norm=...)); with a fixed --loss-scale that must be a power of two")
     ap.add_argument("--lr-schedule", default=None, metavar="nerf|instant_ngp|cosine:N",
                     help="decay the learning rates on the device (Trainer(lr_schedule=...)): NeRF's x0.1 per 250k steps, instant-ngp's x0.33 "
                          "every 10k steps after 20k, or a cosine to 0.01 of the rate over N steps")
@@ -73,6 +78,7 @@ def main():
     ap.add_argument("--skip-nonfinite", action="store_true",
                     help="skip a step whose gradients hold an Inf or a NaN instead of stepping Adam on them; the number skipped is printed")
     a = ap.parse_args()
+    loss_scale = api.loss_scaler(growth_interval=a.growth_interval) if a.loss_scale == "dynamic" else float(a.loss_scale)
     schedule = a.lr_schedule
     if schedule and schedule.startswith("cosine:"):
         schedule = dict(kind="cosine", decay_steps=int(schedule.split(":", 1)[1]), ratio=0.01)
@@ -103,7 +109,8 @@ def main():
                  batch_rays=max(a.batch, ds.image_width * ds.image_height), max_segments=max(a.batch, ds.image_width * ds.image_height) * (3 * R),
                  lr=1e-2 if a.encoding == "hash" else 2e-3, density_scale=150.0, loss=a.loss, opacity_weight=a.opacity_weight,
                  background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C, distortion_weight=a.distortion_weight,
-                 loss_scale=a.loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite)
+                 loss_scale=loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite,
+                 max_grad_norm=a.max_grad_norm)
     white = (1.0, 1.0, 1.0) if rgba else None
 
     def render():
@@ -127,8 +134,12 @@ def main():
                   f"{psnr(render(), gt):.2f} dB", flush=True)
     print(f"final held-out PSNR after {a.steps} steps ({'device batches' if a.device_batches else 'ray dataset'}): "
           f"{psnr(render(), gt):.2f} dB")
-    if tr.skipped_steps is not None and a.skip_nonfinite:
-        print(f"steps skipped for non-finite gradients: {int(tr.skipped_steps.item())} (many: lower --loss-scale)")
+    if tr.loss_scale_now is not None:
+        print(f"loss scale now {float(tr.loss_scale_now.item()):g}: {int(tr.skipped_steps.item())} steps skipped, "
+              f"{int(tr.scale_backoffs.item())} backoffs, {int(tr.scale_growths.item())} growths, {int(tr.clipped_steps.item())} steps clipped, "
+              f"last gradient norm {float(tr.grad_norm.item()):.3e}")
+    elif tr.skipped_steps is not None and a.skip_nonfinite:
+        print(f"steps skipped for non-finite gradients: {int(tr.skipped_steps.item())} (many: lower --loss-scale, or --loss-scale dynamic)")
     img = render().reshape(H, W, 3).cpu().numpy()
     loader.write_png(a.out, img)
     print("wrote", a.out)

@@ -1085,8 +1085,8 @@ int rtxn_train_step_reg(const rtxn_train_step_args* args, const rtxn_train_backg
  * kernels read the skip word before any store to the state: master weights, fp16 parameters, both moments and the table's
  * per-entry counts keep their bits, the gradient is still cleared (RTXN_ADAM_ZERO_GRADS).  The step counter advances all the
  * same -- it keys the sample jitter, the random background and this schedule -- so Adam's global bias-correction step counts
- * ATTEMPTED steps.  The loss scale is a by-value argument of every compositor entry point and is not adapted: guard[1], the
- * number of skipped steps, is what tells the caller to lower it.
+ * ATTEMPTED steps.  The loss scale of these entry points is a by-value argument and stays what it is; rtxn_loss_scaler, below,
+ * keeps it in device memory and lowers it when a step is skipped.
  * Rules (RTXN_ERR_INVALID with a message, before any device is touched): kind is one of the three; ratio in (0, 1];
  * decay_steps >= 1 unless the kind is CONSTANT; warmup_steps >= 0 and decay_start >= 0; staircase only with EXPONENTIAL;
  * weight_decay finite and >= 0; when anything is switched on, lr_factor, and with skip_nonfinite guard, must not be NULL.
@@ -1148,6 +1148,101 @@ int rtxn_adam_step_sparse_opt(long n, float* master, void* params_fp16, void* gr
 int rtxn_train_step_opt(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                         const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
                         rtxn_stream_t stream);
+
+/* ---- dynamic loss scale and gradient-norm clipping (not in the reference) ------------------------------------
+ * The loss scale lives in device memory and the factor the optimizer multiplies raw gradients by lives beside it, so a captured
+ * or one-call step adapts the scale without anything refreshed from the host.  The scale enters a step in one place, the
+ * compositor's per-ray step (the fp16 loss gradients, g_A and the regulariser's k), and leaves it in one place, the factor of
+ * the Adam kernels; everything between just carries it.
+ * Device state (rtxn_loss_scaler_state, 8 words): scale -- what the NEXT compositor launch reads; multiplier -- what this
+ * step's Adam kernels multiply raw gradients by; good -- clean steps since the last change; the counters backoffs, growths,
+ * clipped; grad_norm -- the last clean step's unscaled total norm.  The skipped-step count stays in opt->guard[1].
+ * Per step, once the gradients are complete, with s the scale they were made with, D = loss_scale_divisor (ranks summed) and
+ * sumsq the sum of squares, in double, of every gradient element the optimizer is about to consume (MLP and table together):
+ *   non-finite flag set:  the skip word is set (as rtxn_optimizer_rate does); scale = max(min_scale, s backoff); good = 0;
+ *                         backoffs += 1.  At min_scale the step is still skipped: a NaN from the data is not the scale's fault.
+ *   flag clear:           norm = (float)(sqrt(sumsq) / ((double)s (double)D))
+ *                         coef = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6f)) : 1     (clip_grad_norm_'s rule)
+ *                         multiplier = coef (1.0f / (s D))   -- float; coef == 1 gives exactly 1.0f / (s D)
+ *                         grad_norm = norm; clipped += (coef < 1); good += 1;
+ *                         good >= growth_interval: scale = min(max_scale, s growth), good = 0, growths += 1 if the scale moved.
+ * The step counter advances either way.  Scales and factors are powers of two, so multiplying by them is exact in fp32: a run
+ * whose scale never moves and that never clips is the fixed-scale run under skip_nonfinite, bit for bit.
+ * Rules (RTXN_ERR_INVALID with a message, before any device is touched): init_scale, growth, backoff, min_scale and max_scale
+ * are exact powers of two; min_scale <= init_scale <= max_scale; growth >= 1; 0 < backoff < 1; growth_interval >= 1;
+ * max_grad_norm finite and >= 0 (0: no clipping).  The entry points that take the struct also need `state` and `partials`, and
+ * options with skip_nonfinite, lr_factor and guard: dynamic scaling implies the non-finite guard.  RTXN_VR_NERF only. */
+typedef struct rtxn_loss_scaler_state {
+  float scale;
+  float multiplier;
+  int good;
+  unsigned backoffs, growths, clipped;
+  float grad_norm;
+  int reserved;
+} rtxn_loss_scaler_state;
+enum { RTXN_GRAD_STATS_MAX_BLOCKS = 2048 };
+typedef struct rtxn_loss_scaler {
+  float init_scale;
+  float growth;                     /* default 2 */
+  float backoff;                    /* default 0.5 */
+  int growth_interval;              /* clean steps between two growths; default 2000 */
+  float min_scale;                  /* default 1 */
+  float max_scale;                  /* default 65536 */
+  float max_grad_norm;              /* 0: no clipping */
+  rtxn_loss_scaler_state* state;    /* DEVICE, initialised from rtxn_loss_scaler_init_state */
+  double* partials;                 /* DEVICE workspace of rtxn_loss_scaler_workspace_bytes() bytes: per-block sums of squares,
+                                       [RTXN_MAX_GRAD_BUFFERS][RTXN_GRAD_STATS_MAX_BLOCKS] */
+} rtxn_loss_scaler;
+/* The rules above without the two pointers (what a caller checks before it allocates anything). */
+int rtxn_loss_scaler_check(const rtxn_loss_scaler* scaler);
+size_t rtxn_loss_scaler_workspace_bytes(void);
+/* HOST: the state a run starts from (scale = init_scale, multiplier = 1 / init_scale, everything else 0), to be copied to
+ * scaler->state. */
+int rtxn_loss_scaler_init_state(const rtxn_loss_scaler* scaler, rtxn_loss_scaler_state* state_out);
+/* HOST twin of the device state machine, on the restatement both share: *state_out = the state after a step whose gradients
+ * were made with state_in->scale, with the non-finite flag `flag`, the sum of squares `sumsq` and the divisor D. */
+int rtxn_loss_scaler_advance(const rtxn_loss_scaler* scaler, const rtxn_loss_scaler_state* state_in, int flag, double sumsq,
+                             float divisor, rtxn_loss_scaler_state* state_out);
+/* rtxn_check_gradients' pass plus the norm: ORs *flag as it does, and stores one double sum of squares per block at
+ * scaler->partials[buffer][block].  A buffer's blocks, and the elements each lane visits, are a pure function of that buffer's
+ * count, element type and alignment; a lane sums in double in visiting order, a wave and then a block reduce in a fixed order
+ * and no atomic touches the sums: the same bits run to run, in or out of deterministic mode, alone or beside other buffers. */
+int rtxn_gradient_statistics(const rtxn_grad_buffer* buffers, int n_buffers, unsigned* flag, const rtxn_loss_scaler* scaler,
+                             rtxn_stream_t stream);
+/* rtxn_optimizer_rate's sibling, one block: reduces the partials rtxn_gradient_statistics left for these same buffers (only
+ * their counts and types are read here) in a fixed tree, does everything rtxn_optimizer_rate does and then moves
+ * scaler->state as stated above with D = divisor.  Every stepping path launches this one kernel. */
+int rtxn_loss_scaler_step(const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_grad_buffer* buffers,
+                          int n_buffers, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
+                          float* effective_lr, float* table_effective_lr, float divisor, rtxn_stream_t stream);
+/* rtxn_adam_step_opt / rtxn_adam_step_sparse_opt with the factor on the raw gradient read from scaler->state->multiplier
+ * instead of formed from a loss_scale argument; everything else is those calls. */
+int rtxn_adam_step_scaled(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                          const float* effective_lr, float lr, float beta1, float beta2, float eps,
+                          const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, rtxn_stream_t stream);
+int rtxn_adam_step_sparse_scaled(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                 unsigned* param_steps, float lr, float beta1, float beta2, float eps,
+                                 const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, rtxn_stream_t stream);
+/* rtxn_volrender_reg_train reading the loss scale from scaler->state->scale (one scalar load per wave); `loss_scale` is then
+ * ignored.  Always the loss compositor's kernels, plain L2 included (bg, loss and reg may each be NULL).  scaler == NULL:
+ * exactly rtxn_volrender_reg_train. */
+int rtxn_volrender_scaled_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                                int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
+                                void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                                const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
+                                const rtxn_loss_scaler* scaler, rtxn_stream_t stream);
+/* rtxn_train_gradients_reg with the scaler: batch->loss_scale is ignored, the compositor reads the device word.
+ * batch->vr_mode must be RTXN_VR_NERF.  scaler == NULL: exactly rtxn_train_gradients_reg. */
+int rtxn_train_gradients_scaled(const rtxn_train_batch* batch, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                                rtxn_stream_t stream);
+/* rtxn_train_step_opt with the scaler: gradients, rtxn_gradient_statistics over the buffers rtxn_train_step_opt checks,
+ * rtxn_loss_scaler_step with D = args->opt.loss_scale_divisor, scaled Adam on the MLP, the training-weight re-pack, scaled
+ * Adam on the table -- all on `stream`, so the next step's compositor is ordered behind this step's scaler kernel.
+ * scaler == NULL: exactly rtxn_train_step_opt. */
+int rtxn_train_step_scaled(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                           const rtxn_loss_scaler* scaler, rtxn_stream_t stream);
 
 /* fp32 <-> fp16 copies of a gradient block on the device (no counterpart in the reference, which is single-GPU): the
  * data-parallel exchange sends the hashed levels' gradient in fp16 -- tiny-cuda-nn holds that gradient in fp16 throughout. */

@@ -148,6 +148,19 @@ class GradBuffer(C.Structure):
     _fields_ = [("data", C.c_void_p), ("count", C.c_long), ("is_fp16", C.c_int)]
 
 
+class LossScalerState(C.Structure):
+    """struct rtxn_loss_scaler_state (include/rtxn.h): the scaler's eight device words."""
+    _fields_ = [("scale", C.c_float), ("multiplier", C.c_float), ("good", C.c_int), ("backoffs", C.c_uint), ("growths", C.c_uint),
+                ("clipped", C.c_uint), ("grad_norm", C.c_float), ("reserved", C.c_int)]
+
+
+class LossScaler(C.Structure):
+    """struct rtxn_loss_scaler (include/rtxn.h)."""
+    _fields_ = [("init_scale", C.c_float), ("growth", C.c_float), ("backoff", C.c_float), ("growth_interval", C.c_int),
+                ("min_scale", C.c_float), ("max_scale", C.c_float), ("max_grad_norm", C.c_float), ("state", C.c_void_p),
+                ("partials", C.c_void_p)]
+
+
 class ImageSet(C.Structure):
     """struct rtxn_image_set (include/rtxn.h)."""
     _fields_ = [("images", C.c_void_p), ("poses", C.c_void_p), ("n_images", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32),
@@ -335,6 +348,22 @@ SYMBOLS = {
     "rtxn_adam_step_sparse_opt": (_I, [_L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, C.POINTER(OptimizerOptions), _P]),
     "rtxn_train_step_opt": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                  C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), _P]),
+    "rtxn_loss_scaler_check": (_I, [C.POINTER(LossScaler)]),
+    "rtxn_loss_scaler_workspace_bytes": (C.c_size_t, []),
+    "rtxn_loss_scaler_init_state": (_I, [C.POINTER(LossScaler), C.POINTER(LossScalerState)]),
+    "rtxn_loss_scaler_advance": (_I, [C.POINTER(LossScaler), C.POINTER(LossScalerState), _I, C.c_double, _F, C.POINTER(LossScalerState)]),
+    "rtxn_gradient_statistics": (_I, [C.POINTER(GradBuffer), _I, _P, C.POINTER(LossScaler), _P]),
+    "rtxn_loss_scaler_step": (_I, [C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(GradBuffer), _I, _P, _I, _F, _F, _F, _F, _P,
+                                   _P, _F, _P]),
+    "rtxn_adam_step_scaled": (_I, [_L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, C.POINTER(OptimizerOptions), C.POINTER(LossScaler), _P]),
+    "rtxn_adam_step_sparse_scaled": (_I, [_L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, C.POINTER(OptimizerOptions), C.POINTER(LossScaler),
+                                          _P]),
+    "rtxn_volrender_scaled_train": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(TrainBackground), C.POINTER(TrainLoss),
+                                         C.POINTER(TrainRegularizer), C.POINTER(LossScaler), _P]),
+    "rtxn_train_gradients_scaled": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                         C.POINTER(TrainRegularizer), C.POINTER(LossScaler), _P]),
+    "rtxn_train_step_scaled": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                    C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), _P]),
     "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),

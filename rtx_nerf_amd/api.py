@@ -9,6 +9,7 @@ torch's current stream.  Nothing here computes on the CPU.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -970,15 +971,21 @@ def optimizer_rate(opt, step, effective_lr, lr=1e-3, table_lr=0.0, table_effecti
                                          _ptr(table_effective_lr, torch.float32, "table_effective_lr"), _stream()), "rtxn_optimizer_rate")
 
 
-def check_gradients(buffers, flag):
-    """rtxn_check_gradients: OR the device int32 `flag` (an options' guard) if any element of the fp32 / fp16 tensors in `buffers`
-    (at most 4; None and empty ones are skipped) is Inf or NaN."""
+def _grad_buffers(buffers):
+    """(struct rtxn_grad_buffer array, its length) over the fp32 / fp16 tensors in `buffers`; None and empty ones are skipped"""
     bufs = [b for b in buffers if b is not None and b.numel()]
     arr = (_lib.GradBuffer * max(1, len(bufs)))()
     for k, b in enumerate(bufs):
         half = b.dtype == torch.float16
         arr[k].data, arr[k].count, arr[k].is_fp16 = _ptr(b, torch.float16 if half else torch.float32, "buffers[%d]" % k), b.numel(), int(half)
-    check(_lib.lib().rtxn_check_gradients(arr, len(bufs), _ptr(flag, torch.int32, "flag"), _stream()), "rtxn_check_gradients")
+    return arr, len(bufs)
+
+
+def check_gradients(buffers, flag):
+    """rtxn_check_gradients: OR the device int32 `flag` (an options' guard) if any element of the fp32 / fp16 tensors in `buffers`
+    (at most 4; None and empty ones are skipped) is Inf or NaN."""
+    arr, n = _grad_buffers(buffers)
+    check(_lib.lib().rtxn_check_gradients(arr, n, _ptr(flag, torch.int32, "flag"), _stream()), "rtxn_check_gradients")
 
 
 def adam_step_opt(master, params_fp16, grads, m, v, effective_lr, opt, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, loss_scale=1.0,
@@ -1006,6 +1013,123 @@ def adam_step_sparse_opt(master, params_fp16, grads, m, v, param_steps, opt, lr=
                                                _ptr(m, torch.float32, "m"), _ptr(v, torch.float32, "v"),
                                                _ptr(param_steps, torch.int32, "param_steps"), lr, beta1, beta2, eps, loss_scale,
                                                _byref(opt), _stream()), "rtxn_adam_step_sparse_opt")
+
+
+# --------------------------------------------------------------------------- dynamic loss scale, gradient clipping
+def loss_scaler(init_scale=128.0, growth=2.0, backoff=0.5, growth_interval=2000, min_scale=1.0, max_scale=65536.0, max_grad_norm=0.0,
+                state=None, partials=None):
+    """struct rtxn_loss_scaler (include/rtxn.h): the loss scale kept in device memory -- halved (backoff) when a step's gradients
+    are not finite, doubled (growth) after growth_interval clean steps, inside [min_scale, max_scale] -- and gradient-norm clipping
+    at max_grad_norm (0: none; torch.nn.utils.clip_grad_norm_'s rule).  The five scales and factors are exact powers of two.
+    state: device int32[8] (loss_scaler_state_tensor); partials: device float64 workspace (loss_scaler_workspace); both stay
+    referenced by the struct.  Accepts a dict of these arguments, or a struct, as well.  The rules are the library's
+    (rtxn_loss_scaler_check), applied here, before anything touches a device."""
+    if isinstance(init_scale, _lib.LossScaler):
+        return init_scale
+    if isinstance(init_scale, dict):
+        return loss_scaler(**init_scale)
+    s = _lib.LossScaler()
+    s.init_scale, s.growth, s.backoff, s.growth_interval = float(init_scale), float(growth), float(backoff), int(growth_interval)
+    s.min_scale, s.max_scale, s.max_grad_norm = float(min_scale), float(max_scale), float(max_grad_norm)
+    if int(growth_interval) != growth_interval:
+        raise _lib.RtxnError(f"loss_scaler: growth_interval = {growth_interval!r} is not an integer")
+    check(_lib.lib().rtxn_loss_scaler_check(C.byref(s)), "rtxn_loss_scaler_check")
+    if state is not None and state.numel() < 8:
+        raise _lib.RtxnError(f"loss_scaler: state holds {state.numel()} words, 8 are needed")
+    if partials is not None and partials.numel() * 8 < _lib.lib().rtxn_loss_scaler_workspace_bytes():
+        raise _lib.RtxnError(f"loss_scaler: partials holds {partials.numel()} doubles, "
+                             f"{_lib.lib().rtxn_loss_scaler_workspace_bytes() // 8} are needed")
+    s.state, s.partials = _ptr(state, torch.int32, "state"), _ptr(partials, torch.float64, "partials")
+    s._tensors = (state, partials)
+    return s
+
+
+def loss_scaler_initial_state(scaler):
+    """rtxn_loss_scaler_init_state: the eight words a run starts from, as a numpy int32[8] (view float32 for words 0, 1 and 6)."""
+    st = _lib.LossScalerState()
+    check(_lib.lib().rtxn_loss_scaler_init_state(C.byref(scaler), C.byref(st)), "rtxn_loss_scaler_init_state")
+    return np.frombuffer(bytes(st), dtype=np.int32).copy()
+
+
+def loss_scaler_state_tensor(scaler, device="cuda"):
+    """device int32[8] holding the initial state of `scaler`"""
+    return torch.from_numpy(loss_scaler_initial_state(scaler)).to(device)
+
+
+def loss_scaler_workspace(device="cuda"):
+    """device float64 workspace of the statistics kernel's per-block sums (rtxn_loss_scaler_workspace_bytes)"""
+    return torch.zeros(_lib.lib().rtxn_loss_scaler_workspace_bytes() // 8, dtype=torch.float64, device=device)
+
+
+def loss_scaler_advance(scaler, state, flag, sumsq, divisor=1.0):
+    """rtxn_loss_scaler_advance: the device's state machine on the host.  state: a _lib.LossScalerState; returns the next one."""
+    out = _lib.LossScalerState()
+    check(_lib.lib().rtxn_loss_scaler_advance(C.byref(scaler), C.byref(state), int(bool(flag)), float(sumsq), float(divisor), C.byref(out)),
+          "rtxn_loss_scaler_advance")
+    return out
+
+
+def gradient_statistics(buffers, flag, scaler):
+    """rtxn_gradient_statistics: check_gradients' pass plus one double sum of squares per block, left in the scaler's partials
+    at [buffer][block] (GRAD_STATS_MAX_BLOCKS per buffer)."""
+    arr, n = _grad_buffers(buffers)
+    check(_lib.lib().rtxn_gradient_statistics(arr, n, _ptr(flag, torch.int32, "flag"), C.byref(scaler), _stream()), "rtxn_gradient_statistics")
+
+
+GRAD_STATS_MAX_BLOCKS = 2048
+
+
+def loss_scaler_step(opt, scaler, buffers, step, effective_lr, lr=1e-3, table_lr=0.0, table_effective_lr=None, advance=True, beta1=0.9,
+                     beta2=0.999, divisor=1.0):
+    """rtxn_loss_scaler_step: optimizer_rate's one-block sibling -- reduces the partials gradient_statistics left for these same
+    `buffers`, does what optimizer_rate does, then moves the scaler's device state (divisor: ranks summed into the gradients)."""
+    arr, n = _grad_buffers(buffers)
+    check(_lib.lib().rtxn_loss_scaler_step(C.byref(opt), C.byref(scaler), arr, n, _ptr(step, torch.int32, "step"), int(bool(advance)), lr,
+                                           table_lr, beta1, beta2, _ptr(effective_lr, torch.float32, "effective_lr"),
+                                           _ptr(table_effective_lr, torch.float32, "table_effective_lr"), float(divisor), _stream()),
+          "rtxn_loss_scaler_step")
+
+
+def adam_step_scaled(master, params_fp16, grads, m, v, effective_lr, opt, scaler, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8,
+                     zero_grads=False, weight_decay=True):
+    """rtxn_adam_step_scaled: adam_step_opt with the factor on the raw gradient read from the scaler's device multiplier."""
+    half = grads.dtype == torch.float16
+    flags = (ADAM_GRADS_FP16 if half else 0) | (ADAM_ZERO_GRADS if zero_grads else 0) | (0 if weight_decay else ADAM_NO_WEIGHT_DECAY)
+    check(_lib.lib().rtxn_adam_step_scaled(master.numel(), _ptr(master, torch.float32, "master"), _ptr(params_fp16, torch.float16, "params"),
+                                           _ptr(grads, torch.float16 if half else torch.float32, "grads"), flags,
+                                           _ptr(m, torch.float32, "m"), _ptr(v, torch.float32, "v"),
+                                           _ptr(effective_lr, torch.float32, "effective_lr"), lr, beta1, beta2, eps,
+                                           _byref(opt), _byref(scaler), _stream()), "rtxn_adam_step_scaled")
+
+
+def adam_step_sparse_scaled(master, params_fp16, grads, m, v, param_steps, opt, scaler, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8,
+                            zero_grads=False, weight_decay=True):
+    """rtxn_adam_step_sparse_scaled: adam_step_sparse_opt with the factor read from the scaler's device multiplier."""
+    half = grads.dtype == torch.float16
+    flags = (ADAM_GRADS_FP16 if half else 0) | (ADAM_ZERO_GRADS if zero_grads else 0) | (0 if weight_decay else ADAM_NO_WEIGHT_DECAY)
+    check(_lib.lib().rtxn_adam_step_sparse_scaled(master.numel(), _ptr(master, torch.float32, "master"),
+                                                  _ptr(params_fp16, torch.float16, "params"),
+                                                  _ptr(grads, torch.float16 if half else torch.float32, "grads"), flags,
+                                                  _ptr(m, torch.float32, "m"), _ptr(v, torch.float32, "v"),
+                                                  _ptr(param_steps, torch.int32, "param_steps"), lr, beta1, beta2, eps,
+                                                  _byref(opt), _byref(scaler), _stream()), "rtxn_adam_step_sparse_scaled")
+
+
+def volrender_scaled_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, scaler, pixels,
+                           loss_gradients, loss_sum, radiance_gradients, background=None, loss=None, regularizer=None):
+    """rtxn_volrender_scaled_train: volrender_reg_train reading the loss scale from the scaler's device word; always the loss
+    compositor's kernels, plain L2 included."""
+    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
+        raise _lib.RtxnError(f"volrender_scaled_train: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
+    _check_regularizer("volrender_scaled_train", regularizer, batch_size, ray_hit.numel() // int(num_samples_per_hit))
+    check(_lib.lib().rtxn_volrender_scaled_train(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
+                                                 _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
+                                                 num_samples_per_hit, _ptr(target, torch.float32, "target"), 0.0,
+                                                 _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
+                                                 _ptr(loss_sum, torch.float32, "loss_sum"),
+                                                 _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
+                                                 _byref(background), _byref(loss), _byref(regularizer), C.byref(scaler), _stream()),
+          "rtxn_volrender_scaled_train")
 
 
 def deterministic_shadow(n_params, device="cuda"):
@@ -1039,14 +1163,21 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
                     total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                     encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                     loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                    workspace_lean=False, background=None, jitter=None, loss=None, regularizer=None):
+                    workspace_lean=False, background=None, jitter=None, loss=None, regularizer=None, scaler=None):
     """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781).
     background: train_background(...) -> rtxn_train_gradients_ex (targets float[n_rays][background.target_channels]);
     jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> rtxn_train_gradients_jitter (with or without a background);
     loss: train_loss(...) -> rtxn_train_gradients_loss (with or without either);
-    regularizer: train_regularizer(...) -> rtxn_train_gradients_reg (with or without any of the three)."""
-    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer")}
-    if regularizer is not None:
+    regularizer: train_regularizer(...) -> rtxn_train_gradients_reg (with or without any of the three);
+    scaler: loss_scaler(...) -> rtxn_train_gradients_scaled (with or without any of the four; loss_scale is then not read)."""
+    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer", "scaler")}
+    if scaler is not None:
+        if regularizer is not None:
+            _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
+        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
+        check(_lib.lib().rtxn_train_gradients_scaled(C.byref(b), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
+                                                     C.byref(scaler), _stream()), "rtxn_train_gradients_scaled")
+    elif regularizer is not None:
         _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
         b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
         check(_lib.lib().rtxn_train_gradients_reg(C.byref(b), _byref(background), _jit(jitter), _byref(loss), C.byref(regularizer), _stream()),
@@ -1111,15 +1242,21 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None):
+def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
     jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
     loss: train_loss(...) -> rtxn_train_step_loss (with or without either);
     regularizer: train_regularizer(...) -> rtxn_train_step_reg (with or without any of the three): the write pass of the traversal
     stores the segments' t_start / t_end into the regulariser's buffers;
-    optimizer: optimizer_options(...) -> rtxn_train_step_opt (with or without any of the four)."""
-    if optimizer is not None:
+    optimizer: optimizer_options(...) -> rtxn_train_step_opt (with or without any of the four);
+    scaler: loss_scaler(...) -> rtxn_train_step_scaled (needs `optimizer` with skip_nonfinite)."""
+    if scaler is not None:
+        if regularizer is not None:
+            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
+        check(_lib.lib().rtxn_train_step_scaled(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
+                                                _byref(optimizer), C.byref(scaler), _stream()), "rtxn_train_step_scaled")
+    elif optimizer is not None:
         if regularizer is not None:
             _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
         check(_lib.lib().rtxn_train_step_opt(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),

@@ -65,6 +65,10 @@ int check_train_regularizer(const rtxn_train_regularizer* reg, int vr_mode, int 
 // an active struct must also carry lr_factor and, with skip_nonfinite, guard.
 int check_optimizer_options(const rtxn_optimizer_options* opt, const char* who, bool need_buffers, bool* active);
 
+// The rules of the loss scaler (rtxn_loss_scaler, include/rtxn.h), host only, optimizer.hip: RTXN_ERR_INVALID with a message
+// naming the field.  need_buffers: the struct must also carry state and partials.
+int check_loss_scaler(const rtxn_loss_scaler* scaler, const char* who, bool need_buffers);
+
 // MurmurHash3's 32-bit finaliser: the integer hash behind RTXN_BG_RANDOM and the occupancy refresh's jitter (include/rtxn.h
 // states both uses bit for bit)
 __host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {

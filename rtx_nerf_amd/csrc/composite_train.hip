@@ -17,6 +17,9 @@
 // measurements behind both.  The volrender_l2_* kernels (volrender.hip) stay copies of these schedules: their machine code is
 // pinned by tests/test_compositor_isa.py.  Loss kind, parameter, lambda and the background flag are wave-uniform values of an
 // argument struct; the loss is evaluated once per ray on three channels, so the kernels are not instantiated per kind.
+// DEV (rtxn_volrender_scaled_train): the loss scale is a word of device memory (rtxn_loss_scaler_state::scale) instead
+// of an argument -- the argument's type and the two reads through scale_value() are all that differs, so DEV = false is the
+// by-value kernel byte for byte (profiles/r14/compositor_scaled_ab.txt).
 #include <cmath>
 #include <type_traits>
 
@@ -31,6 +34,13 @@ namespace {
 // a ray's sample count and loop index
 template <bool REG>
 using sample_index = std::conditional_t<REG, int, long>;
+
+// The loss scale of a launch: the by-value argument, or (DEV) the word rtxn_loss_scaler keeps in device memory.  The pointer is a
+// kernel argument and the address is the same in every lane, so the read is one scalar load per wave, not a load per lane.
+template <bool DEV>
+using scale_arg = std::conditional_t<DEV, const float*, float>;
+__device__ __forceinline__ float scale_value(float s) { return s; }
+__device__ __forceinline__ float scale_value(const float* s) { return *s; }
 
 // What a ray's wave does between the sweeps: pixel, loss gradient (fp16, stored and handed on in that form), the ray's share of
 // the loss -- with REG the regulariser's included -- and the per-ray outputs; returns the share.  Every value is wave-uniform;
@@ -90,10 +100,11 @@ __device__ __forceinline__ float ray_step(const BgArgs& bga, const LossArgs& la,
 // ahead of d, wi, mi and q are declared outside the loop and assigned under `if constexpr` (through wi_, mi_), gc is updated
 // in place; in the pair kernel w0, w1, q0, q1 are declared without a value and the loss instantiation forms Ti (1 - ex)
 // inside the product with gc.  Re-run the comparison after moving a declaration in either kernel.
-template <bool REG>
+template <bool REG, bool DEV>
 __global__ __launch_bounds__(256) void composite_train_kernel(const float4* __restrict__ radiance, const float* __restrict__ step_len,
                                                               const int* __restrict__ num_hits, const int* __restrict__ indices,
-                                                              int batch_size, int K, const float* __restrict__ target, float loss_scale,
+                                                              int batch_size, int K, const float* __restrict__ target,
+                                                              scale_arg<DEV> loss_scale,
                                                               float* __restrict__ pixels, __half* __restrict__ loss_gradients,
                                                               float* __restrict__ loss_sum, half4* __restrict__ grads, BgArgs bga, LossArgs la,
                                                               RegArgs ra) {
@@ -149,11 +160,11 @@ __global__ __launch_bounds__(256) void composite_train_kernel(const float4* __re
   const float Wt = W_carry, Bt = M_carry;             // REG: A and B as the prefixes of sweep 2 will sum them
   float bg[3];
   RayGrad g;
-  const float value = ray_step<REG>(bga, la, ra, target, ray, batch_size, lane, loss_scale, ar, ag, ab, aw, L, Bt, pixels, loss_gradients, bg, g);
+  const float value = ray_step<REG>(bga, la, ra, target, ray, batch_size, lane, scale_value(loss_scale), ar, ag, ab, aw, L, Bt, pixels, loss_gradients, bg, g);
   if (lane == 0 && loss_sum) atomicAdd(loss_sum, value);
   const float g0 = g.g0, g1 = g.g1, g2 = g.g2;
   const float gbg = g0 * bg[0] + g1 * bg[1] + g2 * bg[2];
-  const float kq = ra.k;
+  const float kq = reg_k<DEV>(ra, scale_value(loss_scale), batch_size);
   const float S0 = ((g0 * ar + g1 * ag + g2 * ab) - gbg * aw) + g.gA * aw;     // = sum_k w_k (g . (c_k - bg) + g_A)
   const float S = REG ? S0 + 2.0f * kq * L : S0;
   // sweep 2: per-sample gradients
@@ -210,11 +221,11 @@ __global__ __launch_bounds__(256) void composite_train_kernel(const float4* __re
 // aligned step lengths, 16-byte aligned gradients.  The loss is reduced per block and added once per block at the very end.
 // REG: a pair never straddles two segments (K even): one t_start / t_end pair per lane and block, turned into the pair's two
 // midpoints and their common width as it is loaded.
-template <bool REG, int U>
+template <bool REG, int U, bool DEV>
 __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4* __restrict__ radiance, const float* __restrict__ step_len,
                                                                     const int* __restrict__ num_hits, const int* __restrict__ indices,
                                                                     int batch_size, int K, const float* __restrict__ target,
-                                                                    float loss_scale, float* __restrict__ pixels,
+                                                                    scale_arg<DEV> loss_scale, float* __restrict__ pixels,
                                                                     __half* __restrict__ loss_gradients, float* __restrict__ loss_sum,
                                                                     half4* __restrict__ grads, BgArgs bga, LossArgs la, RegArgs ra) {
   using idx_t = sample_index<REG>;
@@ -301,10 +312,10 @@ __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4
     const float Wt = W_carry, Bt = M_carry;           // REG: A and B as the prefixes of sweep 2 will sum them
     float bg[3];
     RayGrad g;
-    loss_part = ray_step<REG>(bga, la, ra, target, ray, batch_size, lane, loss_scale, ar, ag, ab, aw, L, Bt, pixels, loss_gradients, bg, g);
+    loss_part = ray_step<REG>(bga, la, ra, target, ray, batch_size, lane, scale_value(loss_scale), ar, ag, ab, aw, L, Bt, pixels, loss_gradients, bg, g);
     const float g0 = g.g0, g1 = g.g1, g2 = g.g2;
     const float gbg = g0 * bg[0] + g1 * bg[1] + g2 * bg[2];
-    const float kq = ra.k;
+    const float kq = reg_k<DEV>(ra, scale_value(loss_scale), batch_size);
     const float S0 = ((g0 * ar + g1 * ag + g2 * ab) - gbg * aw) + g.gA * aw;     // = sum_k w_k (g . (c_k - bg) + g_A)
     const float S = REG ? S0 + 2.0f * kq * L : S0;
     // sweep 2: per-sample gradients (the radiance is re-read: cache hits)
@@ -396,10 +407,12 @@ __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4
 
 // rtxn_volrender_loss_train (reg_entry = false, reg = NULL) and rtxn_volrender_reg_train.  An inactive struct falls through to
 // the entry point without it -- reg -> loss -> rtxn_volrender_l2_train_ex -- which is then exactly what runs.
+// scale_dev (rtxn_volrender_scaled_train): the device word the DEV instantiations read instead of loss_scale; nothing falls
+// through then, plain L2 is one of loss_term's kinds.
 int composite_train(const char* who, bool reg_entry, const float* network_outputs, const float* ray_hit, const int* num_hits,
                     const int* indices, int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
                     void* loss_gradients_half, float* loss_sum, void* radiance_gradients, const rtxn_train_background* bg,
-                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
+                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const float* scale_dev, rtxn_stream_t stream) {
   bool bg_active = false, loss_active = false, reg_active = false;
   int rc = rtxn::check_train_background(bg, RTXN_VR_NERF, who, &bg_active);
   if (rc != RTXN_OK) return rc;
@@ -407,10 +420,10 @@ int composite_train(const char* who, bool reg_entry, const float* network_output
   if (rc != RTXN_OK) return rc;
   rc = rtxn::check_train_regularizer(reg, RTXN_VR_NERF, -1, who, &reg_active);
   if (rc != RTXN_OK) return rc;
-  if (reg_entry && !reg_active)
+  if (!scale_dev && reg_entry && !reg_active)
     return rtxn_volrender_loss_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
                                      loss_gradients_half, loss_sum, radiance_gradients, bg, loss, stream);
-  if (!reg_entry && !loss_active)
+  if (!scale_dev && !reg_entry && !loss_active)
     return rtxn_volrender_l2_train_ex(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
                                       loss_gradients_half, loss_sum, radiance_gradients, bg, stream);
   RTXN_REQUIRE(batch_size >= 0, "%s: batch_size = %d < 0", who, batch_size);
@@ -438,12 +451,20 @@ int composite_train(const char* who, bool reg_entry, const float* network_output
   const RegArgs ra = make_reg_args(reg, loss_scale, batch_size);
   // 512 samples per step, two per lane: an even K, 8-byte-aligned step lengths and 16-byte-aligned gradients
   const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)ray_hit & 7) == 0 && ((uintptr_t)radiance_gradients & 15) == 0;
-  auto* const kernel = reg_active ? (pairs ? composite_train_multi_kernel<true, 4> : composite_train_kernel<true>)
-                                  : (pairs ? composite_train_multi_kernel<false, 4> : composite_train_kernel<false>);
-  kernel<<<dim3((batch_size + 3) / 4), dim3(256), 0, s>>>(reinterpret_cast<const float4*>(network_outputs), ray_hit, num_hits, indices, batch_size,
-                                                          num_samples_per_hit, target, loss_scale, pixels,
-                                                          static_cast<__half*>(loss_gradients_half), det_loss ? nullptr : loss_sum,
-                                                          static_cast<half4*>(radiance_gradients), a, la, ra);
+  const dim3 grid((batch_size + 3) / 4), block(256);
+  const float4* const rad = reinterpret_cast<const float4*>(network_outputs);
+  __half* const lg = static_cast<__half*>(loss_gradients_half);
+  float* const ls = det_loss ? nullptr : loss_sum;
+  half4* const rg = static_cast<half4*>(radiance_gradients);
+  if (scale_dev) {
+    auto* const kernel = reg_active ? (pairs ? composite_train_multi_kernel<true, 4, true> : composite_train_kernel<true, true>)
+                                    : (pairs ? composite_train_multi_kernel<false, 4, true> : composite_train_kernel<false, true>);
+    kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, scale_dev, pixels, lg, ls, rg, a, la, ra);
+  } else {
+    auto* const kernel = reg_active ? (pairs ? composite_train_multi_kernel<true, 4, false> : composite_train_kernel<true, false>)
+                                    : (pairs ? composite_train_multi_kernel<false, 4, false> : composite_train_kernel<false, false>);
+    kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels, lg, ls, rg, a, la, ra);
+  }
   RTXN_LAUNCH_CHECK("composite_train_kernel");
   if (det_loss) return rtxn::loss_fixed_order(pixels, target, batch_size, bg, loss, reg, loss_sum, s);
   return RTXN_OK;
@@ -499,7 +520,7 @@ extern "C" int rtxn_volrender_loss_train(const float* network_outputs, const flo
                                          void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
                                          const rtxn_train_background* bg, const rtxn_train_loss* loss, rtxn_stream_t stream) {
   return composite_train("rtxn_volrender_loss_train", false, network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
-                         loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, bg, loss, nullptr, stream);
+                         loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, bg, loss, nullptr, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_reg_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
@@ -508,5 +529,21 @@ extern "C" int rtxn_volrender_reg_train(const float* network_outputs, const floa
                                         const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
                                         rtxn_stream_t stream) {
   return composite_train("rtxn_volrender_reg_train", true, network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
-                         loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, bg, loss, reg, stream);
+                         loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, bg, loss, reg, nullptr, stream);
+}
+
+// the loss scale read from the scaler's device word; scaler == NULL: rtxn_volrender_reg_train
+extern "C" int rtxn_volrender_scaled_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                                           int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
+                                           void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                                           const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
+                                           const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
+  const char* who = "rtxn_volrender_scaled_train";
+  if (!scaler)
+    return rtxn_volrender_reg_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
+                                    loss_gradients_half, loss_sum, radiance_gradients, bg, loss, reg, stream);
+  const int rc = rtxn::check_loss_scaler(scaler, who, true);
+  if (rc != RTXN_OK) return rc;
+  return composite_train(who, true, network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, 0.0f, pixels,
+                         loss_gradients_half, loss_sum, radiance_gradients, bg, loss, reg, &scaler->state->scale, stream);
 }

@@ -5,11 +5,19 @@
 //   adam_opt_kernel, adam_sparse_opt_kernel    train.hip's adam_kernel / adam_sparse_kernel reading the rate, the factor and the
 //                             skip word from device memory; siblings, so that the kernels a step without options launches are
 //                             the ones it always launched
+// ... and the dynamic loss scale with gradient-norm clipping (rtxn_loss_scaler):
+//   gradient_statistics_kernel  check_gradients_kernel's pass plus a double sum of squares per block, summed in a fixed order
+//   loss_scaler_kernel          optimizer_rate_kernel's sibling, one block: reduces those sums, then the rate kernel's work and
+//                             the scaler's state machine (loss_scaler_advance, shared with the host)
+//   adam_opt_kernel<.., true>, adam_sparse_opt_kernel<.., true>    the _opt kernels with the factor on the raw gradient read
+//                             from device memory
 #include "common.h"
 #include "mlp_internal.h"
 #include "adam_internal.h"
+#include "wave_scan_internal.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -35,8 +43,8 @@ __host__ __device__ inline float schedule_factor(const rtxn_lr_schedule& s, int 
 // rounded once, sqrtf and the division correctly rounded -- with lr_t = lr factor in place of lr; then the guard: the flag the
 // check kernel ORed becomes this step's skip word, is cleared for the next step and counted.  One thread: every stepping path
 // launches this one kernel, so their rates are the same bits by construction.
-__global__ void optimizer_rate_kernel(int* step, int advance, rtxn_lr_schedule s, float lr, float table_lr, float beta1, float beta2,
-                                      float* lr_eff, float* table_lr_eff, float* factor_out, unsigned* guard) {
+__device__ __forceinline__ unsigned rate_update(int* step, int advance, const rtxn_lr_schedule& s, float lr, float table_lr, float beta1,
+                                                float beta2, float* lr_eff, float* table_lr_eff, float* factor_out, unsigned* guard) {
   int t = *step;
   if (advance) {
     t += 1;
@@ -47,12 +55,18 @@ __global__ void optimizer_rate_kernel(int* step, int advance, rtxn_lr_schedule s
   const float p2 = (float)pow((double)beta2, (double)t), p1 = (float)pow((double)beta1, (double)t);
   *lr_eff = (lr * factor) * sqrtf(1.0f - p2) / (1.0f - p1);
   if (table_lr_eff) *table_lr_eff = (table_lr * factor) * sqrtf(1.0f - p2) / (1.0f - p1);
+  unsigned bad = 0u;
   if (guard) {
-    const unsigned bad = guard[0] != 0u ? 1u : 0u;
+    bad = guard[0] != 0u ? 1u : 0u;
     guard[0] = 0u;
     guard[1] += bad;
     guard[2] = bad;
   }
+  return bad;
+}
+__global__ void optimizer_rate_kernel(int* step, int advance, rtxn_lr_schedule s, float lr, float table_lr, float beta1, float beta2,
+                                      float* lr_eff, float* table_lr_eff, float* factor_out, unsigned* guard) {
+  rate_update(step, advance, s, lr, table_lr, beta1, beta2, lr_eff, table_lr_eff, factor_out, guard);
 }
 
 struct GradList {
@@ -111,15 +125,25 @@ __global__ __launch_bounds__(kThreads) void check_gradients_kernel(GradList L, u
   if (any && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
 
+// The factor on the raw gradient: 1 / loss_scale by value or (DEV, rtxn_loss_scaler) the multiplier word of the scaler's state, a
+// kernel-argument pointer every lane reads at the same address: one scalar load.  The kernels stay the templates themselves, not
+// wrappers round a shared body: a wrapper moved the code of the by-value instantiations, this does not
+// (profiles/r14/compositor_scaled_ab.txt lists both builds).
+template <bool DEV>
+using grad_factor = std::conditional_t<DEV, const float*, float>;
+__device__ __forceinline__ float factor_value(float f) { return f; }
+__device__ __forceinline__ float factor_value(const float* f) { return *f; }
+
 // adam_kernel (train.hip) under the options.  lr_dev: the bias-corrected rate; factor_dev: factor(t), for the decay term
 // lr_t weight_decay w with lr_t = lr factor (no bias correction); skip (may be NULL): this step's skip word -- set, nothing of
 // the state is stored, and ZERO still clears the gradient.
-template <bool HALF_GRADS, bool ZERO>
+template <bool HALF_GRADS, bool ZERO, bool DEV>
 __global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
                                                             void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
                                                             const float* __restrict__ lr_dev, const float* __restrict__ factor_dev, float lr,
                                                             float weight_decay, const unsigned* __restrict__ skip, float beta1, float beta2,
-                                                            float eps, float inv_loss_scale) {
+                                                            float eps, grad_factor<DEV> inv_loss_scale_arg) {
+
   float* gf = static_cast<float*>(grads_v);
   __half* gh = static_cast<__half*>(grads_v);
   const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
@@ -137,6 +161,7 @@ __global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __res
     }
     return;
   }
+  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
   const float lr_eff = *lr_dev;
   const float decay = (lr * *factor_dev) * weight_decay;          // w -= lr_t weight_decay w
   auto one = [&](float g, float& mi, float& vi, float& w) {
@@ -181,13 +206,14 @@ __global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __res
 // adam_sparse_kernel (train.hip) under the options: lr_t = lr factor in the entry's own bias correction, the decay term on the
 // entries it updates, and the skip word -- set, the update counts keep their bits with the rest of the state, and ZERO clears
 // every non-zero gradient word (also a NaN, which is not == 0).
-template <bool HALF_GRADS, bool ZERO>
+template <bool HALF_GRADS, bool ZERO, bool DEV>
 __global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
                                                                    void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
                                                                    unsigned* __restrict__ steps, const float* __restrict__ factor_dev, float lr,
                                                                    float weight_decay, const unsigned* __restrict__ skip, float beta1,
-                                                                   float beta2, float eps, float inv_loss_scale, float log2_beta1,
+                                                                   float beta2, float eps, grad_factor<DEV> inv_loss_scale_arg, float log2_beta1,
                                                                    float log2_beta2) {
+
   float* gf = static_cast<float*>(grads_v);
   __half* gh = static_cast<__half*>(grads_v);
   const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)steps | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
@@ -210,6 +236,7 @@ __global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float
     }
     return;
   }
+  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
   const float lr_t = lr * *factor_dev;
   const float decay = lr_t * weight_decay;
   auto one = [&](float g, float& mi, float& vi, float& w, unsigned& st) {
@@ -377,8 +404,9 @@ extern "C" int rtxn_adam_step_opt(long n, float* master, void* params_fp16, void
   const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
   const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
   const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  static decltype(&adam_opt_kernel<false, false>) const table[2][2] = {{adam_opt_kernel<false, false>, adam_opt_kernel<false, true>},   // [HALF_GRADS][ZERO]
-                                                                       {adam_opt_kernel<true, false>, adam_opt_kernel<true, true>}};
+  static decltype(&adam_opt_kernel<false, false, false>) const table[2][2] = {
+      {adam_opt_kernel<false, false, false>, adam_opt_kernel<false, true, false>},   // [HALF_GRADS][ZERO]
+      {adam_opt_kernel<true, false, false>, adam_opt_kernel<true, true, false>}};
   table[half][zero]<<<blocks, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, effective_lr,
                                                                       opt->lr_factor, lr, wd, opt->skip_nonfinite ? opt->guard + 2 : nullptr, beta1,
                                                                       beta2, eps, 1.0f / loss_scale);
@@ -407,12 +435,339 @@ extern "C" int rtxn_adam_step_sparse_opt(long n, float* master, void* params_fp1
   const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
   const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
   const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  static decltype(&adam_sparse_opt_kernel<false, false>) const table[2][2] = {
-      {adam_sparse_opt_kernel<false, false>, adam_sparse_opt_kernel<false, true>},   // [HALF_GRADS][ZERO]
-      {adam_sparse_opt_kernel<true, false>, adam_sparse_opt_kernel<true, true>}};
+  static decltype(&adam_sparse_opt_kernel<false, false, false>) const table[2][2] = {
+      {adam_sparse_opt_kernel<false, false, false>, adam_sparse_opt_kernel<false, true, false>},   // [HALF_GRADS][ZERO]
+      {adam_sparse_opt_kernel<true, false, false>, adam_sparse_opt_kernel<true, true, false>}};
   table[half][zero]<<<gridx, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, param_steps,
                                                                      opt->lr_factor, lr, wd, opt->skip_nonfinite ? opt->guard + 2 : nullptr, beta1,
                                                                      beta2, eps, 1.0f / loss_scale, l2b1, l2b2);
   RTXN_LAUNCH_CHECK("adam_sparse_opt_kernel");
+  return RTXN_OK;
+}
+
+// ------------------------------------------------------------------------- dynamic loss scale, gradient-norm clipping
+namespace {
+
+// The scaler's state machine of include/rtxn.h, the one restatement host and device share (as schedule_factor is): st holds
+// the scale the step's gradients were made with; bad: the non-finite flag; sumsq: the sum of squares of the scaled gradients.
+__host__ __device__ inline void loss_scaler_advance(const rtxn_loss_scaler& c, rtxn_loss_scaler_state& st, bool bad, double sumsq, float D) {
+  const float s = st.scale;
+  if (bad) {
+    st.scale = fmaxf(c.min_scale, s * c.backoff);
+    st.good = 0;
+    st.backoffs += 1u;
+    return;
+  }
+  const float norm = (float)(sqrt(sumsq) / ((double)s * (double)D));
+  const float coef = c.max_grad_norm > 0.0f ? fminf(1.0f, c.max_grad_norm / (norm + 1e-6f)) : 1.0f;
+  st.multiplier = coef * (1.0f / (s * D));
+  st.grad_norm = norm;
+  st.clipped += coef < 1.0f ? 1u : 0u;
+  st.good += 1;
+  if (st.good >= c.growth_interval) {
+    const float grown = fminf(c.max_scale, s * c.growth);
+    st.good = 0;
+    st.growths += grown != s ? 1u : 0u;
+    st.scale = grown;
+  }
+}
+
+// the buffers of a statistics launch: GradList and each buffer's own block count, a function of its count and type alone
+struct StatList {
+  GradList g;
+  int blocks[RTXN_MAX_GRAD_BUFFERS];
+};
+
+__device__ __forceinline__ double square_d(float x) {
+  const double d = (double)x;
+  return d * d;
+}
+struct StatF32 {
+  __device__ __forceinline__ void operator()(unsigned w, bool& bad, double& s) const {
+    bad |= nonfinite_f32(w);
+    s += square_d(__uint_as_float(w));
+  }
+};
+struct StatH2 {
+  __device__ __forceinline__ void operator()(unsigned w, bool& bad, double& s) const {
+    bad |= nonfinite_h2(w);
+    s += square_d((float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)));
+    s += square_d((float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)));
+  }
+};
+
+// any_word with the sums: the four loads of a trip feed four sums of their own, joined pairwise at the end -- a fixed order
+template <typename Word>
+__device__ __forceinline__ double stat_words(const uint4* __restrict__ q, long body, long gid, long stride, Word word, bool& bad) {
+  double sa = 0.0, sb = 0.0, sc = 0.0, sd = 0.0;
+  long k = gid;
+  for (; k + 3 * stride < body; k += 4 * stride) {
+    const uint4 a = q[k], b = q[k + stride], c = q[k + 2 * stride], d = q[k + 3 * stride];
+    word(a.x, bad, sa); word(a.y, bad, sa); word(a.z, bad, sa); word(a.w, bad, sa);
+    word(b.x, bad, sb); word(b.y, bad, sb); word(b.z, bad, sb); word(b.w, bad, sb);
+    word(c.x, bad, sc); word(c.y, bad, sc); word(c.z, bad, sc); word(c.w, bad, sc);
+    word(d.x, bad, sd); word(d.y, bad, sd); word(d.z, bad, sd); word(d.w, bad, sd);
+  }
+  for (; k < body; k += stride) {
+    const uint4 w = q[k];
+    word(w.x, bad, sa); word(w.y, bad, sa); word(w.z, bad, sa); word(w.w, bad, sa);
+  }
+  return (sa + sb) + (sc + sd);
+}
+
+// check_gradients_kernel's pass and traffic shape; besides the OR every lane sums the squares of what it reads in double, in
+// visiting order.  blockIdx.y: the buffer, over L.blocks[b] blocks of its own (a block past them leaves whole).  The sums meet
+// in a fixed order -- wave (the DPP scan), then the block's four waves through LDS -- and one double per block is stored at
+// partials[buffer][block]: no atomic touches them.  The flag stays one atomic OR per wave after a ballot.
+__global__ __launch_bounds__(kThreads) void gradient_statistics_kernel(StatList L, unsigned* __restrict__ flag, double* __restrict__ partials) {
+  __shared__ double red[kThreads / 64];
+  const int b = blockIdx.y;
+  const int nb = L.blocks[b];
+  if ((int)blockIdx.x >= nb) return;
+  const long n = L.g.count[b];
+  const long gid = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)nb * kThreads;
+  const uintptr_t base = (uintptr_t)L.g.data[b];
+  const int esize = L.g.is_fp16[b] ? 2 : 4, per16 = 16 / esize;
+  long head = (long)(((16u - (unsigned)(base & 15u)) & 15u) / (unsigned)esize);
+  if (head > n) head = n;
+  const long body = (n - head) / per16, tail = head + body * per16;
+  bool bad = false;
+  double sum = 0.0;
+  if (L.g.is_fp16[b]) {
+    const unsigned short* h = reinterpret_cast<const unsigned short*>(base);
+    for (long i = gid; i < head; i += stride) {
+      bad |= (h[i] & 0x7c00u) == 0x7c00u;
+      sum += square_d((float)__builtin_bit_cast(_Float16, h[i]));
+    }
+    sum += stat_words(reinterpret_cast<const uint4*>(h + head), body, gid, stride, StatH2(), bad);
+    for (long i = tail + gid; i < n; i += stride) {
+      bad |= (h[i] & 0x7c00u) == 0x7c00u;
+      sum += square_d((float)__builtin_bit_cast(_Float16, h[i]));
+    }
+  } else {
+    const unsigned* f = reinterpret_cast<const unsigned*>(base);
+    for (long i = gid; i < head; i += stride) StatF32()(f[i], bad, sum);
+    sum += stat_words(reinterpret_cast<const uint4*>(f + head), body, gid, stride, StatF32(), bad);
+    for (long i = tail + gid; i < n; i += stride) StatF32()(f[i], bad, sum);
+  }
+  const bool any = __ballot(bad) != 0;
+  if (any && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+  const double wsum = wave_sum_d(sum);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wsum;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[(long)b * RTXN_GRAD_STATS_MAX_BLOCKS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// optimizer_rate_kernel's sibling, one block.  Thread t sums the partials t, t + 256, ... of each buffer in turn, the 256 sums
+// meet in a halving tree through LDS; thread 0 then does the rate kernel's work and moves the scaler's state.  One launch,
+// shared by every stepping path: their scales, multipliers and rates are the same bits by construction.
+__global__ __launch_bounds__(kThreads) void loss_scaler_kernel(int* step, int advance, rtxn_lr_schedule s, float lr, float table_lr, float beta1,
+                                                               float beta2, float* lr_eff, float* table_lr_eff, float* factor_out,
+                                                               unsigned* guard, rtxn_loss_scaler cfg, float divisor, StatList L) {
+  __shared__ double red[kThreads];
+  double acc = 0.0;
+  for (int b = 0; b < RTXN_MAX_GRAD_BUFFERS; ++b)
+    for (int j = threadIdx.x; j < L.blocks[b]; j += kThreads) acc += cfg.partials[(long)b * RTXN_GRAD_STATS_MAX_BLOCKS + j];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const unsigned bad = rate_update(step, advance, s, lr, table_lr, beta1, beta2, lr_eff, table_lr_eff, factor_out, guard);
+    rtxn_loss_scaler_state st = *cfg.state;
+    loss_scaler_advance(cfg, st, bad != 0u, red[0], divisor);
+    *cfg.state = st;
+  }
+}
+
+bool power_of_two(float x) {
+  int e;
+  return std::isfinite(x) && x > 0.0f && frexpf(x, &e) == 0.5f;
+}
+
+// rtxn_check_gradients' argument checks and compaction (buffers with count 0 are skipped), plus each buffer's block count:
+// four 16-byte words per lane and trip, at most RTXN_GRAD_STATS_MAX_BLOCKS.  need_data: the pointers are checked as well.
+int make_stat_list(const char* who, const rtxn_grad_buffer* buffers, int n_buffers, bool need_data, StatList* out, int* k_out, int* most_out) {
+  RTXN_REQUIRE(n_buffers >= 0 && n_buffers <= RTXN_MAX_GRAD_BUFFERS && (buffers || n_buffers == 0), "%s: n_buffers = %d (0 .. %d), buffers = %p", who,
+               n_buffers, (int)RTXN_MAX_GRAD_BUFFERS, (const void*)buffers);
+  StatList L = {};
+  int k = 0, most = 0;
+  for (int i = 0; i < n_buffers; ++i) {
+    const rtxn_grad_buffer& b = buffers[i];
+    RTXN_REQUIRE(b.count >= 0, "%s: buffers[%d].count = %ld", who, i, b.count);
+    if (b.count == 0) continue;
+    const int esize = b.is_fp16 ? 2 : 4;
+    if (need_data)
+      RTXN_REQUIRE(b.data && ((uintptr_t)b.data & (uintptr_t)(esize - 1)) == 0, "%s: buffers[%d].data = %p (NULL, or not aligned to its element)",
+                   who, i, b.data);
+    L.g.data[k] = b.data;
+    L.g.count[k] = b.count;
+    L.g.is_fp16[k] = b.is_fp16 != 0;
+    const long words = (b.count * esize + 15) / 16;
+    const long blocks = (words + 4 * kThreads - 1) / (4 * kThreads);
+    L.blocks[k] = (int)(blocks > RTXN_GRAD_STATS_MAX_BLOCKS ? RTXN_GRAD_STATS_MAX_BLOCKS : blocks);
+    most = L.blocks[k] > most ? L.blocks[k] : most;
+    ++k;
+  }
+  *out = L;
+  *k_out = k;
+  *most_out = most;
+  return RTXN_OK;
+}
+
+// what every entry point that takes the scaler asks of it and of the options beside it
+int check_scaled(const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const char* who) {
+  RTXN_REQUIRE(scaler, "%s: NULL scaler", who);
+  int rc = rtxn::check_loss_scaler(scaler, who, true);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(opt, "%s: NULL options: the loss scaler needs the non-finite guard (opt->skip_nonfinite, opt->guard)", who);
+  bool active = false;
+  rc = rtxn::check_optimizer_options(opt, who, true, &active);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(opt->skip_nonfinite && opt->guard && opt->lr_factor,
+               "%s: the loss scaler needs opt->skip_nonfinite with opt->guard and opt->lr_factor (skip_nonfinite = %d, guard = %p, lr_factor = %p)", who,
+               opt->skip_nonfinite, (void*)opt->guard, (void*)opt->lr_factor);
+  return RTXN_OK;
+}
+
+}  // namespace
+
+int rtxn::check_loss_scaler(const rtxn_loss_scaler* c, const char* who, bool need_buffers) {
+  RTXN_REQUIRE(c, "%s: NULL scaler", who);
+  RTXN_REQUIRE(power_of_two(c->init_scale), "%s: scaler->init_scale = %g is not a power of two", who, (double)c->init_scale);
+  RTXN_REQUIRE(power_of_two(c->growth) && c->growth >= 1.0f, "%s: scaler->growth = %g (a power of two >= 1)", who, (double)c->growth);
+  RTXN_REQUIRE(power_of_two(c->backoff) && c->backoff < 1.0f, "%s: scaler->backoff = %g (a power of two in (0, 1))", who, (double)c->backoff);
+  RTXN_REQUIRE(power_of_two(c->min_scale), "%s: scaler->min_scale = %g is not a power of two", who, (double)c->min_scale);
+  RTXN_REQUIRE(power_of_two(c->max_scale), "%s: scaler->max_scale = %g is not a power of two", who, (double)c->max_scale);
+  RTXN_REQUIRE(c->min_scale <= c->init_scale && c->init_scale <= c->max_scale, "%s: scaler->min_scale = %g <= init_scale = %g <= max_scale = %g does not hold",
+               who, (double)c->min_scale, (double)c->init_scale, (double)c->max_scale);
+  RTXN_REQUIRE(c->growth_interval >= 1, "%s: scaler->growth_interval = %d < 1", who, c->growth_interval);
+  RTXN_REQUIRE(std::isfinite(c->max_grad_norm) && c->max_grad_norm >= 0.0f, "%s: scaler->max_grad_norm = %g (finite, >= 0; 0: no clipping)", who,
+               (double)c->max_grad_norm);
+  if (need_buffers)
+    RTXN_REQUIRE(c->state && c->partials && ((uintptr_t)c->partials & 7) == 0 && ((uintptr_t)c->state & 3) == 0,
+                 "%s: scaler->state = %p, scaler->partials = %p (NULL or misaligned)", who, (void*)c->state, (void*)c->partials);
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_loss_scaler_check(const rtxn_loss_scaler* scaler) { return rtxn::check_loss_scaler(scaler, "rtxn_loss_scaler_check", false); }
+
+extern "C" size_t rtxn_loss_scaler_workspace_bytes(void) { return sizeof(double) * RTXN_MAX_GRAD_BUFFERS * RTXN_GRAD_STATS_MAX_BLOCKS; }
+
+extern "C" int rtxn_loss_scaler_init_state(const rtxn_loss_scaler* scaler, rtxn_loss_scaler_state* state_out) {
+  const int rc = rtxn::check_loss_scaler(scaler, "rtxn_loss_scaler_init_state", false);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(state_out, "rtxn_loss_scaler_init_state: NULL state_out");
+  rtxn_loss_scaler_state st = {};
+  st.scale = scaler->init_scale;
+  st.multiplier = 1.0f / scaler->init_scale;
+  *state_out = st;
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_loss_scaler_advance(const rtxn_loss_scaler* scaler, const rtxn_loss_scaler_state* state_in, int flag, double sumsq,
+                                        float divisor, rtxn_loss_scaler_state* state_out) {
+  const char* who = "rtxn_loss_scaler_advance";
+  const int rc = rtxn::check_loss_scaler(scaler, who, false);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(state_in && state_out, "%s: state_in = %p, state_out = %p", who, (const void*)state_in, (void*)state_out);
+  RTXN_REQUIRE(state_in->scale > 0.0f && divisor > 0.0f && sumsq >= 0.0, "%s: scale = %g, divisor = %g, sumsq = %g", who, (double)state_in->scale,
+               (double)divisor, sumsq);
+  rtxn_loss_scaler_state st = *state_in;
+  loss_scaler_advance(*scaler, st, flag != 0, sumsq, divisor);
+  *state_out = st;
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_gradient_statistics(const rtxn_grad_buffer* buffers, int n_buffers, unsigned* flag, const rtxn_loss_scaler* scaler,
+                                        rtxn_stream_t stream) {
+  const char* who = "rtxn_gradient_statistics";
+  int rc = rtxn::check_loss_scaler(scaler, who, true);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(flag, "%s: NULL flag", who);
+  StatList L;
+  int k = 0, most = 0;
+  rc = make_stat_list(who, buffers, n_buffers, true, &L, &k, &most);
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  if (k == 0) return RTXN_OK;
+  gradient_statistics_kernel<<<dim3((unsigned)most, (unsigned)k), kThreads, 0, rtxn::as_stream(stream)>>>(L, flag, scaler->partials);
+  RTXN_LAUNCH_CHECK("gradient_statistics_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_loss_scaler_step(const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_grad_buffer* buffers,
+                                     int n_buffers, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
+                                     float* effective_lr, float* table_effective_lr, float divisor, rtxn_stream_t stream) {
+  const char* who = "rtxn_loss_scaler_step";
+  int rc = check_scaled(opt, scaler, who);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(step && effective_lr, "%s: step = %p, effective_lr = %p", who, (void*)step, (void*)effective_lr);
+  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
+               (double)beta2);
+  RTXN_REQUIRE(divisor > 0.0f && std::isfinite(divisor), "%s: divisor = %g", who, (double)divisor);
+  StatList L;
+  int k = 0, most = 0;
+  rc = make_stat_list(who, buffers, n_buffers, false, &L, &k, &most);
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  loss_scaler_kernel<<<1, kThreads, 0, rtxn::as_stream(stream)>>>(step, advance, opt->schedule, lr, table_lr, beta1, beta2, effective_lr,
+                                                                  table_effective_lr, opt->lr_factor, opt->guard, *scaler, divisor, L);
+  RTXN_LAUNCH_CHECK("loss_scaler_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_adam_step_scaled(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                     const float* effective_lr, float lr, float beta1, float beta2, float eps,
+                                     const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_scaled";
+  const int rc = check_scaled(opt, scaler, who);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v, "%s: NULL buffer", who);
+  const long work = (n + 3) / 4;
+  const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
+  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  static decltype(&adam_opt_kernel<false, false, true>) const table[2][2] = {
+      {adam_opt_kernel<false, false, true>, adam_opt_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
+      {adam_opt_kernel<true, false, true>, adam_opt_kernel<true, true, true>}};
+  table[half][zero]<<<blocks, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, effective_lr,
+                                                                      opt->lr_factor, lr, wd, opt->guard + 2, beta1, beta2, eps,
+                                                                      &scaler->state->multiplier);
+  RTXN_LAUNCH_CHECK("adam_opt_kernel (device multiplier)");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_adam_step_sparse_scaled(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                            unsigned* param_steps, float lr, float beta1, float beta2, float eps,
+                                            const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_sparse_scaled";
+  const int rc = check_scaled(opt, scaler, who);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
+               (double)beta2);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps, "%s: NULL buffer", who);
+  const long blocks = (n / 4 + kThreads - 1) / kThreads;
+  const unsigned gridx = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
+  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
+  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  static decltype(&adam_sparse_opt_kernel<false, false, true>) const table[2][2] = {
+      {adam_sparse_opt_kernel<false, false, true>, adam_sparse_opt_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
+      {adam_sparse_opt_kernel<true, false, true>, adam_sparse_opt_kernel<true, true, true>}};
+  table[half][zero]<<<gridx, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, param_steps,
+                                                                     opt->lr_factor, lr, wd, opt->guard + 2, beta1, beta2, eps,
+                                                                     &scaler->state->multiplier, l2b1, l2b2);
+  RTXN_LAUNCH_CHECK("adam_sparse_opt_kernel (device multiplier)");
   return RTXN_OK;
 }

@@ -29,6 +29,14 @@ inline RegArgs make_reg_args(const rtxn_train_regularizer* reg, float loss_scale
   return ra;
 }
 
+// the factor of q_i in a kernel: RegArgs::k as make_reg_args formed it on the host or (DEV: the loss scale is a device word,
+// rtxn_loss_scaler) its expression in its order, an IEEE division, from the scale the wave read
+template <bool DEV>
+__device__ __forceinline__ float reg_k(const RegArgs& ra, float loss_scale, int n_rays) {
+  if constexpr (DEV) return loss_scale * ra.weight / (float)n_rays;
+  else return ra.k;
+}
+
 // midpoint of sub-interval k of a segment (volrender_aux_kernel's depth expression with u0 = 0.5)
 __device__ __forceinline__ float reg_midpoint(int k, float rK, float ts, float te) { return fmaf(((float)k + 0.5f) * rK, te - ts, ts); }
 

@@ -4007,8 +4007,10 @@ extern "C" int rtxn_hashgrid_backward_segments_live_jitter(const rtxn_hashgrid* 
 }
 
 // ------------------------------------------------------------------------- a whole batch, segment count on the device
+// scaler (rtxn_train_gradients_scaled): the compositor reads the loss scale from its device word, b->loss_scale is not read
 static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                                const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
+                                const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                                rtxn_stream_t stream) {
   RTXN_REQUIRE(b && b->mlp, "rtxn_train_gradients: NULL batch or model");
   const rtxn_mlp* m = b->mlp;
   int rc = check_train(m, "rtxn_train_gradients");
@@ -4071,7 +4073,11 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   rc = train_forward_impl(m, fused ? nullptr : b->encT, cap_samples, b->workspace, b->output_half, b->radiance, dc, stream, fwd);
   if (rc != RTXN_OK) return rc;
   // launch_volrender_cuda, loss->evaluate, launch_volrender_backward_cuda (main.cu:737-767): per ray, no sample count needed
-  if (b->vr_mode == RTXN_VR_NERF) {
+  if (scaler) {                                                // vr_mode is RTXN_VR_NERF: the entry point saw to that
+    rc = rtxn_volrender_scaled_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, 0.0f, b->pixels,
+                                     b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, loss, reg, scaler, stream);
+    if (rc != RTXN_OK) return rc;
+  } else if (b->vr_mode == RTXN_VR_NERF) {
     rc = reg  ? rtxn_volrender_reg_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
                                          b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, loss, reg, stream)
        : loss ? rtxn_volrender_loss_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
@@ -4117,7 +4123,7 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   return rc;
 }
 
-extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, nullptr, nullptr, nullptr, stream); }
+extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, nullptr, nullptr, nullptr, nullptr, stream); }
 
 // over a background: the one difference is the compositor (rtxn_volrender_l2_train_ex); NULL / NONE + 3 channels: the plain call
 extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
@@ -4125,7 +4131,7 @@ extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_tra
   bool active = false;
   const int rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_ex", &active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, nullptr, nullptr, nullptr, stream);
+  return train_gradients_impl(b, active ? bg : nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the sampler's jitter (RTXN_SAMPLING_JITTER_WORLD): both optional, NULL + NULL is rtxn_train_gradients
@@ -4137,7 +4143,7 @@ extern "C" int rtxn_train_gradients_jitter(const rtxn_train_batch* b, const rtxn
   bool active = false;
   rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_jitter", &active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, nullptr, nullptr, stream);
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the loss of rtxn_train_loss: the compositor (RTXN_VR_NERF: rtxn_volrender_loss_train) or the loss launch between
@@ -4152,22 +4158,42 @@ extern "C" int rtxn_train_gradients_loss(const rtxn_train_batch* b, const rtxn_t
   if (rc != RTXN_OK) return rc;
   rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, b->vr_mode, "rtxn_train_gradients_loss", &loss_active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, nullptr, stream);
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the distortion regulariser (rtxn_train_regularizer): the compositor (rtxn_volrender_reg_train) is the one
 // difference; NULL, or weight 0 without outputs: rtxn_train_gradients_loss
-extern "C" int rtxn_train_gradients_reg(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                                        const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
-  RTXN_REQUIRE(b, "rtxn_train_gradients_reg: NULL batch");
-  int rc = rtxn::check_sample_jitter("rtxn_train_gradients_reg", b->sample_type, jitter, b->vr_mode);
+// rtxn_train_gradients_reg and rtxn_train_gradients_scaled: with the scaler (rtxn_loss_scaler, optimizer.hip) the compositor
+// is rtxn_volrender_scaled_train, the RTXN_VR_NERF one alone
+static int train_gradients_reg(const char* who, const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                               const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                               rtxn_stream_t stream) {
+  RTXN_REQUIRE(b, "%s: NULL batch", who);
+  int rc = rtxn::check_sample_jitter(who, b->sample_type, jitter, b->vr_mode);
   if (rc != RTXN_OK) return rc;
   bool active = false, loss_active = false, reg_active = false;
-  rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_reg", &active);
+  rc = rtxn::check_train_background(bg, b->vr_mode, who, &active);
   if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, b->vr_mode, "rtxn_train_gradients_reg", &loss_active);
+  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, b->vr_mode, who, &loss_active);
   if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_regularizer(reg, b->vr_mode, b->sample_type, "rtxn_train_gradients_reg", &reg_active);
+  rc = rtxn::check_train_regularizer(reg, b->vr_mode, b->sample_type, who, &reg_active);
   if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, reg_active ? reg : nullptr, stream);
+  if (scaler) {
+    rc = rtxn::check_loss_scaler(scaler, who, true);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(b->vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor, which reads the scale from device memory "
+                 "(vr_mode = %d: the three-launch route takes it by value)", who, b->vr_mode);
+  }
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, reg_active ? reg : nullptr, scaler, stream);
+}
+
+extern "C" int rtxn_train_gradients_reg(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                        const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
+  return train_gradients_reg("rtxn_train_gradients_reg", b, bg, jitter, loss, reg, nullptr, stream);
+}
+
+extern "C" int rtxn_train_gradients_scaled(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                                           rtxn_stream_t stream) {
+  return train_gradients_reg(scaler ? "rtxn_train_gradients_scaled" : "rtxn_train_gradients_reg", b, bg, jitter, loss, reg, scaler, stream);
 }

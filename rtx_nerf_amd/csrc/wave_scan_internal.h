@@ -33,6 +33,27 @@ __device__ __forceinline__ float wave_sum(float v) { return lane63(wave_incl_sca
 // lane - 1's value (lane 0: 0): DPP wave_shr:1
 __device__ __forceinline__ float lane_below(float v) { return dpp_term<0x138, 0xf>(v); }
 
+// The same sum for a double, the two words of each value moved by the same DPP pattern (a row or lane the pattern does not
+// reach reads both words as 0, i.e. +0.0): a fixed order, the same in every launch.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_term_d(double v) {
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, 0xf, true);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROW_MASK, 0xf, true);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+  v += dpp_term_d<0x111, 0xf>(v);
+  v += dpp_term_d<0x112, 0xf>(v);
+  v += dpp_term_d<0x114, 0xf>(v);
+  v += dpp_term_d<0x118, 0xf>(v);
+  v += dpp_term_d<0x142, 0xa>(v);
+  v += dpp_term_d<0x143, 0xc>(v);
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
 struct alignas(8) half4 {
   __half x, y, z, w;
 };

@@ -59,14 +59,24 @@ class Trainer:
                  hashgrid=None, n_dir_freqs=4, batch_rays=4096, max_segments=None, lr=1e-3, loss_scale=128.0,
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
                  target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0,
-                 distortion_weight=0.0, lr_schedule=None, weight_decay=0.0, skip_nonfinite=False):
-        """lr_schedule: None, or api.lr_schedule(...) / a dict of its arguments / a preset name ("nerf": x0.1 per 250k steps;
+                 distortion_weight=0.0, lr_schedule=None, weight_decay=0.0, skip_nonfinite=False, max_grad_norm=None):
+        """loss_scale: a float (fixed, the reference's), "dynamic" (api.loss_scaler()'s defaults: from 128, x2 per 2000 clean steps, x0.5
+        per skipped step, within [1, 65536]), or api.loss_scaler(init_scale=..., growth_interval=..., ...) / a dict
+        of its arguments: the scale lives in device memory, is multiplied by `backoff` when a step's gradients are not finite (the
+        step is skipped) and by `growth` after growth_interval clean steps, and the compositor, the optimizer, the captured and the
+        one-call step all read it there (librtxn: rtxn_loss_scaler, rtxn_train_step_scaled).  max_grad_norm: clip the
+        total gradient norm (MLP and table together, unscaled) to this value by torch.nn.utils.clip_grad_norm_'s rule; with a float
+        loss_scale the scale stays fixed (a power of two then) and only the clipping is added, through the same path.  Either one
+        switches the non-finite guard on (skipped_steps), needs mode "nerf" and the fused compositor.  loss_scale_now, grad_norm,
+        clipped_steps, scale_backoffs and scale_growths are device tensors no stepping method reads; checkpoints hold them.  Both at
+        their defaults: nothing is allocated and every call is the one made without the arguments.
+        lr_schedule: None, or api.lr_schedule(...) / a dict of its arguments / a preset name ("nerf": x0.1 per 250k steps;
         "instant_ngp": x0.33 every 10k steps after 20k): the factor on lr and on the table's 10 lr, evaluated on the device from the
         step counter (librtxn: rtxn_optimizer_options, rtxn_optimizer_rate); current_lr() is its host restatement.
         weight_decay: AdamW's decoupled decay w -= lr_t weight_decay w, on the MLP only.  skip_nonfinite: a step whose gradients hold
         an Inf or a NaN leaves weights, moments and update counts as they are, clears the gradients and counts one up in
         skipped_steps (a device tensor, never read by the stepping methods); step_count advances all the same, so Adam's bias
-        correction counts attempted steps.  The loss scale is not adapted: a growing skipped_steps says to lower it.  All three at
+        correction counts attempted steps.  A fixed loss scale stays what it is (loss_scale="dynamic" lowers it on every skipped step).  All three at
         their defaults (or a constant schedule without warm-up): nothing is allocated and every call is the one made without the
         arguments.  Configuration, not state, as loss is; checkpoints hold only the skipped count.
         distortion_weight: lambda_d of mip-NeRF 360's distortion regulariser (librtxn: rtxn_volrender_reg_train /
@@ -105,7 +115,8 @@ class Trainer:
         self._init_jitter(sample_jitter, jitter_seed)
         self._init_loss(loss, loss_param, opacity_weight)
         self._init_regularizer(distortion_weight)
-        self._init_optimizer(lr_schedule, weight_decay, skip_nonfinite)
+        self._init_scaler(loss_scale, max_grad_norm)
+        self._init_optimizer(lr_schedule, weight_decay, skip_nonfinite or self._scaler_cfg is not None)
         self.image_set = None      # attach_images(): batches drawn on the device
         self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
         self._draw_step = None
@@ -158,6 +169,14 @@ class Trainer:
             self._opt_step = torch.zeros(1, dtype=torch.int32, device=d)
             self._opt_step_host = 0
             self._opt_lr = torch.zeros(2, device=d)
+        # the loss scaler: its eight state words, the statistics kernel's per-block sums, and the struct over both
+        self._scaler = self._scaler_state = self._scaler_ws = None
+        if self._scaler_cfg is not None:
+            c = self._scaler_cfg
+            self._scaler_state = api.loss_scaler_state_tensor(c, device=d)
+            self._scaler_ws = api.loss_scaler_workspace(device=d)
+            self._scaler = api.loss_scaler(c.init_scale, c.growth, c.backoff, c.growth_interval, c.min_scale, c.max_scale, c.max_grad_norm,
+                                           state=self._scaler_state, partials=self._scaler_ws)
         # 64-wide models (configs[2]): forward without saved activations + ONE fused backward kernel that recomputes them and
         # keeps every weight gradient on the chip (librtxn: mlp_bwd_fused64_kernel).  RTXN_TRAIN_RECOMPUTE=0 selects the
         # three-kernel path (saved activations, dgrad chain, weight-gradient GEMM) for A/B runs.
@@ -303,6 +322,68 @@ class Trainer:
             raise ValueError("Trainer: distortion_weight > 0 needs the fused training compositor (RTXN_TRAIN_FUSE_COMPOSITOR=0 selects "
                              "the three-launch compositor, which has no regulariser)")
         self.distortion_weight = lam
+
+    def _init_scaler(self, loss_scale, max_grad_norm):
+        """loss_scale / max_grad_norm -> self._scaler_cfg (a struct without buffers, or None) and self.loss_scale (the fixed or the
+        initial scale); the library's own rules (rtxn_loss_scaler_check), before anything is allocated"""
+        try:
+            mgn = 0.0 if max_grad_norm is None else float(max_grad_norm)
+            if not (np.isfinite(mgn) and mgn >= 0.0):
+                raise ValueError("max_grad_norm must be finite and >= 0")
+            if isinstance(loss_scale, str):
+                if loss_scale != "dynamic":
+                    raise ValueError("a float, 'dynamic' or api.loss_scaler(...)")
+                cfg = api.loss_scaler()
+            elif isinstance(loss_scale, (dict, api._lib.LossScaler)):
+                cfg = api.loss_scaler(loss_scale)
+            elif mgn > 0.0:       # a fixed scale through the scaled path: nothing moves it
+                ls = float(loss_scale)
+                cfg = api.loss_scaler(init_scale=ls, growth=1.0, backoff=0.5, growth_interval=1, min_scale=ls, max_scale=ls)
+            else:
+                self._scaler_cfg, self.loss_scale = None, loss_scale
+                return
+            if max_grad_norm is not None:
+                cfg = api.loss_scaler(cfg.init_scale, cfg.growth, cfg.backoff, cfg.growth_interval, cfg.min_scale, cfg.max_scale, mgn)
+        except (api._lib.RtxnError, TypeError, ValueError) as e:
+            raise ValueError(f"Trainer: loss_scale = {loss_scale!r}, max_grad_norm = {max_grad_norm!r}: {e}") from None
+        if self.mode != "nerf":
+            raise ValueError("Trainer: a dynamic loss scale / max_grad_norm needs mode='nerf': the scale is read from device memory by "
+                             "the fused NeRF compositor alone")
+        if os.environ.get("RTXN_TRAIN_FUSE_COMPOSITOR", "1") == "0":
+            raise ValueError("Trainer: a dynamic loss scale / max_grad_norm needs the fused training compositor "
+                             "(RTXN_TRAIN_FUSE_COMPOSITOR=0 selects the three-launch compositor, which takes the scale by value)")
+        self._scaler_cfg, self.loss_scale = cfg, float(cfg.init_scale)
+
+    def _scaler_word(self, k, as_float=False):
+        if self._scaler_state is None:
+            return None
+        w = self._scaler_state[k:k + 1]
+        return w.view(torch.float32) if as_float else w
+
+    @property
+    def loss_scale_now(self):
+        """device float32[1]: the scale the NEXT compositor launch reads (None without a scaler)"""
+        return self._scaler_word(0, True)
+
+    @property
+    def grad_norm(self):
+        """device float32[1]: the last clean step's unscaled total gradient norm (None without a scaler)"""
+        return self._scaler_word(6, True)
+
+    @property
+    def clipped_steps(self):
+        """device int32[1]: steps whose gradient was clipped so far (None without a scaler)"""
+        return self._scaler_word(5)
+
+    @property
+    def scale_backoffs(self):
+        """device int32[1]: times the scale was lowered = steps skipped under the scaler (None without a scaler)"""
+        return self._scaler_word(3)
+
+    @property
+    def scale_growths(self):
+        """device int32[1]: times the scale was raised (None without a scaler)"""
+        return self._scaler_word(4)
 
     def _init_optimizer(self, lr_schedule, weight_decay, skip_nonfinite):
         """the library's own rules (rtxn_optimizer_options_check), before anything is allocated"""
@@ -586,7 +667,10 @@ class Trainer:
                     self.dtable.zero_()
         self._dp_pending = None
         if S == 0:
-            if self._reg is not None:
+            if self._scaler is not None:
+                api.volrender_scaled_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self._scaler,
+                                           self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
+            elif self._reg is not None:
                 api.volrender_reg_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
                                         self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
             elif self._loss is not None and self.mode == "nerf" and self.fuse_compositor:
@@ -603,7 +687,10 @@ class Trainer:
         self._forward(S, save=not self.two_pass, jitter=jit)
         if self.mode == "nerf" and self.fuse_compositor:
             with _Stage(self, "composite_fwd+l2+bwd"):   # one launch: the backward's first sweep IS the forward
-                if self._reg is not None:
+                if self._scaler is not None:             # the loss scale is the scaler's device word
+                    api.volrender_scaled_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self._scaler,
+                                               self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
+                elif self._reg is not None:
                     api.volrender_reg_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
                                             self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
                 elif self._loss is not None:
@@ -668,7 +755,7 @@ class Trainer:
             if self._opt_step_host != self.step_count:
                 self._opt_step.fill_(self.step_count)
             with _Stage(self, "adam"):
-                self._apply_opt(self._opt_step, self._opt_lr, self.loss_scale * grad_divisor)
+                self._apply_opt(self._opt_step, self._opt_lr, self.loss_scale * grad_divisor, grad_divisor)
             self.step_count += 1
             self._opt_step_host = self.step_count
             self._grads_clean = True           # cleared as they were consumed, skipped step or not
@@ -692,16 +779,37 @@ class Trainer:
                 else:
                     api.adam_step(self.table_master, self.table, self.dtable, self.table_m, self.table_v, self.step_count, **kw)
 
-    def _apply_opt(self, step, rates, ls):
+    def _apply_opt(self, step, rates, ls, grad_divisor=1.0):
         """The optimizer under rtxn_optimizer_options, as rtxn_train_step_opt sequences it: the gradients are complete (data
         parallel: summed), so one pass looks for Inf / NaN, the rate kernel advances the device int32 `step`, writes the factor,
         the two bias-corrected rates (`rates`: MLP, dense table) and the skip word, and the _opt Adam kernels read them.  Every
-        gradient is cleared as it is consumed.  Capturable; nothing is read on the host."""
+        gradient is cleared as it is consumed.  Capturable; nothing is read on the host.
+        With the loss scaler, as rtxn_train_step_scaled: the statistics pass in place of the check, the scaler kernel in place of the
+        rate kernel (grad_divisor is its D), and the Adam kernels that read the multiplier it leaves; `ls` is not read."""
         hash_ = self.encoding == "hash"
         lo = self.hashed_lo if hash_ else 0
         parts = []
         if hash_:
             parts = [(slice(0, lo), self.dtable[:lo]), (slice(lo, None), self.dtable_h)] if self.hash_fp16 else [(slice(None), self.dtable)]
+        if self._scaler is not None:
+            bufs = [self.dparams] + [g for _, g in parts]
+            api.gradient_statistics(bufs, self._opt_guard, self._scaler)
+            api.loss_scaler_step(self._opt, self._scaler, bufs, step, rates[0:1], lr=self.lr, table_lr=self.lr * 10.0,
+                                 table_effective_lr=rates[1:2], divisor=grad_divisor)
+            api.adam_step_scaled(self.master, self.params, self.dparams, self.adam_m, self.adam_v, rates[0:1], self._opt, self._scaler,
+                                 lr=self.lr, zero_grads=True)
+            self.net.set_params_training(self.params)
+            for sl, g in parts:
+                if not g.numel():
+                    continue
+                if self.table_adam_sparse:
+                    api.adam_step_sparse_scaled(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl],
+                                                self.table_steps[sl], self._opt, self._scaler, lr=self.lr * 10.0, eps=1e-15, zero_grads=True,
+                                                weight_decay=False)
+                else:
+                    api.adam_step_scaled(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], rates[1:2], self._opt,
+                                         self._scaler, lr=self.lr * 10.0, eps=1e-15, zero_grads=True, weight_decay=False)
+            return
         if self.skip_nonfinite:
             api.check_gradients([self.dparams] + [g for _, g in parts], self._opt_guard)
         api.optimizer_rate(self._opt, step, rates[0:1], lr=self.lr, table_lr=self.lr * 10.0, table_effective_lr=rates[1:2])
@@ -832,6 +940,30 @@ class Trainer:
                         table_adam_v=self.table_v, table_adam_steps=self.table_steps)
         return arrs
 
+    _SCALER_WORDS = (("scale", 0, True), ("multiplier", 1, True), ("good", 2, False), ("backoffs", 3, False), ("growths", 4, False),
+                     ("clipped", 5, False), ("grad_norm", 6, True))
+
+    def _scaler_header(self):
+        """the scaler's state for a checkpoint header (None without a scaler); a float32 survives JSON's double exactly"""
+        if self._scaler_state is None:
+            return None
+        w = self._scaler_state.cpu().numpy()
+        return {nm: (float(w.view(np.float32)[k]) if fl else int(w[k])) for nm, k, fl in self._SCALER_WORDS}
+
+    def _scaler_restore(self, saved):
+        """the state a loaded run continues from: the file's, or (a file written without a scaler) the initial one"""
+        if self._scaler_state is None:
+            return
+        w = api.loss_scaler_initial_state(self._scaler)
+        if saved:
+            for nm, k, fl in self._SCALER_WORDS:
+                if nm in saved:
+                    if fl:
+                        w.view(np.float32)[k] = np.float32(saved[nm])
+                    else:
+                        w[k] = int(saved[nm])
+        self._scaler_state.copy_(torch.from_numpy(w))
+
     def save_checkpoint(self, path):
         """The header's "draw_count" is the number of batches DRAWN (attach_images): the loaded trainer draws batch draw_count
         next.  With capture_step(prefetch=True, draw=True) one batch is drawn ahead of the step that trains on it, so a
@@ -840,6 +972,7 @@ class Trainer:
         cfg = self.net.cfg
         header = {"step": self.step_count, "draw_count": self.draw_count,
                   "skipped_steps": 0 if self._opt_guard is None else int(self._opt_guard[1].item()),
+                  "loss_scaler": self._scaler_header(),
                   "encoding": self.encoding, "grid_res": self.R, "mode": self.mode,
                   "mlp": {f: getattr(cfg, f) for f, _ in cfg._fields_},
                   "hashgrid": None if self.hg is None else {**{f: getattr(self.hg.cfg, f) for f, _ in self.hg.cfg._fields_},
@@ -890,6 +1023,7 @@ class Trainer:
         if self._opt_guard is not None:                          # the schedule itself has no state: it continues from `step`
             self._opt_guard.zero_()
             self._opt_guard[1] = int(header.get("skipped_steps", 0))
+        self._scaler_restore(header.get("loss_scaler"))
         self.net.set_params(self.params)
         return header
 
@@ -992,6 +1126,7 @@ class Trainer:
         tstate = (self.table_master.clone(), self.table.clone(), self.table_m.clone(), self.table_v.clone(),
                   self.table_steps.clone()) if self.encoding == "hash" else None
         guard = None if self._opt_guard is None else self._opt_guard.clone()
+        scaler_state = None if self._scaler_state is None else self._scaler_state.clone()
         clear_grads = self._clear_grads
         with torch.cuda.stream(side):
             clear_grads()
@@ -1011,6 +1146,8 @@ class Trainer:
                 dst.copy_(src)
         if guard is not None:
             self._opt_guard.copy_(guard)            # a warm-up pass over non-finite inputs is not a skipped step
+        if scaler_state is not None:
+            self._scaler_state.copy_(scaler_state)  # ... and moves neither the scale nor its counters
         self.net.set_params_training(self.params)
         self._g_step.fill_(self.step_count)
         self._g_step_host = self.step_count     # host mirror of the device counter (see _sync_device_step)
@@ -1148,7 +1285,7 @@ class Trainer:
             api.draw_batch_launch(self._entry_draw)
             self._draw_step.add_(1)
             self.draw_count += 1
-        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt)
+        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt, self._scaler)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -1195,7 +1332,7 @@ class Trainer:
                             dtable=self.dtable if hash_ else None, dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
                             live_ws=self.live_ws if self.live_segments else None, skip_table_backward=self._g_split,
                             workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit, loss=self._loss,
-                            regularizer=st["reg"])
+                            regularizer=st["reg"], scaler=self._scaler)
 
     def _captured_table_bwd(self, k):
         """the hash scatter of set k's batch over the live list the gradient graph left (its count is on the device)"""
@@ -1207,7 +1344,7 @@ class Trainer:
         if self._opt is not None:
             # the rate kernel advances the counter's low word itself and evaluates schedule and bias correction from it: no table
             # lookup, so the schedule keeps running past _LR_TABLE steps
-            self._apply_opt(self._g_step.view(torch.int32)[:1], self._g_lr[0], self.loss_scale * grad_divisor)
+            self._apply_opt(self._g_step.view(torch.int32)[:1], self._g_lr[0], self.loss_scale * grad_divisor, grad_divisor)
             return
         self._g_step.add_(1)
         torch.clamp(self._g_step, max=self._LR_TABLE - 1, out=self._g_idx)

@@ -3,7 +3,7 @@
 configs[2]-shaped trainer (4096 rays, hash grid + 4x64 MLP, 128^3 stand-in occupancy) with the same targets, and the compositor
 kernels alone:
   (a) off            distortion_weight = 0: rtxn_volrender_l2_train's volrender_l2_multi_kernel<4>, the step as it was;
-  (b) on             distortion_weight = --weight: composite_train_multi_kernel<true, 4>, and the traversal's write pass stores
+  (b) on             distortion_weight = --weight: composite_train_multi_kernel<true, 4, false>, and the traversal's write pass stores
                      t_start / t_end;
   (c) kernel_l2 / kernel_reg: api.volrender_l2_train against api.volrender_reg_train (the same weight, L_r written) on the same
       radiance, step lengths and targets (launch + kernel).

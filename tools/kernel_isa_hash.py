@@ -4,7 +4,10 @@ contain the given substrings.  A PMC summary under profiles/ is stamped with the
 (tools/make_pmc_json.py) and bench.py quotes its `traffic` only while the library being run still carries the same code --
 the measured ISA, not the source file, is what is compared (a comment edit does not invalidate a measurement, a compiler
 flag that changes the code does).
-  python tools/kernel_isa_hash.py mlp_fwd16_kernelILi128ELi3ELi10ELi2ELi12ELi1ELi3E [more substrings...]"""
+  python tools/kernel_isa_hash.py mlp_fwd16_kernelILi128ELi3ELi10ELi2ELi12ELi1ELi3E [more substrings...]
+  python tools/kernel_isa_hash.py --list [--lib PATH] substring...    one line per matching function: bytes, sha-256 (16 digits)
+      of its machine code ALONE, name -- the fingerprint above also covers the symbol name, so it moves when a template gains a
+      parameter although no instruction did; PATH may be librtxn.so or one translation unit's object file"""
 import hashlib
 import os
 import re
@@ -81,6 +84,24 @@ def kernel_isa_sha16(substrings, lib_path=None):
     return h.hexdigest()[:16]
 
 
+def kernel_isa_listing(substrings, lib_path=None):
+    """[(mangled name, code bytes, sha-256[:16] of the code alone)] of every matching function, in name order"""
+    lib_path = lib_path or os.path.join(ROOT, "rtx_nerf_amd", "librtxn.so")
+    found = {}
+    for co in _code_objects(lib_path):
+        for name, code in _functions(co).items():
+            if any(s in name for s in substrings):
+                found[name] = code
+    return [(name, len(found[name]), hashlib.sha256(found[name]).hexdigest()[:16]) for name in sorted(found)]
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--list"]:
+        args, lib = sys.argv[2:], None
+        if args[:1] == ["--lib"]:
+            lib, args = args[1], args[2:]
+        for name, size, sha in kernel_isa_listing(args, lib):
+            print(f"{size:7d}  {sha}  {name}")
+        sys.exit(0)
     subs = sys.argv[1:] or ["mlp_fwd16_kernelILi128ELi3ELi10ELi2ELi12ELi1ELi3E"]
     print(kernel_isa_sha16(subs))

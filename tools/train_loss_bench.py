@@ -3,7 +3,7 @@
 configs[2]-shaped trainer (4096 rays, hash grid + 4x64 MLP, 128^3 stand-in occupancy), all over a constant white background
 with the same RGBA targets, and the compositor kernels alone:
   (a) l2             the L2 step: rtxn_volrender_l2_train_ex's volrender_l2_bg_multi_kernel<4>, as before the losses existed;
-  (b) huber          loss="huber": composite_train_multi_kernel<false, 4>;
+  (b) huber          loss="huber": composite_train_multi_kernel<false, 4, false>;
   (c) huber_alpha    loss="huber", opacity_weight=0.1: the same kernel with the alpha term and the opacity store;
   (d) kernel_l2_bg / kernel_loss: api.volrender_l2_train_ex against api.volrender_loss_train (huber, lambda = 0.1, opacities
       written) on the same radiance, step lengths and targets (launch + kernel).
