@@ -10,6 +10,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego --loss huber --opacity-weight 0.1     (Huber, and the frames' alpha fitted)
   python examples/train_synthetic.py --data /path/to/lego --distortion-weight 0.01 --loss-scale 4096     (mip-NeRF 360's distortion loss)
   python examples/train_synthetic.py --data /path/to/lego --steps 20000 --lr-schedule cosine:20000 --weight-decay 1e-6 --skip-nonfinite
+  python examples/train_synthetic.py --data /path/to/lego --steps 20000 --ema-decay 0.99     (held-out PSNR of the live and the averaged weights)
 """
 import argparse
 import json
@@ -77,6 +78,9 @@ def main():
     ap.add_argument("--weight-decay", type=float, default=0.0, help="AdamW's decoupled weight decay on the MLP")
     ap.add_argument("--skip-nonfinite", action="store_true",
                     help="skip a step whose gradients hold an Inf or a NaN instead of stepping Adam on them; the number skipped is printed")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep the debiased exponential moving average of the weights with this decay (Trainer(ema_decay=...), DESIGN 5.15) "
+                         "and report the held-out PSNR of the averaged weights beside the live ones")
     a = ap.parse_args()
     loss_scale = api.loss_scaler(growth_interval=a.growth_interval) if a.loss_scale == "dynamic" else float(a.loss_scale)
     schedule = a.lr_schedule
@@ -104,17 +108,39 @@ def main():
         rays, focal = RayDataset.from_images(train_ds, origin_scale=0.1)
         n_rays, held = rays.n, sum(t.numel() * t.element_size() for t in (rays.rays_o, rays.rays_d, rays.pixels))
     R = a.grid
-    tr = Trainer(R, None, encoding=a.encoding, n_neurons=64, n_hidden_layers=2 if a.encoding == "hash" else 4,
+    model = dict(encoding=a.encoding, n_neurons=64, n_hidden_layers=2 if a.encoding == "hash" else 4,
                  hashgrid=dict(n_levels=8, n_features=2, log2_hashmap_size=15, base_resolution=8, per_level_scale=1.5),
                  batch_rays=max(a.batch, ds.image_width * ds.image_height), max_segments=max(a.batch, ds.image_width * ds.image_height) * (3 * R),
-                 lr=1e-2 if a.encoding == "hash" else 2e-3, density_scale=150.0, loss=a.loss, opacity_weight=a.opacity_weight,
+                 density_scale=150.0)
+    tr = Trainer(R, None, lr=1e-2 if a.encoding == "hash" else 2e-3, loss=a.loss, opacity_weight=a.opacity_weight,
                  background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C, distortion_weight=a.distortion_weight,
                  loss_scale=loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite,
-                 max_grad_norm=a.max_grad_norm)
+                 max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay, **model)
     white = (1.0, 1.0, 1.0) if rgba else None
 
     def render():
         return tr.render_rays(o_t, d_t, background=white)
+
+    viewer = []
+
+    def render_ema():
+        """the held-out view from the averaged weights: a second model of the same shape set to ema_parameters(), behind the
+        live model's occupancy (render_rays itself stays on the live weights)"""
+        if not viewer:
+            viewer.append(Trainer(R, None, **model))
+        view = viewer[0]
+        mlp, table = tr.ema_parameters()
+        view.params.copy_(mlp.half())
+        view.net.set_params_training(view.params)
+        if table is not None:
+            view.table.copy_(table.half())
+        if tr.occ is not None:
+            view._set_occupancy(tr.occ.clone())
+        return view.render_rays(o_t, d_t, background=white)
+
+    def held_out():
+        live = f"{psnr(render(), gt):.2f} dB"
+        return live if a.ema_decay is None else f"{live} live, {psnr(render_ema(), gt):.2f} dB averaged"
 
     if a.device_batches:
         tr.attach_images(images)
@@ -131,9 +157,9 @@ def main():
         if (it + 1) % 100 == 0:
             frac = tr.update_occupancy(threshold=0.01) if it + 1 >= 200 else 1.0
             print(f"step {it + 1:5d} loss {float(loss.item()):.6f} lr {tr.current_lr():.3e} occupied {100 * frac:.1f}% held-out PSNR "
-                  f"{psnr(render(), gt):.2f} dB", flush=True)
+                  f"{held_out()}", flush=True)
     print(f"final held-out PSNR after {a.steps} steps ({'device batches' if a.device_batches else 'ray dataset'}): "
-          f"{psnr(render(), gt):.2f} dB")
+          f"{held_out()}")
     if tr.loss_scale_now is not None:
         print(f"loss scale now {float(tr.loss_scale_now.item()):g}: {int(tr.skipped_steps.item())} steps skipped, "
               f"{int(tr.scale_backoffs.item())} backoffs, {int(tr.scale_growths.item())} growths, {int(tr.clipped_steps.item())} steps clipped, "

@@ -1244,6 +1244,80 @@ int rtxn_train_step_scaled(const rtxn_train_step_args* args, const rtxn_train_ba
                            const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
                            const rtxn_loss_scaler* scaler, rtxn_stream_t stream);
 
+/* ---- exponential moving average of the weights (tiny-cuda-nn's EMA optimizer) ------------------------------
+ * d: the decay, 0 < d < 1.  u: the number of APPLIED updates, a device word (state->updates); a step the non-finite guard skips
+ * does not advance it.  Per parameter an accumulator s, fp32, zero at the start.  After Adam's update number u has written w_u:
+ *   s_u = d s_{u-1} + (1 - d) w_u                 -- float: two products and a sum, 1 - d formed once on the host
+ *   read-out:  w_ema = s_u correction(u),   correction(u) = (float)(1 / (1 - d^u))   -- in double ((double)d), rounded once
+ *              u = 0: w_ema = w, and correction(0) = 1
+ * (the debiased form: the initial weights carry no weight of their own).  The rate kernel advances u behind its other work,
+ * unless this step's skip word is set, and stores correction(u) beside it.
+ * DENSE form (the MLP; a table stepped by the dense rule): the line above for every element, in the Adam kernel, behind the
+ * weight-decay term.
+ * LAZY form (a table under the sparse rule, whose kernel leaves an element with a zero gradient untouched): a stamp e per
+ * parameter (uint32, zero at the start) holds the u at which s was last current.  Between two touches w is a constant, and over a
+ * constant the recurrence has a closed form: catch_up(s, w, gap) = gap == 0 ? s : fma(d^gap, s - w, w), with
+ * d^gap = exp2((float)gap * (float)log2((double)d)) -- gap == 0 returns s itself, bit for bit.  When the sparse kernel updates an
+ * element at update u (g != 0), with w_old read before Adam:
+ *   s = catch_up(s, w_old, u - 1 - e);   s = d s + (1 - d) w_new;   e = u
+ * The read-out is catch_up(s, w, u - e) correction(u) and is PURE: it stores neither s nor e, so rendering in the middle of a
+ * run does not change a bit of the training state.  An entry never touched reads out as its weight (to the roundings of the
+ * fma, the exp2 and the product).  A skipped step stores nothing to s, e, updates or correction; gradients are still cleared.
+ * Rules (RTXN_ERR_INVALID with a message, before any device is touched): decay finite and strictly inside (0, 1).  The entry
+ * points that take the struct also need `state`, and options (opt != NULL) with lr_factor -- and guard with skip_nonfinite --
+ * whether or not anything else is switched on: under the EMA a step always takes its rate from the rate kernel.  The EMA does
+ * not switch the guard on. */
+typedef struct rtxn_ema_state {
+  unsigned updates;                 /* u */
+  float correction;                 /* correction(u), written by the rate kernel */
+  unsigned reserved[2];
+} rtxn_ema_state;
+typedef struct rtxn_weight_ema {
+  float decay;
+  rtxn_ema_state* state;            /* DEVICE, zero-initialised */
+  float* mlp_ema;                   /* DEVICE float[n MLP parameters], zero-initialised: s, dense form */
+  float* table_ema;                 /* DEVICE float[n table parameters], zero-initialised; NULL without a hash grid */
+  unsigned* table_stamps;           /* DEVICE unsigned[n table parameters], zero-initialised: e, lazy form; NULL: dense form */
+} rtxn_weight_ema;
+/* The rules above without the pointers (what a caller checks before it allocates anything); NULL is valid. */
+int rtxn_weight_ema_check(const rtxn_weight_ema* ema);
+/* HOST twins of the device arithmetic, on the restatement both share.  rtxn_ema_catch_up: catch_up(s, w, gap) above (a decay
+ * outside (0, 1): NaN and a message).  rtxn_ema_correction: correction(updates); updates = 0 gives 1.0f (-1 and a message for
+ * a decay outside (0, 1)). */
+float rtxn_ema_catch_up(float s, float w, unsigned gap, float decay);
+float rtxn_ema_correction(float decay, unsigned updates);
+/* rtxn_optimizer_rate / rtxn_loss_scaler_step -- the same kernels -- that behind their work advance ema->state: one update of
+ * the average per call that advances the step counter (advance != 0) and is not skipped; with advance == 0 the state keeps its
+ * bits.  ema == NULL: exactly those calls.  opt may have nothing switched on but must carry lr_factor. */
+int rtxn_optimizer_rate_ema(const rtxn_optimizer_options* opt, const rtxn_weight_ema* ema, int* step, int advance, float lr, float table_lr,
+                            float beta1, float beta2, float* effective_lr, float* table_effective_lr, rtxn_stream_t stream);
+int rtxn_loss_scaler_step_ema(const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema,
+                              const rtxn_grad_buffer* buffers, int n_buffers, int* step, int advance, float lr, float table_lr, float beta1,
+                              float beta2, float* effective_lr, float* table_effective_lr, float divisor, rtxn_stream_t stream);
+/* rtxn_adam_step_scaled / rtxn_adam_step_sparse_scaled that also keep the average of the n parameters they step: ema_acc is
+ * their s (dense form), ema_stamps their e (the sparse call: lazy form, required).  scaler == NULL: the factor on the raw
+ * gradient is 1 / loss_scale, as rtxn_adam_step_opt forms it (with a scaler loss_scale is ignored).  The sparse kernel loads s
+ * and e only for the quads whose gradient is not zero.  ema == NULL: exactly the _scaled call, or with scaler == NULL the _opt
+ * call. */
+int rtxn_adam_step_ema(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                       const float* effective_lr, float lr, float beta1, float beta2, float eps, float loss_scale,
+                       const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, float* ema_acc,
+                       rtxn_stream_t stream);
+int rtxn_adam_step_sparse_ema(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                              unsigned* param_steps, float lr, float beta1, float beta2, float eps, float loss_scale,
+                              const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema,
+                              float* ema_acc, unsigned* ema_stamps, rtxn_stream_t stream);
+/* The read-out of n parameters: out_f32 and / or out_f16 (DEVICE, either may be NULL, not both) = the debiased average;
+ * stamps == NULL: the dense form.  Reads master, ema_acc, stamps and state; stores only the outputs. */
+int rtxn_ema_weights(long n, const float* master, const float* ema_acc, const unsigned* stamps, const rtxn_ema_state* state, float decay,
+                     float* out_f32, void* out_f16, rtxn_stream_t stream);
+/* rtxn_train_step_scaled's sequence (scaler == NULL: rtxn_train_step_opt's) with the _ema rate kernel call and the _ema Adam
+ * calls in their slots: ema->mlp_ema for the MLP, ema->table_ema and ema->table_stamps (both required with a hash grid: this
+ * call steps the table by the sparse rule) for the table.  ema == NULL: exactly rtxn_train_step_scaled. */
+int rtxn_train_step_ema(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                        const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                        const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream);
+
 /* fp32 <-> fp16 copies of a gradient block on the device (no counterpart in the reference, which is single-GPU): the
  * data-parallel exchange sends the hashed levels' gradient in fp16 -- tiny-cuda-nn holds that gradient in fp16 throughout. */
 int rtxn_convert_f32_to_f16(const float* src, void* dst_half, long n, rtxn_stream_t stream);

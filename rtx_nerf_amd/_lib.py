@@ -161,6 +161,17 @@ class LossScaler(C.Structure):
                 ("partials", C.c_void_p)]
 
 
+class EmaState(C.Structure):
+    """struct rtxn_ema_state (include/rtxn.h): the weight EMA's four device words."""
+    _fields_ = [("updates", C.c_uint), ("correction", C.c_float), ("reserved", C.c_uint * 2)]
+
+
+class WeightEma(C.Structure):
+    """struct rtxn_weight_ema (include/rtxn.h)."""
+    _fields_ = [("decay", C.c_float), ("state", C.c_void_p), ("mlp_ema", C.c_void_p), ("table_ema", C.c_void_p),
+                ("table_stamps", C.c_void_p)]
+
+
 class ImageSet(C.Structure):
     """struct rtxn_image_set (include/rtxn.h)."""
     _fields_ = [("images", C.c_void_p), ("poses", C.c_void_p), ("n_images", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32),
@@ -364,6 +375,19 @@ SYMBOLS = {
                                          C.POINTER(TrainRegularizer), C.POINTER(LossScaler), _P]),
     "rtxn_train_step_scaled": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                     C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), _P]),
+    "rtxn_weight_ema_check": (_I, [C.POINTER(WeightEma)]),
+    "rtxn_ema_catch_up": (_F, [_F, _F, C.c_uint, _F]),
+    "rtxn_ema_correction": (_F, [_F, C.c_uint]),
+    "rtxn_optimizer_rate_ema": (_I, [C.POINTER(OptimizerOptions), C.POINTER(WeightEma), _P, _I, _F, _F, _F, _F, _P, _P, _P]),
+    "rtxn_loss_scaler_step_ema": (_I, [C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma), C.POINTER(GradBuffer), _I, _P,
+                                       _I, _F, _F, _F, _F, _P, _P, _F, _P]),
+    "rtxn_adam_step_ema": (_I, [_L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, C.POINTER(OptimizerOptions), C.POINTER(LossScaler),
+                                C.POINTER(WeightEma), _P, _P]),
+    "rtxn_adam_step_sparse_ema": (_I, [_L, _P, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, C.POINTER(OptimizerOptions), C.POINTER(LossScaler),
+                                       C.POINTER(WeightEma), _P, _P, _P]),
+    "rtxn_ema_weights": (_I, [_L, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "rtxn_train_step_ema": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                 C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma), _P]),
     "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),

@@ -1115,6 +1115,114 @@ def adam_step_sparse_scaled(master, params_fp16, grads, m, v, param_steps, opt, 
                                                   _byref(opt), _byref(scaler), _stream()), "rtxn_adam_step_sparse_scaled")
 
 
+# --------------------------------------------------------------------------- exponential moving average of the weights
+def weight_ema(decay, state=None, mlp_ema=None, table_ema=None, table_stamps=None):
+    """struct rtxn_weight_ema (include/rtxn.h): the debiased EMA of the weights, s = d s + (1 - d) w after every APPLIED update,
+    read out as s / (1 - d^u).  state: device int32[4], zeroed (updates, correction as float32 bits, two reserved words); mlp_ema,
+    table_ema: device float32 accumulators, zeroed; table_stamps: device int32 per table parameter, zeroed -- the update at which
+    an entry's s was last current, for the sparse table rule, which keeps the average lazily (None: dense).  The tensors stay
+    referenced by the struct.  The rule is the library's (rtxn_weight_ema_check), applied here, before anything touches a device."""
+    if isinstance(decay, _lib.WeightEma):
+        return decay
+    e = _lib.WeightEma()
+    e.decay = float(decay)
+    check(_lib.lib().rtxn_weight_ema_check(C.byref(e)), "rtxn_weight_ema_check")
+    if state is not None and state.numel() < 4:
+        raise _lib.RtxnError(f"weight_ema: state holds {state.numel()} words, 4 are needed")
+    if table_stamps is not None and (table_ema is None or table_stamps.numel() != table_ema.numel()):
+        raise _lib.RtxnError("weight_ema: table_stamps without a table_ema of the same size")
+    e.state, e.mlp_ema = _ptr(state, torch.int32, "state"), _ptr(mlp_ema, torch.float32, "mlp_ema")
+    e.table_ema, e.table_stamps = _ptr(table_ema, torch.float32, "table_ema"), _ptr(table_stamps, torch.int32, "table_stamps")
+    e._tensors = (state, mlp_ema, table_ema, table_stamps)
+    return e
+
+
+def ema_catch_up(s, w, gap, decay):
+    """rtxn_ema_catch_up: the device's lazy catch-up on the host -- s after `gap` updates during which the weight stayed w."""
+    weight_ema(decay)                         # the rule; a NaN below is then the arithmetic's own (inf - inf)
+    return float(_lib.lib().rtxn_ema_catch_up(float(s), float(w), int(gap), float(decay)))
+
+
+def ema_correction(decay, updates):
+    """rtxn_ema_correction: (float)(1 / (1 - d^updates)), the read-out's debias factor; updates = 0 gives 1."""
+    r = _lib.lib().rtxn_ema_correction(float(decay), int(updates))
+    if r < 0.0:
+        check(1, "rtxn_ema_correction")
+    return float(r)
+
+
+def optimizer_rate_ema(opt, ema, step, effective_lr, lr=1e-3, table_lr=0.0, table_effective_lr=None, advance=True, beta1=0.9, beta2=0.999):
+    """rtxn_optimizer_rate_ema: optimizer_rate that also advances the EMA's update count (unless the step is skipped) and writes
+    its debias factor.  `opt` may have nothing switched on but needs lr_factor."""
+    check(_lib.lib().rtxn_optimizer_rate_ema(C.byref(opt), _byref(ema), _ptr(step, torch.int32, "step"), int(bool(advance)), lr, table_lr,
+                                             beta1, beta2, _ptr(effective_lr, torch.float32, "effective_lr"),
+                                             _ptr(table_effective_lr, torch.float32, "table_effective_lr"), _stream()), "rtxn_optimizer_rate_ema")
+
+
+def loss_scaler_step_ema(opt, scaler, ema, buffers, step, effective_lr, lr=1e-3, table_lr=0.0, table_effective_lr=None, advance=True,
+                         beta1=0.9, beta2=0.999, divisor=1.0):
+    """rtxn_loss_scaler_step_ema: loss_scaler_step that also advances the EMA's state."""
+    arr, n = _grad_buffers(buffers)
+    check(_lib.lib().rtxn_loss_scaler_step_ema(_byref(opt), _byref(scaler), _byref(ema), arr, n, _ptr(step, torch.int32, "step"),
+                                               int(bool(advance)), lr, table_lr, beta1, beta2, _ptr(effective_lr, torch.float32, "effective_lr"),
+                                               _ptr(table_effective_lr, torch.float32, "table_effective_lr"), float(divisor), _stream()),
+          "rtxn_loss_scaler_step_ema")
+
+
+def _ema_acc(who, acc, master, dtype=torch.float32, name="ema_acc", ema=True):
+    if ema is None and acc is None:           # no EMA: the call without _ema
+        return None
+    if acc is None or acc.numel() != master.numel():
+        raise _lib.RtxnError(f"{who}: {name} must hold one element per parameter ({master.numel()})")
+    return _ptr(acc, dtype, name)
+
+
+def adam_step_ema(master, params_fp16, grads, m, v, effective_lr, opt, ema, ema_acc, scaler=None, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8,
+                  loss_scale=1.0, zero_grads=False, weight_decay=True):
+    """rtxn_adam_step_ema: adam_step_scaled (scaler=None: adam_step_opt) that also keeps s = d s + (1 - d) w of the parameters it
+    steps in ema_acc (the dense form)."""
+    half = grads.dtype == torch.float16
+    flags = (ADAM_GRADS_FP16 if half else 0) | (ADAM_ZERO_GRADS if zero_grads else 0) | (0 if weight_decay else ADAM_NO_WEIGHT_DECAY)
+    check(_lib.lib().rtxn_adam_step_ema(master.numel(), _ptr(master, torch.float32, "master"), _ptr(params_fp16, torch.float16, "params"),
+                                        _ptr(grads, torch.float16 if half else torch.float32, "grads"), flags,
+                                        _ptr(m, torch.float32, "m"), _ptr(v, torch.float32, "v"),
+                                        _ptr(effective_lr, torch.float32, "effective_lr"), lr, beta1, beta2, eps, loss_scale,
+                                        _byref(opt), _byref(scaler), _byref(ema), _ema_acc("adam_step_ema", ema_acc, master, ema=ema), _stream()),
+          "rtxn_adam_step_ema")
+
+
+def adam_step_sparse_ema(master, params_fp16, grads, m, v, param_steps, opt, ema, ema_acc, ema_stamps, scaler=None, lr=1e-3, beta1=0.9,
+                         beta2=0.999, eps=1e-8, loss_scale=1.0, zero_grads=False, weight_decay=True):
+    """rtxn_adam_step_sparse_ema: adam_step_sparse_scaled (scaler=None: adam_step_sparse_opt) that keeps the average lazily: the
+    entries it updates are caught up over the updates they sat out (ema_stamps), then averaged."""
+    half = grads.dtype == torch.float16
+    flags = (ADAM_GRADS_FP16 if half else 0) | (ADAM_ZERO_GRADS if zero_grads else 0) | (0 if weight_decay else ADAM_NO_WEIGHT_DECAY)
+    who = "adam_step_sparse_ema"
+    check(_lib.lib().rtxn_adam_step_sparse_ema(master.numel(), _ptr(master, torch.float32, "master"),
+                                               _ptr(params_fp16, torch.float16, "params"),
+                                               _ptr(grads, torch.float16 if half else torch.float32, "grads"), flags,
+                                               _ptr(m, torch.float32, "m"), _ptr(v, torch.float32, "v"),
+                                               _ptr(param_steps, torch.int32, "param_steps"), lr, beta1, beta2, eps, loss_scale,
+                                               _byref(opt), _byref(scaler), _byref(ema), _ema_acc(who, ema_acc, master, ema=ema),
+                                               _ema_acc(who, ema_stamps, master, torch.int32, "ema_stamps", ema=ema), _stream()),
+          "rtxn_adam_step_sparse_ema")
+
+
+def ema_weights(master, ema_acc, stamps, state, decay, out_f32=None, out_f16=None):
+    """rtxn_ema_weights: the debiased average of `master`'s parameters from their accumulator (and stamps: the lazy form; None:
+    dense) into out_f32 and / or out_f16.  Pure: the training state is only read."""
+    who = "ema_weights"
+    for nm, t in (("out_f32", out_f32), ("out_f16", out_f16)):
+        if t is not None and t.numel() != master.numel():
+            raise _lib.RtxnError(f"{who}: {nm} holds {t.numel()} elements, {master.numel()} parameters")
+    if state is None or state.numel() < 4:
+        raise _lib.RtxnError(f"{who}: state must hold 4 words")
+    check(_lib.lib().rtxn_ema_weights(master.numel(), _ptr(master, torch.float32, "master"), _ema_acc(who, ema_acc, master),
+                                      _ema_acc(who, stamps, master, torch.int32, "stamps") if stamps is not None else None,
+                                      _ptr(state, torch.int32, "state"), float(decay), _ptr(out_f32, torch.float32, "out_f32"),
+                                      _ptr(out_f16, torch.float16, "out_f16"), _stream()), "rtxn_ema_weights")
+
+
 def volrender_scaled_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, scaler, pixels,
                            loss_gradients, loss_sum, radiance_gradients, background=None, loss=None, regularizer=None):
     """rtxn_volrender_scaled_train: volrender_reg_train reading the loss scale from the scaler's device word; always the loss
@@ -1242,7 +1350,7 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None):
+def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None, ema=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
     jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
@@ -1250,8 +1358,14 @@ def train_step(args, background=None, jitter=None, loss=None, regularizer=None, 
     regularizer: train_regularizer(...) -> rtxn_train_step_reg (with or without any of the three): the write pass of the traversal
     stores the segments' t_start / t_end into the regulariser's buffers;
     optimizer: optimizer_options(...) -> rtxn_train_step_opt (with or without any of the four);
-    scaler: loss_scaler(...) -> rtxn_train_step_scaled (needs `optimizer` with skip_nonfinite)."""
-    if scaler is not None:
+    scaler: loss_scaler(...) -> rtxn_train_step_scaled (needs `optimizer` with skip_nonfinite);
+    ema: weight_ema(...) -> rtxn_train_step_ema (needs `optimizer`, which may have nothing switched on; with or without a scaler)."""
+    if ema is not None:
+        if regularizer is not None:
+            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
+        check(_lib.lib().rtxn_train_step_ema(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
+                                             _byref(optimizer), _byref(scaler), C.byref(ema), _stream()), "rtxn_train_step_ema")
+    elif scaler is not None:
         if regularizer is not None:
             _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
         check(_lib.lib().rtxn_train_step_scaled(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),

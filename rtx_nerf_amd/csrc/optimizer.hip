@@ -11,6 +11,11 @@
 //                             the scaler's state machine (loss_scaler_advance, shared with the host)
 //   adam_opt_kernel<.., true>, adam_sparse_opt_kernel<.., true>    the _opt kernels with the factor on the raw gradient read
 //                             from device memory
+// ... and the exponential moving average of the weights (rtxn_weight_ema):
+//   adam_ema_kernel, adam_sparse_ema_kernel    siblings of the _opt kernels that also keep the average: densely, or (sparse) lazily,
+//                             catching an entry up over the updates it sat out when Adam touches it
+//   ema_weights_kernel          the read-out: master, accumulator, stamps, state -> debiased fp32 / fp16; stores nothing else
+//   the two rate kernels advance the EMA's update count through a nullable pointer
 #include "common.h"
 #include "mlp_internal.h"
 #include "adam_internal.h"
@@ -64,9 +69,38 @@ __device__ __forceinline__ unsigned rate_update(int* step, int advance, const rt
   }
   return bad;
 }
+
+// The weight EMA's arithmetic (include/rtxn.h, rtxn_weight_ema), the one restatement host and device share.
+// correction(u) = 1 / (1 - d^u) in double, rounded once; u = 0: 1.
+__host__ __device__ inline float ema_correction(float d, unsigned u) {
+  return u == 0u ? 1.0f : (float)(1.0 / (1.0 - pow((double)d, (double)u)));
+}
+// s brought over `gap` updates during which the weight stayed w: w + d^gap (s - w), one fma and one exp2 (d^gap = 2^(gap log2 d),
+// as the sparse Adam forms beta^t).  gap == 0 returns s itself: w + 1 (s - w) is not s in fp32.
+__host__ __device__ inline float ema_catch_up(float s, float w, unsigned gap, float log2_d) {
+  if (gap == 0u) return s;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float p = __builtin_amdgcn_exp2f((float)gap * log2_d);
+#else
+  const float p = exp2f((float)gap * log2_d);
+#endif
+  return fmaf(p, s - w, w);
+}
+// behind the rate kernel's work: an applied update counts; a skipped one, and a call that does not advance the step counter
+// (it only re-evaluates the rates), leave both words as they are
+__device__ __forceinline__ void ema_advance(rtxn_ema_state* st, float d, unsigned bad, int advance) {
+  if (!st || bad || !advance) return;
+  const unsigned u = st->updates + 1u;
+  st->updates = u;
+  st->correction = ema_correction(d, u);
+}
+
+// ema (may be NULL): the weight EMA's state, advanced behind everything else
 __global__ void optimizer_rate_kernel(int* step, int advance, rtxn_lr_schedule s, float lr, float table_lr, float beta1, float beta2,
-                                      float* lr_eff, float* table_lr_eff, float* factor_out, unsigned* guard) {
-  rate_update(step, advance, s, lr, table_lr, beta1, beta2, lr_eff, table_lr_eff, factor_out, guard);
+                                      float* lr_eff, float* table_lr_eff, float* factor_out, unsigned* guard, rtxn_ema_state* ema,
+                                      float ema_decay) {
+  const unsigned bad = rate_update(step, advance, s, lr, table_lr, beta1, beta2, lr_eff, table_lr_eff, factor_out, guard);
+  ema_advance(ema, ema_decay, bad, advance);
 }
 
 struct GradList {
@@ -336,9 +370,21 @@ extern "C" int rtxn_optimizer_options_check(const rtxn_optimizer_options* opt) {
   return rtxn::check_optimizer_options(opt, "rtxn_optimizer_options_check", false, &active);
 }
 
-extern "C" int rtxn_optimizer_rate(const rtxn_optimizer_options* opt, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
-                                   float* effective_lr, float* table_effective_lr, rtxn_stream_t stream) {
-  const char* who = "rtxn_optimizer_rate";
+// what every entry point that takes the EMA asks of it; with_opt: and of the options beside it (lr_factor whether or not anything
+// is switched on: under the EMA the rate always comes from the rate kernel)
+static int check_ema(const rtxn_weight_ema* ema, const rtxn_optimizer_options* opt, bool with_opt, const char* who) {
+  RTXN_REQUIRE(ema, "%s: NULL ema", who);
+  RTXN_REQUIRE(std::isfinite(ema->decay) && ema->decay > 0.0f && ema->decay < 1.0f, "%s: ema->decay = %g (finite, strictly inside (0, 1))", who,
+               (double)ema->decay);
+  if (!with_opt) return RTXN_OK;
+  RTXN_REQUIRE(ema->state && ((uintptr_t)ema->state & 3) == 0, "%s: ema->state = %p (NULL or misaligned)", who, (void*)ema->state);
+  RTXN_REQUIRE(opt && opt->lr_factor, "%s: the weight EMA needs options that carry lr_factor (opt = %p): its steps take the rate from the rate kernel",
+               who, (const void*)opt);
+  return RTXN_OK;
+}
+
+static int optimizer_rate_impl(const char* who, const rtxn_optimizer_options* opt, const rtxn_weight_ema* ema, int* step, int advance, float lr,
+                               float table_lr, float beta1, float beta2, float* effective_lr, float* table_effective_lr, rtxn_stream_t stream) {
   RTXN_REQUIRE(opt, "%s: NULL options", who);
   bool active = false;
   const int rc = rtxn::check_optimizer_options(opt, who, false, &active);
@@ -350,9 +396,26 @@ extern "C" int rtxn_optimizer_rate(const rtxn_optimizer_options* opt, int* step,
                (double)beta2);
   RTXN_DEVICE_OR_FAIL();
   optimizer_rate_kernel<<<1, 1, 0, rtxn::as_stream(stream)>>>(step, advance, opt->schedule, lr, table_lr, beta1, beta2, effective_lr,
-                                                              table_effective_lr, opt->lr_factor, opt->skip_nonfinite ? opt->guard : nullptr);
+                                                              table_effective_lr, opt->lr_factor, opt->skip_nonfinite ? opt->guard : nullptr,
+                                                              ema ? ema->state : nullptr, ema ? ema->decay : 0.0f);
   RTXN_LAUNCH_CHECK("optimizer_rate_kernel");
   return RTXN_OK;
+}
+
+extern "C" int rtxn_optimizer_rate(const rtxn_optimizer_options* opt, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
+                                   float* effective_lr, float* table_effective_lr, rtxn_stream_t stream) {
+  return optimizer_rate_impl("rtxn_optimizer_rate", opt, nullptr, step, advance, lr, table_lr, beta1, beta2, effective_lr, table_effective_lr, stream);
+}
+
+extern "C" int rtxn_optimizer_rate_ema(const rtxn_optimizer_options* opt, const rtxn_weight_ema* ema, int* step, int advance, float lr,
+                                       float table_lr, float beta1, float beta2, float* effective_lr, float* table_effective_lr,
+                                       rtxn_stream_t stream) {
+  const char* who = "rtxn_optimizer_rate_ema";
+  if (ema) {
+    const int rc = check_ema(ema, opt, true, who);
+    if (rc != RTXN_OK) return rc;
+  }
+  return optimizer_rate_impl(who, opt, ema, step, advance, lr, table_lr, beta1, beta2, effective_lr, table_effective_lr, stream);
 }
 
 extern "C" int rtxn_check_gradients(const rtxn_grad_buffer* buffers, int n_buffers, unsigned* flag, rtxn_stream_t stream) {
@@ -563,7 +626,8 @@ __global__ __launch_bounds__(kThreads) void gradient_statistics_kernel(StatList 
 // shared by every stepping path: their scales, multipliers and rates are the same bits by construction.
 __global__ __launch_bounds__(kThreads) void loss_scaler_kernel(int* step, int advance, rtxn_lr_schedule s, float lr, float table_lr, float beta1,
                                                                float beta2, float* lr_eff, float* table_lr_eff, float* factor_out,
-                                                               unsigned* guard, rtxn_loss_scaler cfg, float divisor, StatList L) {
+                                                               unsigned* guard, rtxn_loss_scaler cfg, float divisor, StatList L,
+                                                               rtxn_ema_state* ema, float ema_decay) {
   __shared__ double red[kThreads];
   double acc = 0.0;
   for (int b = 0; b < RTXN_MAX_GRAD_BUFFERS; ++b)
@@ -579,6 +643,7 @@ __global__ __launch_bounds__(kThreads) void loss_scaler_kernel(int* step, int ad
     rtxn_loss_scaler_state st = *cfg.state;
     loss_scaler_advance(cfg, st, bad != 0u, red[0], divisor);
     *cfg.state = st;
+    ema_advance(ema, ema_decay, bad, advance);
   }
 }
 
@@ -698,10 +763,9 @@ extern "C" int rtxn_gradient_statistics(const rtxn_grad_buffer* buffers, int n_b
   return RTXN_OK;
 }
 
-extern "C" int rtxn_loss_scaler_step(const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_grad_buffer* buffers,
-                                     int n_buffers, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
-                                     float* effective_lr, float* table_effective_lr, float divisor, rtxn_stream_t stream) {
-  const char* who = "rtxn_loss_scaler_step";
+static int loss_scaler_step_impl(const char* who, const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema,
+                                 const rtxn_grad_buffer* buffers, int n_buffers, int* step, int advance, float lr, float table_lr, float beta1,
+                                 float beta2, float* effective_lr, float* table_effective_lr, float divisor, rtxn_stream_t stream) {
   int rc = check_scaled(opt, scaler, who);
   if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(step && effective_lr, "%s: step = %p, effective_lr = %p", who, (void*)step, (void*)effective_lr);
@@ -714,9 +778,30 @@ extern "C" int rtxn_loss_scaler_step(const rtxn_optimizer_options* opt, const rt
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
   loss_scaler_kernel<<<1, kThreads, 0, rtxn::as_stream(stream)>>>(step, advance, opt->schedule, lr, table_lr, beta1, beta2, effective_lr,
-                                                                  table_effective_lr, opt->lr_factor, opt->guard, *scaler, divisor, L);
+                                                                  table_effective_lr, opt->lr_factor, opt->guard, *scaler, divisor, L,
+                                                                  ema ? ema->state : nullptr, ema ? ema->decay : 0.0f);
   RTXN_LAUNCH_CHECK("loss_scaler_kernel");
   return RTXN_OK;
+}
+
+extern "C" int rtxn_loss_scaler_step(const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_grad_buffer* buffers,
+                                     int n_buffers, int* step, int advance, float lr, float table_lr, float beta1, float beta2,
+                                     float* effective_lr, float* table_effective_lr, float divisor, rtxn_stream_t stream) {
+  return loss_scaler_step_impl("rtxn_loss_scaler_step", opt, scaler, nullptr, buffers, n_buffers, step, advance, lr, table_lr, beta1, beta2,
+                               effective_lr, table_effective_lr, divisor, stream);
+}
+
+extern "C" int rtxn_loss_scaler_step_ema(const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema,
+                                         const rtxn_grad_buffer* buffers, int n_buffers, int* step, int advance, float lr, float table_lr,
+                                         float beta1, float beta2, float* effective_lr, float* table_effective_lr, float divisor,
+                                         rtxn_stream_t stream) {
+  const char* who = "rtxn_loss_scaler_step_ema";
+  if (ema) {
+    const int rc = check_ema(ema, opt, true, who);
+    if (rc != RTXN_OK) return rc;
+  }
+  return loss_scaler_step_impl(who, opt, scaler, ema, buffers, n_buffers, step, advance, lr, table_lr, beta1, beta2, effective_lr,
+                               table_effective_lr, divisor, stream);
 }
 
 extern "C" int rtxn_adam_step_scaled(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
@@ -769,5 +854,361 @@ extern "C" int rtxn_adam_step_sparse_scaled(long n, float* master, void* params_
                                                                      opt->lr_factor, lr, wd, opt->guard + 2, beta1, beta2, eps,
                                                                      &scaler->state->multiplier, l2b1, l2b2);
   RTXN_LAUNCH_CHECK("adam_sparse_opt_kernel (device multiplier)");
+  return RTXN_OK;
+}
+
+// ------------------------------------------------------------------------- exponential moving average of the weights
+namespace {
+
+// adam_opt_kernel that also keeps the average of what it steps, dense form: s = d s + (1 - d) w behind the decay term, +8 bytes per
+// element.  A sibling, not a template parameter: without the EMA every path launches the kernels it always launched.
+template <bool HALF_GRADS, bool ZERO, bool DEV>
+__global__ __launch_bounds__(kThreads) void adam_ema_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                            void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ acc, const float* __restrict__ lr_dev,
+                                                            const float* __restrict__ factor_dev, float lr, float weight_decay,
+                                                            const unsigned* __restrict__ skip, float beta1, float beta2, float eps,
+                                                            grad_factor<DEV> inv_loss_scale_arg, float d, float omd) {
+  float* gf = static_cast<float*>(grads_v);
+  __half* gh = static_cast<__half*>(grads_v);
+  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
+  const long n4 = vec ? n / 4 : 0;
+  const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
+  if (skip && *skip != 0u) {
+    if (ZERO) {
+      for (long q = first; q < n4; q += stride) {
+        if (HALF_GRADS) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+        else reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      for (long i = 4 * n4 + first; i < n; i += stride) {
+        if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f;
+      }
+    }
+    return;
+  }
+  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
+  const float lr_eff = *lr_dev;
+  const float decay = (lr * *factor_dev) * weight_decay;          // w -= lr_t weight_decay w
+  auto one = [&](float g, float& mi, float& vi, float& w, float& s) {
+    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
+    if (decay != 0.0f) w = w - decay * w;
+    s = d * s + omd * w;
+  };
+  for (long q = first; q < n4; q += stride) {
+    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
+    float4 s4 = reinterpret_cast<float4*>(acc)[q];
+    float g[4];
+    if (HALF_GRADS) {
+      const half4v h = reinterpret_cast<const half4v*>(gh)[q];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
+      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+    } else {
+      const float4 f = reinterpret_cast<const float4*>(gf)[q];
+      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
+      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    one(g[0], m4.x, v4.x, w4.x, s4.x);
+    one(g[1], m4.y, v4.y, w4.y, s4.y);
+    one(g[2], m4.z, v4.z, w4.z, s4.z);
+    one(g[3], m4.w, v4.w, w4.w, s4.w);
+    reinterpret_cast<float4*>(master)[q] = w4;
+    reinterpret_cast<float4*>(m)[q] = m4;
+    reinterpret_cast<float4*>(v)[q] = v4;
+    reinterpret_cast<float4*>(acc)[q] = s4;
+    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
+    reinterpret_cast<half4v*>(params)[q] = o;
+  }
+  for (long i = 4 * n4 + first; i < n; i += stride) {
+    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
+    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
+    float mi = m[i], vi = v[i], w = master[i], s = acc[i];
+    one(g, mi, vi, w, s);
+    m[i] = mi;
+    v[i] = vi;
+    master[i] = w;
+    acc[i] = s;
+    params[i] = __float2half(w);
+  }
+}
+
+// adam_sparse_opt_kernel that also keeps the average, lazy form: s and the stamps are loaded only for the quads that pass the
+// non-zero test, and of those only the updated elements move -- caught up over the updates they sat out, then the EMA line, then
+// the stamp.  ema: a kernel-argument pointer every lane reads at the same address, one scalar load; updates was advanced by the
+// rate kernel, so it is the number u of this update.
+template <bool HALF_GRADS, bool ZERO, bool DEV>
+__global__ __launch_bounds__(kThreads) void adam_sparse_ema_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                                   void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                                   unsigned* __restrict__ steps, float* __restrict__ acc,
+                                                                   unsigned* __restrict__ stamps, const rtxn_ema_state* __restrict__ ema,
+                                                                   const float* __restrict__ factor_dev, float lr, float weight_decay,
+                                                                   const unsigned* __restrict__ skip, float beta1, float beta2, float eps,
+                                                                   grad_factor<DEV> inv_loss_scale_arg, float log2_beta1, float log2_beta2,
+                                                                   float d, float omd, float log2_d) {
+  float* gf = static_cast<float*>(grads_v);
+  __half* gh = static_cast<__half*>(grads_v);
+  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)steps | (uintptr_t)acc | (uintptr_t)stamps | (uintptr_t)grads_v) & 15) == 0 &&
+                   ((uintptr_t)params & 7) == 0;
+  const long n4 = vec ? n / 4 : 0;
+  const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
+  if (skip && *skip != 0u) {
+    if (ZERO) {
+      for (long q = first; q < n4; q += stride) {
+        if (HALF_GRADS) {
+          const uint2 raw = reinterpret_cast<const uint2*>(gh)[q];
+          if ((raw.x | raw.y) != 0u) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+        } else {
+          const uint4 raw = reinterpret_cast<const uint4*>(gf)[q];
+          if ((raw.x | raw.y | raw.z | raw.w) != 0u) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      for (long i = 4 * n4 + first; i < n; i += stride) {
+        if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f;
+      }
+    }
+    return;
+  }
+  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
+  const float lr_t = lr * *factor_dev;
+  const float decay = lr_t * weight_decay;
+  const unsigned u = ema->updates;
+  auto one = [&](float g, float& mi, float& vi, float& w, unsigned& st, float& s, unsigned& e) {
+    if (g == 0.0f) return;
+    const float w_old = w;
+    st += 1u;
+    const float t = (float)st;
+    // beta^t = 2^(t log2 beta), as adam_sparse_kernel
+    const float lr_eff = lr_t * sqrtf(1.0f - __builtin_amdgcn_exp2f(t * log2_beta2)) / (1.0f - __builtin_amdgcn_exp2f(t * log2_beta1));
+    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
+    if (decay != 0.0f) w = w - decay * w;
+    s = ema_catch_up(s, w_old, u - 1u - e, log2_d);
+    s = d * s + omd * w;
+    e = u;
+  };
+  for (long q = first; q < n4; q += stride) {
+    float g[4];
+    if (HALF_GRADS) {
+      const uint2 raw = reinterpret_cast<const uint2*>(gh)[q];
+      if (((raw.x | raw.y) & 0x7fff7fffu) == 0u) continue;
+      const half4v h = __builtin_bit_cast(half4v, raw);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
+      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
+    } else {
+      const float4 f = reinterpret_cast<const float4*>(gf)[q];
+      if (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f && f.w == 0.0f) continue;
+      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
+      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
+    uint4 s4 = reinterpret_cast<uint4*>(steps)[q];
+    float4 a4 = reinterpret_cast<float4*>(acc)[q];
+    uint4 e4 = reinterpret_cast<uint4*>(stamps)[q];
+    one(g[0], m4.x, v4.x, w4.x, s4.x, a4.x, e4.x);
+    one(g[1], m4.y, v4.y, w4.y, s4.y, a4.y, e4.y);
+    one(g[2], m4.z, v4.z, w4.z, s4.z, a4.z, e4.z);
+    one(g[3], m4.w, v4.w, w4.w, s4.w, a4.w, e4.w);
+    reinterpret_cast<float4*>(master)[q] = w4;
+    reinterpret_cast<float4*>(m)[q] = m4;
+    reinterpret_cast<float4*>(v)[q] = v4;
+    reinterpret_cast<uint4*>(steps)[q] = s4;
+    reinterpret_cast<float4*>(acc)[q] = a4;
+    reinterpret_cast<uint4*>(stamps)[q] = e4;
+    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
+    reinterpret_cast<half4v*>(params)[q] = o;
+  }
+  for (long i = 4 * n4 + first; i < n; i += stride) {
+    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
+    if (g == 0.0f) continue;
+    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
+    float mi = m[i], vi = v[i], w = master[i], s = acc[i];
+    unsigned st = steps[i], e = stamps[i];
+    one(g, mi, vi, w, st, s, e);
+    m[i] = mi;
+    v[i] = vi;
+    master[i] = w;
+    steps[i] = st;
+    acc[i] = s;
+    stamps[i] = e;
+    params[i] = __float2half(w);
+  }
+}
+
+// The read-out: catch_up(s, w, u - e) correction(u), or w itself at u = 0.  Pure -- it stores only the outputs.  One 16-byte
+// word per lane and array, and two quads per trip: four to six independent loads in flight per lane (one load in flight per lane
+// left a pass of this shape at half the HBM rate).  LAZY: with stamps.
+template <bool LAZY>
+__global__ __launch_bounds__(kThreads) void ema_weights_kernel(long n, const float* __restrict__ master, const float* __restrict__ acc,
+                                                               const unsigned* __restrict__ stamps, const rtxn_ema_state* __restrict__ ema,
+                                                               float log2_d, float* __restrict__ out32, __half* __restrict__ out16) {
+  const unsigned u = ema->updates;
+  const float corr = ema->correction;
+  auto one = [&](float w, float s, unsigned e) { return u == 0u ? w : (LAZY ? ema_catch_up(s, w, u - e, log2_d) : s) * corr; };
+  const bool vec = (((uintptr_t)master | (uintptr_t)acc | (uintptr_t)stamps | (uintptr_t)out32) & 15) == 0 && ((uintptr_t)out16 & 7) == 0;
+  const long n4 = vec ? n / 4 : 0;
+  const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
+  auto quad = [&](float4 w, float4 s, uint4 e, long q) {
+    const float4 o = make_float4(one(w.x, s.x, e.x), one(w.y, s.y, e.y), one(w.z, s.z, e.z), one(w.w, s.w, e.w));
+    if (out32) reinterpret_cast<float4*>(out32)[q] = o;
+    if (out16) {
+      const half4v h = {(_Float16)o.x, (_Float16)o.y, (_Float16)o.z, (_Float16)o.w};
+      reinterpret_cast<half4v*>(out16)[q] = h;
+    }
+  };
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  long q = first;
+  for (; q + stride < n4; q += 2 * stride) {
+    const float4 wa = reinterpret_cast<const float4*>(master)[q], wb = reinterpret_cast<const float4*>(master)[q + stride];
+    const float4 sa = reinterpret_cast<const float4*>(acc)[q], sb = reinterpret_cast<const float4*>(acc)[q + stride];
+    const uint4 ea = LAZY ? reinterpret_cast<const uint4*>(stamps)[q] : zero, eb = LAZY ? reinterpret_cast<const uint4*>(stamps)[q + stride] : zero;
+    quad(wa, sa, ea, q);
+    quad(wb, sb, eb, q + stride);
+  }
+  for (; q < n4; q += stride)
+    quad(reinterpret_cast<const float4*>(master)[q], reinterpret_cast<const float4*>(acc)[q], LAZY ? reinterpret_cast<const uint4*>(stamps)[q] : zero, q);
+  for (long i = 4 * n4 + first; i < n; i += stride) {
+    const float o = one(master[i], acc[i], LAZY ? stamps[i] : 0u);
+    if (out32) out32[i] = o;
+    if (out16) out16[i] = __float2half(o);
+  }
+}
+
+// the factor on the raw gradient of an _ema Adam call: the scaler's multiplier word, or 1 / loss_scale
+int check_ema_step(const char* who, const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, float loss_scale,
+                   int grad_flags) {
+  int rc = check_ema(ema, opt, true, who);
+  if (rc != RTXN_OK) return rc;
+  if (scaler) {
+    rc = check_scaled(opt, scaler, who);
+  } else {
+    bool active = false;
+    rc = rtxn::check_optimizer_options(opt, who, true, &active);
+    if (rc == RTXN_OK) RTXN_REQUIRE(!opt->skip_nonfinite || opt->guard, "%s: opt->guard is NULL with opt->skip_nonfinite set", who);
+    if (rc == RTXN_OK) RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
+  }
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  return RTXN_OK;
+}
+
+}  // namespace
+
+extern "C" int rtxn_weight_ema_check(const rtxn_weight_ema* ema) { return ema ? check_ema(ema, nullptr, false, "rtxn_weight_ema_check") : RTXN_OK; }
+
+extern "C" float rtxn_ema_catch_up(float s, float w, unsigned gap, float decay) {
+  if (!(std::isfinite(decay) && decay > 0.0f && decay < 1.0f)) {
+    rtxn::set_error("rtxn_ema_catch_up: decay = %g (finite, strictly inside (0, 1))", (double)decay);
+    return NAN;
+  }
+  return ema_catch_up(s, w, gap, (float)log2((double)decay));
+}
+
+extern "C" float rtxn_ema_correction(float decay, unsigned updates) {
+  if (!(std::isfinite(decay) && decay > 0.0f && decay < 1.0f)) {
+    rtxn::set_error("rtxn_ema_correction: decay = %g (finite, strictly inside (0, 1))", (double)decay);
+    return -1.0f;
+  }
+  return ema_correction(decay, updates);
+}
+
+extern "C" int rtxn_adam_step_ema(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                  const float* effective_lr, float lr, float beta1, float beta2, float eps, float loss_scale,
+                                  const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, float* ema_acc,
+                                  rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_ema";
+  if (!ema)
+    return scaler ? rtxn_adam_step_scaled(n, master, params_fp16, grads, grad_flags, m, v, effective_lr, lr, beta1, beta2, eps, opt, scaler, stream)
+                  : rtxn_adam_step_opt(n, master, params_fp16, grads, grad_flags, m, v, effective_lr, lr, beta1, beta2, eps, loss_scale, opt, stream);
+  const int rc = check_ema_step(who, opt, scaler, ema, loss_scale, grad_flags);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v && ema_acc, "%s: NULL buffer", who);
+  const long work = (n + 3) / 4;
+  const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
+  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  const unsigned* skip = opt->skip_nonfinite ? opt->guard + 2 : nullptr;
+  const float d = ema->decay, omd = 1.0f - d;
+  hipStream_t hs = rtxn::as_stream(stream);
+  __half* p16 = static_cast<__half*>(params_fp16);
+  if (scaler) {
+    static decltype(&adam_ema_kernel<false, false, true>) const table[2][2] = {
+        {adam_ema_kernel<false, false, true>, adam_ema_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
+        {adam_ema_kernel<true, false, true>, adam_ema_kernel<true, true, true>}};
+    table[half][zero]<<<blocks, kThreads, 0, hs>>>(n, master, p16, grads, m, v, ema_acc, effective_lr, opt->lr_factor, lr, wd, skip, beta1, beta2, eps,
+                                                   &scaler->state->multiplier, d, omd);
+  } else {
+    static decltype(&adam_ema_kernel<false, false, false>) const table[2][2] = {
+        {adam_ema_kernel<false, false, false>, adam_ema_kernel<false, true, false>},
+        {adam_ema_kernel<true, false, false>, adam_ema_kernel<true, true, false>}};
+    table[half][zero]<<<blocks, kThreads, 0, hs>>>(n, master, p16, grads, m, v, ema_acc, effective_lr, opt->lr_factor, lr, wd, skip, beta1, beta2, eps,
+                                                   1.0f / loss_scale, d, omd);
+  }
+  RTXN_LAUNCH_CHECK("adam_ema_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_adam_step_sparse_ema(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                         unsigned* param_steps, float lr, float beta1, float beta2, float eps, float loss_scale,
+                                         const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema,
+                                         float* ema_acc, unsigned* ema_stamps, rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_sparse_ema";
+  if (!ema)
+    return scaler ? rtxn_adam_step_sparse_scaled(n, master, params_fp16, grads, grad_flags, m, v, param_steps, lr, beta1, beta2, eps, opt, scaler, stream)
+                  : rtxn_adam_step_sparse_opt(n, master, params_fp16, grads, grad_flags, m, v, param_steps, lr, beta1, beta2, eps, loss_scale, opt,
+                                              stream);
+  const int rc = check_ema_step(who, opt, scaler, ema, loss_scale, grad_flags);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
+               (double)beta2);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps && ema_acc && ema_stamps,
+               "%s: NULL buffer (the sparse rule keeps the average lazily: ema_acc and ema_stamps)", who);
+  const long blocks = (n / 4 + kThreads - 1) / kThreads;
+  const unsigned gridx = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
+  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
+  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  const unsigned* skip = opt->skip_nonfinite ? opt->guard + 2 : nullptr;
+  const float d = ema->decay, omd = 1.0f - d, l2d = (float)log2((double)d);
+  hipStream_t hs = rtxn::as_stream(stream);
+  __half* p16 = static_cast<__half*>(params_fp16);
+  if (scaler) {
+    static decltype(&adam_sparse_ema_kernel<false, false, true>) const table[2][2] = {
+        {adam_sparse_ema_kernel<false, false, true>, adam_sparse_ema_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
+        {adam_sparse_ema_kernel<true, false, true>, adam_sparse_ema_kernel<true, true, true>}};
+    table[half][zero]<<<gridx, kThreads, 0, hs>>>(n, master, p16, grads, m, v, param_steps, ema_acc, ema_stamps, ema->state, opt->lr_factor, lr, wd,
+                                                  skip, beta1, beta2, eps, &scaler->state->multiplier, l2b1, l2b2, d, omd, l2d);
+  } else {
+    static decltype(&adam_sparse_ema_kernel<false, false, false>) const table[2][2] = {
+        {adam_sparse_ema_kernel<false, false, false>, adam_sparse_ema_kernel<false, true, false>},
+        {adam_sparse_ema_kernel<true, false, false>, adam_sparse_ema_kernel<true, true, false>}};
+    table[half][zero]<<<gridx, kThreads, 0, hs>>>(n, master, p16, grads, m, v, param_steps, ema_acc, ema_stamps, ema->state, opt->lr_factor, lr, wd,
+                                                  skip, beta1, beta2, eps, 1.0f / loss_scale, l2b1, l2b2, d, omd, l2d);
+  }
+  RTXN_LAUNCH_CHECK("adam_sparse_ema_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_ema_weights(long n, const float* master, const float* ema_acc, const unsigned* stamps, const rtxn_ema_state* state, float decay,
+                                float* out_f32, void* out_f16, rtxn_stream_t stream) {
+  const char* who = "rtxn_ema_weights";
+  RTXN_REQUIRE(std::isfinite(decay) && decay > 0.0f && decay < 1.0f, "%s: decay = %g (finite, strictly inside (0, 1))", who, (double)decay);
+  RTXN_REQUIRE(state && ((uintptr_t)state & 3) == 0, "%s: state = %p (NULL or misaligned)", who, (const void*)state);
+  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+  RTXN_REQUIRE(out_f32 || out_f16, "%s: neither out_f32 nor out_f16", who);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && ema_acc, "%s: master = %p, ema_acc = %p", who, (const void*)master, (const void*)ema_acc);
+  const long blocks = ((n + 3) / 4 + 2 * kThreads - 1) / (2 * kThreads);            // two quads per lane and trip
+  const unsigned gridx = (unsigned)(blocks > 4096 ? 4096 : blocks);
+  const float l2d = (float)log2((double)decay);
+  (stamps ? ema_weights_kernel<true> : ema_weights_kernel<false>)<<<gridx, kThreads, 0, rtxn::as_stream(stream)>>>(
+      n, master, ema_acc, stamps, state, l2d, out_f32, static_cast<__half*>(out_f16));
+  RTXN_LAUNCH_CHECK("ema_weights_kernel");
   return RTXN_OK;
 }

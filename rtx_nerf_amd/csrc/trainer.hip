@@ -32,14 +32,17 @@ static long fp32_gradient_params(const rtxn_train_batch& b) {
   return n;
 }
 
-// optimizer->step under ACTIVE options (include/rtxn.h, rtxn_optimizer_options): the gradients are complete -- one pass looks
-// for Inf / NaN in every buffer the optimizer is about to consume, the rate kernel advances the step, evaluates the schedule and
-// turns the flag into the skip word, and the _opt Adam kernels read rate, factor and skip word from the device.  Weight decay:
-// the MLP only.
+// optimizer->step under options (include/rtxn.h, rtxn_optimizer_options): the gradients are complete -- one pass looks for Inf / NaN
+// in every buffer the optimizer is about to consume, the rate kernel advances the step, evaluates the schedule and turns the flag
+// into the skip word, and the Adam kernels read rate, factor and skip word from the device.  Weight decay: the MLP only.
 // scaler (rtxn_loss_scaler; rtxn_train_step_scaled): the statistics pass in place of the check, the scaler kernel in place of the
 // rate kernel, and the Adam kernels that read the multiplier it leaves -- all on the one stream.
+// ema (rtxn_weight_ema; rtxn_train_step_ema): the rate call advances its update count and the Adam kernels keep the average; opt
+// need not have anything switched on then.
+// ONE sequence for every combination: the _ema entry points with ema == NULL are the _scaled calls, and those with scaler == NULL
+// the _opt calls -- the launches of a step without the EMA are the ones it always made.
 static int optimizer_step_opt(const rtxn_train_step_args* a, const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler,
-                              rtxn_stream_t stream) {
+                              const rtxn_weight_ema* ema, rtxn_stream_t stream) {
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
   const bool hash = b.grid != nullptr;
@@ -49,64 +52,47 @@ static int optimizer_step_opt(const rtxn_train_step_args* a, const rtxn_optimize
   if (scaler) {
     rc = rtxn_gradient_statistics(bufs, 3, opt->guard, scaler, stream);
     if (rc != RTXN_OK) return rc;
-    rc = rtxn_loss_scaler_step(opt, scaler, bufs, 3, o.step, 1, o.lr, o.table_lr, o.beta1, o.beta2, o.effective_lr, nullptr, o.loss_scale_divisor,
-                               stream);
-    if (rc != RTXN_OK) return rc;
-    rc = rtxn_adam_step_scaled(n_mlp, o.mlp_master, o.mlp_params_fp16, b.dparams, RTXN_ADAM_ZERO_GRADS, o.mlp_m, o.mlp_v, o.effective_lr, o.lr,
-                               o.beta1, o.beta2, o.eps, opt, scaler, stream);
-    if (rc != RTXN_OK) return rc;
-    rc = rtxn_mlp_set_params_training(const_cast<rtxn_mlp*>(b.mlp), o.mlp_params_fp16, stream);
-    if (rc != RTXN_OK) return rc;
-    if (hash) {
-      __half* p16 = static_cast<__half*>(o.table_params_fp16);
-      const int flags = RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY;
-      if (lo > 0) {
-        rc = rtxn_adam_step_sparse_scaled(lo, o.table_master, p16, b.dtable, flags, o.table_m, o.table_v, o.table_steps, o.table_lr, o.beta1,
-                                          o.beta2, o.table_eps, opt, scaler, stream);
-        if (rc != RTXN_OK) return rc;
-      }
-      if (lo < n) {
-        rc = rtxn_adam_step_sparse_scaled(n - lo, o.table_master + lo, p16 + lo, b.dtable_hashed_half, flags | RTXN_ADAM_GRADS_FP16,
-                                          o.table_m + lo, o.table_v + lo, o.table_steps + lo, o.table_lr, o.beta1, o.beta2, o.table_eps, opt,
-                                          scaler, stream);
-        if (rc != RTXN_OK) return rc;
-      }
+    rc = rtxn_loss_scaler_step_ema(opt, scaler, ema, bufs, 3, o.step, 1, o.lr, o.table_lr, o.beta1, o.beta2, o.effective_lr, nullptr,
+                                   o.loss_scale_divisor, stream);
+  } else {
+    if (opt->skip_nonfinite) {
+      rc = rtxn_check_gradients(bufs, 3, opt->guard, stream);
+      if (rc != RTXN_OK) return rc;
     }
-    return RTXN_OK;
+    rc = rtxn_optimizer_rate_ema(opt, ema, o.step, 1, o.lr, o.table_lr, o.beta1, o.beta2, o.effective_lr, nullptr, stream);
   }
-  if (opt->skip_nonfinite) {
-    rc = rtxn_check_gradients(bufs, 3, opt->guard, stream);
-    if (rc != RTXN_OK) return rc;
-  }
-  rc = rtxn_optimizer_rate(opt, o.step, 1, o.lr, o.table_lr, o.beta1, o.beta2, o.effective_lr, nullptr, stream);
   if (rc != RTXN_OK) return rc;
   const float ls = b.loss_scale * o.loss_scale_divisor;
-  rc = rtxn_adam_step_opt(n_mlp, o.mlp_master, o.mlp_params_fp16, b.dparams, RTXN_ADAM_ZERO_GRADS, o.mlp_m, o.mlp_v, o.effective_lr, o.lr, o.beta1,
-                          o.beta2, o.eps, ls, opt, stream);
+  rc = rtxn_adam_step_ema(n_mlp, o.mlp_master, o.mlp_params_fp16, b.dparams, RTXN_ADAM_ZERO_GRADS, o.mlp_m, o.mlp_v, o.effective_lr, o.lr, o.beta1,
+                          o.beta2, o.eps, ls, opt, scaler, ema, ema ? ema->mlp_ema : nullptr, stream);
   if (rc != RTXN_OK) return rc;
   rc = rtxn_mlp_set_params_training(const_cast<rtxn_mlp*>(b.mlp), o.mlp_params_fp16, stream);
   if (rc != RTXN_OK) return rc;
   if (hash) {
     __half* p16 = static_cast<__half*>(o.table_params_fp16);
     const int flags = RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY;
+    float* acc = ema ? ema->table_ema : nullptr;
+    unsigned* stamps = ema ? ema->table_stamps : nullptr;
     if (lo > 0) {
-      rc = rtxn_adam_step_sparse_opt(lo, o.table_master, p16, b.dtable, flags, o.table_m, o.table_v, o.table_steps, o.table_lr, o.beta1, o.beta2,
-                                     o.table_eps, ls, opt, stream);
+      rc = rtxn_adam_step_sparse_ema(lo, o.table_master, p16, b.dtable, flags, o.table_m, o.table_v, o.table_steps, o.table_lr, o.beta1, o.beta2,
+                                     o.table_eps, ls, opt, scaler, ema, acc, stamps, stream);
       if (rc != RTXN_OK) return rc;
     }
     if (lo < n) {
-      rc = rtxn_adam_step_sparse_opt(n - lo, o.table_master + lo, p16 + lo, b.dtable_hashed_half, flags | RTXN_ADAM_GRADS_FP16, o.table_m + lo,
-                                     o.table_v + lo, o.table_steps + lo, o.table_lr, o.beta1, o.beta2, o.table_eps, ls, opt, stream);
+      rc = rtxn_adam_step_sparse_ema(n - lo, o.table_master + lo, p16 + lo, b.dtable_hashed_half, flags | RTXN_ADAM_GRADS_FP16, o.table_m + lo,
+                                     o.table_v + lo, o.table_steps + lo, o.table_lr, o.beta1, o.beta2, o.table_eps, ls, opt, scaler, ema,
+                                     ema ? acc + lo : nullptr, ema ? stamps + lo : nullptr, stream);
       if (rc != RTXN_OK) return rc;
     }
   }
   return RTXN_OK;
 }
 
-// opt: ACTIVE optimizer options (rtxn_train_step_opt, optimizer.hip) or NULL; scaler: the loss scaler (with opt) or NULL
+// opt: ACTIVE optimizer options (rtxn_train_step_opt, optimizer.hip) or NULL; scaler: the loss scaler (with opt) or NULL;
+// ema: the weight EMA (with opt, active or not) or NULL
 static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                            const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
-                           const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
+                           const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
@@ -158,7 +144,7 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
      : jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
   if (rc != RTXN_OK) return rc;
 
-  if (opt) return optimizer_step_opt(a, opt, scaler, stream);
+  if (opt) return optimizer_step_opt(a, opt, scaler, ema, stream);
   // ---- optimizer->step (main.cu:787): every gradient is cleared as it is consumed ----
   advance_step_kernel<<<1, 1, 0, rtxn::as_stream(stream)>>>(o.step, o.lr, o.beta1, o.beta2, o.effective_lr);
   RTXN_LAUNCH_CHECK("advance_step_kernel");
@@ -185,18 +171,18 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   return RTXN_OK;
 }
 
-extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream); }
+extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream); }
 
 extern "C" int rtxn_train_step_ex(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "rtxn_train_step_ex: NULL arguments");
   bool active = false;
   const int rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_ex", &active);
   if (rc != RTXN_OK) return rc;
-  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
   // RANDOM without a counter of its own: the optimizer's, read by the compositor before advance_step_kernel increments it
   rtxn_train_background own = *bg;
   if (own.mode == RTXN_BG_RANDOM && !own.step) own.step = a->opt.step;
-  return train_step_impl(a, &own, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  return train_step_impl(a, &own, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the sampler's jitter; a NULL jitter->step is the optimizer's counter too, by the same rule
@@ -218,7 +204,7 @@ extern "C" int rtxn_train_step_jitter(const rtxn_train_step_args* a, const rtxn_
     own_jitter = *jitter;
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the loss of rtxn_train_loss (rtxn_train_gradients_loss); NULL, or plain L2: rtxn_train_step_jitter
@@ -242,14 +228,14 @@ extern "C" int rtxn_train_step_loss(const rtxn_train_step_args* a, const rtxn_tr
     own_jitter = *jitter;
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, nullptr, nullptr, nullptr, stream);
+  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and with the distortion regulariser (rtxn_train_gradients_reg): the write pass of the traversal stores t_start / t_end
 // into the struct's buffers; NULL, or weight 0 without outputs: rtxn_train_step_loss
 static int train_step_reg(const char* who, const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
-                          const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
+                          const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream) {
   RTXN_REQUIRE(a, "%s: NULL arguments", who);
   if (scaler)
     RTXN_REQUIRE(a->batch.vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor (batch.vr_mode = %d)", who, a->batch.vr_mode);
@@ -276,12 +262,12 @@ static int train_step_reg(const char* who, const rtxn_train_step_args* a, const 
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
   return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, reg_active ? reg : nullptr,
-                         opt, scaler, stream);
+                         opt, scaler, ema, stream);
 }
 
 extern "C" int rtxn_train_step_reg(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
-  return train_step_reg("rtxn_train_step_reg", a, bg, jitter, loss, reg, nullptr, nullptr, stream);
+  return train_step_reg("rtxn_train_step_reg", a, bg, jitter, loss, reg, nullptr, nullptr, nullptr, stream);
 }
 
 // ... and under the optimizer options (optimizer.hip); NULL, or nothing switched on: rtxn_train_step_reg
@@ -292,7 +278,7 @@ extern "C" int rtxn_train_step_opt(const rtxn_train_step_args* a, const rtxn_tra
   const int rc = rtxn::check_optimizer_options(opt, "rtxn_train_step_opt", true, &opt_active);
   if (rc != RTXN_OK) return rc;
   if (!opt_active) return rtxn_train_step_reg(a, bg, jitter, loss, reg, stream);
-  return train_step_reg("rtxn_train_step_opt", a, bg, jitter, loss, reg, opt, nullptr, stream);
+  return train_step_reg("rtxn_train_step_opt", a, bg, jitter, loss, reg, opt, nullptr, nullptr, stream);
 }
 
 // ... and with the dynamic loss scale (rtxn_loss_scaler, optimizer.hip), which implies the non-finite guard; NULL: rtxn_train_step_opt
@@ -308,5 +294,31 @@ extern "C" int rtxn_train_step_scaled(const rtxn_train_step_args* a, const rtxn_
   if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(opt && opt->skip_nonfinite && opt->guard && opt->lr_factor,
                "%s: the loss scaler needs options with skip_nonfinite, guard and lr_factor: dynamic scaling implies the non-finite guard", who);
-  return train_step_reg(who, a, bg, jitter, loss, reg, opt, scaler, stream);
+  return train_step_reg(who, a, bg, jitter, loss, reg, opt, scaler, nullptr, stream);
+}
+
+// ... and with the weight EMA (rtxn_weight_ema, optimizer.hip); NULL: rtxn_train_step_scaled.  The options may have nothing switched
+// on: the step goes through the rate kernel all the same, which advances the EMA's update count.
+extern "C" int rtxn_train_step_ema(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                   const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                                   const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream) {
+  const char* who = "rtxn_train_step_ema";
+  if (!ema) return rtxn_train_step_scaled(a, bg, jitter, loss, reg, opt, scaler, stream);
+  int rc = rtxn_weight_ema_check(ema);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(a, "%s: NULL arguments", who);
+  RTXN_REQUIRE(ema->state && ema->mlp_ema, "%s: ema->state = %p, ema->mlp_ema = %p", who, (void*)ema->state, (void*)ema->mlp_ema);
+  RTXN_REQUIRE(!a->batch.grid || (ema->table_ema && ema->table_stamps),
+               "%s: a hash grid needs ema->table_ema and ema->table_stamps (this call steps the table by the sparse rule)", who);
+  bool opt_active = false;
+  rc = rtxn::check_optimizer_options(opt, who, true, &opt_active);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(opt && opt->lr_factor && (!opt->skip_nonfinite || opt->guard),
+               "%s: the weight EMA needs options that carry lr_factor (and guard with skip_nonfinite), with or without anything switched on", who);
+  if (scaler) {
+    rc = rtxn::check_loss_scaler(scaler, who, true);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(opt->skip_nonfinite, "%s: the loss scaler needs options with skip_nonfinite: dynamic scaling implies the non-finite guard", who);
+  }
+  return train_step_reg(who, a, bg, jitter, loss, reg, opt, scaler, ema, stream);
 }

@@ -59,8 +59,19 @@ class Trainer:
                  hashgrid=None, n_dir_freqs=4, batch_rays=4096, max_segments=None, lr=1e-3, loss_scale=128.0,
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
                  target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0,
-                 distortion_weight=0.0, lr_schedule=None, weight_decay=0.0, skip_nonfinite=False, max_grad_norm=None):
-        """loss_scale: a float (fixed, the reference's), "dynamic" (api.loss_scaler()'s defaults: from 128, x2 per 2000 clean steps, x0.5
+                 distortion_weight=0.0, lr_schedule=None, weight_decay=0.0, skip_nonfinite=False, max_grad_norm=None,
+                 ema_decay=None):
+        """ema_decay: None, or a float d strictly inside (0, 1): keep the debiased exponential moving average of the weights
+        (tiny-cuda-nn's EMA optimizer; librtxn: rtxn_weight_ema, rtxn_train_step_ema), s = d s + (1 - d) w after every
+        APPLIED update -- inside the Adam kernels of step(), step_captured() and step_entry(), which share the one state and may be
+        mixed.  The MLP's average is kept densely; the hash table's lazily under the sparse rule (only the entries Adam touches are
+        brought up to date, the read-out catches the rest up), densely under RTXN_TABLE_ADAM=dense.  A step the non-finite guard
+        skips does not move the average; the EMA does not switch the guard on, but its steps take their rate from the device rate
+        kernel, as every step under lr_schedule / weight_decay / skip_nonfinite does.  ema_updates is a device tensor no stepping
+        method reads; ema_parameters() reads the average out, sync_ema() refreshes the model render_pipeline(weights="ema") draws;
+        checkpoints hold the accumulators, the stamps and the state.  None: nothing is allocated and every call is the one made
+        without the argument.
+        loss_scale: a float (fixed, the reference's), "dynamic" (api.loss_scaler()'s defaults: from 128, x2 per 2000 clean steps, x0.5
         per skipped step, within [1, 65536]), or api.loss_scaler(init_scale=..., growth_interval=..., ...) / a dict
         of its arguments: the scale lives in device memory, is multiplied by `backoff` when a step's gradients are not finite (the
         step is skipped) and by `growth` after growth_interval clean steps, and the compositor, the optimizer, the captured and the
@@ -116,6 +127,7 @@ class Trainer:
         self._init_loss(loss, loss_param, opacity_weight)
         self._init_regularizer(distortion_weight)
         self._init_scaler(loss_scale, max_grad_norm)
+        self._init_ema(ema_decay)
         self._init_optimizer(lr_schedule, weight_decay, skip_nonfinite or self._scaler_cfg is not None)
         self.image_set = None      # attach_images(): batches drawn on the device
         self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
@@ -177,6 +189,17 @@ class Trainer:
             self._scaler_ws = api.loss_scaler_workspace(device=d)
             self._scaler = api.loss_scaler(c.init_scale, c.growth, c.backoff, c.growth_interval, c.min_scale, c.max_scale, c.max_grad_norm,
                                            state=self._scaler_state, partials=self._scaler_ws)
+        # the weight EMA: four state words, the accumulators, the table's stamps under the sparse rule, and the struct over them;
+        # the model and table sync_ema() fills are made on first use
+        self._ema = self._ema_state = self.ema_mlp = self.ema_table = self.ema_stamps = None
+        self._ema_net = self._ema_table16 = None
+        if self.ema_decay is not None:
+            self._ema_state = torch.zeros(4, dtype=torch.int32, device=d)
+            self.ema_mlp = torch.zeros_like(self.master)
+            if encoding == "hash":
+                self.ema_table = torch.zeros_like(self.table_master)
+                self.ema_stamps = torch.zeros_like(self.table_steps) if self.table_adam_sparse else None
+            self._ema = api.weight_ema(self.ema_decay, self._ema_state, self.ema_mlp, self.ema_table, self.ema_stamps)
         # 64-wide models (configs[2]): forward without saved activations + ONE fused backward kernel that recomputes them and
         # keeps every weight gradient on the chip (librtxn: mlp_bwd_fused64_kernel).  RTXN_TRAIN_RECOMPUTE=0 selects the
         # three-kernel path (saved activations, dgrad chain, weight-gradient GEMM) for A/B runs.
@@ -323,6 +346,54 @@ class Trainer:
                              "the three-launch compositor, which has no regulariser)")
         self.distortion_weight = lam
 
+    def _init_ema(self, ema_decay):
+        """the library's own rule (rtxn_weight_ema_check), before anything is allocated"""
+        self.ema_decay = None
+        if ema_decay is None:
+            return
+        try:
+            self.ema_decay = float(api.weight_ema(float(ema_decay)).decay)
+        except (api._lib.RtxnError, TypeError, ValueError) as e:
+            raise ValueError(f"Trainer: ema_decay = {ema_decay!r}: {e}") from None
+
+    @property
+    def ema_updates(self):
+        """device int32[1]: applied updates the average has seen (None without ema_decay)"""
+        return None if self._ema_state is None else self._ema_state[0:1]
+
+    def ema_parameters(self):
+        """(mlp fp32, table fp32 | None): the debiased average of the weights now (rtxn_ema_weights), in the layouts of master and
+        table_master; before the first applied update, the weights themselves.  Reads the training state, changes none of it."""
+        if self._ema is None:
+            raise RuntimeError("ema_parameters: this trainer was made without ema_decay")
+        mlp = torch.empty_like(self.master)
+        api.ema_weights(self.master, self.ema_mlp, None, self._ema_state, self.ema_decay, out_f32=mlp)
+        table = None
+        if self.encoding == "hash":
+            table = torch.empty_like(self.table_master)
+            api.ema_weights(self.table_master, self.ema_table, self.ema_stamps, self._ema_state, self.ema_decay, out_f32=table)
+        return mlp, table
+
+    def sync_ema(self):
+        """Refresh the averaged model render_pipeline(weights="ema") draws: a second model handle and a second fp16 table, filled
+        from the read-out.  The handle goes through set_params, so the frequency model's fused inference packing is refreshed too.
+        The live model, its table and the training state are only read."""
+        if self._ema is None:
+            raise RuntimeError("sync_ema: this trainer was made without ema_decay")
+        if self._ema_net is None:
+            c = self.net.cfg
+            self._ema_net = api.Network(n_neurons=c.n_neurons, n_hidden_layers=c.n_hidden_layers, n_pos_freqs=c.n_pos_freqs,
+                                        n_dir_freqs=c.n_dir_freqs, n_pos_dims=c.n_pos_dims, n_dir_dims=c.n_dir_dims,
+                                        n_output_dims=c.n_output_dims, output_activation=c.output_activation,
+                                        n_encoded_features=c.n_encoded_features)
+            self._ema_params16 = torch.empty_like(self.params)
+            if self.encoding == "hash":
+                self._ema_table16 = torch.empty_like(self.table)
+        api.ema_weights(self.master, self.ema_mlp, None, self._ema_state, self.ema_decay, out_f16=self._ema_params16)
+        self._ema_net.set_params(self._ema_params16)
+        if self.encoding == "hash":
+            api.ema_weights(self.table_master, self.ema_table, self.ema_stamps, self._ema_state, self.ema_decay, out_f16=self._ema_table16)
+
     def _init_scaler(self, loss_scale, max_grad_norm):
         """loss_scale / max_grad_norm -> self._scaler_cfg (a struct without buffers, or None) and self.loss_scale (the fixed or the
         initial scale); the library's own rules (rtxn_loss_scaler_check), before anything is allocated"""
@@ -395,7 +466,8 @@ class Trainer:
             raise ValueError(f"Trainer: lr_schedule = {lr_schedule!r}, weight_decay = {weight_decay!r}: {e}") from None
         sch = self._schedule
         scheduled = sch is not None and (sch.kind != api.LR_CONSTANT or sch.warmup_steps > 0)
-        self._opt_active = scheduled or self.weight_decay > 0.0 or self.skip_nonfinite
+        # the weight EMA's steps take the options path with whatever is switched on, nothing included: the rate kernel counts its updates
+        self._opt_active = scheduled or self.weight_decay > 0.0 or self.skip_nonfinite or self.ema_decay is not None
         if not scheduled:
             self._schedule = None
 
@@ -609,22 +681,36 @@ class Trainer:
                                       api.NUM_SAMPLES_PER_SEGMENT, self.pixels[:n], mode=vr)
         return self.pixels[:n]
 
-    def render_pipeline(self, width, height, focal_length, max_segments=None, **kw):
+    def render_pipeline(self, width, height, focal_length, max_segments=None, weights="live", **kw):
         """A render.RenderPipeline over this trainer's LIVE model: the fast inference path (rtxn_render_frame: traversal, the fused
         frequency / hash-encode + MLP kernel, compact compositor; pipelined and ray-shardable) drawing whatever the parameters are
         at the time of each frame -- the pipeline holds the trainer's own model handle, hash table and occupancy tensors, and
         rtxn_mlp_set_params[_training] / Adam update them in place.  Compositor and sampling follow the trainer's mode ("nerf":
         midpoint samples, world-space steps x density_scale, exclusive transmittance; "compat": the reference's).  The
         frequency model renders through its fused inference kernel, whose weights a training-only update leaves stale:
-        call sync_inference_weights() before rendering.  update_occupancy() refreshes the pipelines made here."""
+        call sync_inference_weights() before rendering.  update_occupancy() refreshes the pipelines made here.
+        weights="ema" (ema_decay; call sync_ema() first, and again whenever the frames should follow the training): the pipeline is
+        built over the averaged model and fp16 table sync_ema() fills instead of the live ones; render_rays(), update_occupancy()
+        and refresh_occupancy() stay on the live weights.  A model without a fused inference kernel renders its average from
+        ema_parameters()."""
         from . import render
         nerf = self.mode == "nerf"
+        if weights not in ("live", "ema"):
+            raise ValueError(f"render_pipeline: weights = {weights!r}: 'live' or 'ema'")
+        net, table = self.net, getattr(self, "table", None)
+        if weights == "ema":
+            if self._ema is None:
+                raise RuntimeError("render_pipeline(weights='ema'): this trainer was made without ema_decay")
+            if self._ema_net is None:
+                raise RuntimeError("render_pipeline(weights='ema'): call sync_ema() first")
+            net, table = self._ema_net, self._ema_table16
         if self.encoding == "hash":
             if not api.hashmlp_supported(self.net, self.hg):
                 raise api._lib.RtxnError("render_pipeline: no fused hash-grid inference kernel for this model (built: 64 wide, <= 8 hidden "
-                                         "layers, 2 features per level, an even number of levels); use render_rays()")
-            kw.update(hashgrid=self.hg, table=self.table)
-        pipe = render.RenderPipeline(self.net, self.R, width, height, focal_length, occupancy=self.occ, max_segments=max_segments,
+                                         "layers, 2 features per level, an even number of levels); use render_rays()"
+                                         + (" on a model set to ema_parameters()" if weights == "ema" else ""))
+            kw.update(hashgrid=self.hg, table=table)
+        pipe = render.RenderPipeline(net, self.R, width, height, focal_length, occupancy=self.occ, max_segments=max_segments,
                                      vr_mode=api.VR_NERF if nerf else api.VR_COMPAT, step_scale=self.density_scale if nerf else 1.0, **kw)
         self._pipelines = [r for r in getattr(self, "_pipelines", []) if r() is not None] + [weakref.ref(pipe)]
         return pipe
@@ -791,40 +877,33 @@ class Trainer:
         parts = []
         if hash_:
             parts = [(slice(0, lo), self.dtable[:lo]), (slice(lo, None), self.dtable_h)] if self.hash_fp16 else [(slice(None), self.dtable)]
-        if self._scaler is not None:
-            bufs = [self.dparams] + [g for _, g in parts]
-            api.gradient_statistics(bufs, self._opt_guard, self._scaler)
-            api.loss_scaler_step(self._opt, self._scaler, bufs, step, rates[0:1], lr=self.lr, table_lr=self.lr * 10.0,
-                                 table_effective_lr=rates[1:2], divisor=grad_divisor)
-            api.adam_step_scaled(self.master, self.params, self.dparams, self.adam_m, self.adam_v, rates[0:1], self._opt, self._scaler,
-                                 lr=self.lr, zero_grads=True)
-            self.net.set_params_training(self.params)
-            for sl, g in parts:
-                if not g.numel():
-                    continue
-                if self.table_adam_sparse:
-                    api.adam_step_sparse_scaled(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl],
-                                                self.table_steps[sl], self._opt, self._scaler, lr=self.lr * 10.0, eps=1e-15, zero_grads=True,
-                                                weight_decay=False)
-                else:
-                    api.adam_step_scaled(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], rates[1:2], self._opt,
-                                         self._scaler, lr=self.lr * 10.0, eps=1e-15, zero_grads=True, weight_decay=False)
-            return
-        if self.skip_nonfinite:
-            api.check_gradients([self.dparams] + [g for _, g in parts], self._opt_guard)
-        api.optimizer_rate(self._opt, step, rates[0:1], lr=self.lr, table_lr=self.lr * 10.0, table_effective_lr=rates[1:2])
-        api.adam_step_opt(self.master, self.params, self.dparams, self.adam_m, self.adam_v, rates[0:1], self._opt, lr=self.lr, loss_scale=ls,
-                          zero_grads=True)
+        # one sequence for every combination: the _ema entry points with ema None are the _scaled calls, and those with scaler None
+        # the _opt calls -- the same launches (rtxn_train_step_ema sequences its calls the same way)
+        ema, scaler = self._ema, self._scaler
+        bufs = [self.dparams] + [g for _, g in parts]
+        if scaler is not None:
+            api.gradient_statistics(bufs, self._opt_guard, scaler)
+            api.loss_scaler_step_ema(self._opt, scaler, ema, bufs, step, rates[0:1], lr=self.lr, table_lr=self.lr * 10.0,
+                                     table_effective_lr=rates[1:2], divisor=grad_divisor)
+        else:
+            if self.skip_nonfinite:
+                api.check_gradients(bufs, self._opt_guard)
+            api.optimizer_rate_ema(self._opt, ema, step, rates[0:1], lr=self.lr, table_lr=self.lr * 10.0, table_effective_lr=rates[1:2])
+        kw = dict(scaler=scaler, loss_scale=ls, zero_grads=True)
+        api.adam_step_ema(self.master, self.params, self.dparams, self.adam_m, self.adam_v, rates[0:1], self._opt, ema, self.ema_mlp,
+                          lr=self.lr, **kw)
         self.net.set_params_training(self.params)
+        cut = lambda t, sl: None if t is None else t[sl]
         for sl, g in parts:
             if not g.numel():
                 continue
             if self.table_adam_sparse:
-                api.adam_step_sparse_opt(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], self.table_steps[sl],
-                                         self._opt, lr=self.lr * 10.0, eps=1e-15, loss_scale=ls, zero_grads=True, weight_decay=False)
+                api.adam_step_sparse_ema(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], self.table_steps[sl],
+                                         self._opt, ema, cut(self.ema_table, sl), cut(self.ema_stamps, sl), lr=self.lr * 10.0, eps=1e-15,
+                                         weight_decay=False, **kw)
             else:
-                api.adam_step_opt(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], rates[1:2], self._opt,
-                                  lr=self.lr * 10.0, eps=1e-15, loss_scale=ls, zero_grads=True, weight_decay=False)
+                api.adam_step_ema(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], rates[1:2], self._opt,
+                                  ema, cut(self.ema_table, sl), lr=self.lr * 10.0, eps=1e-15, weight_decay=False, **kw)
 
     def _table_adam_sparse(self, **kw):
         """rtxn_adam_step_sparse over the table: the densely stored levels from the fp32 gradient, the hashed ones from the fp16 one"""
@@ -940,6 +1019,27 @@ class Trainer:
                         table_adam_v=self.table_v, table_adam_steps=self.table_steps)
         return arrs
 
+    _EMA_ARRAYS = ("ema_state", "ema_mlp", "ema_table", "ema_table_stamps")
+
+    def _ema_header(self):
+        """the weight EMA's configuration for a checkpoint header (None without ema_decay): the decay (a float32 survives JSON's
+        double exactly) and the form of the table's average"""
+        if self._ema is None:
+            return None
+        return {"decay": float(np.float32(self.ema_decay)),
+                "table": None if self.ema_table is None else "lazy" if self.ema_stamps is not None else "dense"}
+
+    def _ema_arrays(self):
+        """the weight EMA's share of a checkpoint (nothing without ema_decay): optional on loading, unlike state_arrays()"""
+        if self._ema is None:
+            return {}
+        arrs = {"ema_state": self._ema_state, "ema_mlp": self.ema_mlp}
+        if self.ema_table is not None:
+            arrs["ema_table"] = self.ema_table
+        if self.ema_stamps is not None:
+            arrs["ema_table_stamps"] = self.ema_stamps
+        return arrs
+
     _SCALER_WORDS = (("scale", 0, True), ("multiplier", 1, True), ("good", 2, False), ("backoffs", 3, False), ("growths", 4, False),
                      ("clipped", 5, False), ("grad_norm", 6, True))
 
@@ -968,11 +1068,11 @@ class Trainer:
         """The header's "draw_count" is the number of batches DRAWN (attach_images): the loaded trainer draws batch draw_count
         next.  With capture_step(prefetch=True, draw=True) one batch is drawn ahead of the step that trains on it, so a
         checkpoint saved between replays resumes one batch further on: the pending batch is skipped, none is repeated."""
-        arrs = {k: v.detach().cpu().numpy() for k, v in self.state_arrays().items()}
+        arrs = {k: v.detach().cpu().numpy() for k, v in {**self.state_arrays(), **self._ema_arrays()}.items()}
         cfg = self.net.cfg
         header = {"step": self.step_count, "draw_count": self.draw_count,
                   "skipped_steps": 0 if self._opt_guard is None else int(self._opt_guard[1].item()),
-                  "loss_scaler": self._scaler_header(),
+                  "loss_scaler": self._scaler_header(), "weight_ema": self._ema_header(),
                   "encoding": self.encoding, "grid_res": self.R, "mode": self.mode,
                   "mlp": {f: getattr(cfg, f) for f, _ in cfg._fields_},
                   "hashgrid": None if self.hg is None else {**{f: getattr(self.hg.cfg, f) for f, _ in self.hg.cfg._fields_},
@@ -1002,6 +1102,23 @@ class Trainer:
                 raise ValueError(f"{path}: version {version} / encoding {header['encoding']} does not match this trainer")
             dst = self.state_arrays()
             missing = set(dst) - {ent["name"] for ent in header["arrays"]}
+            # the weight EMA's arrays are optional both ways: a file without them starts the average at u = 0, a trainer without
+            # the EMA reads past them.  An average kept with another decay, or in the other form of the table's average (lazy with
+            # stamps under the sparse rule, dense without under RTXN_TABLE_ADAM=dense), cannot be continued -- a lazy accumulator
+            # read as a dense one is stale wherever Adam did not touch it: such a file starts the average at u = 0 as well, loudly
+            ema = self._ema_arrays()
+            in_file = {ent["name"] for ent in header["arrays"]}
+            saved = header.get("weight_ema")
+            ema_in_file = bool(in_file & {"ema_state", "ema_mlp", "ema_table", "ema_table_stamps"})
+            if ema and ema_in_file and (saved != self._ema_header() or set(ema) != in_file & set(self._EMA_ARRAYS)):
+                import warnings
+                warnings.warn(f"{path}: the checkpoint's weight EMA ({saved}) is not this trainer's ({self._ema_header()}): "
+                              "the average starts over at u = 0")
+                ema_in_file = False
+            if ema and not ema_in_file:
+                for t in ema.values():
+                    t.zero_()
+                ema = {}
             if missing == {"table_adam_steps"} and version == 1:
                 import warnings
                 warnings.warn(f"{path}: version-1 checkpoint without per-entry table step counts: every entry's count is set to the "
@@ -1012,7 +1129,9 @@ class Trainer:
             for ent in header["arrays"]:
                 f.seek((-f.tell()) % 64, 1)
                 a = np.frombuffer(f.read(int(np.prod(ent["shape"])) * np.dtype(ent["dtype"]).itemsize), dtype=ent["dtype"])
-                t = dst[ent["name"]]
+                t = dst.get(ent["name"], ema.get(ent["name"]))
+                if t is None:
+                    continue
                 if list(t.shape) != ent["shape"]:
                     raise ValueError(f"{path}: {ent['name']} has shape {ent['shape']}, model needs {list(t.shape)}")
                 t.copy_(torch.from_numpy(a.reshape(ent["shape"]).copy()))
@@ -1127,6 +1246,7 @@ class Trainer:
                   self.table_steps.clone()) if self.encoding == "hash" else None
         guard = None if self._opt_guard is None else self._opt_guard.clone()
         scaler_state = None if self._scaler_state is None else self._scaler_state.clone()
+        ema_state = {k: v.clone() for k, v in self._ema_arrays().items()}
         clear_grads = self._clear_grads
         with torch.cuda.stream(side):
             clear_grads()
@@ -1148,6 +1268,8 @@ class Trainer:
             self._opt_guard.copy_(guard)            # a warm-up pass over non-finite inputs is not a skipped step
         if scaler_state is not None:
             self._scaler_state.copy_(scaler_state)  # ... and moves neither the scale nor its counters
+        for k, v in self._ema_arrays().items():
+            v.copy_(ema_state[k])                   # ... nor is it an update of the average
         self.net.set_params_training(self.params)
         self._g_step.fill_(self.step_count)
         self._g_step_host = self.step_count     # host mirror of the device counter (see _sync_device_step)
@@ -1285,7 +1407,7 @@ class Trainer:
             api.draw_batch_launch(self._entry_draw)
             self._draw_step.add_(1)
             self.draw_count += 1
-        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt, self._scaler)
+        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt, self._scaler, self._ema)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
