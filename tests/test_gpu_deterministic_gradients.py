@@ -75,7 +75,8 @@ def _segments(torch, api, rng, P, stype):
 
 
 # --------------------------------------------------------------------------------------------------------------- A.1 scatter
-@pytest.mark.parametrize("levels,feat,log2,base,scale,P", [(16, 2, 19, 16, 1.5, 19_000), (4, 2, 10, 4, 1.7, 400), (8, 4, 14, 8, 2.0, 3000)])
+@pytest.mark.parametrize("levels,feat,log2,base,scale,P", [(16, 2, 19, 16, 1.5, 19_000), (4, 2, 10, 4, 1.7, 400), (8, 4, 14, 8, 2.0, 3000),
+                                                                   (5, 1, 10, 4, 1.7, 300), (2, 8, 12, 8, 2.0, 300)])
 def test_deterministic_hash_scatter_matches_float64(gpu, oracle, levels, feat, log2, base, scale, P):
     """The deterministic scatter (hashgrid_backward_kernel<false, true> + det_fold_kernel) per element against the oracle's double
     sum, in every form: HashGrid.backward, backward_mixed (hashed levels folded into fp16), backward_segments (REGULAR and

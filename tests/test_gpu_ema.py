@@ -260,7 +260,8 @@ def _occ(torch):
 def _trainer(torch, encoding, neurons, layers, **kw):
     from rtx_nerf_amd.train import Trainer
     kw.setdefault("deterministic", True)
-    return Trainer(R, _occ(torch), encoding=encoding, n_neurons=neurons, n_hidden_layers=layers, hashgrid=HGD if encoding == "hash" else None,
+    hgd = kw.pop("hashgrid", HGD)
+    return Trainer(R, _occ(torch), encoding=encoding, n_neurons=neurons, n_hidden_layers=layers, hashgrid=hgd if encoding == "hash" else None,
                    n_dir_freqs=4, batch_rays=B, max_segments=B * 30, lr=1e-2, loss_scale=LS, density_scale=120.0, mode="nerf", seed=3, **kw)
 
 
@@ -406,8 +407,19 @@ def test_a_step_the_guard_skips_does_not_count_on_any_path(gpu, encoding, neuron
 
 
 def test_the_three_stepping_methods_of_one_trainer_share_the_average(gpu):
+    _mixed_against_eager(gpu)
+
+
+def test_the_three_stepping_methods_share_the_average_on_a_one_feature_grid(gpu):
+    """five levels of ONE feature: an odd level count, the fp32 scatter, and four table entries per quad of the lazy kernel"""
+    mixed = _mixed_against_eager(gpu, hashgrid=dict(HGD, n_levels=5, n_features=1))
+    assert mixed.hg.cfg.n_features == 1 and not mixed.hash_fp16
+    assert bool((mixed.ema_stamps == 0).any()) and bool((mixed.ema_stamps == 6).any())
+
+
+def _mixed_against_eager(gpu, **kw):
     torch = gpu
-    mixed, eager = (_trainer(torch, "hash", 64, 4, ema_decay=0.9, skip_nonfinite=True) for _ in range(2))
+    mixed, eager = (_trainer(torch, "hash", 64, 4, ema_decay=0.9, skip_nonfinite=True, **kw) for _ in range(2))
     mixed.capture_step(B, launch_segments=B * 30)
     mixed.entry_args(B, launch_segments=B * 30)
     for i, p in enumerate(("eager", "captured", "entry", "captured", "eager", "entry")):
@@ -416,6 +428,7 @@ def test_the_three_stepping_methods_of_one_trainer_share_the_average(gpu):
     torch.cuda.synchronize()
     assert int(mixed.ema_updates.item()) == 6
     assert _same(torch, _ema_state(eager), _ema_state(mixed)) == [] and _same(torch, _state(eager), _state(mixed)) == []
+    return mixed
 
 
 def test_dense_table_rule_keeps_the_table_average_densely(gpu, monkeypatch):

@@ -62,12 +62,22 @@ def test_occupancy_refresh_from_density(gpu):
 
 
 def test_data_parallel_equals_single_process(gpu, tmp_path):
+    _dp_equals_single_process(tmp_path, "29533", [])
+
+
+def test_data_parallel_equals_single_process_with_four_features(gpu, tmp_path):
+    """F = 4: the scatter is fp32 on every level and Trainer._allreduce_table_grad stages the hashed levels in fp16 for the wire
+    (convert, all-reduce, widen back): the same bars as the two-feature grid, whose hashed gradient is fp16 throughout."""
+    _dp_equals_single_process(tmp_path, "29571", ["--features", "4"])
+
+
+def _dp_equals_single_process(tmp_path, port, extra):
     env = dict(os.environ, RTXN_REHEARSE_ON_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     ref, dp = str(tmp_path / "ref.npy"), str(tmp_path / "dp.npy")
     tool = os.path.join(ROOT, "tools", "train_dp_check.py")
-    subprocess.check_call([sys.executable, tool, "--out", ref], env=env, timeout=600)
+    subprocess.check_call([sys.executable, tool, "--out", ref] + extra, env=env, timeout=600)
     subprocess.check_call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                           "--master-addr", "127.0.0.1", "--master-port", "29533", tool, "--out", dp], env=env, timeout=900)
+                           "--master-addr", "127.0.0.1", "--master-port", port, tool, "--out", dp] + extra, env=env, timeout=900)
     a, b = np.load(ref), np.load(dp)
     assert a.shape == b.shape and np.isfinite(b).all()
     ga, gb = a[0], b[0]

@@ -19,9 +19,37 @@ def test_training_converges(gpu, encoding, steps, gain):
     assert p1 > p0 + gain, (p0, p1)          # held-out pose, measured: hash +10.5 dB, freq +7.7 dB
 
 
+TODAY = dict(n_levels=4, n_features=2, log2_hashmap_size=11, base_resolution=4, per_level_scale=1.6)
+# The same step on the grids the Trainer had never seen (tests/test_gpu_hashgrid_float64.py holds the kernels themselves to
+# float64): four features (fp32 scatter, general encoder), one feature with an odd level count, every level hashed
+# (hashed_offset() == 0: empty dense slices into Adam) and every level dense (hashed_offset() == n_params: no fp16 gradient).
+OTHER_GRIDS = {
+    "f4": dict(TODAY, n_features=4),
+    "f1-odd": dict(TODAY, n_levels=5, n_features=1),
+    "all-hashed": dict(n_levels=4, n_features=2, log2_hashmap_size=8, base_resolution=16, per_level_scale=1.6),
+    "all-dense": dict(n_levels=3, n_features=2, log2_hashmap_size=19, base_resolution=4, per_level_scale=1.6),
+}
+
+
 def test_config3_training_step_matches_oracle_chain(gpu, oracle):
     """BASELINE configs[2] in miniature (hash-grid encoding + 4x64 MLP, one ray batch): every stage of one
     optimisation step on the GPU against the same step chained from oracle functions."""
+    _config3_step(gpu, oracle, TODAY)
+
+
+@pytest.mark.parametrize("grid", list(OTHER_GRIDS))
+def test_config3_training_step_matches_oracle_chain_on_other_grids(gpu, oracle, grid):
+    hgd = OTHER_GRIDS[grid]
+    tr = _config3_step(gpu, oracle, hgd)
+    n = tr.hg.n_params()
+    if grid in ("all-hashed", "all-dense"):
+        assert tr.hashed_lo == (0 if grid == "all-hashed" else n)
+    else:
+        assert 0 < tr.hashed_lo < n
+    assert tr.hash_fp16 == (hgd["n_features"] == 2 and tr.hashed_lo < n)
+
+
+def _config3_step(gpu, oracle, hgd):
     import numpy as np
     torch = gpu
     from rtx_nerf_amd import api, scenes
@@ -30,7 +58,6 @@ def test_config3_training_step_matches_oracle_chain(gpu, oracle):
     dense = scenes.sphere_density(R, 0.75)
     words = scenes.pack_occupancy(dense)
     occ = torch.from_numpy(words.view(np.int32).copy()).cuda()
-    hgd = dict(n_levels=4, n_features=2, log2_hashmap_size=11, base_resolution=4, per_level_scale=1.6)
     tr = Trainer(R, occ, encoding="hash", n_neurons=64, n_hidden_layers=4, hashgrid=hgd, n_dir_freqs=4, batch_rays=B,
                  max_segments=B * 30, lr=1e-2, loss_scale=ls, density_scale=scale, mode="nerf", seed=3)
     # give the table non-trivial values so the encoding is not ~0
@@ -111,6 +138,7 @@ def test_config3_training_step_matches_oracle_chain(gpu, oracle):
     np.testing.assert_allclose(tr.table_master.cpu().numpy(), tmaster0, rtol=0, atol=2e-6)
     np.testing.assert_array_equal(tr.table_steps.cpu().numpy().view(np.uint32), steps)
     assert 0 < int(steps.sum()) < steps.size
+    return tr
 
 
 def test_compat_training_step_matches_oracle_chain(gpu, oracle):
@@ -174,14 +202,14 @@ def test_compat_training_step_matches_oracle_chain(gpu, oracle):
     np.testing.assert_allclose(tr.master.cpu().numpy(), master0, rtol=0, atol=2e-6)
 
 
-def _small_trainer(torch, encoding, mode, neurons, layers, seed=3, **kw):
+def _small_trainer(torch, encoding, mode, neurons, layers, seed=3, hgd=None, **kw):
     import numpy as np
     from rtx_nerf_amd import scenes
     from rtx_nerf_amd.train import Trainer
     R, B = 16, 900
     words = scenes.pack_occupancy(scenes.sphere_density(R, 0.75))
     occ = torch.from_numpy(words.view(np.int32).copy()).cuda()
-    hgd = dict(n_levels=4, n_features=2, log2_hashmap_size=11, base_resolution=4, per_level_scale=1.6)
+    hgd = hgd or TODAY
     return Trainer(R, occ, encoding=encoding, n_neurons=neurons, n_hidden_layers=layers, hashgrid=hgd if encoding == "hash" else None,
                    n_dir_freqs=4, batch_rays=B, max_segments=B * 30, lr=1e-2, loss_scale=128.0,
                    density_scale=120.0 if mode == "nerf" else 1.0, mode=mode, seed=seed, **kw)
@@ -190,6 +218,15 @@ def _small_trainer(torch, encoding, mode, neurons, layers, seed=3, **kw):
 @pytest.mark.parametrize("encoding,mode,neurons,layers", [("hash", "nerf", 64, 4), ("freq", "nerf", 128, 2), ("freq", "compat", 64, 2),
                                                           ("hash", "compat", 128, 2)])
 def test_captured_step_matches_the_eager_step(gpu, encoding, mode, neurons, layers):
+    _captured_vs_eager(gpu, encoding, mode, neurons, layers)
+
+
+@pytest.mark.parametrize("grid", ["f4", "all-hashed"])
+def test_captured_step_matches_the_eager_step_on_other_grids(gpu, grid):
+    _captured_vs_eager(gpu, "hash", "nerf", 64, 4, hgd=OTHER_GRIDS[grid])
+
+
+def _captured_vs_eager(gpu, encoding, mode, neurons, layers, hgd=None):
     """Trainer.capture_step / step_captured (one hipGraph: traversal -> rtxn_train_gradients with the segment count read on the
     device -> Adam -> re-pack) against Trainer.step (per-stage entry points, segment count on the host) on the same batches:
     same loss and the same parameters after several steps, up to the order of the fp32 / fp16 atomics.  Covers the recompute
@@ -199,8 +236,8 @@ def test_captured_step_matches_the_eager_step(gpu, encoding, mode, neurons, laye
     torch = gpu
     from rtx_nerf_amd import scenes
     from rtx_nerf_amd.train import camera_rays
-    a = _small_trainer(torch, encoding, mode, neurons, layers)
-    b = _small_trainer(torch, encoding, mode, neurons, layers)
+    a = _small_trainer(torch, encoding, mode, neurons, layers, hgd=hgd)
+    b = _small_trainer(torch, encoding, mode, neurons, layers, hgd=hgd)
     B = 900
     focal = scenes.lego_focal_length(True)
     rng = np.random.default_rng(1)
@@ -240,6 +277,15 @@ def test_captured_step_matches_the_eager_step(gpu, encoding, mode, neurons, laye
 
 @pytest.mark.parametrize("encoding,mode,neurons,layers", [("hash", "nerf", 64, 4), ("freq", "compat", 128, 2), ("freq", "nerf", 128, 3)])
 def test_train_step_entry_matches_the_eager_step(gpu, encoding, mode, neurons, layers):
+    _entry_vs_eager(gpu, encoding, mode, neurons, layers)
+
+
+@pytest.mark.parametrize("grid", ["f4", "all-hashed"])
+def test_train_step_entry_matches_the_eager_step_on_other_grids(gpu, grid):
+    _entry_vs_eager(gpu, "hash", "nerf", 64, 4, hgd=OTHER_GRIDS[grid])
+
+
+def _entry_vs_eager(gpu, encoding, mode, neurons, layers, hgd=None):
     """rtxn_train_step -- traversal, rtxn_train_gradients, tiny-cuda-nn's Adam (device step counter) and the weight re-pack of one
     batch as ONE C call, what a C++ host uses (examples/train_host.cpp) -- against Trainer.step (per-stage entry points, host
     step count) on the same batches: same losses, same parameters up to the order of the atomics; then the same call captured
@@ -248,8 +294,8 @@ def test_train_step_entry_matches_the_eager_step(gpu, encoding, mode, neurons, l
     torch = gpu
     from rtx_nerf_amd import scenes
     from rtx_nerf_amd.train import camera_rays
-    a = _small_trainer(torch, encoding, mode, neurons, layers)
-    b = _small_trainer(torch, encoding, mode, neurons, layers)
+    a = _small_trainer(torch, encoding, mode, neurons, layers, hgd=hgd)
+    b = _small_trainer(torch, encoding, mode, neurons, layers, hgd=hgd)
     a_table0 = a.table_master.cpu().numpy().copy() if encoding == "hash" else None
     B = 900
     focal = scenes.lego_focal_length(True)

@@ -23,6 +23,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--out", required=True)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--encoding", default="hash")
+ap.add_argument("--features", type=int, default=2, help="features per hash-grid level (other than 2: the fp32 scatter, whose hashed "
+                "levels are staged in fp16 for the wire)")
 ap.add_argument("--empty-odd", action="store_true", help="every odd ray of the global batch (= all of rank 1's share in a 2-rank run) "
                 "points away from the grid: that rank has NO samples and must still take part in every collective and Adam step")
 ap.add_argument("--captured", action="store_true", help="Trainer.capture_step / step_captured: gradients and optimizer as two hipGraphs "
@@ -38,7 +40,7 @@ if world > 1:
 R, res, B = 32, 32, 2048
 occ = torch.from_numpy(scenes.pack_occupancy(scenes.sphere_density(R, 0.72)).view(np.int32).copy()).cuda()
 tr = Trainer(R, occ, encoding=a.encoding, n_neurons=64, n_hidden_layers=2,
-             hashgrid=dict(n_levels=4, n_features=2, log2_hashmap_size=12, base_resolution=8, per_level_scale=1.5),
+             hashgrid=dict(n_levels=4, n_features=a.features, log2_hashmap_size=12, base_resolution=8, per_level_scale=1.5),
              batch_rays=B, max_segments=B * 40, lr=1e-2, loss_scale=128.0, density_scale=150.0, seed=0)
 focal = scenes.lego_focal_length(True)
 o, d = camera_rays(scenes.pose_spherical(20.0, -30.0, origin_scale=10.0), focal, res, res)
