@@ -11,6 +11,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego --distortion-weight 0.01 --loss-scale 4096     (mip-NeRF 360's distortion loss)
   python examples/train_synthetic.py --data /path/to/lego --steps 20000 --lr-schedule cosine:20000 --weight-decay 1e-6 --skip-nonfinite
   python examples/train_synthetic.py --data /path/to/lego --steps 20000 --ema-decay 0.99     (held-out PSNR of the live and the averaged weights)
+  python examples/train_synthetic.py --data /path/to/lego --pose-noise 0.5,0.02 --refine-poses 1e-3     (noisy poses, refined on the device)
 """
 import argparse
 import json
@@ -47,6 +48,29 @@ def make_demo(path, n_frames=16, res=64, grid=32):
     return path
 
 
+def perturb_poses(poses, rot_deg, trans, seed=0):
+    """[N, 4, 4] camera-to-world poses, each rotated about a random axis by rot_deg degrees (a left multiplication, the frame the
+    refinement corrects in) and moved by `trans` in a random direction; seeded."""
+    rng = np.random.default_rng(seed)
+    out = np.array(poses, np.float64)
+    for p in out:
+        axis, step = rng.standard_normal(3), rng.standard_normal(3)
+        w = axis / np.linalg.norm(axis) * np.deg2rad(rot_deg)
+        K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+        th = np.linalg.norm(w)
+        Rw = np.eye(3) if th == 0 else np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * (K @ K)
+        p[:3, :3] = Rw @ p[:3, :3]
+        p[:3, 3] += step / np.linalg.norm(step) * trans
+    return out.astype(np.float32)
+
+
+def pose_errors(poses, true_poses):
+    """(mean rotation angle in degrees, mean translation distance) between two sets of [N, 4, 4] poses"""
+    a, b = np.asarray(poses, np.float64).reshape(-1, 4, 4), np.asarray(true_poses, np.float64).reshape(-1, 4, 4)
+    cos = (np.einsum("nij,nij->n", a[:, :3, :3], b[:, :3, :3]) - 1.0) / 2.0
+    return float(np.degrees(np.arccos(np.clip(cos, -1.0, 1.0))).mean()), float(np.linalg.norm(a[:, :3, 3] - b[:, :3, 3], axis=1).mean())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True)
@@ -81,7 +105,17 @@ def main():
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
                     help="keep the debiased exponential moving average of the weights with this decay (Trainer(ema_decay=...), DESIGN 5.15) "
                          "and report the held-out PSNR of the averaged weights beside the live ones")
+    ap.add_argument("--refine-poses", nargs="?", const=1e-3, type=float, default=None, metavar="LR",
+                    help="refine a 6-DoF correction per training image on the device from the rays' gradients "
+                         "(Trainer(ray_gradients=True), attach_images(refine_poses=...), DESIGN 5.16); implies --device-batches")
+    ap.add_argument("--pose-noise", default=None, metavar="ROT_DEG,TRANS",
+                    help="perturb the training poses on load by a seeded random rotation of ROT_DEG degrees and a translation of "
+                         "length TRANS; the mean errors against the true poses are printed before and after training")
     a = ap.parse_args()
+    if a.refine_poses is not None:
+        a.device_batches = True
+        if a.encoding != "hash":
+            sys.exit("--refine-poses needs --encoding hash (ray gradients go through the hash grid)")
     loss_scale = api.loss_scaler(growth_interval=a.growth_interval) if a.loss_scale == "dynamic" else float(a.loss_scale)
     schedule = a.lr_schedule
     if schedule and schedule.startswith("cosine:"):
@@ -99,7 +133,12 @@ def main():
     if rgba and float(ds.images[..., 3].min()) == 1.0:
         sys.exit("--opacity-weight: these frames carry no alpha (every pixel is opaque): there is no mask to fit")
     n_hold = max(1, ds.images.shape[0] // 8)
-    train_ds = loader.ImageDataset(ds.images[:-n_hold], ds.poses[:-n_hold], ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
+    true_poses = np.array(ds.poses[:-n_hold], np.float32).reshape(-1, 4, 4)
+    train_poses = true_poses
+    if a.pose_noise:
+        rot_deg, trans = (float(v) for v in a.pose_noise.split(","))
+        train_poses = perturb_poses(true_poses, rot_deg, trans, seed=0)
+    train_ds = loader.ImageDataset(ds.images[:-n_hold], train_poses.reshape(ds.poses[:-n_hold].shape), ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
     if a.device_batches:
         # flags=2 frames are k/255: one byte per channel holds them exactly
         images, focal = api.ImageSet.from_dataset(train_ds, storage="u8")
@@ -115,7 +154,7 @@ def main():
     tr = Trainer(R, None, lr=1e-2 if a.encoding == "hash" else 2e-3, loss=a.loss, opacity_weight=a.opacity_weight,
                  background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C, distortion_weight=a.distortion_weight,
                  loss_scale=loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite,
-                 max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay, **model)
+                 max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay, ray_gradients=a.refine_poses is not None, **model)
     white = (1.0, 1.0, 1.0) if rgba else None
 
     def render():
@@ -143,7 +182,7 @@ def main():
         return live if a.ema_decay is None else f"{live} live, {psnr(render_ema(), gt):.2f} dB averaged"
 
     if a.device_batches:
-        tr.attach_images(images)
+        tr.attach_images(images, refine_poses=None if a.refine_poses is None else dict(lr=a.refine_poses))
     g = torch.Generator(device="cuda").manual_seed(0)
     W, H = ds.image_width, ds.image_height
     o_t, d_t = camera_rays(ds.poses[-1], focal, W, H, origin_scale=0.1)
@@ -160,6 +199,13 @@ def main():
                   f"{held_out()}", flush=True)
     print(f"final held-out PSNR after {a.steps} steps ({'device batches' if a.device_batches else 'ray dataset'}): "
           f"{held_out()}")
+    if a.pose_noise or a.refine_poses is not None:
+        r0, t0 = pose_errors(train_poses, true_poses)
+        line = f"training poses against the true ones: mean rotation error {r0:.4f} deg, mean translation error {t0:.5f} as loaded"
+        if a.refine_poses is not None:
+            r1, t1 = pose_errors(tr.refined_poses().cpu().numpy(), true_poses)
+            line += f"; {r1:.4f} deg, {t1:.5f} after refinement ({int(tr.pose_updates.min().item())}+ updates per image)"
+        print(line)
     if tr.loss_scale_now is not None:
         print(f"loss scale now {float(tr.loss_scale_now.item()):g}: {int(tr.skipped_steps.item())} steps skipped, "
               f"{int(tr.scale_backoffs.item())} backoffs, {int(tr.scale_growths.item())} growths, {int(tr.clipped_steps.item())} steps clipped, "

@@ -1414,6 +1414,98 @@ typedef struct rtxn_draw_batch_args {
 } rtxn_draw_batch_args;
 int rtxn_draw_batch(const rtxn_draw_batch_args* a, rtxn_stream_t stream);
 
+/* ---- ray gradients through the hash grid, and camera pose refinement ---------------------------------------
+ * tiny-cuda-nn's dL/dinput and instant-ngp's extrinsics optimisation.  Three stages, each without atomics and in a fixed order:
+ * the same bits on every run, in default and in deterministic mode.  Everything is stream-ordered and hipGraph-capturable.
+ *
+ * 1. rtxn_hashgrid_input_gradient_segments: dL/d(position), reduced to the segment's end points.  Sample s = 32 j + i sits at
+ *    x = fmaf(u, end_j - start_j, start_j), u = i/32 (REGULAR), (i + 0.5)/32 (MIDPOINT_WORLD) or (i + u(seed, step, s))/32
+ *    (JITTER_WORLD) -- the forward's own expressions.  Per level l, with fr and the corner indices as the encoder forms them,
+ *      d enc_{l,f} / d x_a = (scale_l / 2) sum over the 8 corners c of  sgn_a(c) prod_{b != a} w_b(c) T_l[idx(c)][f],
+ *      sgn_a(c) = +1 where bit a of c is set, else -1;  w_b = fr_b or 1 - fr_b
+ *    (the exact derivative of the trilinear interpolant inside the cell; a level with scale_l == 0 contributes 0), and
+ *      g_s[a]       = sum_{l ascending} sum_{f ascending} (float)dencT[l F + f][s] * d enc_{l,f} / d x_a
+ *      dstart[j][a] = k sum_i (1 - u_i) g_s[a],      dend[j][a] = k sum_i u_i g_s[a]          (float[capacity][3] each)
+ *    in fp32; the 32-sample sum is a fixed butterfly inside the half wave.  k = unscale (1 / loss_scale), or with scale_device
+ *    1 / *scale_device (rtxn_loss_scaler_state::scale, read on the device).  dencT has the row stride the scatter takes it with,
+ *    rtxn_padded_samples(32 n_segments).  live_ws (rtxn_live_segments; may be NULL): dencT holds values for the listed segments
+ *    only; those are visited, and every unlisted segment of the batch reads back as exact zeros.  jitter may be NULL.
+ *    The view-direction columns of dencT are NOT differentiated (instant-ngp's extrinsic gradient does not use them either).
+ * 2. rtxn_ray_gradients_reduce: the traversal forms start = fmaf(t_start, d, o), end = fmaf(t_end, d, o), so with the segments
+ *    j = indices[r] .. indices[r] + num_stored[r] - 1 of ray r
+ *      d_origin[r]    = sum_j (dstart_j + dend_j),      d_direction[r] = sum_j (t_start_j dstart_j + t_end_j dend_j)
+ *    (eight lanes per ray, lane q the segments j = q mod 8 in ascending order, then a fixed tree over the lanes; a ray without
+ *    segments gets zeros).  These are the partial derivatives with the segment distances and the step lengths HELD FIXED: the
+ *    motion of the cell crossings, MIDPOINT_WORLD's step length |end - start| / 32 and which cells are occupied are not
+ *    differentiated -- instant-ngp's approximation.  Needs the RTXN_TRACE_DDA distances.
+ * 3. rtxn_pose_gradients / rtxn_pose_step: a 6-DoF correction delta = (omega, tau) per image against the untouched poses0,
+ *      poses[i] = ( R(omega) R0 | t0 + tau ; poses0's last row ),   R(omega) = I + A K + B K^2,  K = [omega]x,  th = |omega|,
+ *      A = sin(th) / th,  B = 2 sin^2(th / 2) / th^2;  below th = 0.25 the Taylor forms through th^8 (truncation < 3e-14).
+ *    delta == 0 gives poses[i] == poses0[i] bit for bit.  omega is a LEFT perturbation at the current pose, d' = R(omega) d,
+ *    whose gradient is taken at omega = 0 of the current rotation: exact there, first-order accurate beyond (instant-ngp's choice):
+ *      g_omega[i] = sum_r rays_d[r] x d_direction[r],   g_tau[i] = sum_r d_origin[r] / 10,   count[i] = number of rays r
+ *    over the rays with drawn[r][0] == i (one block per image, each thread its rays in ascending r, then a fixed tree).
+ *    rtxn_pose_step, per image: nothing changes when count == 0 (the table's sparse rule), nothing for any image when *skip != 0
+ *    (the optimizer guard's skip word, opt->guard + 2), nothing when a gradient component is not finite (that adds one to
+ *    *skipped).  Otherwise  steps += 1;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
+ *      delta -= lr (m / (1 - b1^steps)) / (sqrt(v / (1 - b2^steps)) + eps)          (1 - b^steps in double, rounded once)
+ *    and poses[i] is rewritten from delta.  eps defaults to 1e-15 (tiny-cuda-nn's): pose gradients are of order 1e-6.
+ * Rules (RTXN_ERR_INVALID with a message naming the field, before any device is touched): a batch without a hash grid
+ * (rtxn_ray_gradients_supported == 0: the lean and frequency paths form no dencT); a NULL among the six buffers of
+ * rtxn_ray_gradients; pose without rays; lr < 0, a beta outside [0, 1), eps <= 0, any of them not finite; n_images < 1;
+ * RTXN_TRACE_COMPAT in the step.  With a regulariser rays->t_start / t_end must be the regulariser's buffers. */
+typedef struct rtxn_ray_gradients {
+  float* t_start;        /* DEVICE float[segment_capacity]: written by the step's traversal (as rtxn_train_regularizer's) */
+  float* t_end;
+  float* dstart;         /* DEVICE float[segment_capacity][3] */
+  float* dend;
+  float* d_origin;       /* DEVICE float[n_rays][3]: dL/d(rays_o), unscaled */
+  float* d_direction;    /* DEVICE float[n_rays][3]: dL/d(rays_d), unscaled */
+} rtxn_ray_gradients;
+typedef struct rtxn_pose_refinement {
+  int n_images;
+  const float* poses0;   /* DEVICE float[n][16]: the poses as loaded, never written */
+  float* poses;          /* DEVICE float[n][16]: what rtxn_image_set.poses points at, rewritten by the step */
+  float* delta;          /* DEVICE float[n][6]: (omega, tau) */
+  float* m;              /* DEVICE float[n][6] */
+  float* v;              /* DEVICE float[n][6] */
+  int* steps;            /* DEVICE int[n]: updates applied per image */
+  float* grad;           /* DEVICE float[n][8]: g_omega, g_tau, the ray count, one pad */
+  float lr, beta1, beta2, eps;
+  const unsigned* skip;  /* optional DEVICE word: != 0 = this step was skipped (rtxn_optimizer_options.guard + 2) */
+  unsigned* skipped;     /* optional DEVICE counter of updates refused for a non-finite gradient */
+  const uint32_t* drawn; /* DEVICE uint32[n_rays][2] as rtxn_draw_batch records it: read by rtxn_train_step_rays only */
+} rtxn_pose_refinement;
+int rtxn_ray_gradients_supported(const rtxn_mlp* mlp, const rtxn_hashgrid* grid);
+int rtxn_hashgrid_input_gradient_segments(const rtxn_hashgrid* grid, const void* table_fp16, const float* start_points,
+                                          const float* end_points, long n_segments, int sample_type, const void* dencT,
+                                          const void* live_ws, const rtxn_sample_jitter* jitter, float unscale,
+                                          const float* scale_device, float* dstart, float* dend, rtxn_stream_t stream);
+int rtxn_ray_gradients_reduce(const int* indices, const int* num_stored, const float* t_start, const float* t_end,
+                              const float* dstart, const float* dend, int n_rays, float* d_origin, float* d_direction,
+                              rtxn_stream_t stream);
+/* The rules above without the device buffers (what a caller checks before it allocates anything). */
+int rtxn_pose_refinement_check(const rtxn_pose_refinement* pose);
+int rtxn_pose_gradients(const uint32_t* drawn, const float* rays_d, const float* d_origin, const float* d_direction, int n_rays,
+                        const rtxn_pose_refinement* pose, rtxn_stream_t stream);
+int rtxn_pose_step(const rtxn_pose_refinement* pose, rtxn_stream_t stream);
+/* poses[i] from delta[i] and poses0[i] alone, for every image (a loaded checkpoint, a reset): nothing else is read or written. */
+int rtxn_pose_compose(const rtxn_pose_refinement* pose, rtxn_stream_t stream);
+/* rtxn_train_gradients_scaled with the ray gradients behind the table scatter (stages 1 and 2 over the batch's dencT, live list
+ * and samples; k from batch->loss_scale or the scaler's device word); rays == NULL: exactly rtxn_train_gradients_scaled. */
+int rtxn_train_gradients_rays(const rtxn_train_batch* batch, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                              const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                              const rtxn_ray_gradients* rays, rtxn_stream_t stream);
+/* rtxn_train_step_ema with the ray gradients and, optionally, the pose refinement: the traversal's write pass stores t_start /
+ * t_end into rays' buffers, stages 1 and 2 run right behind the table scatter -- before any counter advances, so a jitter keyed on
+ * the optimizer's step sees the forward's value -- and, with pose, rtxn_pose_gradients (over pose->drawn and trace.rays_d) and
+ * rtxn_pose_step run behind the optimizer, where they see the guard's skip word.  rays == NULL and pose == NULL: exactly
+ * rtxn_train_step_ema. */
+int rtxn_train_step_rays(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                         const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                         const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
+                         const rtxn_pose_refinement* pose, rtxn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,19 @@ class DrawBatchArgs(C.Structure):
                 ("rays_d", C.c_void_p), ("targets", C.c_void_p), ("drawn", C.c_void_p)]
 
 
+class RayGradients(C.Structure):
+    """struct rtxn_ray_gradients (include/rtxn.h)."""
+    _fields_ = [("t_start", C.c_void_p), ("t_end", C.c_void_p), ("dstart", C.c_void_p), ("dend", C.c_void_p), ("d_origin", C.c_void_p),
+                ("d_direction", C.c_void_p)]
+
+
+class PoseRefinement(C.Structure):
+    """struct rtxn_pose_refinement (include/rtxn.h)."""
+    _fields_ = [("n_images", C.c_int), ("poses0", C.c_void_p), ("poses", C.c_void_p), ("delta", C.c_void_p), ("m", C.c_void_p),
+                ("v", C.c_void_p), ("steps", C.c_void_p), ("grad", C.c_void_p), ("lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("skip", C.c_void_p), ("skipped", C.c_void_p), ("drawn", C.c_void_p)]
+
+
 class RenderConfig(C.Structure):
     """struct rtxn_render_config (include/rtxn.h)."""
     _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("table_fp16", C.c_void_p), ("n_dir_freqs", C.c_int),
@@ -389,6 +402,18 @@ SYMBOLS = {
     "rtxn_train_step_ema": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                  C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma), _P]),
     "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
+    "rtxn_ray_gradients_supported": (_I, [_P, _P]),
+    "rtxn_hashgrid_input_gradient_segments": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, C.POINTER(SampleJitter), _F, _P, _P, _P, _P]),
+    "rtxn_ray_gradients_reduce": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "rtxn_pose_refinement_check": (_I, [C.POINTER(PoseRefinement)]),
+    "rtxn_pose_gradients": (_I, [_P, _P, _P, _P, _I, C.POINTER(PoseRefinement), _P]),
+    "rtxn_pose_step": (_I, [C.POINTER(PoseRefinement), _P]),
+    "rtxn_pose_compose": (_I, [C.POINTER(PoseRefinement), _P]),
+    "rtxn_train_gradients_rays": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                       C.POINTER(TrainRegularizer), C.POINTER(LossScaler), C.POINTER(RayGradients), _P]),
+    "rtxn_train_step_rays": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                  C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma),
+                                  C.POINTER(RayGradients), C.POINTER(PoseRefinement), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),
     "rtxn_load_llff": (_I, [C.c_char_p, _I, _I, C.POINTER(ImageDataset), C.POINTER(C.POINTER(C.c_float))]),

@@ -641,6 +641,10 @@ class HashGrid:
         check(getattr(_lib.lib(), name)(*head, *tail), name)
         return dtable
 
+    def input_gradient_segments(self, table_fp16, start_points, end_points, n_segments, sample_type, dencT, dstart, dend, **kw):
+        """hashgrid_input_gradient_segments(self, ...): dL/d(position) reduced to the segments' end points."""
+        return hashgrid_input_gradient_segments(self, table_fp16, start_points, end_points, n_segments, sample_type, dencT, dstart, dend, **kw)
+
     def backward_mixed(self, inputs, dencT, dtable, dtable_hashed_half):
         """backward with the hashed levels' gradient accumulated in fp16 (packed atomics; n_features == 2)."""
         n = inputs.numel() // 5
@@ -1271,15 +1275,24 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
                     total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                     encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                     loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                    workspace_lean=False, background=None, jitter=None, loss=None, regularizer=None, scaler=None):
+                    workspace_lean=False, background=None, jitter=None, loss=None, regularizer=None, scaler=None, rays=None):
     """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781).
+    rays: ray_gradients(...) -> rtxn_train_gradients_rays (with or without any of the five below): dL/d(rays_o), dL/d(rays_d)
+    behind the table scatter; its t_start / t_end must already hold the batch's distances (trace_grid, TRACE_DDA).
     background: train_background(...) -> rtxn_train_gradients_ex (targets float[n_rays][background.target_channels]);
     jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> rtxn_train_gradients_jitter (with or without a background);
     loss: train_loss(...) -> rtxn_train_gradients_loss (with or without either);
     regularizer: train_regularizer(...) -> rtxn_train_gradients_reg (with or without any of the three);
     scaler: loss_scaler(...) -> rtxn_train_gradients_scaled (with or without any of the four; loss_scale is then not read)."""
-    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer", "scaler")}
-    if scaler is not None:
+    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer", "scaler", "rays")}
+    if rays is not None:
+        if regularizer is not None:
+            _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
+        _check_ray_gradients("train_gradients", rays, n_rays, segment_capacity)
+        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
+        check(_lib.lib().rtxn_train_gradients_rays(C.byref(b), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
+                                                   _byref(scaler), C.byref(rays), _stream()), "rtxn_train_gradients_rays")
+    elif scaler is not None:
         if regularizer is not None:
             _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
         b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
@@ -1350,7 +1363,7 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None, ema=None):
+def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None, ema=None, rays=None, pose=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
     jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
@@ -1359,8 +1372,19 @@ def train_step(args, background=None, jitter=None, loss=None, regularizer=None, 
     stores the segments' t_start / t_end into the regulariser's buffers;
     optimizer: optimizer_options(...) -> rtxn_train_step_opt (with or without any of the four);
     scaler: loss_scaler(...) -> rtxn_train_step_scaled (needs `optimizer` with skip_nonfinite);
-    ema: weight_ema(...) -> rtxn_train_step_ema (needs `optimizer`, which may have nothing switched on; with or without a scaler)."""
-    if ema is not None:
+    ema: weight_ema(...) -> rtxn_train_step_ema (needs `optimizer`, which may have nothing switched on; with or without a scaler);
+    rays: ray_gradients(...), pose: pose_refinement(...) -> rtxn_train_step_rays (with or without any of the seven; pose needs rays):
+    the write pass stores t_start / t_end into rays' buffers, the ray gradients are formed behind the table scatter and the pose
+    gradient and step run behind the optimizer."""
+    if rays is not None or pose is not None:
+        if regularizer is not None:
+            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
+        if rays is not None:
+            _check_ray_gradients("train_step", rays, args.batch.n_rays, args.batch.segment_capacity)
+        check(_lib.lib().rtxn_train_step_rays(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
+                                              _byref(optimizer), _byref(scaler), _byref(ema), _byref(rays), _byref(pose), _stream()),
+              "rtxn_train_step_rays")
+    elif ema is not None:
         if regularizer is not None:
             _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
         check(_lib.lib().rtxn_train_step_ema(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
@@ -1542,3 +1566,106 @@ def draw_batch(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None):
 def draw_batch_launch(args):
     """rtxn_draw_batch over a struct draw_batch_args() built earlier (its tensors still alive), on the current stream."""
     check(_lib.lib().rtxn_draw_batch(C.byref(args), _stream()), "rtxn_draw_batch")
+
+
+# --------------------------------------------------------------------------- ray gradients and pose refinement
+def ray_gradients(t_start, t_end, dstart, dend, d_origin, d_direction):
+    """struct rtxn_ray_gradients (include/rtxn.h) over device float32 tensors (which the struct keeps referenced): t_start, t_end
+    [>= segments] as trace_grid writes them (TRACE_DDA), dstart, dend [>= segments, 3], d_origin, d_direction [>= n_rays, 3]."""
+    s = _lib.RayGradients()
+    s._tensors = dict(t_start=t_start, t_end=t_end, dstart=dstart, dend=dend, d_origin=d_origin, d_direction=d_direction)
+    for nm, t in s._tensors.items():
+        setattr(s, nm, _ptr(t, torch.float32, nm))
+    return s
+
+
+def _check_ray_gradients(who, rays, n_rays, n_segments):
+    tensors = getattr(rays, "_tensors", None)      # a _lib.RayGradients filled by hand: nothing to size, the library checks the rest
+    if tensors is None:
+        return
+    for nm, need in (("t_start", n_segments), ("t_end", n_segments), ("dstart", 3 * n_segments), ("dend", 3 * n_segments),
+                     ("d_origin", 3 * n_rays), ("d_direction", 3 * n_rays)):
+        t = tensors[nm]
+        if t is not None and t.numel() < int(need):
+            raise _lib.RtxnError(f"{who}: rays.{nm} holds {t.numel()} elements, {int(need)} needed")
+
+
+def ray_gradients_supported(net, grid=None):
+    """rtxn_ray_gradients_supported: whether a step of this model forms d(encoding) -- hash-grid models do."""
+    return bool(_lib.lib().rtxn_ray_gradients_supported(net._h if net is not None else None, grid._h if grid is not None else None))
+
+
+def hashgrid_input_gradient_segments(grid, table_fp16, start_points, end_points, n_segments, sample_type, dencT, dstart, dend, *, live_ws=None,
+                                     jitter=None, loss_scale=1.0, scale_device=None):
+    """rtxn_hashgrid_input_gradient_segments: dstart, dend float32 [>= n_segments, 3] = k times the (1 - u)- and u-weighted sums of
+    every segment's 32 sample gradients dL/dx, from dencT as the scatter takes it.  k = 1 / loss_scale (float32), or with
+    scale_device (a device float32 tensor, the scaler's loss_scale_now) 1 / its value, read on the device.  live_ws: the listed
+    segments only, every other segment of the batch reads back as zeros."""
+    n = int(n_segments)
+    for nm, t in (("dstart", dstart), ("dend", dend)):
+        if t.numel() < 3 * n:
+            raise _lib.RtxnError(f"hashgrid_input_gradient_segments: {nm} holds {t.numel()} elements, {3 * n} needed")
+    if dencT.numel() < grid.cfg.n_levels * grid.cfg.n_features * padded_samples(32 * n):
+        raise _lib.RtxnError(f"hashgrid_input_gradient_segments: dencT holds {dencT.numel()} elements for {n} segments")
+    check(_lib.lib().rtxn_hashgrid_input_gradient_segments(
+        grid._h, _ptr(table_fp16, torch.float16, "table"), _ptr(start_points, torch.float32, "start_points"),
+        _ptr(end_points, torch.float32, "end_points"), n, sample_type, _ptr(dencT, torch.float16, "dencT"), _ptr(live_ws, None, "live_ws"),
+        _jit(jitter), float(np.float32(1.0) / np.float32(loss_scale)), _ptr(scale_device, torch.float32, "scale_device"),
+        _ptr(dstart, torch.float32, "dstart"), _ptr(dend, torch.float32, "dend"), _stream()), "rtxn_hashgrid_input_gradient_segments")
+    return dstart, dend
+
+
+def ray_gradients_reduce(indices, num_stored, t_start, t_end, dstart, dend, n_rays, d_origin, d_direction):
+    """rtxn_ray_gradients_reduce: d_origin, d_direction float32 [>= n_rays, 3] from the segments' end-point gradients."""
+    n = int(n_rays)
+    for nm, t, need in (("indices", indices, n), ("num_stored", num_stored, n), ("d_origin", d_origin, 3 * n), ("d_direction", d_direction, 3 * n)):
+        if t.numel() < need:
+            raise _lib.RtxnError(f"ray_gradients_reduce: {nm} holds {t.numel()} elements, {need} needed")
+    check(_lib.lib().rtxn_ray_gradients_reduce(_ptr(indices, torch.int32, "indices"), _ptr(num_stored, torch.int32, "num_stored"),
+                                               _ptr(t_start, torch.float32, "t_start"), _ptr(t_end, torch.float32, "t_end"),
+                                               _ptr(dstart, torch.float32, "dstart"), _ptr(dend, torch.float32, "dend"), n,
+                                               _ptr(d_origin, torch.float32, "d_origin"), _ptr(d_direction, torch.float32, "d_direction"),
+                                               _stream()), "rtxn_ray_gradients_reduce")
+    return d_origin, d_direction
+
+
+def pose_refinement(n_images=1, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-15, *, poses0=None, poses=None, delta=None, m=None, v=None,
+                    steps=None, grad=None, skip=None, skipped=None, drawn=None):
+    """struct rtxn_pose_refinement (include/rtxn.h), its rules checked (rtxn_pose_refinement_check) before any buffer is looked at.
+    Without tensors: the configuration alone (what a caller checks before it allocates).  poses0, poses float32 [n, 16]; delta, m,
+    v float32 [n, 6]; steps int32 [n]; grad float32 [n, 8]; skip: the optimizer guard's skip word (guard[2:3]) or None; skipped:
+    int32 [1] or None; drawn int32 [n_rays, 2] (train_step only).  The tensors stay referenced by the struct."""
+    s = _lib.PoseRefinement()
+    s.n_images, s.lr, s.beta1, s.beta2, s.eps = int(n_images), float(lr), float(beta1), float(beta2), float(eps)
+    check(_lib.lib().rtxn_pose_refinement_check(C.byref(s)), "rtxn_pose_refinement_check")
+    n = s.n_images
+    s._tensors = dict(poses0=poses0, poses=poses, delta=delta, m=m, v=v, steps=steps, grad=grad, skip=skip, skipped=skipped, drawn=drawn)
+    for nm, t, dt, need in (("poses0", poses0, torch.float32, 16 * n), ("poses", poses, torch.float32, 16 * n), ("delta", delta, torch.float32, 6 * n),
+                            ("m", m, torch.float32, 6 * n), ("v", v, torch.float32, 6 * n), ("steps", steps, torch.int32, n),
+                            ("grad", grad, torch.float32, 8 * n), ("skip", skip, torch.int32, 1), ("skipped", skipped, torch.int32, 1),
+                            ("drawn", drawn, torch.int32, 0)):
+        if t is not None and t.numel() < need:
+            raise _lib.RtxnError(f"pose_refinement: {nm} holds {t.numel()} elements, {need} needed for {n} images")
+        setattr(s, nm, _ptr(t, dt, nm))
+    return s
+
+
+def pose_gradients(drawn, rays_d, d_origin, d_direction, n_rays, pose):
+    """rtxn_pose_gradients: pose.grad[i] = (sum rays_d x d_direction, sum d_origin / 10, ray count, 0) over the rays drawn from image i."""
+    n = int(n_rays)
+    for nm, t, need in (("drawn", drawn, 2 * n), ("rays_d", rays_d, 3 * n), ("d_origin", d_origin, 3 * n), ("d_direction", d_direction, 3 * n)):
+        if t.numel() < need:
+            raise _lib.RtxnError(f"pose_gradients: {nm} holds {t.numel()} elements, {need} needed")
+    check(_lib.lib().rtxn_pose_gradients(_ptr(drawn, torch.int32, "drawn"), _ptr(rays_d, torch.float32, "rays_d"),
+                                         _ptr(d_origin, torch.float32, "d_origin"), _ptr(d_direction, torch.float32, "d_direction"), n,
+                                         C.byref(pose), _stream()), "rtxn_pose_gradients")
+
+
+def pose_step(pose):
+    """rtxn_pose_step: the per-image Adam on delta from pose.grad, then poses = (R(omega) R0 | t0 + tau)."""
+    check(_lib.lib().rtxn_pose_step(C.byref(pose), _stream()), "rtxn_pose_step")
+
+
+def pose_compose(pose):
+    """rtxn_pose_compose: poses from delta and poses0 alone (after a checkpoint was loaded into delta, or a reset)."""
+    check(_lib.lib().rtxn_pose_compose(C.byref(pose), _stream()), "rtxn_pose_compose")

@@ -93,6 +93,13 @@ __device__ __forceinline__ float jitter_u(unsigned h0, unsigned s) { return (flo
 // and type 4's t_vals are step lengths, which RTXN_VR_COMPAT does not take (vr_mode < 0: the entry point has no compositor).
 int check_sample_jitter(const char* who, int sample_type, const rtxn_sample_jitter* jitter, int vr_mode);
 
+// The rules of the ray-gradient buffers (rtxn_ray_gradients, include/rtxn.h), host only, train.hip: a batch with a hash grid, no
+// NULL among the six buffers, and t_start / t_end shared with an active regulariser (reg: ACTIVE or NULL).
+int check_ray_gradients(const char* who, const rtxn_ray_gradients* rays, const rtxn_train_batch* batch, const rtxn_train_regularizer* reg);
+// The rules of the pose refinement (rtxn_pose_refinement, include/rtxn.h), host only, pose.hip.  need_buffers: the struct must also
+// carry its device buffers.
+int check_pose_refinement(const rtxn_pose_refinement* pose, const char* who, bool need_buffers);
+
 }  // namespace rtxn
 
 #define RTXN_HIP(expr)                                          \

@@ -22,6 +22,7 @@
 //   wgrad_kernel              dW += dZ X^T : 64x64 output super-tile per wave, K = samples,
 //                             fp32 atomics into the tcnn-layout gradient buffer
 //   hashgrid_backward_kernel  scatter-add of denc into the table gradient (fp32 atomics)
+//   hashgrid_input_gradient_kernel  the scatter's transposed twin: denc -> dL/d(position) per segment end point (no atomics)
 //   l2_loss_kernel, adam_kernel
 #include "mlp_internal.h"
 #include "hashgrid_internal.h"
@@ -538,6 +539,111 @@ __global__ __launch_bounds__(kThreads) void hashgrid_backward_kernel(HgLevels lv
           else atomicAdd(&gdst[(size_t)idx * F + f], v);
         }
       }
+    }
+  }
+}
+
+// The scatter's transposed twin: dL/d(position) of every sample through the trilinear interpolant, reduced to the two end points
+// of the sample's segment (rtxn_hashgrid_input_gradient_segments, include/rtxn.h states the arithmetic).  One thread per sample
+// walks all levels, as hashgrid_encode_f2_kernel does: the position and u are formed once, from the same expressions and the same
+// s as the forward's (sample_pos_unmasked / sample_offset), the cell and its eight indices per level as the encoders form them
+// (hg_corner_indices, out-of-domain wrap included).  Per level the slope along axis a is
+//   (scale / 2) sum_c sgn_a(c) w_b(c) w_c(c) T[idx(c)][f]        eight sequential fmaf over the corners, in corner order
+// and g[a] collects dencT[l F + f][s] times it over levels and features, ascending.  Sample i of a segment then hands (1 - u_i) g
+// to the segment's start and u_i g to its end: a segment is 32 consecutive samples, half a wave, summed by a fixed xor butterfly
+// (1, 2, 4, 8, 16) -- no atomics, no LDS, no fixed-point shadow: the same bits on every run, in or out of deterministic mode.
+// live_list: the launch walks the listed segments only (the caller zero-fills dstart / dend first); dencT columns of unlisted
+// segments are never loaded -- lanes past the end redo the LAST listed sample and store nothing.  Loads are unconditional on that
+// clamped index (see hashgrid_backward_kernel).  (An entry-wide load for tables aligned to 2 F bytes came out of hipcc as the same
+// machine code as the element loads, byte for byte: there is one form.)
+template <int F>
+__global__ __launch_bounds__(kThreads) void hashgrid_input_gradient_kernel(HgLevels lv, const _Float16* __restrict__ table, SampleSrc src,
+                                                                           const _Float16* __restrict__ dencT, long S, long Sp, float unscale,
+                                                                           const float* __restrict__ scale_dev, float* __restrict__ dstart,
+                                                                           float* __restrict__ dend, DevCount dc,
+                                                                           const int* __restrict__ live_list, const int* __restrict__ live_count) {
+  S = live_samples(dc, S);
+  if (live_list) S = 32L * *live_count;                         // the launch walks the listed segments only
+  if ((long)blockIdx.x * kThreads >= S) return;                 // whole block past the live samples (block-uniform)
+  const long s = (long)blockIdx.x * kThreads + threadIdx.x;     // every lane stays: the butterfly reads across the half wave
+  const bool ok = s < S;
+  const long sl = ok ? s : S - 1;
+  const long sc = live_list ? (long)live_list[sl >> 5] * 32 + (sl & 31) : sl;
+  float x3[3], x01[3];
+  sample_pos_unmasked(src, sc, x3);
+  const float u = ((float)(int)(sc & 31) + sample_offset(src, sc)) * (1.0f / 32);     // sample_pos_unmasked's t
+#pragma unroll
+  for (int a = 0; a < 3; ++a) x01[a] = fmaf(x3[a], 0.5f, 0.5f);
+  const _Float16* dcol = dencT + sc;
+  float gx[3] = {0.0f, 0.0f, 0.0f};
+  for (int l = 0; l < lv.n_levels; ++l) {
+    const float scale = lv.scale[l];
+    if (scale == 0.0f) continue;                                // a one-cell level is constant in x (scalar branch)
+    const unsigned res = lv.res[l], size = lv.size[l];
+    const bool hashed = (unsigned long long)res * res * res > size;
+    const _Float16* base = table + (size_t)lv.offset[l] * F;    // scalar
+    float fr[3];
+    unsigned g[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float p = fmaf(x01[a], scale, 0.5f), fl = floorf(p);
+      g[a] = (unsigned)(int)fl;
+      fr[a] = p - fl;
+    }
+    unsigned i_lo[4], i_hi[4];
+    rtxn::hg_corner_indices(g, res, size, hashed, i_lo, i_hi);
+    float d[F], t[8][F];
+#pragma unroll
+    for (int f = 0; f < F; ++f) d[f] = (float)dcol[(long)(l * F + f) * Sp];
+#pragma unroll
+    for (int corner = 0; corner < 8; ++corner)                  // all of a level's gathers before the first use
+    {
+      const _Float16* e = base + (size_t)((corner & 1) ? i_hi[corner >> 1] : i_lo[corner >> 1]) * F;
+#pragma unroll
+      for (int f = 0; f < F; ++f) t[corner][f] = (float)e[f];
+    }
+    const float w[3][2] = {{1.0f - fr[0], fr[0]}, {1.0f - fr[1], fr[1]}, {1.0f - fr[2], fr[2]}};
+    float acc[3][F];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int f = 0; f < F; ++f) acc[a][f] = 0.0f;
+#pragma unroll
+    for (int corner = 0; corner < 8; ++corner) {
+      const int b0 = corner & 1, b1 = (corner >> 1) & 1, b2 = corner >> 2;
+      const float p12 = w[1][b1] * w[2][b2], p02 = w[0][b0] * w[2][b2], p01 = w[0][b0] * w[1][b1];
+      const float s0 = b0 ? p12 : -p12, s1 = b1 ? p02 : -p02, s2 = b2 ? p01 : -p01;
+#pragma unroll
+      for (int f = 0; f < F; ++f) {
+        acc[0][f] = fmaf(s0, t[corner][f], acc[0][f]);
+        acc[1][f] = fmaf(s1, t[corner][f], acc[1][f]);
+        acc[2][f] = fmaf(s2, t[corner][f], acc[2][f]);
+      }
+    }
+    const float hs = scale * 0.5f;
+#pragma unroll
+    for (int f = 0; f < F; ++f)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) gx[a] = fmaf(d[f], hs * acc[a][f], gx[a]);
+  }
+  const float k = scale_dev ? 1.0f / *scale_dev : unscale;      // the scaler's device word: one scalar load per wave
+  const float u0 = 1.0f - u;
+  float v[6];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    v[a] = ok ? u0 * gx[a] : 0.0f;
+    v[3 + a] = ok ? u * gx[a] : 0.0f;
+  }
+#pragma unroll
+  for (int m = 1; m < 32; m <<= 1)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] += __shfl_xor(v[j], m);
+  if (ok && (sc & 31) == 0) {
+    const long seg = (sc >> 5) * 3;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      dstart[seg + a] = k * v[a];
+      dend[seg + a] = k * v[3 + a];
     }
   }
 }
@@ -4006,11 +4112,80 @@ extern "C" int rtxn_hashgrid_backward_segments_live_jitter(const rtxn_hashgrid* 
                                           true, live_ws, dtable, dtable_hashed_half, jitter, stream);
 }
 
+// ------------------------------------------------------------------------- ray gradients: dL/d(position) per segment end point
+// dstart / dend [capacity][3] of the segments `input` names.  With a live list the buffers are cleared over the whole launch
+// first (a kernel: common.h, zero_words) and the kernel then writes the listed segments.  k = unscale, or 1 / *scale_device.
+static int hashgrid_input_gradient_impl(const rtxn_hashgrid* g, const void* table_fp16, const SampleSrc& input, const void* dencT,
+                                        long n_samples, float unscale, const float* scale_device, float* dstart, float* dend, DevCount dc,
+                                        rtxn_stream_t stream, LiveRef live = LiveRef()) {
+  const long Sp = padded(n_samples);
+  hipStream_t st = rtxn::as_stream(stream);
+  if (live.list) {
+    RTXN_HIP(rtxn::zero_words(dstart, (size_t)(n_samples / 32) * 3, st));
+    RTXN_HIP(rtxn::zero_words(dend, (size_t)(n_samples / 32) * 3, st));
+  }
+  const HgLevels lv = levels_of(g);
+  const _Float16* tb = static_cast<const _Float16*>(table_fp16);
+  const _Float16* de = static_cast<const _Float16*>(dencT);
+  const unsigned sblocks = (unsigned)((n_samples + kThreads - 1) / kThreads);
+  const int F = g->cfg.n_features;
+#define RTXN_INPUT_GRADIENT(FEATURES)                                                                                     \
+  hashgrid_input_gradient_kernel<FEATURES><<<sblocks, kThreads, 0, st>>>(lv, tb, input, de, n_samples, Sp, unscale, scale_device, \
+                                                                         dstart, dend, dc, live.list, live.count)
+  switch (F) {
+    case 1: RTXN_INPUT_GRADIENT(1); break;
+    case 2: RTXN_INPUT_GRADIENT(2); break;
+    case 4: RTXN_INPUT_GRADIENT(4); break;
+    case 8: RTXN_INPUT_GRADIENT(8); break;
+    default: RTXN_REQUIRE(false, "rtxn_hashgrid_input_gradient_segments: n_features = %d (1, 2, 4 or 8)", F);
+  }
+#undef RTXN_INPUT_GRADIENT
+  RTXN_LAUNCH_CHECK("hashgrid_input_gradient_kernel");
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_hashgrid_input_gradient_segments(const rtxn_hashgrid* g, const void* table_fp16, const float* start_points,
+                                                     const float* end_points, long n_segments, int sample_type, const void* dencT,
+                                                     const void* live_ws, const rtxn_sample_jitter* jitter, float unscale,
+                                                     const float* scale_device, float* dstart, float* dend, rtxn_stream_t stream) {
+  const char* who = "rtxn_hashgrid_input_gradient_segments";
+  int rc = rtxn::check_sample_jitter(who, sample_type, jitter, -1);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(g, "%s: NULL grid", who);
+  rc = check_segments(who, start_points, end_points, start_points, n_segments, sample_type, jitter);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(scale_device || std::isfinite(unscale), "%s: unscale = %g", who, (double)unscale);
+  RTXN_REQUIRE(!live_ws || ((uintptr_t)live_ws & 15) == 0, "%s: live_ws not 16-byte aligned", who);
+  RTXN_DEVICE_OR_FAIL();
+  if (n_segments == 0) return RTXN_OK;
+  RTXN_REQUIRE(table_fp16 && dencT && dstart && dend, "%s: NULL buffer", who);
+  const SampleSrc src = segment_src(start_points, end_points, nullptr, sample_type, jitter);
+  return hashgrid_input_gradient_impl(g, table_fp16, src, dencT, n_segments * 32, unscale, scale_device, dstart, dend, kHostCount, stream,
+                                      LiveRef(live_ws));
+}
+
+extern "C" int rtxn_ray_gradients_supported(const rtxn_mlp* m, const rtxn_hashgrid* g) { return m && g ? 1 : 0; }
+
+// The rules of a rtxn_ray_gradients struct (include/rtxn.h), host only: the six buffers, and a model that writes dencT
+int rtxn::check_ray_gradients(const char* who, const rtxn_ray_gradients* rays, const rtxn_train_batch* b, const rtxn_train_regularizer* reg) {
+  RTXN_REQUIRE(rtxn_ray_gradients_supported(b->mlp, b->grid), "%s: rays: ray gradients need a hash grid (batch.grid is NULL: the lean and "
+               "frequency paths form no d(encoding))", who);
+  RTXN_REQUIRE(rays->t_start, "%s: rays->t_start is NULL", who);
+  RTXN_REQUIRE(rays->t_end, "%s: rays->t_end is NULL", who);
+  RTXN_REQUIRE(rays->dstart, "%s: rays->dstart is NULL", who);
+  RTXN_REQUIRE(rays->dend, "%s: rays->dend is NULL", who);
+  RTXN_REQUIRE(rays->d_origin, "%s: rays->d_origin is NULL", who);
+  RTXN_REQUIRE(rays->d_direction, "%s: rays->d_direction is NULL", who);
+  RTXN_REQUIRE(!reg || !reg->t_start || (reg->t_start == rays->t_start && reg->t_end == rays->t_end),
+               "%s: rays->t_start / t_end and reg->t_start / t_end must be the same buffers (the traversal writes them once)", who);
+  return RTXN_OK;
+}
+
 // ------------------------------------------------------------------------- a whole batch, segment count on the device
 // scaler (rtxn_train_gradients_scaled): the compositor reads the loss scale from its device word, b->loss_scale is not read
 static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                 const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
-                                rtxn_stream_t stream) {
+                                rtxn_stream_t stream, const rtxn_ray_gradients* rays = nullptr) {
   RTXN_REQUIRE(b && b->mlp, "rtxn_train_gradients: NULL batch or model");
   const rtxn_mlp* m = b->mlp;
   int rc = check_train(m, "rtxn_train_gradients");
@@ -4119,6 +4294,17 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   if (hash && !b->skip_table_backward) {
     const SampleSrc bsrc = segment_src(b->start_points, b->end_points, nullptr, b->sample_type, jitter);    // the forward's samples
     rc = hashgrid_backward_impl(b->grid, bsrc, b->dencT, cap_samples, b->dtable, b->dtable_hashed_half, dc, stream, live);
+    if (rc != RTXN_OK) return rc;
+  }
+  if (rays) {
+    // dL/d(ray): the gather over the same dencT, live list and samples as the scatter, then the per-ray reduction.  Right behind
+    // the scatter, before any counter advances: a jitter keyed on the optimizer's step must still see the forward's value.
+    const SampleSrc gsrc = segment_src(b->start_points, b->end_points, nullptr, b->sample_type, jitter);
+    rc = hashgrid_input_gradient_impl(b->grid, b->table_fp16, gsrc, b->dencT, cap_samples, 1.0f / b->loss_scale,
+                                      scaler ? &scaler->state->scale : nullptr, rays->dstart, rays->dend, dc, stream, live);
+    if (rc != RTXN_OK) return rc;
+    rc = rtxn_ray_gradients_reduce(b->indices, b->num_stored, rays->t_start, rays->t_end, rays->dstart, rays->dend, b->n_rays, rays->d_origin,
+                                   rays->d_direction, stream);
   }
   return rc;
 }
@@ -4167,7 +4353,7 @@ extern "C" int rtxn_train_gradients_loss(const rtxn_train_batch* b, const rtxn_t
 // is rtxn_volrender_scaled_train, the RTXN_VR_NERF one alone
 static int train_gradients_reg(const char* who, const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
-                               rtxn_stream_t stream) {
+                               rtxn_stream_t stream, const rtxn_ray_gradients* rays = nullptr) {
   RTXN_REQUIRE(b, "%s: NULL batch", who);
   int rc = rtxn::check_sample_jitter(who, b->sample_type, jitter, b->vr_mode);
   if (rc != RTXN_OK) return rc;
@@ -4184,7 +4370,13 @@ static int train_gradients_reg(const char* who, const rtxn_train_batch* b, const
     RTXN_REQUIRE(b->vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor, which reads the scale from device memory "
                  "(vr_mode = %d: the three-launch route takes it by value)", who, b->vr_mode);
   }
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, reg_active ? reg : nullptr, scaler, stream);
+  if (rays) {
+    rc = rtxn::check_ray_gradients(who, rays, b, reg_active ? reg : nullptr);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(scaler || (b->loss_scale > 0.0f && std::isfinite(b->loss_scale)), "%s: batch.loss_scale = %g (ray gradients are unscaled by it)",
+                 who, (double)b->loss_scale);
+  }
+  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, reg_active ? reg : nullptr, scaler, stream, rays);
 }
 
 extern "C" int rtxn_train_gradients_reg(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
@@ -4196,4 +4388,13 @@ extern "C" int rtxn_train_gradients_scaled(const rtxn_train_batch* b, const rtxn
                                            const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
                                            rtxn_stream_t stream) {
   return train_gradients_reg(scaler ? "rtxn_train_gradients_scaled" : "rtxn_train_gradients_reg", b, bg, jitter, loss, reg, scaler, stream);
+}
+
+// ... and with the ray gradients (rtxn_ray_gradients): behind the table scatter, the gather rtxn_hashgrid_input_gradient_segments
+// over the batch's dencT and live list and the per-ray reduction; rays == NULL: exactly rtxn_train_gradients_scaled
+extern "C" int rtxn_train_gradients_rays(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                         const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                                         const rtxn_ray_gradients* rays, rtxn_stream_t stream) {
+  if (!rays) return rtxn_train_gradients_scaled(b, bg, jitter, loss, reg, scaler, stream);
+  return train_gradients_reg("rtxn_train_gradients_rays", b, bg, jitter, loss, reg, scaler, stream, rays);
 }

@@ -88,11 +88,45 @@ static int optimizer_step_opt(const rtxn_train_step_args* a, const rtxn_optimize
   return RTXN_OK;
 }
 
+// optimizer->step (main.cu:787): every gradient is cleared as it is consumed.  opt: under the options (optimizer_step_opt).
+static int optimizer_step(const rtxn_train_step_args* a, const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler,
+                          const rtxn_weight_ema* ema, rtxn_stream_t stream) {
+  if (opt) return optimizer_step_opt(a, opt, scaler, ema, stream);
+  const rtxn_train_batch& b = a->batch;
+  const rtxn_train_state& o = a->opt;
+  const bool hash = b.grid != nullptr;
+  int rc;
+  advance_step_kernel<<<1, 1, 0, rtxn::as_stream(stream)>>>(o.step, o.lr, o.beta1, o.beta2, o.effective_lr);
+  RTXN_LAUNCH_CHECK("advance_step_kernel");
+  const float ls = b.loss_scale * o.loss_scale_divisor;
+  rc = rtxn_adam_step_captured(rtxn_mlp_n_params(b.mlp), o.mlp_master, o.mlp_params_fp16, b.dparams, RTXN_ADAM_ZERO_GRADS, o.mlp_m, o.mlp_v,
+                               o.effective_lr, o.beta1, o.beta2, o.eps, ls, stream);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn_mlp_set_params_training(const_cast<rtxn_mlp*>(b.mlp), o.mlp_params_fp16, stream);
+  if (rc != RTXN_OK) return rc;
+  if (hash) {
+    const long n = rtxn_hashgrid_n_params(b.grid), lo = fp32_gradient_params(b);
+    __half* p16 = static_cast<__half*>(o.table_params_fp16);
+    if (lo > 0) {
+      rc = rtxn_adam_step_sparse(lo, o.table_master, p16, b.dtable, RTXN_ADAM_ZERO_GRADS, o.table_m, o.table_v, o.table_steps, o.table_lr, o.beta1,
+                                 o.beta2, o.table_eps, ls, stream);
+      if (rc != RTXN_OK) return rc;
+    }
+    if (lo < n) {
+      rc = rtxn_adam_step_sparse(n - lo, o.table_master + lo, p16 + lo, b.dtable_hashed_half, RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS,
+                                 o.table_m + lo, o.table_v + lo, o.table_steps + lo, o.table_lr, o.beta1, o.beta2, o.table_eps, ls, stream);
+      if (rc != RTXN_OK) return rc;
+    }
+  }
+  return RTXN_OK;
+}
+
 // opt: ACTIVE optimizer options (rtxn_train_step_opt, optimizer.hip) or NULL; scaler: the loss scaler (with opt) or NULL;
 // ema: the weight EMA (with opt, active or not) or NULL
 static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                            const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
-                           const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream) {
+                           const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream,
+                           const rtxn_ray_gradients* rays = nullptr, const rtxn_pose_refinement* pose = nullptr) {
   RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
   const rtxn_train_batch& b = a->batch;
   const rtxn_train_state& o = a->opt;
@@ -134,41 +168,27 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
     t.t_start = const_cast<float*>(reg->t_start);
     t.t_end = const_cast<float*>(reg->t_end);
   }
+  if (rays) {                                                 // ... and the ray gradients': the same buffers when both are given
+    t.t_start = rays->t_start;
+    t.t_end = rays->t_end;
+  }
   rc = rtxn_trace_grid(&t, stream);
   if (rc != RTXN_OK) return rc;
 
   // ---- sampler ... backward (main.cu:703-781), segment count read on the device ----
-  rc = scaler ? rtxn_train_gradients_scaled(&b, bg, jitter, loss, reg, scaler, stream)
+  rc = rays   ? rtxn_train_gradients_rays(&b, bg, jitter, loss, reg, scaler, rays, stream)
+     : scaler ? rtxn_train_gradients_scaled(&b, bg, jitter, loss, reg, scaler, stream)
      : reg    ? rtxn_train_gradients_reg(&b, bg, jitter, loss, reg, stream)
      : loss   ? rtxn_train_gradients_loss(&b, bg, jitter, loss, stream)
      : jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
   if (rc != RTXN_OK) return rc;
 
-  if (opt) return optimizer_step_opt(a, opt, scaler, ema, stream);
-  // ---- optimizer->step (main.cu:787): every gradient is cleared as it is consumed ----
-  advance_step_kernel<<<1, 1, 0, rtxn::as_stream(stream)>>>(o.step, o.lr, o.beta1, o.beta2, o.effective_lr);
-  RTXN_LAUNCH_CHECK("advance_step_kernel");
-  const float ls = b.loss_scale * o.loss_scale_divisor;
-  rc = rtxn_adam_step_captured(rtxn_mlp_n_params(b.mlp), o.mlp_master, o.mlp_params_fp16, b.dparams, RTXN_ADAM_ZERO_GRADS, o.mlp_m, o.mlp_v,
-                               o.effective_lr, o.beta1, o.beta2, o.eps, ls, stream);
+  rc = optimizer_step(a, opt, scaler, ema, stream);
+  if (rc != RTXN_OK || !pose) return rc;
+  // ---- the pose gradient and the pose step, behind the optimizer: they see the guard's skip word ----
+  rc = rtxn_pose_gradients(pose->drawn, a->trace.rays_d, rays->d_origin, rays->d_direction, b.n_rays, pose, stream);
   if (rc != RTXN_OK) return rc;
-  rc = rtxn_mlp_set_params_training(const_cast<rtxn_mlp*>(b.mlp), o.mlp_params_fp16, stream);
-  if (rc != RTXN_OK) return rc;
-  if (hash) {
-    const long n = rtxn_hashgrid_n_params(b.grid), lo = fp32_gradient_params(b);
-    __half* p16 = static_cast<__half*>(o.table_params_fp16);
-    if (lo > 0) {
-      rc = rtxn_adam_step_sparse(lo, o.table_master, p16, b.dtable, RTXN_ADAM_ZERO_GRADS, o.table_m, o.table_v, o.table_steps, o.table_lr, o.beta1,
-                                 o.beta2, o.table_eps, ls, stream);
-      if (rc != RTXN_OK) return rc;
-    }
-    if (lo < n) {
-      rc = rtxn_adam_step_sparse(n - lo, o.table_master + lo, p16 + lo, b.dtable_hashed_half, RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS,
-                                 o.table_m + lo, o.table_v + lo, o.table_steps + lo, o.table_lr, o.beta1, o.beta2, o.table_eps, ls, stream);
-      if (rc != RTXN_OK) return rc;
-    }
-  }
-  return RTXN_OK;
+  return rtxn_pose_step(pose, stream);
 }
 
 extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream); }
@@ -235,7 +255,8 @@ extern "C" int rtxn_train_step_loss(const rtxn_train_step_args* a, const rtxn_tr
 // into the struct's buffers; NULL, or weight 0 without outputs: rtxn_train_step_loss
 static int train_step_reg(const char* who, const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
-                          const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream) {
+                          const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream,
+                          const rtxn_ray_gradients* rays = nullptr, const rtxn_pose_refinement* pose = nullptr) {
   RTXN_REQUIRE(a, "%s: NULL arguments", who);
   if (scaler)
     RTXN_REQUIRE(a->batch.vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor (batch.vr_mode = %d)", who, a->batch.vr_mode);
@@ -251,6 +272,19 @@ static int train_step_reg(const char* who, const rtxn_train_step_args* a, const 
   if (reg_active)
     RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the regulariser's t_start / t_end are written by the "
                  "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
+  if (rays) {
+    rc = rtxn::check_ray_gradients(who, rays, &a->batch, reg_active ? reg : nullptr);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the ray gradients' t_start / t_end are written by the "
+                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
+  }
+  if (pose) {
+    RTXN_REQUIRE(rays, "%s: pose without rays: the pose gradient is formed from the ray gradients", who);
+    rc = rtxn::check_pose_refinement(pose, who, true);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(pose->drawn && a->trace.rays_d, "%s: pose->drawn = %p, trace.rays_d = %p: the pose gradient reads (image, pixel) per ray "
+                 "and the explicit rays", who, (const void*)pose->drawn, (const void*)a->trace.rays_d);
+  }
   rtxn_train_background own_bg;
   if (active) {
     own_bg = *bg;
@@ -262,7 +296,7 @@ static int train_step_reg(const char* who, const rtxn_train_step_args* a, const 
     if (!own_jitter.step) own_jitter.step = a->opt.step;
   }
   return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, reg_active ? reg : nullptr,
-                         opt, scaler, ema, stream);
+                         opt, scaler, ema, stream, rays, pose);
 }
 
 extern "C" int rtxn_train_step_reg(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
@@ -321,4 +355,37 @@ extern "C" int rtxn_train_step_ema(const rtxn_train_step_args* a, const rtxn_tra
     RTXN_REQUIRE(opt->skip_nonfinite, "%s: the loss scaler needs options with skip_nonfinite: dynamic scaling implies the non-finite guard", who);
   }
   return train_step_reg(who, a, bg, jitter, loss, reg, opt, scaler, ema, stream);
+}
+
+// ... and with the ray gradients and the pose refinement (train.hip, pose.hip); both NULL: rtxn_train_step_ema.  The other
+// structs keep the rules of the entry point that introduced them: what is NULL or switched off makes the call it always made.
+extern "C" int rtxn_train_step_rays(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                                    const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
+                                    const rtxn_pose_refinement* pose, rtxn_stream_t stream) {
+  const char* who = "rtxn_train_step_rays";
+  if (!rays && !pose) return rtxn_train_step_ema(a, bg, jitter, loss, reg, opt, scaler, ema, stream);
+  RTXN_REQUIRE(rays, "%s: pose without rays: the pose gradient is formed from the ray gradients", who);
+  RTXN_REQUIRE(a, "%s: NULL arguments", who);
+  int rc;
+  bool opt_active = false;
+  if (ema) {
+    rc = rtxn_weight_ema_check(ema);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(ema->state && ema->mlp_ema, "%s: ema->state = %p, ema->mlp_ema = %p", who, (void*)ema->state, (void*)ema->mlp_ema);
+    RTXN_REQUIRE(!a->batch.grid || (ema->table_ema && ema->table_stamps),
+                 "%s: a hash grid needs ema->table_ema and ema->table_stamps (this call steps the table by the sparse rule)", who);
+  }
+  rc = rtxn::check_optimizer_options(opt, who, true, &opt_active);
+  if (rc != RTXN_OK) return rc;
+  if (ema)
+    RTXN_REQUIRE(opt && opt->lr_factor && (!opt->skip_nonfinite || opt->guard),
+                 "%s: the weight EMA needs options that carry lr_factor (and guard with skip_nonfinite), with or without anything switched on", who);
+  if (scaler) {
+    rc = rtxn::check_loss_scaler(scaler, who, true);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(opt && opt->skip_nonfinite && opt->guard && opt->lr_factor,
+                 "%s: the loss scaler needs options with skip_nonfinite, guard and lr_factor: dynamic scaling implies the non-finite guard", who);
+  }
+  return train_step_reg(who, a, bg, jitter, loss, reg, (ema || opt_active) ? opt : nullptr, scaler, ema, stream, rays, pose);
 }

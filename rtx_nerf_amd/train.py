@@ -60,8 +60,14 @@ class Trainer:
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
                  target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0,
                  distortion_weight=0.0, lr_schedule=None, weight_decay=0.0, skip_nonfinite=False, max_grad_norm=None,
-                 ema_decay=None):
-        """ema_decay: None, or a float d strictly inside (0, 1): keep the debiased exponential moving average of the weights
+                 ema_decay=None, ray_gradients=False):
+        """ray_gradients: leave dL/d(rays_o) and dL/d(rays_d) of every step's loss, unscaled, in rays_o_grad / rays_d_grad
+        [batch_rays, 3] (the first n rows, after gradients(), step(), step_captured() and step_entry(); librtxn:
+        rtxn_hashgrid_input_gradient_segments, rtxn_ray_gradients_reduce, rtxn_train_gradients_rays, rtxn_train_step_rays): the
+        gather over d(encoding) behind the table scatter, then the per-ray reduction with the segment distances held fixed
+        (instant-ngp's approximation).  Hash encoding only.  attach_images(refine_poses=...) builds the per-image pose correction on
+        it.  False: nothing is allocated and every call is the one made without the argument.
+        ema_decay: None, or a float d strictly inside (0, 1): keep the debiased exponential moving average of the weights
         (tiny-cuda-nn's EMA optimizer; librtxn: rtxn_weight_ema, rtxn_train_step_ema), s = d s + (1 - d) w after every
         APPLIED update -- inside the Adam kernels of step(), step_captured() and step_entry(), which share the one state and may be
         mixed.  The MLP's average is kept densely; the hash table's lazily under the sparse rule (only the entries Adam touches are
@@ -129,6 +135,11 @@ class Trainer:
         self._init_scaler(loss_scale, max_grad_norm)
         self._init_ema(ema_decay)
         self._init_optimizer(lr_schedule, weight_decay, skip_nonfinite or self._scaler_cfg is not None)
+        if ray_gradients and encoding != "hash":
+            raise ValueError(f"Trainer: ray_gradients needs encoding='hash' (got {encoding!r}): the frequency and lean paths form no "
+                             "d(encoding) to differentiate through")
+        self.ray_gradients = bool(ray_gradients)
+        self._pose = None          # attach_images(refine_poses=...): the per-image pose correction
         self.image_set = None      # attach_images(): batches drawn on the device
         self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
         self._draw_step = None
@@ -277,6 +288,14 @@ class Trainer:
             self.t_start, self.t_end = torch.zeros(M, device=d), torch.zeros(M, device=d)
             self.distortion = torch.zeros(B, device=d)
             self._reg = api.train_regularizer(self.distortion_weight, self.t_start, self.t_end, self.distortion)
+        # the ray gradients: the segments' distances (shared with the regulariser), their end-point gradients, and dL/d(ray)
+        self.dstart = self.dend = self.rays_o_grad = self.rays_d_grad = self._rays = None
+        if self.ray_gradients:
+            if self.t_start is None:
+                self.t_start, self.t_end = torch.zeros(M, device=d), torch.zeros(M, device=d)
+            self.dstart, self.dend = torch.zeros((M, 3), device=d), torch.zeros((M, 3), device=d)
+            self.rays_o_grad, self.rays_d_grad = torch.zeros((B, 3), device=d), torch.zeros((B, 3), device=d)
+            self._rays = api.ray_gradients(self.t_start, self.t_end, self.dstart, self.dend, self.rays_o_grad, self.rays_d_grad)
         # data parallel (world > 1): the MLP gradient's all-reduce is issued from inside gradients(), right behind the MLP
         # backward, and runs beside the hash scatter; the hashed levels go through dp.Half2GradExchange (lists where a level
         # is sparse, RTXN_DP_SPARSE=0: always the dense fp16 level)
@@ -483,8 +502,8 @@ class Trainer:
         return float(np.float32(self.lr) * np.float32(f))
 
     def _reg_t(self, st=None):
-        """the write pass's t_start / t_end arguments: the regulariser's buffers (of buffer set st), or nothing"""
-        if self._reg is None:
+        """the write pass's t_start / t_end arguments: the regulariser's and the ray gradients' buffers (of buffer set st), or nothing"""
+        if self.t_start is None:
             return {}
         return dict(t_start=self.t_start if st is None else st["t_start"], t_end=self.t_end if st is None else st["t_end"])
 
@@ -517,7 +536,7 @@ class Trainer:
         return api.train_background(self.background, seed=seed, step=step, target_channels=n_channels)
 
     # ------------------------------------------------------------------------------------------ device batches
-    def attach_images(self, image_set, draw_seed=0):
+    def attach_images(self, image_set, draw_seed=0, refine_poses=None):
         """Draw this trainer's batches on the device from the resident frames of an api.ImageSet (librtxn: rtxn_draw_batch,
         DESIGN 5.10): step_images(), capture_step(draw=True) and entry_args(draw=True) then need no rays or targets from the
         caller.  The set's channel count must be the trainer's target width (3, or 4 = straight RGBA over its background).
@@ -526,7 +545,15 @@ class Trainer:
         not the optimizer's step, so batch k is the same batch on all three stepping paths, with or without prefetch.
         self.draw_count mirrors it on the host (checkpoints keep it); self.drawn holds (image, y*W + x) of the last draw.
         A graph captured with draw=True and the struct of entry_args(draw=True) hold the counter's, the frames' and the
-        poses' addresses, so once either exists another set cannot be attached: build a new Trainer for it."""
+        poses' addresses, so once either exists another set cannot be attached: build a new Trainer for it.
+        refine_poses: None, True, or a dict of lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-15 (a trainer built with ray_gradients=True;
+        DESIGN 5.16; librtxn: rtxn_pose_refinement): a 6-DoF correction (omega, tau) per image, optimised on the device inside
+        step_images(), step_captured() (capture_step(draw=True)) and step_entry() (entry_args(draw=True)) behind the optimizer, by
+        Adam on the gradient the batch's rays carry.  The set's poses are rewritten IN PLACE as (R(omega) R0 | t0 + tau) against a
+        clone of the poses as attached, so the next draw generates its rays from the refined poses with nothing else to change.
+        pose_delta [N, 6], pose_updates [N] and pose_skipped [1] are device tensors no stepping method reads; refined_poses()
+        returns the poses, reset_poses() restores the attached ones; checkpoints hold delta, moments, counts and the skipped count.
+        An image without a ray in the batch keeps its moments and count; a step the non-finite guard skips moves nothing."""
         if getattr(self, "_g_draw", False) or getattr(self, "_entry_draw", None) is not None:
             raise RuntimeError("Trainer.attach_images: a captured graph or an entry struct of this trainer already draws from the attached "
                                "set (capture_step(draw=True) / entry_args(draw=True) keep its addresses); build a new Trainer")
@@ -535,6 +562,24 @@ class Trainer:
             raise ValueError(f"Trainer.attach_images: a {c}-channel image set for a trainer that takes {self.target_channels}-channel targets" +
                              (" (RGBA frames need a background and target_channels=4)" if c == 4 else
                               " (this trainer composites straight RGBA targets over its background: load the frames with their alpha)"))
+        cfg = None
+        if refine_poses is not None and refine_poses is not False:      # refused before anything is allocated
+            if not self.ray_gradients:
+                raise ValueError("Trainer.attach_images: refine_poses needs a trainer built with ray_gradients=True")
+            if _world() > 1:
+                raise ValueError("Trainer.attach_images: refine_poses is single-GPU (every rank would move its own copy of the poses); "
+                                 "ray_gradients alone is per rank and allowed")
+            if refine_poses is not True and not isinstance(refine_poses, dict):
+                raise ValueError(f"Trainer.attach_images: refine_poses = {refine_poses!r}: None, True or a dict of lr, beta1, beta2, eps")
+            cfg = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-15)
+            extra = set(refine_poses) - set(cfg) if isinstance(refine_poses, dict) else set()
+            if extra:
+                raise ValueError(f"Trainer.attach_images: refine_poses has no {sorted(extra)} (lr, beta1, beta2, eps)")
+            cfg.update(refine_poses if isinstance(refine_poses, dict) else {})
+            try:
+                api.pose_refinement(int(image_set.n_images), **{k: float(v) for k, v in cfg.items()})
+            except (api._lib.RtxnError, TypeError, ValueError) as e:
+                raise ValueError(f"Trainer.attach_images: refine_poses = {refine_poses!r}: {e}") from None
         if not image_set.images.is_cuda:
             raise api._lib.RtxnError("Trainer.attach_images: the image set must live on the device (librtxn has no CPU path)")
         d = self.dev
@@ -544,7 +589,53 @@ class Trainer:
         self.draw_rays_d = torch.empty((self.B, 3), device=d)
         self.draw_targets = torch.empty((self.B, c), device=d)
         self.drawn = torch.zeros((self.B, 2), dtype=torch.int32, device=d)
+        self._pose = None
+        if cfg is not None:
+            N = int(image_set.n_images)
+            self.poses0 = image_set.poses.clone()
+            self.pose_delta, self._pose_m, self._pose_v = (torch.zeros((N, 6), device=d) for _ in range(3))
+            self.pose_updates = torch.zeros(N, dtype=torch.int32, device=d)
+            self.pose_skipped = torch.zeros(1, dtype=torch.int32, device=d)
+            self._pose_grad = torch.zeros((N, 8), device=d)
+            self._pose = api.pose_refinement(N, **{k: float(v) for k, v in cfg.items()}, poses0=self.poses0, poses=image_set.poses,
+                                             delta=self.pose_delta, m=self._pose_m, v=self._pose_v, steps=self.pose_updates,
+                                             grad=self._pose_grad, skip=None if self._opt_guard is None else self._opt_guard[2:3],
+                                             skipped=self.pose_skipped, drawn=self.drawn)
         return self
+
+    def refined_poses(self):
+        """[N, 4, 4]: the attached set's poses as the refinement has left them (a copy)"""
+        if self.image_set is None:
+            raise RuntimeError("refined_poses: call attach_images() first")
+        return self.image_set.poses.view(-1, 4, 4).clone()
+
+    def reset_poses(self):
+        """Zero the pose correction, its moments and counts, and restore the poses as attached."""
+        if self._pose is None:
+            raise RuntimeError("reset_poses: attach_images(refine_poses=...) first")
+        for t in self._pose_arrays().values():
+            t.zero_()
+        self.image_set.poses.copy_(self.poses0)
+
+    def _pose_arrays(self):
+        """the pose refinement's share of a checkpoint (nothing without refine_poses): optional on loading, a missing key means zeros"""
+        if self._pose is None:
+            return {}
+        return {"pose_delta": self.pose_delta, "pose_m": self._pose_m, "pose_v": self._pose_v, "pose_steps": self.pose_updates,
+                "pose_skipped": self.pose_skipped}
+
+    def _pose_update(self, n, rays_d):
+        """enqueue: the pose gradient of the batch just stepped (its rays drawn from the attached set) and the pose step"""
+        api.pose_gradients(self.drawn, rays_d, self.rays_o_grad, self.rays_d_grad, n, self._pose)
+        api.pose_step(self._pose)
+
+    def _ray_gradients(self, P, n, jit):
+        """enqueue: dL/d(ray) of the batch whose backward just ran, from its dencT, live list and segments"""
+        api.hashgrid_input_gradient_segments(self.hg, self.table, self.start, self.end, P, self._stype(jit), self.dencT, self.dstart,
+                                             self.dend, live_ws=self.live_ws if self.live_segments else None, jitter=jit,
+                                             loss_scale=self.loss_scale, scale_device=self.loss_scale_now)
+        api.ray_gradients_reduce(self.indices, self.num_stored, self.t_start, self.t_end, self.dstart, self.dend, n,
+                                 self.rays_o_grad, self.rays_d_grad)
 
     def _draw_seed(self):
         seed = self.draw_seed
@@ -566,7 +657,11 @@ class Trainer:
             raise ValueError(f"step_images: n = {n} outside [1, batch_rays = {self.B}]")
         self._draw(n, self.draw_rays_o, self.draw_rays_d, self.draw_targets)
         self.draw_count += 1
-        return self.step(self.draw_rays_o[:n], self.draw_rays_d[:n], self.draw_targets[:n])
+        loss = self.step(self.draw_rays_o[:n], self.draw_rays_d[:n], self.draw_targets[:n])
+        if self._pose is not None and self._stepped:       # behind the optimizer: the step sees the guard's skip word
+            with _Stage(self, "pose"):
+                self._pose_update(n, self.draw_rays_d)
+        return loss
 
     def _target_width(self, targets, n):
         tc = int(targets.shape[-1]) if targets.dim() == 2 and targets.shape[0] >= n else -1
@@ -767,6 +862,9 @@ class Trainer:
                                           self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg)
             else:
                 self.loss.zero_()
+            if self._rays is not None:
+                self.rays_o_grad[:n].zero_()
+                self.rays_d_grad[:n].zero_()
             return 0
         if not self.fold_sampler:
             self._sample(n, P, jit)
@@ -833,6 +931,9 @@ class Trainer:
                     self.hg.backward_mixed(self.samples[:S], self.dencT, self.dtable, self.dtable_h)
                 else:
                     self.hg.backward(self.samples[:S], self.dencT, self.dtable)
+        if self._rays is not None:
+            with _Stage(self, "ray_grad"):
+                self._ray_gradients(P, n, jit)
         return S
 
     def apply_gradients(self, grad_divisor=1.0):
@@ -931,7 +1032,8 @@ class Trainer:
         gradients are zero) -- so the ranks can neither deadlock nor drift apart in step count."""
         world = _world()
         S = self.gradients(rays_o, rays_d, targets)
-        if S == 0 and world == 1:
+        self._stepped = not (S == 0 and world == 1)
+        if not self._stepped:
             return self.loss                  # nothing to learn from: no Adam step, step_count unchanged
         if world > 1:
             with _Stage(self, "allreduce"):
@@ -1068,7 +1170,7 @@ class Trainer:
         """The header's "draw_count" is the number of batches DRAWN (attach_images): the loaded trainer draws batch draw_count
         next.  With capture_step(prefetch=True, draw=True) one batch is drawn ahead of the step that trains on it, so a
         checkpoint saved between replays resumes one batch further on: the pending batch is skipped, none is repeated."""
-        arrs = {k: v.detach().cpu().numpy() for k, v in {**self.state_arrays(), **self._ema_arrays()}.items()}
+        arrs = {k: v.detach().cpu().numpy() for k, v in {**self.state_arrays(), **self._ema_arrays(), **self._pose_arrays()}.items()}
         cfg = self.net.cfg
         header = {"step": self.step_count, "draw_count": self.draw_count,
                   "skipped_steps": 0 if self._opt_guard is None else int(self._opt_guard[1].item()),
@@ -1119,6 +1221,10 @@ class Trainer:
                 for t in ema.values():
                     t.zero_()
                 ema = {}
+            pose = self._pose_arrays()          # optional both ways, as "draw_count" is: a missing array means zeros
+            for nm, t in pose.items():
+                if nm not in in_file:
+                    t.zero_()
             if missing == {"table_adam_steps"} and version == 1:
                 import warnings
                 warnings.warn(f"{path}: version-1 checkpoint without per-entry table step counts: every entry's count is set to the "
@@ -1129,7 +1235,7 @@ class Trainer:
             for ent in header["arrays"]:
                 f.seek((-f.tell()) % 64, 1)
                 a = np.frombuffer(f.read(int(np.prod(ent["shape"])) * np.dtype(ent["dtype"]).itemsize), dtype=ent["dtype"])
-                t = dst.get(ent["name"], ema.get(ent["name"]))
+                t = dst.get(ent["name"], ema.get(ent["name"], pose.get(ent["name"])))
                 if t is None:
                     continue
                 if list(t.shape) != ent["shape"]:
@@ -1143,6 +1249,8 @@ class Trainer:
             self._opt_guard.zero_()
             self._opt_guard[1] = int(header.get("skipped_steps", 0))
         self._scaler_restore(header.get("loss_scaler"))
+        if self._pose is not None:
+            api.pose_compose(self._pose)                         # the poses are not in the file: delta against poses0 is
         self.net.set_params(self.params)
         return header
 
@@ -1175,6 +1283,9 @@ class Trainer:
         Data parallel: gradients and optimizer are captured as two graphs with the all-reduces between them."""
         if draw and self.image_set is None:
             raise RuntimeError("capture_step(draw=True): call attach_images() first")
+        if prefetch and self.ray_gradients:
+            raise ValueError("capture_step(prefetch=True) with ray_gradients: the next batch's traversal would overwrite the segment "
+                             "buffers the gather reads")
         if not self.fold_sampler:
             raise RuntimeError("capture_step needs the folded sampler (RTXN_TRAIN_FOLD_SAMPLER=0 is set)")
         n = int(n_rays)
@@ -1191,7 +1302,7 @@ class Trainer:
         self._g_n, self._g_cap, self._g_prefetch, self._g_draw = n, cap, bool(prefetch), bool(draw)
         # the traversal's outputs, once per buffer set (set 0 = the trainer's own buffers)
         names = ("view_dirs", "num_hits", "indices", "num_stored", "sub_hits", "total", "start", "end", "seg_view")
-        if self._reg is not None:
+        if self.t_start is not None:
             names += ("t_start", "t_end")
         set0 = {k: getattr(self, k) for k in names}
         sets = [set0]
@@ -1247,6 +1358,7 @@ class Trainer:
         guard = None if self._opt_guard is None else self._opt_guard.clone()
         scaler_state = None if self._scaler_state is None else self._scaler_state.clone()
         ema_state = {k: v.clone() for k, v in self._ema_arrays().items()}
+        pose_state = {k: v.clone() for k, v in self._pose_arrays().items()} if draw else {}
         clear_grads = self._clear_grads
         with torch.cuda.stream(side):
             clear_grads()
@@ -1256,6 +1368,7 @@ class Trainer:
             if self._g_split:
                 self._captured_table_bwd(0)
             self._captured_apply(float(world))
+            self._captured_pose()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         # undo the warm-up step: same parameters and step number as before capture_step()
@@ -1270,6 +1383,10 @@ class Trainer:
             self._scaler_state.copy_(scaler_state)  # ... and moves neither the scale nor its counters
         for k, v in self._ema_arrays().items():
             v.copy_(ema_state[k])                   # ... nor is it an update of the average
+        if pose_state:
+            for k, v in self._pose_arrays().items():
+                v.copy_(pose_state[k])              # ... nor of the poses
+            api.pose_compose(self._pose)
         self.net.set_params_training(self.params)
         self._g_step.fill_(self.step_count)
         self._g_step_host = self.step_count     # host mirror of the device counter (see _sync_device_step)
@@ -1302,6 +1419,7 @@ class Trainer:
                 self._captured_gradients(k)
                 if with_apply:
                     self._captured_apply(float(world))
+                    self._captured_pose()
             return body
 
         one = world == 1
@@ -1407,7 +1525,8 @@ class Trainer:
             api.draw_batch_launch(self._entry_draw)
             self._draw_step.add_(1)
             self.draw_count += 1
-        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt, self._scaler, self._ema)
+        api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt, self._scaler, self._ema,
+                       rays=self._rays, pose=self._pose if self._entry_draw is not None else None)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -1454,13 +1573,18 @@ class Trainer:
                             dtable=self.dtable if hash_ else None, dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
                             live_ws=self.live_ws if self.live_segments else None, skip_table_backward=self._g_split,
                             workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit, loss=self._loss,
-                            regularizer=st["reg"], scaler=self._scaler)
+                            regularizer=st["reg"], scaler=self._scaler, rays=self._rays)
 
     def _captured_table_bwd(self, k):
         """the hash scatter of set k's batch over the live list the gradient graph left (its count is on the device)"""
         st = self._g_sets[k]
         self.hg.backward_segments(st["start"], st["end"], self._g_cap, self._stype(self._g_jit), self.dencT, self.dtable,
                                   self.dtable_h if self.hash_fp16 else None, live_ws=self.live_ws, jitter=self._g_jit)
+
+    def _captured_pose(self):
+        """behind the captured optimizer: the pose gradient and step of a batch the graph drew itself"""
+        if self._pose is not None and self._g_draw:
+            self._pose_update(self._g_n, self._g_sets[0]["rays_d"])
 
     def _captured_apply(self, grad_divisor):
         if self._opt is not None:
