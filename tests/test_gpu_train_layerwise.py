@@ -5,8 +5,9 @@ restatement of the ONE stage that produced it, computed from the kernel's own st
 (tests/_train_float64.py).  What is left between the two is one fp32 accumulation and one rounding to fp16, so the bound is
 derived (half an fp16 ulp + the accumulation), not measured; tests/test_train_float64_reference.py shows on the CPU what it
 catches.  With test_saved_activation_weight_gradients_match_float64, which starts from these dZ and activations, every tensor of
-the saved-activation path is held per element; the lean path inherits that through its bit-for-bit comparisons
-(tests/test_gpu_train.py) and is decoded here once more from its own workspace.
+the saved-activation path is held per element.  The lean path's masks and dZ equal these bit for bit (tests/test_gpu_train.py)
+and are decoded here once more from its own workspace; its weight gradients, which recompute the activations, and the fused
+64-wide kernel's are held per element by tests/test_gpu_wgrad_float64.py against the tensors pinned here.
 
 Shapes: 16 encoded features is one k-step; 176 is wider than W and ends on a ragged 48-row chunk in layer 0; 16, 48, 112 and 176
 are all off multiples of 32 (the dencT row-tile edge); n = 700 is two tiles plus 188, so the last wave stops inside a column
