@@ -1,10 +1,14 @@
-// Optimizer options (include/rtxn.h, rtxn_optimizer_options): a learning-rate schedule evaluated on the device from
-// the step counter, decoupled weight decay and a guard that skips a step whose gradients are not finite.
+// The optimizer: all of Adam (optimizer->step of the reference's training loop, main.cu:787; tiny-cuda-nn is un-vendored and
+// unpinned, numerics follow oracle/rtxn_oracle.c's orc_adam_step) ...
+//   adam_dense_body, adam_sparse_body    the two walks over the parameters, each written once; the six Adam kernels of this file
+//                             are thin templates over them that differ in the rule for one element
+//   adam_kernel, adam_sparse_kernel      the step without options: the rate by value or from one device float
+// ... the optimizer options (include/rtxn.h, rtxn_optimizer_options): a learning-rate schedule evaluated on the
+// device from the step counter, decoupled weight decay and a guard that skips a step whose gradients are not finite:
 //   optimizer_rate_kernel     one thread: step counter, factor(t), the bias-corrected rate(s), the guard words
 //   check_gradients_kernel    Inf / NaN anywhere in up to four gradient buffers -> one flag
-//   adam_opt_kernel, adam_sparse_opt_kernel    train.hip's adam_kernel / adam_sparse_kernel reading the rate, the factor and the
-//                             skip word from device memory; siblings, so that the kernels a step without options launches are
-//                             the ones it always launched
+//   adam_opt_kernel, adam_sparse_opt_kernel    adam_kernel / adam_sparse_kernel reading the rate, the factor and the skip word
+//                             from device memory; kernels of their own, so that a step without options launches none of that
 // ... and the dynamic loss scale with gradient-norm clipping (rtxn_loss_scaler):
 //   gradient_statistics_kernel  check_gradients_kernel's pass plus a double sum of squares per block, summed in a fixed order
 //   loss_scaler_kernel          optimizer_rate_kernel's sibling, one block: reduces those sums, then the rate kernel's work and
@@ -12,13 +16,12 @@
 //   adam_opt_kernel<.., true>, adam_sparse_opt_kernel<.., true>    the _opt kernels with the factor on the raw gradient read
 //                             from device memory
 // ... and the exponential moving average of the weights (rtxn_weight_ema):
-//   adam_ema_kernel, adam_sparse_ema_kernel    siblings of the _opt kernels that also keep the average: densely, or (sparse) lazily,
+//   adam_ema_kernel, adam_sparse_ema_kernel    the _opt kernels that also keep the average: densely, or (sparse) lazily,
 //                             catching an entry up over the updates it sat out when Adam touches it
 //   ema_weights_kernel          the read-out: master, accumulator, stamps, state -> debiased fp32 / fp16; stores nothing else
 //   the two rate kernels advance the EMA's update count through a nullable pointer
 #include "common.h"
 #include "mlp_internal.h"
-#include "adam_internal.h"
 #include "wave_scan_internal.h"
 
 #include <cmath>
@@ -159,28 +162,54 @@ __global__ __launch_bounds__(kThreads) void check_gradients_kernel(GradList L, u
   if (any && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
 
+// ------------------------------------------------------------------------- Adam: two walks, six kernels
+// One Adam update (tcnn "Adam": no weight decay, bias correction folded into lr_eff on the host / lr_dev).
+__device__ __forceinline__ void adam_one(float g, float& mi, float& vi, float& w, float lr_eff, float beta1, float beta2, float eps) {
+  mi = beta1 * mi + (1.0f - beta1) * g;
+  vi = beta2 * vi + (1.0f - beta2) * g * g;
+  w = w - lr_eff * mi / (sqrtf(vi) + eps);
+}
+
 // The factor on the raw gradient: 1 / loss_scale by value or (DEV, rtxn_loss_scaler) the multiplier word of the scaler's state, a
-// kernel-argument pointer every lane reads at the same address: one scalar load.  The kernels stay the templates themselves, not
-// wrappers round a shared body: a wrapper moved the code of the by-value instantiations, this does not
-// (profiles/r14/compositor_scaled_ab.txt lists both builds).
+// kernel-argument pointer every lane reads at the same address: one scalar load.
 template <bool DEV>
 using grad_factor = std::conditional_t<DEV, const float*, float>;
 __device__ __forceinline__ float factor_value(float f) { return f; }
 __device__ __forceinline__ float factor_value(const float* f) { return *f; }
 
-// adam_kernel (train.hip) under the options.  lr_dev: the bias-corrected rate; factor_dev: factor(t), for the decay term
-// lr_t weight_decay w with lr_t = lr factor (no bias correction); skip (may be NULL): this step's skip word -- set, nothing of
-// the state is stored, and ZERO still clears the gradient.
-template <bool HALF_GRADS, bool ZERO, bool DEV>
-__global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
-                                                            void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
-                                                            const float* __restrict__ lr_dev, const float* __restrict__ factor_dev, float lr,
-                                                            float weight_decay, const unsigned* __restrict__ skip, float beta1, float beta2,
-                                                            float eps, grad_factor<DEV> inv_loss_scale_arg) {
+// What a kernel hands its walk, formed behind the skip branch: the factor on the raw gradient and the update of one element.
+template <typename One>
+struct AdamRule {
+  float grad_factor;
+  One one;
+};
+template <typename One>
+__device__ __forceinline__ AdamRule<One> adam_rule(float grad_factor, One one) { return {grad_factor, one}; }
 
+// The six Adam kernels below are thin __global__ templates over these two walks: every instantiation is still a kernel of its
+// own, under the name it always had (tools/pmc_kernels_json.py, the fingerprints under profiles/), so a step without options,
+// without the scaler or without the EMA launches code that carries nothing of them -- skip is a literal nullptr there and the
+// branch folds away, acc and stamps are touched under EMA alone.  What the walks fix for all of them: the alignment predicate,
+// the skip branch and what it clears, the order gradient clear -> update -> stores, and (sparse) that state is loaded only for
+// quads that pass the zero test.  While the features landed the kernels were copies, so that each change left the existing
+// ones' code byte for byte.  Folding the copies left none of the 40 instantiations byte-identical and moved no vector-memory,
+// floating-point or branch instruction, no VGPR count and no private segment off 0 in any of them: scalar address set-up and
+// register names differ, and adam_kernel / adam_sparse_kernel read the grid size once where their tail loop used to read it
+// again (profiles/r18/adam_bodies_ab.txt lists both builds).
+//
+// The dense walk.  HBM-bound (22-28 B per parameter, +8 under EMA): four parameters per thread, 16-byte accesses; pointers that
+// do not allow them send every element through the scalar tail.  ZERO: the gradient is cleared as it is consumed (the next
+// step accumulates into zeros without a separate fill pass).  skip (may be NULL): this step's skip word -- set, nothing of the
+// state is stored, and ZERO still clears the gradient.  rule_of_step() -> AdamRule whose one(g, m, v, w, s) updates an element;
+// s is the EMA accumulator's, a dummy without EMA.
+template <bool HALF_GRADS, bool ZERO, bool EMA, typename RuleOfStep>
+__device__ __forceinline__ void adam_dense_body(long n, float* __restrict__ master, __half* __restrict__ params, void* __restrict__ grads_v,
+                                                float* __restrict__ m, float* __restrict__ v, float* __restrict__ acc,
+                                                const unsigned* __restrict__ skip, RuleOfStep rule_of_step) {
   float* gf = static_cast<float*>(grads_v);
   __half* gh = static_cast<__half*>(grads_v);
-  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
+  const uintptr_t acc_bits = EMA ? (uintptr_t)acc : 0;
+  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | acc_bits | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
   const long n4 = vec ? n / 4 : 0;
   const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
   if (skip && *skip != 0u) {
@@ -195,15 +224,12 @@ __global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __res
     }
     return;
   }
-  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
-  const float lr_eff = *lr_dev;
-  const float decay = (lr * *factor_dev) * weight_decay;          // w -= lr_t weight_decay w
-  auto one = [&](float g, float& mi, float& vi, float& w) {
-    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
-    if (decay != 0.0f) w = w - decay * w;
-  };
+  const auto rule = rule_of_step();
+  const float inv_loss_scale = rule.grad_factor;
   for (long q = first; q < n4; q += stride) {
     float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
+    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (EMA) s4 = reinterpret_cast<float4*>(acc)[q];
     float g[4];
     if (HALF_GRADS) {
       const half4v h = reinterpret_cast<const half4v*>(gh)[q];
@@ -215,42 +241,49 @@ __global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __res
       g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
       if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    one(g[0], m4.x, v4.x, w4.x);
-    one(g[1], m4.y, v4.y, w4.y);
-    one(g[2], m4.z, v4.z, w4.z);
-    one(g[3], m4.w, v4.w, w4.w);
+    rule.one(g[0], m4.x, v4.x, w4.x, s4.x);
+    rule.one(g[1], m4.y, v4.y, w4.y, s4.y);
+    rule.one(g[2], m4.z, v4.z, w4.z, s4.z);
+    rule.one(g[3], m4.w, v4.w, w4.w, s4.w);
     reinterpret_cast<float4*>(master)[q] = w4;
     reinterpret_cast<float4*>(m)[q] = m4;
     reinterpret_cast<float4*>(v)[q] = v4;
+    if constexpr (EMA) reinterpret_cast<float4*>(acc)[q] = s4;
     const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
     reinterpret_cast<half4v*>(params)[q] = o;
   }
   for (long i = 4 * n4 + first; i < n; i += stride) {
     const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
     if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
-    float mi = m[i], vi = v[i], w = master[i];
-    one(g, mi, vi, w);
+    float mi = m[i], vi = v[i], w = master[i], s = 0.0f;
+    if constexpr (EMA) s = acc[i];
+    rule.one(g, mi, vi, w, s);
     m[i] = mi;
     v[i] = vi;
     master[i] = w;
+    if constexpr (EMA) acc[i] = s;
     params[i] = __float2half(w);
   }
 }
 
-// adam_sparse_kernel (train.hip) under the options: lr_t = lr factor in the entry's own bias correction, the decay term on the
-// entries it updates, and the skip word -- set, the update counts keep their bits with the rest of the state, and ZERO clears
-// every non-zero gradient word (also a NaN, which is not == 0).
-template <bool HALF_GRADS, bool ZERO, bool DEV>
-__global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
-                                                                   void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
-                                                                   unsigned* __restrict__ steps, const float* __restrict__ factor_dev, float lr,
-                                                                   float weight_decay, const unsigned* __restrict__ skip, float beta1,
-                                                                   float beta2, float eps, grad_factor<DEV> inv_loss_scale_arg, float log2_beta1,
-                                                                   float log2_beta2) {
-
+// The sparse walk: tiny-cuda-nn's Adam as it treats "non-matrix" parameters -- the hash table (optimizers/adam.h, adam_step): an
+// entry whose gradient is exactly zero is SKIPPED (neither moment decays, the weight stays), and the bias correction uses the
+// entry's OWN count of updates (steps), "since some parameters might see fewer steps than others".  A step's batch touches
+// 0.2 .. 25 % of a hashed level, so this is also the cheap form: the gradient is read everywhere (2 or 4 B per parameter), the
+// 14 B of state (+8 under EMA: acc and stamps, the lazy average) only where a quad's gradient is not all +-0.  ZERO clears what
+// it consumes.  skip: as above -- set, the update counts keep their bits with the rest of the state, and ZERO clears every
+// non-zero gradient word (also a NaN, which is not == 0).  rule_of_step() -> AdamRule whose one(g, m, v, w, steps, s, stamp)
+// leaves an element with g == 0 alone; s and stamp are dummies without EMA.
+template <bool HALF_GRADS, bool ZERO, bool EMA, typename RuleOfStep>
+__device__ __forceinline__ void adam_sparse_body(long n, float* __restrict__ master, __half* __restrict__ params, void* __restrict__ grads_v,
+                                                 float* __restrict__ m, float* __restrict__ v, unsigned* __restrict__ steps,
+                                                 float* __restrict__ acc, unsigned* __restrict__ stamps, const unsigned* __restrict__ skip,
+                                                 RuleOfStep rule_of_step) {
   float* gf = static_cast<float*>(grads_v);
   __half* gh = static_cast<__half*>(grads_v);
-  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)steps | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
+  const uintptr_t ema_bits = EMA ? (uintptr_t)acc | (uintptr_t)stamps : 0;
+  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)steps | ema_bits | (uintptr_t)grads_v) & 15) == 0 &&
+                   ((uintptr_t)params & 7) == 0;
   const long n4 = vec ? n / 4 : 0;
   const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
   if (skip && *skip != 0u) {
@@ -270,18 +303,8 @@ __global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float
     }
     return;
   }
-  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
-  const float lr_t = lr * *factor_dev;
-  const float decay = lr_t * weight_decay;
-  auto one = [&](float g, float& mi, float& vi, float& w, unsigned& st) {
-    if (g == 0.0f) return;
-    st += 1u;
-    const float t = (float)st;
-    // beta^t = 2^(t log2 beta), as adam_sparse_kernel
-    const float lr_eff = lr_t * sqrtf(1.0f - __builtin_amdgcn_exp2f(t * log2_beta2)) / (1.0f - __builtin_amdgcn_exp2f(t * log2_beta1));
-    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
-    if (decay != 0.0f) w = w - decay * w;
-  };
+  const auto rule = rule_of_step();
+  const float inv_loss_scale = rule.grad_factor;
   for (long q = first; q < n4; q += stride) {
     float g[4];
     if (HALF_GRADS) {
@@ -299,14 +322,24 @@ __global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float
     }
     float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
     uint4 s4 = reinterpret_cast<uint4*>(steps)[q];
-    one(g[0], m4.x, v4.x, w4.x, s4.x);
-    one(g[1], m4.y, v4.y, w4.y, s4.y);
-    one(g[2], m4.z, v4.z, w4.z, s4.z);
-    one(g[3], m4.w, v4.w, w4.w, s4.w);
+    float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint4 e4 = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (EMA) {
+      a4 = reinterpret_cast<float4*>(acc)[q];
+      e4 = reinterpret_cast<uint4*>(stamps)[q];
+    }
+    rule.one(g[0], m4.x, v4.x, w4.x, s4.x, a4.x, e4.x);
+    rule.one(g[1], m4.y, v4.y, w4.y, s4.y, a4.y, e4.y);
+    rule.one(g[2], m4.z, v4.z, w4.z, s4.z, a4.z, e4.z);
+    rule.one(g[3], m4.w, v4.w, w4.w, s4.w, a4.w, e4.w);
     reinterpret_cast<float4*>(master)[q] = w4;
     reinterpret_cast<float4*>(m)[q] = m4;
     reinterpret_cast<float4*>(v)[q] = v4;
     reinterpret_cast<uint4*>(steps)[q] = s4;
+    if constexpr (EMA) {
+      reinterpret_cast<float4*>(acc)[q] = a4;
+      reinterpret_cast<uint4*>(stamps)[q] = e4;
+    }
     const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
     reinterpret_cast<half4v*>(params)[q] = o;
   }
@@ -314,16 +347,287 @@ __global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float
     const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
     if (g == 0.0f) continue;
     if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
-    float mi = m[i], vi = v[i], w = master[i];
-    unsigned st = steps[i];
-    one(g, mi, vi, w, st);
+    float mi = m[i], vi = v[i], w = master[i], s = 0.0f;
+    unsigned st = steps[i], e = 0u;
+    if constexpr (EMA) {
+      s = acc[i];
+      e = stamps[i];
+    }
+    rule.one(g, mi, vi, w, st, s, e);
     m[i] = mi;
     v[i] = vi;
     master[i] = w;
     steps[i] = st;
+    if constexpr (EMA) {
+      acc[i] = s;
+      stamps[i] = e;
+    }
     params[i] = __float2half(w);
   }
 }
+
+// The sparse rule's bias-corrected rate of an entry at its own update count: beta^t = 2^(t log2 beta), one v_exp_f32 each (a
+// libm powf here made the kernel slower than the dense one while the gradient is still dense, early in training); relative
+// error ~1e-6 of a factor that multiplies lr
+__device__ __forceinline__ float adam_sparse_rate(float lr, unsigned st, float log2_beta1, float log2_beta2) {
+  const float t = (float)st;
+  return lr * sqrtf(1.0f - __builtin_amdgcn_exp2f(t * log2_beta2)) / (1.0f - __builtin_amdgcn_exp2f(t * log2_beta1));
+}
+
+// lr_dev (may be NULL): the bias-corrected rate of a captured step -- it changes every replay, the graph does not
+template <bool HALF_GRADS, bool ZERO>
+__global__ __launch_bounds__(kThreads) void adam_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                        void* __restrict__ grads_v, float* __restrict__ m,
+                                                        float* __restrict__ v, float lr_eff, float beta1, float beta2,
+                                                        float eps, float inv_loss_scale, const float* __restrict__ lr_dev) {
+  if (lr_dev) lr_eff = *lr_dev;
+  adam_dense_body<HALF_GRADS, ZERO, false>(n, master, params, grads_v, m, v, nullptr, nullptr, [=] {
+    return adam_rule(inv_loss_scale, [=](float g, float& mi, float& vi, float& w, float&) { adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps); });
+  });
+}
+
+template <bool HALF_GRADS, bool ZERO>
+__global__ __launch_bounds__(kThreads) void adam_sparse_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                               void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                               unsigned* __restrict__ steps, float lr, float beta1, float beta2,
+                                                               float eps, float inv_loss_scale, float log2_beta1, float log2_beta2) {
+  adam_sparse_body<HALF_GRADS, ZERO, false>(n, master, params, grads_v, m, v, steps, nullptr, nullptr, nullptr, [=] {
+    return adam_rule(inv_loss_scale, [=](float g, float& mi, float& vi, float& w, unsigned& st, float&, unsigned&) {
+      if (g == 0.0f) return;
+      st += 1u;
+      adam_one(g, mi, vi, w, adam_sparse_rate(lr, st, log2_beta1, log2_beta2), beta1, beta2, eps);
+    });
+  });
+}
+
+// adam_kernel under the options (rtxn_optimizer_options).  lr_dev: the bias-corrected rate; factor_dev: factor(t), for the decay
+// term lr_t weight_decay w with lr_t = lr factor (no bias correction); skip: this step's skip word.  DEV: the _scaled form.
+template <bool HALF_GRADS, bool ZERO, bool DEV>
+__global__ __launch_bounds__(kThreads) void adam_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                            void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                            const float* __restrict__ lr_dev, const float* __restrict__ factor_dev, float lr,
+                                                            float weight_decay, const unsigned* __restrict__ skip, float beta1, float beta2,
+                                                            float eps, grad_factor<DEV> inv_loss_scale_arg) {
+  adam_dense_body<HALF_GRADS, ZERO, false>(n, master, params, grads_v, m, v, nullptr, skip, [=] {
+    const float inv_loss_scale = factor_value(inv_loss_scale_arg);
+    const float lr_eff = *lr_dev;
+    const float decay = (lr * *factor_dev) * weight_decay;          // w -= lr_t weight_decay w
+    return adam_rule(inv_loss_scale, [=](float g, float& mi, float& vi, float& w, float&) {
+      adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
+      if (decay != 0.0f) w = w - decay * w;
+    });
+  });
+}
+
+// adam_sparse_kernel under the options: lr_t = lr factor in the entry's own bias correction, the decay term on the entries it
+// updates, and the skip word.
+template <bool HALF_GRADS, bool ZERO, bool DEV>
+__global__ __launch_bounds__(kThreads) void adam_sparse_opt_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                                   void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                                   unsigned* __restrict__ steps, const float* __restrict__ factor_dev, float lr,
+                                                                   float weight_decay, const unsigned* __restrict__ skip, float beta1,
+                                                                   float beta2, float eps, grad_factor<DEV> inv_loss_scale_arg, float log2_beta1,
+                                                                   float log2_beta2) {
+  adam_sparse_body<HALF_GRADS, ZERO, false>(n, master, params, grads_v, m, v, steps, nullptr, nullptr, skip, [=] {
+    const float inv_loss_scale = factor_value(inv_loss_scale_arg);
+    const float lr_t = lr * *factor_dev;
+    const float decay = lr_t * weight_decay;
+    return adam_rule(inv_loss_scale, [=](float g, float& mi, float& vi, float& w, unsigned& st, float&, unsigned&) {
+      if (g == 0.0f) return;
+      st += 1u;
+      adam_one(g, mi, vi, w, adam_sparse_rate(lr_t, st, log2_beta1, log2_beta2), beta1, beta2, eps);
+      if (decay != 0.0f) w = w - decay * w;
+    });
+  });
+}
+
+// adam_opt_kernel that also keeps the average of what it steps (rtxn_weight_ema), dense form: s = d s + (1 - d) w behind the
+// decay term, +8 bytes per element.
+template <bool HALF_GRADS, bool ZERO, bool DEV>
+__global__ __launch_bounds__(kThreads) void adam_ema_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                            void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ acc, const float* __restrict__ lr_dev,
+                                                            const float* __restrict__ factor_dev, float lr, float weight_decay,
+                                                            const unsigned* __restrict__ skip, float beta1, float beta2, float eps,
+                                                            grad_factor<DEV> inv_loss_scale_arg, float d, float omd) {
+  adam_dense_body<HALF_GRADS, ZERO, true>(n, master, params, grads_v, m, v, acc, skip, [=] {
+    const float inv_loss_scale = factor_value(inv_loss_scale_arg);
+    const float lr_eff = *lr_dev;
+    const float decay = (lr * *factor_dev) * weight_decay;          // w -= lr_t weight_decay w
+    return adam_rule(inv_loss_scale, [=](float g, float& mi, float& vi, float& w, float& s) {
+      adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
+      if (decay != 0.0f) w = w - decay * w;
+      s = d * s + omd * w;
+    });
+  });
+}
+
+// adam_sparse_opt_kernel that also keeps the average, lazy form: of the quads that pass the non-zero test only the updated
+// elements move -- caught up over the updates they sat out, then the EMA line, then the stamp.  ema: a kernel-argument pointer
+// every lane reads at the same address, one scalar load; updates was advanced by the rate kernel, so it is the number u of this
+// update.
+template <bool HALF_GRADS, bool ZERO, bool DEV>
+__global__ __launch_bounds__(kThreads) void adam_sparse_ema_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
+                                                                   void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
+                                                                   unsigned* __restrict__ steps, float* __restrict__ acc,
+                                                                   unsigned* __restrict__ stamps, const rtxn_ema_state* __restrict__ ema,
+                                                                   const float* __restrict__ factor_dev, float lr, float weight_decay,
+                                                                   const unsigned* __restrict__ skip, float beta1, float beta2, float eps,
+                                                                   grad_factor<DEV> inv_loss_scale_arg, float log2_beta1, float log2_beta2,
+                                                                   float d, float omd, float log2_d) {
+  adam_sparse_body<HALF_GRADS, ZERO, true>(n, master, params, grads_v, m, v, steps, acc, stamps, skip, [=] {
+    const float inv_loss_scale = factor_value(inv_loss_scale_arg);
+    const float lr_t = lr * *factor_dev;
+    const float decay = lr_t * weight_decay;
+    const unsigned u = ema->updates;
+    return adam_rule(inv_loss_scale, [=](float g, float& mi, float& vi, float& w, unsigned& st, float& s, unsigned& e) {
+      if (g == 0.0f) return;
+      const float w_old = w;
+      st += 1u;
+      adam_one(g, mi, vi, w, adam_sparse_rate(lr_t, st, log2_beta1, log2_beta2), beta1, beta2, eps);
+      if (decay != 0.0f) w = w - decay * w;
+      s = ema_catch_up(s, w_old, u - 1u - e, log2_d);
+      s = d * s + omd * w;
+      e = u;
+    });
+  });
+}
+
+// ---- the host side of the Adam kernels
+#define ADAM_TRY(call)                 \
+  do {                                 \
+    const int rc_ = (call);            \
+    if (rc_ != RTXN_OK) return rc_;    \
+  } while (0)
+
+// Four elements per lane.  Dense: every quad is worked on, at most 4096 blocks.  Sparse: most quads are only looked at, at most
+// 8192, and at least one, which takes the tail when n < 4.
+unsigned adam_dense_grid(long n) {
+  const long blocks = ((n + 3) / 4 + kThreads - 1) / kThreads;
+  return (unsigned)(blocks < 4096 ? blocks : 4096);
+}
+unsigned adam_sparse_grid(long n) {
+  const long blocks = (n / 4 + kThreads - 1) / kThreads;
+  return (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
+}
+
+// The argument checks the entry points share, each with its one text; an entry point asks them in the order it always has.
+// with_options: the calls that also take RTXN_ADAM_NO_WEIGHT_DECAY.
+int check_grad_flags(const char* who, int grad_flags, bool with_options) {
+  if (with_options)
+    RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  else
+    RTXN_REQUIRE((grad_flags & ~3) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS)", who, grad_flags);
+  return RTXN_OK;
+}
+int check_betas(const char* who, float beta1, float beta2) {
+  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
+               (double)beta2);
+  return RTXN_OK;
+}
+
+// HALF_GRADS and ZERO of grad_flags as compile-time constants: launch(half, zero) is instantiated for the four pairs, so the
+// [HALF_GRADS][ZERO] table of a kernel family is the one template-id in its launch.
+template <typename Launch>
+void with_grad_flags(int grad_flags, Launch launch) {
+  const std::true_type yes;
+  const std::false_type no;
+  if (grad_flags & RTXN_ADAM_GRADS_FP16) {
+    if (grad_flags & RTXN_ADAM_ZERO_GRADS) launch(yes, yes); else launch(yes, no);
+  } else {
+    if (grad_flags & RTXN_ADAM_ZERO_GRADS) launch(no, yes); else launch(no, no);
+  }
+}
+
+float adam_lr_eff(float lr, float beta1, float beta2, int step) {
+  return lr * sqrtf(1.0f - powf(beta2, (float)step)) / (1.0f - powf(beta1, (float)step));
+}
+
+// the dense step without options: the rate by value, or (lr_dev) read on the device
+int adam_impl(const char* who, long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v, float lr_eff,
+              const float* lr_dev, float beta1, float beta2, float eps, float loss_scale, rtxn_stream_t stream) {
+  RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v, "%s: NULL buffer", who);
+  with_grad_flags(grad_flags, [&](auto half, auto zero) {
+    adam_kernel<half(), zero()><<<adam_dense_grid(n), kThreads, 0, rtxn::as_stream(stream)>>>(
+        n, master, static_cast<__half*>(params_fp16), grads, m, v, lr_eff, beta1, beta2, eps, 1.0f / loss_scale, lr_dev);
+  });
+  RTXN_LAUNCH_CHECK("adam_kernel");
+  return RTXN_OK;
+}
+
+// Every dense step under the options, behind its entry point's checks of the structs and the flags: _opt (scaler and ema NULL),
+// _scaled (ema NULL, loss_scale unused) and _ema.  The factor on the raw gradient is the scaler's multiplier word or
+// 1 / loss_scale; with ema the kernel also keeps the average in ema_acc.
+int adam_dense_options(const char* who, long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                       const float* effective_lr, float lr, float beta1, float beta2, float eps, float loss_scale,
+                       const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, float* ema_acc,
+                       rtxn_stream_t stream) {
+  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
+  RTXN_REQUIRE(scaler || loss_scale != 0.0f, "%s: loss_scale = 0", who);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v && (!ema || ema_acc), "%s: NULL buffer", who);
+  const unsigned grid = adam_dense_grid(n);
+  hipStream_t hs = rtxn::as_stream(stream);
+  __half* p16 = static_cast<__half*>(params_fp16);
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  const unsigned* skip = opt->skip_nonfinite ? opt->guard + 2 : nullptr;
+  const float d = ema ? ema->decay : 0.0f, omd = 1.0f - d;
+  auto launch = [&](auto half, auto zero, auto factor) {
+    constexpr bool DEV = std::is_pointer_v<decltype(factor)>;
+    if (ema)
+      adam_ema_kernel<half(), zero(), DEV><<<grid, kThreads, 0, hs>>>(n, master, p16, grads, m, v, ema_acc, effective_lr, opt->lr_factor, lr, wd, skip,
+                                                                      beta1, beta2, eps, factor, d, omd);
+    else
+      adam_opt_kernel<half(), zero(), DEV><<<grid, kThreads, 0, hs>>>(n, master, p16, grads, m, v, effective_lr, opt->lr_factor, lr, wd, skip, beta1,
+                                                                      beta2, eps, factor);
+  };
+  with_grad_flags(grad_flags, [&](auto half, auto zero) {
+    if (scaler) launch(half, zero, static_cast<const float*>(&scaler->state->multiplier)); else launch(half, zero, 1.0f / loss_scale);
+  });
+  RTXN_LAUNCH_CHECK(ema ? "adam_ema_kernel" : scaler ? "adam_opt_kernel (device multiplier)" : "adam_opt_kernel");
+  return RTXN_OK;
+}
+
+// ... and every sparse one: _sparse_opt, _sparse_scaled and _sparse_ema, which keeps the average lazily in ema_acc and ema_stamps.
+int adam_sparse_options(const char* who, long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                        unsigned* param_steps, float lr, float beta1, float beta2, float eps, float loss_scale,
+                        const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, float* ema_acc,
+                        unsigned* ema_stamps, rtxn_stream_t stream) {
+  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+  RTXN_REQUIRE(scaler || loss_scale != 0.0f, "%s: loss_scale = 0", who);
+  ADAM_TRY(check_betas(who, beta1, beta2));
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps && (!ema || (ema_acc && ema_stamps)),
+               ema ? "%s: NULL buffer (the sparse rule keeps the average lazily: ema_acc and ema_stamps)" : "%s: NULL buffer", who);
+  const unsigned grid = adam_sparse_grid(n);
+  hipStream_t hs = rtxn::as_stream(stream);
+  __half* p16 = static_cast<__half*>(params_fp16);
+  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
+  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
+  const unsigned* skip = opt->skip_nonfinite ? opt->guard + 2 : nullptr;
+  const float d = ema ? ema->decay : 0.0f, omd = 1.0f - d, l2d = ema ? (float)log2((double)d) : 0.0f;
+  auto launch = [&](auto half, auto zero, auto factor) {
+    constexpr bool DEV = std::is_pointer_v<decltype(factor)>;
+    if (ema)
+      adam_sparse_ema_kernel<half(), zero(), DEV><<<grid, kThreads, 0, hs>>>(n, master, p16, grads, m, v, param_steps, ema_acc, ema_stamps, ema->state,
+                                                                             opt->lr_factor, lr, wd, skip, beta1, beta2, eps, factor, l2b1, l2b2, d,
+                                                                             omd, l2d);
+    else
+      adam_sparse_opt_kernel<half(), zero(), DEV><<<grid, kThreads, 0, hs>>>(n, master, p16, grads, m, v, param_steps, opt->lr_factor, lr, wd, skip,
+                                                                             beta1, beta2, eps, factor, l2b1, l2b2);
+  };
+  with_grad_flags(grad_flags, [&](auto half, auto zero) {
+    if (scaler) launch(half, zero, static_cast<const float*>(&scaler->state->multiplier)); else launch(half, zero, 1.0f / loss_scale);
+  });
+  RTXN_LAUNCH_CHECK(ema ? "adam_sparse_ema_kernel" : scaler ? "adam_sparse_opt_kernel (device multiplier)" : "adam_sparse_opt_kernel");
+  return RTXN_OK;
+}
+
 
 int check_schedule(const rtxn_lr_schedule& s, const char* who) {
   RTXN_REQUIRE(s.kind == RTXN_LR_CONSTANT || s.kind == RTXN_LR_EXPONENTIAL || s.kind == RTXN_LR_COSINE,
@@ -392,8 +696,7 @@ static int optimizer_rate_impl(const char* who, const rtxn_optimizer_options* op
   RTXN_REQUIRE(opt->lr_factor && (!opt->skip_nonfinite || opt->guard), "%s: opt->lr_factor = %p, opt->guard = %p", who, (void*)opt->lr_factor,
                (void*)opt->guard);
   RTXN_REQUIRE(step && effective_lr, "%s: step = %p, effective_lr = %p", who, (void*)step, (void*)effective_lr);
-  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
-               (double)beta2);
+  ADAM_TRY(check_betas(who, beta1, beta2));
   RTXN_DEVICE_OR_FAIL();
   optimizer_rate_kernel<<<1, 1, 0, rtxn::as_stream(stream)>>>(step, advance, opt->schedule, lr, table_lr, beta1, beta2, effective_lr,
                                                               table_effective_lr, opt->lr_factor, opt->skip_nonfinite ? opt->guard : nullptr,
@@ -449,32 +752,64 @@ extern "C" int rtxn_check_gradients(const rtxn_grad_buffer* buffers, int n_buffe
   return RTXN_OK;
 }
 
+extern "C" int rtxn_adam_step(long n, float* master, void* params_fp16, const float* grads, float* m, float* v, int step,
+                              float lr, float beta1, float beta2, float eps, float loss_scale, rtxn_stream_t stream) {
+  RTXN_REQUIRE(n >= 0 && step >= 1, "rtxn_adam_step: n = %ld, step = %d", n, step);
+  return adam_impl("rtxn_adam_step", n, master, params_fp16, const_cast<float*>(grads), 0, m, v, adam_lr_eff(lr, beta1, beta2, step), nullptr, beta1,
+                   beta2, eps, loss_scale, stream);
+}
+
+extern "C" int rtxn_adam_step_half_grads(long n, float* master, void* params_fp16, const void* grads_fp16, float* m, float* v,
+                                         int step, float lr, float beta1, float beta2, float eps, float loss_scale,
+                                         rtxn_stream_t stream) {
+  RTXN_REQUIRE(n >= 0 && step >= 1, "rtxn_adam_step_half_grads: n = %ld, step = %d", n, step);
+  return adam_impl("rtxn_adam_step_half_grads", n, master, params_fp16, const_cast<void*>(grads_fp16), RTXN_ADAM_GRADS_FP16, m, v,
+                   adam_lr_eff(lr, beta1, beta2, step), nullptr, beta1, beta2, eps, loss_scale, stream);
+}
+
+extern "C" float rtxn_adam_effective_lr(float lr, float beta1, float beta2, int step) {
+  return step >= 1 ? adam_lr_eff(lr, beta1, beta2, step) : 0.0f;
+}
+
+extern "C" int rtxn_adam_step_captured(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m,
+                                       float* v, const float* effective_lr, float beta1, float beta2, float eps, float loss_scale,
+                                       rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_captured";
+  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
+  ADAM_TRY(check_grad_flags(who, grad_flags, false));
+  return adam_impl(who, n, master, params_fp16, grads, grad_flags, m, v, 0.0f, effective_lr, beta1, beta2, eps, loss_scale, stream);
+}
+
+extern "C" int rtxn_adam_step_sparse(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
+                                     unsigned* param_steps, float lr, float beta1, float beta2, float eps, float loss_scale,
+                                     rtxn_stream_t stream) {
+  const char* who = "rtxn_adam_step_sparse";
+  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+  ADAM_TRY(check_grad_flags(who, grad_flags, false));
+  RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
+  RTXN_DEVICE_OR_FAIL();
+  if (n == 0) return RTXN_OK;
+  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps, "%s: NULL buffer", who);
+  ADAM_TRY(check_betas(who, beta1, beta2));
+  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
+  with_grad_flags(grad_flags, [&](auto half, auto zero) {
+    adam_sparse_kernel<half(), zero()><<<adam_sparse_grid(n), kThreads, 0, rtxn::as_stream(stream)>>>(
+        n, master, static_cast<__half*>(params_fp16), grads, m, v, param_steps, lr, beta1, beta2, eps, 1.0f / loss_scale, l2b1, l2b2);
+  });
+  RTXN_LAUNCH_CHECK("adam_sparse_kernel");
+  return RTXN_OK;
+}
+
 extern "C" int rtxn_adam_step_opt(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
                                   const float* effective_lr, float lr, float beta1, float beta2, float eps, float loss_scale,
                                   const rtxn_optimizer_options* opt, rtxn_stream_t stream) {
   const char* who = "rtxn_adam_step_opt";
   bool active = false;
-  const int rc = rtxn::check_optimizer_options(opt, who, true, &active);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  ADAM_TRY(rtxn::check_optimizer_options(opt, who, true, &active));
+  ADAM_TRY(check_grad_flags(who, grad_flags, true));
   if (!active) return rtxn_adam_step_captured(n, master, params_fp16, grads, grad_flags & 3, m, v, effective_lr, beta1, beta2, eps, loss_scale, stream);
-  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
-  RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v, "%s: NULL buffer", who);
-  const long work = (n + 3) / 4;
-  const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
-  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  static decltype(&adam_opt_kernel<false, false, false>) const table[2][2] = {
-      {adam_opt_kernel<false, false, false>, adam_opt_kernel<false, true, false>},   // [HALF_GRADS][ZERO]
-      {adam_opt_kernel<true, false, false>, adam_opt_kernel<true, true, false>}};
-  table[half][zero]<<<blocks, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, effective_lr,
-                                                                      opt->lr_factor, lr, wd, opt->skip_nonfinite ? opt->guard + 2 : nullptr, beta1,
-                                                                      beta2, eps, 1.0f / loss_scale);
-  RTXN_LAUNCH_CHECK("adam_opt_kernel");
-  return RTXN_OK;
+  return adam_dense_options(who, n, master, params_fp16, grads, grad_flags, m, v, effective_lr, lr, beta1, beta2, eps, loss_scale, opt, nullptr, nullptr,
+                            nullptr, stream);
 }
 
 extern "C" int rtxn_adam_step_sparse_opt(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
@@ -482,30 +817,11 @@ extern "C" int rtxn_adam_step_sparse_opt(long n, float* master, void* params_fp1
                                          const rtxn_optimizer_options* opt, rtxn_stream_t stream) {
   const char* who = "rtxn_adam_step_sparse_opt";
   bool active = false;
-  const int rc = rtxn::check_optimizer_options(opt, who, true, &active);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
+  ADAM_TRY(rtxn::check_optimizer_options(opt, who, true, &active));
+  ADAM_TRY(check_grad_flags(who, grad_flags, true));
   if (!active) return rtxn_adam_step_sparse(n, master, params_fp16, grads, grad_flags & 3, m, v, param_steps, lr, beta1, beta2, eps, loss_scale, stream);
-  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
-  RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
-  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
-               (double)beta2);
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps, "%s: NULL buffer", who);
-  const long blocks = (n / 4 + kThreads - 1) / kThreads;
-  const unsigned gridx = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
-  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
-  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  static decltype(&adam_sparse_opt_kernel<false, false, false>) const table[2][2] = {
-      {adam_sparse_opt_kernel<false, false, false>, adam_sparse_opt_kernel<false, true, false>},   // [HALF_GRADS][ZERO]
-      {adam_sparse_opt_kernel<true, false, false>, adam_sparse_opt_kernel<true, true, false>}};
-  table[half][zero]<<<gridx, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, param_steps,
-                                                                     opt->lr_factor, lr, wd, opt->skip_nonfinite ? opt->guard + 2 : nullptr, beta1,
-                                                                     beta2, eps, 1.0f / loss_scale, l2b1, l2b2);
-  RTXN_LAUNCH_CHECK("adam_sparse_opt_kernel");
-  return RTXN_OK;
+  return adam_sparse_options(who, n, master, params_fp16, grads, grad_flags, m, v, param_steps, lr, beta1, beta2, eps, loss_scale, opt, nullptr, nullptr,
+                             nullptr, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------- dynamic loss scale, gradient-norm clipping
@@ -769,8 +1085,7 @@ static int loss_scaler_step_impl(const char* who, const rtxn_optimizer_options* 
   int rc = check_scaled(opt, scaler, who);
   if (rc != RTXN_OK) return rc;
   RTXN_REQUIRE(step && effective_lr, "%s: step = %p, effective_lr = %p", who, (void*)step, (void*)effective_lr);
-  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
-               (double)beta2);
+  ADAM_TRY(check_betas(who, beta1, beta2));
   RTXN_REQUIRE(divisor > 0.0f && std::isfinite(divisor), "%s: divisor = %g", who, (double)divisor);
   StatList L;
   int k = 0, most = 0;
@@ -808,231 +1123,24 @@ extern "C" int rtxn_adam_step_scaled(long n, float* master, void* params_fp16, v
                                      const float* effective_lr, float lr, float beta1, float beta2, float eps,
                                      const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
   const char* who = "rtxn_adam_step_scaled";
-  const int rc = check_scaled(opt, scaler, who);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
-  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v, "%s: NULL buffer", who);
-  const long work = (n + 3) / 4;
-  const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
-  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  static decltype(&adam_opt_kernel<false, false, true>) const table[2][2] = {
-      {adam_opt_kernel<false, false, true>, adam_opt_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
-      {adam_opt_kernel<true, false, true>, adam_opt_kernel<true, true, true>}};
-  table[half][zero]<<<blocks, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, effective_lr,
-                                                                      opt->lr_factor, lr, wd, opt->guard + 2, beta1, beta2, eps,
-                                                                      &scaler->state->multiplier);
-  RTXN_LAUNCH_CHECK("adam_opt_kernel (device multiplier)");
-  return RTXN_OK;
+  ADAM_TRY(check_scaled(opt, scaler, who));
+  ADAM_TRY(check_grad_flags(who, grad_flags, true));
+  return adam_dense_options(who, n, master, params_fp16, grads, grad_flags, m, v, effective_lr, lr, beta1, beta2, eps, 0.0f, opt, scaler, nullptr, nullptr,
+                            stream);
 }
 
 extern "C" int rtxn_adam_step_sparse_scaled(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
                                             unsigned* param_steps, float lr, float beta1, float beta2, float eps,
                                             const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
   const char* who = "rtxn_adam_step_sparse_scaled";
-  const int rc = check_scaled(opt, scaler, who);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
-  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
-  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
-               (double)beta2);
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps, "%s: NULL buffer", who);
-  const long blocks = (n / 4 + kThreads - 1) / kThreads;
-  const unsigned gridx = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
-  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
-  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  static decltype(&adam_sparse_opt_kernel<false, false, true>) const table[2][2] = {
-      {adam_sparse_opt_kernel<false, false, true>, adam_sparse_opt_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
-      {adam_sparse_opt_kernel<true, false, true>, adam_sparse_opt_kernel<true, true, true>}};
-  table[half][zero]<<<gridx, kThreads, 0, rtxn::as_stream(stream)>>>(n, master, static_cast<__half*>(params_fp16), grads, m, v, param_steps,
-                                                                     opt->lr_factor, lr, wd, opt->guard + 2, beta1, beta2, eps,
-                                                                     &scaler->state->multiplier, l2b1, l2b2);
-  RTXN_LAUNCH_CHECK("adam_sparse_opt_kernel (device multiplier)");
-  return RTXN_OK;
+  ADAM_TRY(check_scaled(opt, scaler, who));
+  ADAM_TRY(check_grad_flags(who, grad_flags, true));
+  return adam_sparse_options(who, n, master, params_fp16, grads, grad_flags, m, v, param_steps, lr, beta1, beta2, eps, 0.0f, opt, scaler, nullptr, nullptr,
+                             nullptr, stream);
 }
 
 // ------------------------------------------------------------------------- exponential moving average of the weights
 namespace {
-
-// adam_opt_kernel that also keeps the average of what it steps, dense form: s = d s + (1 - d) w behind the decay term, +8 bytes per
-// element.  A sibling, not a template parameter: without the EMA every path launches the kernels it always launched.
-template <bool HALF_GRADS, bool ZERO, bool DEV>
-__global__ __launch_bounds__(kThreads) void adam_ema_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
-                                                            void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
-                                                            float* __restrict__ acc, const float* __restrict__ lr_dev,
-                                                            const float* __restrict__ factor_dev, float lr, float weight_decay,
-                                                            const unsigned* __restrict__ skip, float beta1, float beta2, float eps,
-                                                            grad_factor<DEV> inv_loss_scale_arg, float d, float omd) {
-  float* gf = static_cast<float*>(grads_v);
-  __half* gh = static_cast<__half*>(grads_v);
-  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
-  const long n4 = vec ? n / 4 : 0;
-  const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
-  if (skip && *skip != 0u) {
-    if (ZERO) {
-      for (long q = first; q < n4; q += stride) {
-        if (HALF_GRADS) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
-        else reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      for (long i = 4 * n4 + first; i < n; i += stride) {
-        if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f;
-      }
-    }
-    return;
-  }
-  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
-  const float lr_eff = *lr_dev;
-  const float decay = (lr * *factor_dev) * weight_decay;          // w -= lr_t weight_decay w
-  auto one = [&](float g, float& mi, float& vi, float& w, float& s) {
-    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
-    if (decay != 0.0f) w = w - decay * w;
-    s = d * s + omd * w;
-  };
-  for (long q = first; q < n4; q += stride) {
-    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
-    float4 s4 = reinterpret_cast<float4*>(acc)[q];
-    float g[4];
-    if (HALF_GRADS) {
-      const half4v h = reinterpret_cast<const half4v*>(gh)[q];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
-      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
-    } else {
-      const float4 f = reinterpret_cast<const float4*>(gf)[q];
-      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
-      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    one(g[0], m4.x, v4.x, w4.x, s4.x);
-    one(g[1], m4.y, v4.y, w4.y, s4.y);
-    one(g[2], m4.z, v4.z, w4.z, s4.z);
-    one(g[3], m4.w, v4.w, w4.w, s4.w);
-    reinterpret_cast<float4*>(master)[q] = w4;
-    reinterpret_cast<float4*>(m)[q] = m4;
-    reinterpret_cast<float4*>(v)[q] = v4;
-    reinterpret_cast<float4*>(acc)[q] = s4;
-    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
-    reinterpret_cast<half4v*>(params)[q] = o;
-  }
-  for (long i = 4 * n4 + first; i < n; i += stride) {
-    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
-    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
-    float mi = m[i], vi = v[i], w = master[i], s = acc[i];
-    one(g, mi, vi, w, s);
-    m[i] = mi;
-    v[i] = vi;
-    master[i] = w;
-    acc[i] = s;
-    params[i] = __float2half(w);
-  }
-}
-
-// adam_sparse_opt_kernel that also keeps the average, lazy form: s and the stamps are loaded only for the quads that pass the
-// non-zero test, and of those only the updated elements move -- caught up over the updates they sat out, then the EMA line, then
-// the stamp.  ema: a kernel-argument pointer every lane reads at the same address, one scalar load; updates was advanced by the
-// rate kernel, so it is the number u of this update.
-template <bool HALF_GRADS, bool ZERO, bool DEV>
-__global__ __launch_bounds__(kThreads) void adam_sparse_ema_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
-                                                                   void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
-                                                                   unsigned* __restrict__ steps, float* __restrict__ acc,
-                                                                   unsigned* __restrict__ stamps, const rtxn_ema_state* __restrict__ ema,
-                                                                   const float* __restrict__ factor_dev, float lr, float weight_decay,
-                                                                   const unsigned* __restrict__ skip, float beta1, float beta2, float eps,
-                                                                   grad_factor<DEV> inv_loss_scale_arg, float log2_beta1, float log2_beta2,
-                                                                   float d, float omd, float log2_d) {
-  float* gf = static_cast<float*>(grads_v);
-  __half* gh = static_cast<__half*>(grads_v);
-  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)steps | (uintptr_t)acc | (uintptr_t)stamps | (uintptr_t)grads_v) & 15) == 0 &&
-                   ((uintptr_t)params & 7) == 0;
-  const long n4 = vec ? n / 4 : 0;
-  const long first = (long)blockIdx.x * kThreads + threadIdx.x, stride = (long)gridDim.x * kThreads;
-  if (skip && *skip != 0u) {
-    if (ZERO) {
-      for (long q = first; q < n4; q += stride) {
-        if (HALF_GRADS) {
-          const uint2 raw = reinterpret_cast<const uint2*>(gh)[q];
-          if ((raw.x | raw.y) != 0u) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
-        } else {
-          const uint4 raw = reinterpret_cast<const uint4*>(gf)[q];
-          if ((raw.x | raw.y | raw.z | raw.w) != 0u) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      }
-      for (long i = 4 * n4 + first; i < n; i += stride) {
-        if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f;
-      }
-    }
-    return;
-  }
-  const float inv_loss_scale = factor_value(inv_loss_scale_arg);
-  const float lr_t = lr * *factor_dev;
-  const float decay = lr_t * weight_decay;
-  const unsigned u = ema->updates;
-  auto one = [&](float g, float& mi, float& vi, float& w, unsigned& st, float& s, unsigned& e) {
-    if (g == 0.0f) return;
-    const float w_old = w;
-    st += 1u;
-    const float t = (float)st;
-    // beta^t = 2^(t log2 beta), as adam_sparse_kernel
-    const float lr_eff = lr_t * sqrtf(1.0f - __builtin_amdgcn_exp2f(t * log2_beta2)) / (1.0f - __builtin_amdgcn_exp2f(t * log2_beta1));
-    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
-    if (decay != 0.0f) w = w - decay * w;
-    s = ema_catch_up(s, w_old, u - 1u - e, log2_d);
-    s = d * s + omd * w;
-    e = u;
-  };
-  for (long q = first; q < n4; q += stride) {
-    float g[4];
-    if (HALF_GRADS) {
-      const uint2 raw = reinterpret_cast<const uint2*>(gh)[q];
-      if (((raw.x | raw.y) & 0x7fff7fffu) == 0u) continue;
-      const half4v h = __builtin_bit_cast(half4v, raw);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
-      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
-    } else {
-      const float4 f = reinterpret_cast<const float4*>(gf)[q];
-      if (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f && f.w == 0.0f) continue;
-      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
-      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
-    uint4 s4 = reinterpret_cast<uint4*>(steps)[q];
-    float4 a4 = reinterpret_cast<float4*>(acc)[q];
-    uint4 e4 = reinterpret_cast<uint4*>(stamps)[q];
-    one(g[0], m4.x, v4.x, w4.x, s4.x, a4.x, e4.x);
-    one(g[1], m4.y, v4.y, w4.y, s4.y, a4.y, e4.y);
-    one(g[2], m4.z, v4.z, w4.z, s4.z, a4.z, e4.z);
-    one(g[3], m4.w, v4.w, w4.w, s4.w, a4.w, e4.w);
-    reinterpret_cast<float4*>(master)[q] = w4;
-    reinterpret_cast<float4*>(m)[q] = m4;
-    reinterpret_cast<float4*>(v)[q] = v4;
-    reinterpret_cast<uint4*>(steps)[q] = s4;
-    reinterpret_cast<float4*>(acc)[q] = a4;
-    reinterpret_cast<uint4*>(stamps)[q] = e4;
-    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
-    reinterpret_cast<half4v*>(params)[q] = o;
-  }
-  for (long i = 4 * n4 + first; i < n; i += stride) {
-    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
-    if (g == 0.0f) continue;
-    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
-    float mi = m[i], vi = v[i], w = master[i], s = acc[i];
-    unsigned st = steps[i], e = stamps[i];
-    one(g, mi, vi, w, st, s, e);
-    m[i] = mi;
-    v[i] = vi;
-    master[i] = w;
-    steps[i] = st;
-    acc[i] = s;
-    stamps[i] = e;
-    params[i] = __float2half(w);
-  }
-}
 
 // The read-out: catch_up(s, w, u - e) correction(u), or w itself at u = 0.  Pure -- it stores only the outputs.  One 16-byte
 // word per lane and array, and two quads per trip: four to six independent loads in flight per lane (one load in flight per lane
@@ -1073,22 +1181,19 @@ __global__ __launch_bounds__(kThreads) void ema_weights_kernel(long n, const flo
   }
 }
 
-// the factor on the raw gradient of an _ema Adam call: the scaler's multiplier word, or 1 / loss_scale
+// what an _ema Adam call asks in front of its launch path: the EMA, the scaler with the options it needs or the options alone and
+// the loss scale by value, then the flags
 int check_ema_step(const char* who, const rtxn_optimizer_options* opt, const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, float loss_scale,
                    int grad_flags) {
-  int rc = check_ema(ema, opt, true, who);
-  if (rc != RTXN_OK) return rc;
+  ADAM_TRY(check_ema(ema, opt, true, who));
   if (scaler) {
-    rc = check_scaled(opt, scaler, who);
+    ADAM_TRY(check_scaled(opt, scaler, who));
   } else {
     bool active = false;
-    rc = rtxn::check_optimizer_options(opt, who, true, &active);
-    if (rc == RTXN_OK) RTXN_REQUIRE(!opt->skip_nonfinite || opt->guard, "%s: opt->guard is NULL with opt->skip_nonfinite set", who);
-    if (rc == RTXN_OK) RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
+    ADAM_TRY(rtxn::check_optimizer_options(opt, who, true, &active));      // with skip_nonfinite set this asks for the guard too
+    RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
   }
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE((grad_flags & ~7) == 0, "%s: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS | RTXN_ADAM_NO_WEIGHT_DECAY)", who, grad_flags);
-  return RTXN_OK;
+  return check_grad_flags(who, grad_flags, true);
 }
 
 }  // namespace
@@ -1119,35 +1224,9 @@ extern "C" int rtxn_adam_step_ema(long n, float* master, void* params_fp16, void
   if (!ema)
     return scaler ? rtxn_adam_step_scaled(n, master, params_fp16, grads, grad_flags, m, v, effective_lr, lr, beta1, beta2, eps, opt, scaler, stream)
                   : rtxn_adam_step_opt(n, master, params_fp16, grads, grad_flags, m, v, effective_lr, lr, beta1, beta2, eps, loss_scale, opt, stream);
-  const int rc = check_ema_step(who, opt, scaler, ema, loss_scale, grad_flags);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(n >= 0 && effective_lr, "%s: n = %ld, effective_lr = %p", who, n, (const void*)effective_lr);
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v && ema_acc, "%s: NULL buffer", who);
-  const long work = (n + 3) / 4;
-  const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
-  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  const unsigned* skip = opt->skip_nonfinite ? opt->guard + 2 : nullptr;
-  const float d = ema->decay, omd = 1.0f - d;
-  hipStream_t hs = rtxn::as_stream(stream);
-  __half* p16 = static_cast<__half*>(params_fp16);
-  if (scaler) {
-    static decltype(&adam_ema_kernel<false, false, true>) const table[2][2] = {
-        {adam_ema_kernel<false, false, true>, adam_ema_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
-        {adam_ema_kernel<true, false, true>, adam_ema_kernel<true, true, true>}};
-    table[half][zero]<<<blocks, kThreads, 0, hs>>>(n, master, p16, grads, m, v, ema_acc, effective_lr, opt->lr_factor, lr, wd, skip, beta1, beta2, eps,
-                                                   &scaler->state->multiplier, d, omd);
-  } else {
-    static decltype(&adam_ema_kernel<false, false, false>) const table[2][2] = {
-        {adam_ema_kernel<false, false, false>, adam_ema_kernel<false, true, false>},
-        {adam_ema_kernel<true, false, false>, adam_ema_kernel<true, true, false>}};
-    table[half][zero]<<<blocks, kThreads, 0, hs>>>(n, master, p16, grads, m, v, ema_acc, effective_lr, opt->lr_factor, lr, wd, skip, beta1, beta2, eps,
-                                                   1.0f / loss_scale, d, omd);
-  }
-  RTXN_LAUNCH_CHECK("adam_ema_kernel");
-  return RTXN_OK;
+  ADAM_TRY(check_ema_step(who, opt, scaler, ema, loss_scale, grad_flags));
+  return adam_dense_options(who, n, master, params_fp16, grads, grad_flags, m, v, effective_lr, lr, beta1, beta2, eps, loss_scale, opt, scaler, ema,
+                            ema_acc, stream);
 }
 
 extern "C" int rtxn_adam_step_sparse_ema(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
@@ -1159,39 +1238,9 @@ extern "C" int rtxn_adam_step_sparse_ema(long n, float* master, void* params_fp1
     return scaler ? rtxn_adam_step_sparse_scaled(n, master, params_fp16, grads, grad_flags, m, v, param_steps, lr, beta1, beta2, eps, opt, scaler, stream)
                   : rtxn_adam_step_sparse_opt(n, master, params_fp16, grads, grad_flags, m, v, param_steps, lr, beta1, beta2, eps, loss_scale, opt,
                                               stream);
-  const int rc = check_ema_step(who, opt, scaler, ema, loss_scale, grad_flags);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
-  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "%s: beta1 = %g, beta2 = %g outside (0, 1)", who, (double)beta1,
-               (double)beta2);
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps && ema_acc && ema_stamps,
-               "%s: NULL buffer (the sparse rule keeps the average lazily: ema_acc and ema_stamps)", who);
-  const long blocks = (n / 4 + kThreads - 1) / kThreads;
-  const unsigned gridx = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
-  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
-  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  const float wd = (grad_flags & RTXN_ADAM_NO_WEIGHT_DECAY) ? 0.0f : opt->weight_decay;
-  const unsigned* skip = opt->skip_nonfinite ? opt->guard + 2 : nullptr;
-  const float d = ema->decay, omd = 1.0f - d, l2d = (float)log2((double)d);
-  hipStream_t hs = rtxn::as_stream(stream);
-  __half* p16 = static_cast<__half*>(params_fp16);
-  if (scaler) {
-    static decltype(&adam_sparse_ema_kernel<false, false, true>) const table[2][2] = {
-        {adam_sparse_ema_kernel<false, false, true>, adam_sparse_ema_kernel<false, true, true>},   // [HALF_GRADS][ZERO]
-        {adam_sparse_ema_kernel<true, false, true>, adam_sparse_ema_kernel<true, true, true>}};
-    table[half][zero]<<<gridx, kThreads, 0, hs>>>(n, master, p16, grads, m, v, param_steps, ema_acc, ema_stamps, ema->state, opt->lr_factor, lr, wd,
-                                                  skip, beta1, beta2, eps, &scaler->state->multiplier, l2b1, l2b2, d, omd, l2d);
-  } else {
-    static decltype(&adam_sparse_ema_kernel<false, false, false>) const table[2][2] = {
-        {adam_sparse_ema_kernel<false, false, false>, adam_sparse_ema_kernel<false, true, false>},
-        {adam_sparse_ema_kernel<true, false, false>, adam_sparse_ema_kernel<true, true, false>}};
-    table[half][zero]<<<gridx, kThreads, 0, hs>>>(n, master, p16, grads, m, v, param_steps, ema_acc, ema_stamps, ema->state, opt->lr_factor, lr, wd,
-                                                  skip, beta1, beta2, eps, 1.0f / loss_scale, l2b1, l2b2, d, omd, l2d);
-  }
-  RTXN_LAUNCH_CHECK("adam_sparse_ema_kernel");
-  return RTXN_OK;
+  ADAM_TRY(check_ema_step(who, opt, scaler, ema, loss_scale, grad_flags));
+  return adam_sparse_options(who, n, master, params_fp16, grads, grad_flags, m, v, param_steps, lr, beta1, beta2, eps, loss_scale, opt, scaler, ema, ema_acc,
+                             ema_stamps, stream);
 }
 
 extern "C" int rtxn_ema_weights(long n, const float* master, const float* ema_acc, const unsigned* stamps, const rtxn_ema_state* state, float decay,

@@ -1,10 +1,10 @@
 // Training path: encoders (Composite-Frequency, multiresolution hash grid), MLP
 // forward with saved activations, MLP backward (dgrad fused across layers + per-layer
-// wgrad), L2 loss and Adam.  Replaces the tiny-cuda-nn calls of the reference's training
+// wgrad) and the L2 loss.  Replaces the tiny-cuda-nn calls of the reference's training
 // loop: network->forward(..., prepare_input_gradients) (main.cu:721), loss->evaluate
-// (:759), network->backward (:781), optimizer->step (:787).  tiny-cuda-nn is un-vendored
-// and unpinned; numerics follow oracle/rtxn_oracle.c (orc_mlpe_*, orc_hg_*, orc_l2_loss,
-// orc_adam_step).  PARITY UNPINNED.
+// (:759), network->backward (:781); optimizer->step (:787) is optimizer.hip.  tiny-cuda-nn
+// is un-vendored and unpinned; numerics follow oracle/rtxn_oracle.c (orc_mlpe_*, orc_hg_*,
+// orc_l2_loss).  PARITY UNPINNED.
 //
 // Layout.  Every per-sample training tensor is FEATURE-MAJOR fp16: X[feature][S_pad],
 // S_pad = S rounded up to 256 (one block tile), padding columns written as zeros.  That is
@@ -23,10 +23,9 @@
 //                             fp32 atomics into the tcnn-layout gradient buffer
 //   hashgrid_backward_kernel  scatter-add of denc into the table gradient (fp32 atomics)
 //   hashgrid_input_gradient_kernel  the scatter's transposed twin: denc -> dL/d(position) per segment end point (no atomics)
-//   l2_loss_kernel, adam_kernel
+//   l2_loss_kernel                  (Adam: optimizer.hip)
 #include "mlp_internal.h"
 #include "hashgrid_internal.h"
-#include "adam_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2720,120 +2719,6 @@ __global__ __launch_bounds__(kThreads) void l2_loss_kernel(const float* __restri
   }
 }
 
-// adam_one: adam_internal.h
-// HBM-bound (22-28 B per parameter): four parameters per thread, 16-byte accesses
-// ZERO: the gradient is cleared as it is consumed (the next step accumulates into zeros without a separate fill pass)
-template <bool HALF_GRADS, bool ZERO>
-__global__ __launch_bounds__(kThreads) void adam_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
-                                                        void* __restrict__ grads_v, float* __restrict__ m,
-                                                        float* __restrict__ v, float lr_eff, float beta1, float beta2,
-                                                        float eps, float inv_loss_scale, const float* __restrict__ lr_dev) {
-  if (lr_dev) lr_eff = *lr_dev;      // captured steps: the bias-corrected rate changes every replay, the graph does not
-  float* gf = static_cast<float*>(grads_v);
-  __half* gh = static_cast<__half*>(grads_v);
-  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
-  const long n4 = vec ? n / 4 : 0;
-  for (long q = (long)blockIdx.x * kThreads + threadIdx.x; q < n4; q += (long)gridDim.x * kThreads) {
-    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
-    float g[4];
-    if (HALF_GRADS) {
-      const half4v h = reinterpret_cast<const half4v*>(gh)[q];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
-      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
-    } else {
-      const float4 f = reinterpret_cast<const float4*>(gf)[q];
-      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
-      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    adam_one(g[0], m4.x, v4.x, w4.x, lr_eff, beta1, beta2, eps);
-    adam_one(g[1], m4.y, v4.y, w4.y, lr_eff, beta1, beta2, eps);
-    adam_one(g[2], m4.z, v4.z, w4.z, lr_eff, beta1, beta2, eps);
-    adam_one(g[3], m4.w, v4.w, w4.w, lr_eff, beta1, beta2, eps);
-    reinterpret_cast<float4*>(master)[q] = w4;
-    reinterpret_cast<float4*>(m)[q] = m4;
-    reinterpret_cast<float4*>(v)[q] = v4;
-    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
-    reinterpret_cast<half4v*>(params)[q] = o;
-  }
-  for (long i = 4 * n4 + (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
-    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
-    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
-    float mi = m[i], vi = v[i], w = master[i];
-    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
-    m[i] = mi;
-    v[i] = vi;
-    master[i] = w;
-    params[i] = __float2half(w);
-  }
-}
-
-// tiny-cuda-nn's Adam as it treats "non-matrix" parameters -- the hash table (optimizers/adam.h, adam_step): an entry whose
-// gradient is exactly zero is SKIPPED (neither moment decays, the weight stays), and the bias correction uses the entry's OWN
-// count of updates (param_steps), "since some parameters might see fewer steps than others".  A step's batch touches 0.2 .. 25 %
-// of a hashed level, so this is also the cheap form: the gradient is read everywhere (2 or 4 B per parameter), the 14 B of
-// state only where it is non-zero.  Four parameters per thread; ZERO clears the gradient as it is consumed.
-template <bool HALF_GRADS, bool ZERO>
-__global__ __launch_bounds__(kThreads) void adam_sparse_kernel(long n, float* __restrict__ master, __half* __restrict__ params,
-                                                               void* __restrict__ grads_v, float* __restrict__ m, float* __restrict__ v,
-                                                               unsigned* __restrict__ steps, float lr, float beta1, float beta2,
-                                                               float eps, float inv_loss_scale, float log2_beta1, float log2_beta2) {
-  float* gf = static_cast<float*>(grads_v);
-  __half* gh = static_cast<__half*>(grads_v);
-  auto one = [&](float g, float& mi, float& vi, float& w, unsigned& st) {
-    if (g == 0.0f) return;
-    st += 1u;
-    const float t = (float)st;
-    // beta^t = 2^(t log2 beta): one v_exp_f32 each (a libm powf here made the kernel slower than the dense one while the
-    // gradient is still dense, early in training); relative error ~1e-6 of a factor that multiplies lr
-    const float lr_eff = lr * sqrtf(1.0f - __builtin_amdgcn_exp2f(t * log2_beta2)) / (1.0f - __builtin_amdgcn_exp2f(t * log2_beta1));
-    adam_one(g, mi, vi, w, lr_eff, beta1, beta2, eps);
-  };
-  const bool vec = (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)steps | (uintptr_t)grads_v) & 15) == 0 && ((uintptr_t)params & 7) == 0;
-  const long n4 = vec ? n / 4 : 0;
-  for (long q = (long)blockIdx.x * kThreads + threadIdx.x; q < n4; q += (long)gridDim.x * kThreads) {
-    float g[4];
-    if (HALF_GRADS) {
-      const uint2 raw = reinterpret_cast<const uint2*>(gh)[q];
-      if (((raw.x | raw.y) & 0x7fff7fffu) == 0u) continue;
-      const half4v h = __builtin_bit_cast(half4v, raw);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] = (float)h[e] * inv_loss_scale;
-      if (ZERO) reinterpret_cast<uint2*>(gh)[q] = make_uint2(0u, 0u);
-    } else {
-      const float4 f = reinterpret_cast<const float4*>(gf)[q];
-      if (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f && f.w == 0.0f) continue;
-      g[0] = f.x * inv_loss_scale; g[1] = f.y * inv_loss_scale; g[2] = f.z * inv_loss_scale; g[3] = f.w * inv_loss_scale;
-      if (ZERO) reinterpret_cast<float4*>(gf)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float4 w4 = reinterpret_cast<float4*>(master)[q], m4 = reinterpret_cast<float4*>(m)[q], v4 = reinterpret_cast<float4*>(v)[q];
-    uint4 s4 = reinterpret_cast<uint4*>(steps)[q];
-    one(g[0], m4.x, v4.x, w4.x, s4.x);
-    one(g[1], m4.y, v4.y, w4.y, s4.y);
-    one(g[2], m4.z, v4.z, w4.z, s4.z);
-    one(g[3], m4.w, v4.w, w4.w, s4.w);
-    reinterpret_cast<float4*>(master)[q] = w4;
-    reinterpret_cast<float4*>(m)[q] = m4;
-    reinterpret_cast<float4*>(v)[q] = v4;
-    reinterpret_cast<uint4*>(steps)[q] = s4;
-    const half4v o = {(_Float16)w4.x, (_Float16)w4.y, (_Float16)w4.z, (_Float16)w4.w};
-    reinterpret_cast<half4v*>(params)[q] = o;
-  }
-  for (long i = 4 * n4 + (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
-    const float g = (HALF_GRADS ? __half2float(gh[i]) : gf[i]) * inv_loss_scale;
-    if (g == 0.0f) continue;
-    if (ZERO) { if (HALF_GRADS) gh[i] = __float2half(0.0f); else gf[i] = 0.0f; }
-    float mi = m[i], vi = v[i], w = master[i];
-    unsigned st = steps[i];
-    one(g, mi, vi, w, st);
-    m[i] = mi;
-    v[i] = vi;
-    master[i] = w;
-    steps[i] = st;
-    params[i] = __float2half(w);
-  }
-}
-
 // fp32 <-> fp16 copies of a gradient block (8 elements per thread): the data-parallel exchange of the hashed levels' gradient
 // travels in fp16 (tcnn keeps that gradient in fp16 to begin with), see rtx_nerf_amd/train.py
 // deterministic mode: fold the fixed-point sums into the gradient buffers they shadow (accumulate semantics, one rounding per
@@ -3967,79 +3852,6 @@ extern "C" int rtxn_l2_loss(const float* pred, const float* target, long n, floa
   const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads < 1024 ? (n + kThreads - 1) / kThreads : 1024);
   l2_loss_kernel<<<blocks, kThreads, 0, s>>>(pred, target, n, loss_scale, values, static_cast<__half*>(grads_half), loss_sum);
   RTXN_LAUNCH_CHECK("l2_loss_kernel");
-  return RTXN_OK;
-}
-
-static float adam_lr_eff(float lr, float beta1, float beta2, int step) {
-  return lr * sqrtf(1.0f - powf(beta2, (float)step)) / (1.0f - powf(beta1, (float)step));
-}
-static int adam_impl(const char* who, long n, float* master, void* params_fp16, void* grads, int grads_fp16, bool zero, float* m, float* v,
-                     float lr_eff, const float* lr_dev, float beta1, float beta2, float eps, float loss_scale, rtxn_stream_t stream) {
-  RTXN_REQUIRE(loss_scale != 0.0f, "%s: loss_scale = 0", who);
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v, "%s: NULL buffer", who);
-  const long work = (n + 3) / 4;
-  const unsigned blocks = (unsigned)((work + kThreads - 1) / kThreads < 4096 ? (work + kThreads - 1) / kThreads : 4096);
-  hipStream_t st = rtxn::as_stream(stream);
-  __half* p16 = static_cast<__half*>(params_fp16);
-  const float ils = 1.0f / loss_scale;
-  static decltype(&adam_kernel<false, false>) const table[2][2] = {{adam_kernel<false, false>, adam_kernel<false, true>},   // [HALF_GRADS][ZERO]
-                                                                   {adam_kernel<true, false>, adam_kernel<true, true>}};
-  table[grads_fp16 != 0][zero]<<<blocks, kThreads, 0, st>>>(n, master, p16, grads, m, v, lr_eff, beta1, beta2, eps, ils, lr_dev);
-  RTXN_LAUNCH_CHECK("adam_kernel");
-  return RTXN_OK;
-}
-
-extern "C" int rtxn_adam_step(long n, float* master, void* params_fp16, const float* grads, float* m, float* v, int step,
-                              float lr, float beta1, float beta2, float eps, float loss_scale, rtxn_stream_t stream) {
-  RTXN_REQUIRE(n >= 0 && step >= 1, "rtxn_adam_step: n = %ld, step = %d", n, step);
-  return adam_impl("rtxn_adam_step", n, master, params_fp16, const_cast<float*>(grads), 0, false, m, v, adam_lr_eff(lr, beta1, beta2, step),
-                   nullptr, beta1, beta2, eps, loss_scale, stream);
-}
-
-extern "C" int rtxn_adam_step_half_grads(long n, float* master, void* params_fp16, const void* grads_fp16, float* m, float* v,
-                                         int step, float lr, float beta1, float beta2, float eps, float loss_scale,
-                                         rtxn_stream_t stream) {
-  RTXN_REQUIRE(n >= 0 && step >= 1, "rtxn_adam_step_half_grads: n = %ld, step = %d", n, step);
-  return adam_impl("rtxn_adam_step_half_grads", n, master, params_fp16, const_cast<void*>(grads_fp16), 1, false, m, v,
-                   adam_lr_eff(lr, beta1, beta2, step), nullptr, beta1, beta2, eps, loss_scale, stream);
-}
-
-extern "C" float rtxn_adam_effective_lr(float lr, float beta1, float beta2, int step) {
-  return step >= 1 ? adam_lr_eff(lr, beta1, beta2, step) : 0.0f;
-}
-
-extern "C" int rtxn_adam_step_captured(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m,
-                                       float* v, const float* effective_lr, float beta1, float beta2, float eps, float loss_scale,
-                                       rtxn_stream_t stream) {
-  RTXN_REQUIRE(n >= 0 && effective_lr, "rtxn_adam_step_captured: n = %ld, effective_lr = %p", n, (const void*)effective_lr);
-  RTXN_REQUIRE((grad_flags & ~3) == 0, "rtxn_adam_step_captured: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS)", grad_flags);
-  return adam_impl("rtxn_adam_step_captured", n, master, params_fp16, grads, grad_flags & RTXN_ADAM_GRADS_FP16,
-                   (grad_flags & RTXN_ADAM_ZERO_GRADS) != 0, m, v, 0.0f, effective_lr, beta1, beta2, eps, loss_scale, stream);
-}
-
-extern "C" int rtxn_adam_step_sparse(long n, float* master, void* params_fp16, void* grads, int grad_flags, float* m, float* v,
-                                     unsigned* param_steps, float lr, float beta1, float beta2, float eps, float loss_scale,
-                                     rtxn_stream_t stream) {
-  RTXN_REQUIRE(n >= 0, "rtxn_adam_step_sparse: n = %ld", n);
-  RTXN_REQUIRE((grad_flags & ~3) == 0, "rtxn_adam_step_sparse: grad_flags = %d (RTXN_ADAM_GRADS_FP16 | RTXN_ADAM_ZERO_GRADS)", grad_flags);
-  RTXN_REQUIRE(loss_scale != 0.0f, "rtxn_adam_step_sparse: loss_scale = 0");
-  RTXN_DEVICE_OR_FAIL();
-  if (n == 0) return RTXN_OK;
-  RTXN_REQUIRE(master && params_fp16 && grads && m && v && param_steps, "rtxn_adam_step_sparse: NULL buffer");
-  const long blocks = (n / 4 + kThreads - 1) / kThreads;
-  const unsigned gridx = (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
-  hipStream_t st = rtxn::as_stream(stream);
-  const float ils = 1.0f / loss_scale;
-  RTXN_REQUIRE(beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f, "rtxn_adam_step_sparse: beta1 = %g, beta2 = %g outside (0, 1)", beta1, beta2);
-  const float l2b1 = (float)log2((double)beta1), l2b2 = (float)log2((double)beta2);
-  __half* p16 = static_cast<__half*>(params_fp16);
-  const bool half = grad_flags & RTXN_ADAM_GRADS_FP16, zero = grad_flags & RTXN_ADAM_ZERO_GRADS;
-  static decltype(&adam_sparse_kernel<false, false>) const table[2][2] = {{adam_sparse_kernel<false, false>, adam_sparse_kernel<false, true>},   // [HALF_GRADS][ZERO]
-                                                                          {adam_sparse_kernel<true, false>, adam_sparse_kernel<true, true>}};
-  table[half][zero]<<<gridx, kThreads, 0, st>>>(n, master, p16, grads, m, v, param_steps, lr, beta1, beta2, eps, ils, l2b1, l2b2);
-  RTXN_LAUNCH_CHECK("adam_sparse_kernel");
   return RTXN_OK;
 }
 
