@@ -271,15 +271,32 @@ def launch_volrender_backward_cuda(loss_values, loss_gradients, sampled_points_r
           "rtxn_volrender_bwd")
 
 
+def _byref(s):
+    return C.byref(s) if s is not None else None
+
+
+def _composite_train(who, args, structs):
+    """rtxn_<who>: the twelve arguments every training-compositor entry point begins with (`args`, in the order of
+    volrender_l2_train's), then the entry point's own structs (`structs`: background, loss, regularizer, scaler, as far as it
+    has them).  The loss's opacity buffer and the regulariser's tensors are sized here; the library checks the rest."""
+    (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels, loss_gradients, loss_sum,
+     radiance_gradients) = args
+    loss, regularizer = (tuple(structs) + (None, None, None))[1:3]
+    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
+        raise _lib.RtxnError(f"{who}: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
+    _check_regularizer(who, regularizer, batch_size, ray_hit.numel() // int(num_samples_per_hit))
+    check(getattr(_lib.lib(), "rtxn_" + who)(
+        _ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"), _ptr(num_hits, torch.int32, "num_hits"),
+        _ptr(indices, torch.int32, "indices"), batch_size, num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
+        _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"), _ptr(loss_sum, torch.float32, "loss_sum"),
+        _ptr(radiance_gradients, torch.float16, "radiance_gradients"), *[_byref(x) for x in structs], _stream()), "rtxn_" + who)
+
+
 def volrender_l2_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
                        loss_gradients, loss_sum, radiance_gradients):
     """launch_volrender_cuda + L2 loss->evaluate + launch_volrender_backward_cuda (main.cu:737-767) in one launch (VR_NERF)."""
-    check(_lib.lib().rtxn_volrender_l2_train(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
-                                             _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
-                                             num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
-                                             _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
-                                             _ptr(loss_sum, torch.float32, "loss_sum"), _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
-                                             _stream()), "rtxn_volrender_l2_train")
+    _composite_train("volrender_l2_train", (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
+                                            pixels, loss_gradients, loss_sum, radiance_gradients), ())
 
 
 BG_NONE, BG_CONSTANT, BG_RANDOM = 0, 1, 2   # enum rtxn_train_background_mode
@@ -312,13 +329,8 @@ def volrender_l2_train_ex(network_outputs, ray_hit, num_hits, indices, batch_siz
                           loss_gradients, loss_sum, radiance_gradients, background):
     """volrender_l2_train over a background (background: train_background(...) or None = the plain call): pixel = sum w c +
     (1 - A) bg, fitted to the (composited) target; exact gradients of that pixel."""
-    check(_lib.lib().rtxn_volrender_l2_train_ex(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
-                                                _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
-                                                num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
-                                                _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
-                                                _ptr(loss_sum, torch.float32, "loss_sum"), _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
-                                                C.byref(background) if background is not None else None, _stream()),
-          "rtxn_volrender_l2_train_ex")
+    _composite_train("volrender_l2_train_ex", (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
+                                               pixels, loss_gradients, loss_sum, radiance_gradients), (background,))
 
 
 LOSS_L2, LOSS_L1, LOSS_HUBER, LOSS_RELATIVE_L2 = 0, 1, 2, 3   # enum rtxn_loss_kind
@@ -341,21 +353,11 @@ def train_loss(kind="l2", param=None, opacity_weight=0.0, opacity=None):
     return s
 
 
-def _byref(s):
-    return C.byref(s) if s is not None else None
-
-
 def volrender_loss_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
                          loss_gradients, loss_sum, radiance_gradients, background=None, loss=None):
     """volrender_l2_train_ex with the loss of train_loss(...) (None, or plain "l2": that very call): the loss compositor."""
-    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
-        raise _lib.RtxnError(f"volrender_loss_train: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
-    check(_lib.lib().rtxn_volrender_loss_train(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
-                                               _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
-                                               num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
-                                               _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
-                                               _ptr(loss_sum, torch.float32, "loss_sum"), _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
-                                               _byref(background), _byref(loss), _stream()), "rtxn_volrender_loss_train")
+    _composite_train("volrender_loss_train", (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
+                                              pixels, loss_gradients, loss_sum, radiance_gradients), (background, loss))
 
 
 def train_regularizer(distortion_weight=0.0, t_start=None, t_end=None, distortion=None, depth=None):
@@ -390,15 +392,8 @@ def _check_regularizer(who, reg, n_rays, n_segments=None):
 def volrender_reg_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
                         loss_gradients, loss_sum, radiance_gradients, background=None, loss=None, regularizer=None):
     """volrender_loss_train with the regulariser of train_regularizer(...) (None, or weight 0 without outputs: that very call)."""
-    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
-        raise _lib.RtxnError(f"volrender_reg_train: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
-    _check_regularizer("volrender_reg_train", regularizer, batch_size, ray_hit.numel() // int(num_samples_per_hit))
-    check(_lib.lib().rtxn_volrender_reg_train(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
-                                              _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
-                                              num_samples_per_hit, _ptr(target, torch.float32, "target"), loss_scale,
-                                              _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
-                                              _ptr(loss_sum, torch.float32, "loss_sum"), _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
-                                              _byref(background), _byref(loss), _byref(regularizer), _stream()), "rtxn_volrender_reg_train")
+    _composite_train("volrender_reg_train", (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
+                                             pixels, loss_gradients, loss_sum, radiance_gradients), (background, loss, regularizer))
 
 
 # --------------------------------------------------------------------------- MLP
@@ -1231,17 +1226,8 @@ def volrender_scaled_train(network_outputs, ray_hit, num_hits, indices, batch_si
                            loss_gradients, loss_sum, radiance_gradients, background=None, loss=None, regularizer=None):
     """rtxn_volrender_scaled_train: volrender_reg_train reading the loss scale from the scaler's device word; always the loss
     compositor's kernels, plain L2 included."""
-    if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
-        raise _lib.RtxnError(f"volrender_scaled_train: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
-    _check_regularizer("volrender_scaled_train", regularizer, batch_size, ray_hit.numel() // int(num_samples_per_hit))
-    check(_lib.lib().rtxn_volrender_scaled_train(_ptr(network_outputs, torch.float32, "network_outputs"), _ptr(ray_hit, torch.float32, "ray_hit"),
-                                                 _ptr(num_hits, torch.int32, "num_hits"), _ptr(indices, torch.int32, "indices"), batch_size,
-                                                 num_samples_per_hit, _ptr(target, torch.float32, "target"), 0.0,
-                                                 _ptr(pixels, torch.float32, "pixels"), _ptr(loss_gradients, torch.float16, "loss_gradients"),
-                                                 _ptr(loss_sum, torch.float32, "loss_sum"),
-                                                 _ptr(radiance_gradients, torch.float16, "radiance_gradients"),
-                                                 _byref(background), _byref(loss), _byref(regularizer), C.byref(scaler), _stream()),
-          "rtxn_volrender_scaled_train")
+    _composite_train("volrender_scaled_train", (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, 0.0,
+                                                pixels, loss_gradients, loss_sum, radiance_gradients), (background, loss, regularizer, scaler))
 
 
 def deterministic_shadow(n_params, device="cuda"):
@@ -1285,38 +1271,27 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
     regularizer: train_regularizer(...) -> rtxn_train_gradients_reg (with or without any of the three);
     scaler: loss_scaler(...) -> rtxn_train_gradients_scaled (with or without any of the four; loss_scale is then not read)."""
     kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer", "scaler", "rays")}
-    if rays is not None:
-        if regularizer is not None:
-            _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
-        _check_ray_gradients("train_gradients", rays, n_rays, segment_capacity)
-        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
-        check(_lib.lib().rtxn_train_gradients_rays(C.byref(b), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
-                                                   _byref(scaler), C.byref(rays), _stream()), "rtxn_train_gradients_rays")
-    elif scaler is not None:
-        if regularizer is not None:
-            _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
-        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
-        check(_lib.lib().rtxn_train_gradients_scaled(C.byref(b), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
-                                                     C.byref(scaler), _stream()), "rtxn_train_gradients_scaled")
-    elif regularizer is not None:
-        _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
-        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
-        check(_lib.lib().rtxn_train_gradients_reg(C.byref(b), _byref(background), _jit(jitter), _byref(loss), C.byref(regularizer), _stream()),
-              "rtxn_train_gradients_reg")
-    elif loss is not None:
-        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
-        check(_lib.lib().rtxn_train_gradients_loss(C.byref(b), _byref(background), _jit(jitter), C.byref(loss), _stream()),
-              "rtxn_train_gradients_loss")
-    elif jitter is not None:
-        b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
-        check(_lib.lib().rtxn_train_gradients_jitter(C.byref(b), C.byref(background) if background is not None else None, _jit(jitter),
-                                                     _stream()), "rtxn_train_gradients_jitter")
-    elif background is None:
-        b = train_batch(**kw)
-        check(_lib.lib().rtxn_train_gradients(C.byref(b), _stream()), "rtxn_train_gradients")
-    else:
-        b = train_batch(**kw, target_channels=background.target_channels)
-        check(_lib.lib().rtxn_train_gradients_ex(C.byref(b), C.byref(background), _stream()), "rtxn_train_gradients_ex")
+    _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
+    _check_ray_gradients("train_gradients", rays, n_rays, segment_capacity)
+    b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
+    options = (background, jitter, loss, regularizer, scaler, rays)
+    name, n_options = _ladder_entry("rtxn_train_gradients", _GRADIENTS_LADDER, options)
+    check(getattr(_lib.lib(), name)(C.byref(b), *map(_byref, options[:n_options]), _stream()), name)
+
+
+# The rungs of the step and gradients ladders (include/rtxn.h; DESIGN 5.17), topmost first: (suffix, how many of the options
+# (background, jitter, loss, regularizer, ...) the rung takes, which of them select it).  The call goes to the topmost rung one of
+# whose own options is given: the lowest entry point that takes everything that is.
+_STEP_LADDER = (("_rays", 9, (7, 8)), ("_ema", 7, (6,)), ("_scaled", 6, (5,)), ("_opt", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)),
+                ("_jitter", 2, (1,)), ("_ex", 1, (0,)), ("", 0, ()))
+_GRADIENTS_LADDER = (("_rays", 6, (5,)), ("_scaled", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)), ("_jitter", 2, (1,)), ("_ex", 1, (0,)),
+                     ("", 0, ()))
+
+
+def _ladder_entry(prefix, ladder, options):
+    for suffix, n_options, own in ladder:
+        if not own or any(options[i] is not None for i in own):
+            return prefix + suffix, n_options
 
 
 def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_points, seg_view, num_stored, indices,
@@ -1376,43 +1351,11 @@ def train_step(args, background=None, jitter=None, loss=None, regularizer=None, 
     rays: ray_gradients(...), pose: pose_refinement(...) -> rtxn_train_step_rays (with or without any of the seven; pose needs rays):
     the write pass stores t_start / t_end into rays' buffers, the ray gradients are formed behind the table scatter and the pose
     gradient and step run behind the optimizer."""
-    if rays is not None or pose is not None:
-        if regularizer is not None:
-            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
-        if rays is not None:
-            _check_ray_gradients("train_step", rays, args.batch.n_rays, args.batch.segment_capacity)
-        check(_lib.lib().rtxn_train_step_rays(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
-                                              _byref(optimizer), _byref(scaler), _byref(ema), _byref(rays), _byref(pose), _stream()),
-              "rtxn_train_step_rays")
-    elif ema is not None:
-        if regularizer is not None:
-            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
-        check(_lib.lib().rtxn_train_step_ema(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
-                                             _byref(optimizer), _byref(scaler), C.byref(ema), _stream()), "rtxn_train_step_ema")
-    elif scaler is not None:
-        if regularizer is not None:
-            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
-        check(_lib.lib().rtxn_train_step_scaled(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
-                                                _byref(optimizer), C.byref(scaler), _stream()), "rtxn_train_step_scaled")
-    elif optimizer is not None:
-        if regularizer is not None:
-            _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
-        check(_lib.lib().rtxn_train_step_opt(C.byref(args), _byref(background), _jit(jitter), _byref(loss), _byref(regularizer),
-                                             C.byref(optimizer), _stream()), "rtxn_train_step_opt")
-    elif regularizer is not None:
-        _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
-        check(_lib.lib().rtxn_train_step_reg(C.byref(args), _byref(background), _jit(jitter), _byref(loss), C.byref(regularizer), _stream()),
-              "rtxn_train_step_reg")
-    elif loss is not None:
-        check(_lib.lib().rtxn_train_step_loss(C.byref(args), _byref(background), _jit(jitter), C.byref(loss), _stream()),
-              "rtxn_train_step_loss")
-    elif jitter is not None:
-        check(_lib.lib().rtxn_train_step_jitter(C.byref(args), C.byref(background) if background is not None else None, _jit(jitter),
-                                                _stream()), "rtxn_train_step_jitter")
-    elif background is None:
-        check(_lib.lib().rtxn_train_step(C.byref(args), _stream()), "rtxn_train_step")
-    else:
-        check(_lib.lib().rtxn_train_step_ex(C.byref(args), C.byref(background), _stream()), "rtxn_train_step_ex")
+    _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
+    _check_ray_gradients("train_step", rays, args.batch.n_rays, args.batch.segment_capacity)
+    options = (background, jitter, loss, regularizer, optimizer, scaler, ema, rays, pose)
+    name, n_options = _ladder_entry("rtxn_train_step", _STEP_LADDER, options)
+    check(getattr(_lib.lib(), name)(C.byref(args), *map(_byref, options[:n_options]), _stream()), name)
 
 
 def half2_workspace(values, block_entries):

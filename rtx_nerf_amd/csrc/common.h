@@ -100,6 +100,57 @@ int check_ray_gradients(const char* who, const rtxn_ray_gradients* rays, const r
 // carry its device buffers.
 int check_pose_refinement(const rtxn_pose_refinement* pose, const char* who, bool need_buffers);
 
+// The option structs of the training entry ladders (rtxn_train_step*, rtxn_train_gradients*), library-internal: a
+// public entry point fills the pointers its signature has and leaves the rest NULL.  check_train_options replaces every
+// inactive struct by NULL; own_bg / own_jitter hold a step's copies of a RANDOM background or a jitter without a counter.
+struct TrainOptions {
+  const rtxn_train_background* bg = nullptr;
+  const rtxn_sample_jitter* jitter = nullptr;
+  const rtxn_train_loss* loss = nullptr;
+  const rtxn_train_regularizer* reg = nullptr;
+  const rtxn_optimizer_options* opt = nullptr;
+  const rtxn_loss_scaler* scaler = nullptr;
+  const rtxn_weight_ema* ema = nullptr;
+  const rtxn_ray_gradients* rays = nullptr;
+  const rtxn_pose_refinement* pose = nullptr;
+  rtxn_train_background own_bg;
+  rtxn_sample_jitter own_jitter;
+};
+// the rungs of both ladders, in the order they were added (the gradients ladder has no _opt and no _ema)
+enum TrainRung { RUNG_PLAIN, RUNG_EX, RUNG_JITTER, RUNG_LOSS, RUNG_REG, RUNG_OPT, RUNG_SCALED, RUNG_EMA, RUNG_RAYS };
+// The one checked path of both ladders, host only, trainer.hip: every struct's rules once, in one order, under the name the
+// rung reports under (the name rule of DESIGN 5.17); then inactive structs become NULL and a step (a: its arguments, b unused)
+// gets its own copies.  A gradients call passes a = NULL and its batch.
+__attribute__((visibility("hidden"))) int check_train_options(TrainRung rung, bool step, const rtxn_train_step_args* a,
+                                                              const rtxn_train_batch* b, TrainOptions* o);
+// rtxn_train_gradients under CHECKED options (train.hip): what every rung of the gradients ladder and the one-call step run
+__attribute__((visibility("hidden"))) int train_gradients(const rtxn_train_batch* b, const TrainOptions& o, rtxn_stream_t stream);
+
+// The buffers of a training-compositor call, in the order of rtxn_volrender_l2_train's arguments
+struct CompositeArgs {
+  const float* network_outputs;
+  const float* ray_hit;
+  const int* num_hits;
+  const int* indices;
+  int batch_size, num_samples_per_hit;
+  const float* target;
+  float loss_scale;
+  float* pixels;
+  void* loss_gradients_half;
+  float* loss_sum;
+  void* radiance_gradients;
+};
+// The one RTXN_VR_NERF training compositor under the five rtxn_volrender_*_train entry points and rtxn_train_gradients
+// (composite_train.hip): the structs' rules under `who`, then the kernel their active set selects -- nothing active: the plain
+// volrender_l2_fused kernels, a background alone: volrender_l2_bg, else composite_train's, the DEV ones with scale_dev (the
+// scaler's device word, read instead of c.loss_scale).  The shared checks report under the entry point that introduced the
+// topmost active struct, under `who` with scale_dev.
+__attribute__((visibility("hidden"))) int composite_train(const char* who, const CompositeArgs& c, const rtxn_train_background* bg,
+                                                          const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
+                                                          const float* scale_dev, rtxn_stream_t stream);
+// ... and the launcher of the first two (volrender.hip, whose kernels they are); bg: ACTIVE or NULL
+__attribute__((visibility("hidden"))) int l2_train(const char* who, const CompositeArgs& c, const rtxn_train_background* bg, rtxn_stream_t stream);
+
 }  // namespace rtxn
 
 #define RTXN_HIP(expr)                                          \

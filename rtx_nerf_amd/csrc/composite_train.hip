@@ -405,14 +405,11 @@ __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4
   }
 }
 
-// rtxn_volrender_loss_train (reg_entry = false, reg = NULL) and rtxn_volrender_reg_train.  An inactive struct falls through to
-// the entry point without it -- reg -> loss -> rtxn_volrender_l2_train_ex -- which is then exactly what runs.
-// scale_dev (rtxn_volrender_scaled_train): the device word the DEV instantiations read instead of loss_scale; nothing falls
-// through then, plain L2 is one of loss_term's kinds.
-int composite_train(const char* who, bool reg_entry, const float* network_outputs, const float* ray_hit, const int* num_hits,
-                    const int* indices, int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
-                    void* loss_gradients_half, float* loss_sum, void* radiance_gradients, const rtxn_train_background* bg,
-                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const float* scale_dev, rtxn_stream_t stream) {
+}  // namespace
+
+// The one RTXN_VR_NERF training compositor (common.h): the five rtxn_volrender_*_train entry points and rtxn_train_gradients.
+int rtxn::composite_train(const char* who, const rtxn::CompositeArgs& c, const rtxn_train_background* bg, const rtxn_train_loss* loss,
+                          const rtxn_train_regularizer* reg, const float* scale_dev, rtxn_stream_t stream) {
   bool bg_active = false, loss_active = false, reg_active = false;
   int rc = rtxn::check_train_background(bg, RTXN_VR_NERF, who, &bg_active);
   if (rc != RTXN_OK) return rc;
@@ -420,57 +417,56 @@ int composite_train(const char* who, bool reg_entry, const float* network_output
   if (rc != RTXN_OK) return rc;
   rc = rtxn::check_train_regularizer(reg, RTXN_VR_NERF, -1, who, &reg_active);
   if (rc != RTXN_OK) return rc;
-  if (!scale_dev && reg_entry && !reg_active)
-    return rtxn_volrender_loss_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
-                                     loss_gradients_half, loss_sum, radiance_gradients, bg, loss, stream);
-  if (!scale_dev && !reg_entry && !loss_active)
-    return rtxn_volrender_l2_train_ex(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
-                                      loss_gradients_half, loss_sum, radiance_gradients, bg, stream);
+  if (!bg_active) bg = nullptr;
+  if (!loss_active) loss = nullptr;
+  if (!reg_active) reg = nullptr;
+  // An inactive struct runs exactly what the entry point without it runs, under that entry point's name.  With scale_dev nothing
+  // falls through: plain L2 is one of loss_term's kinds.
+  if (!scale_dev) {
+    if (!reg && !loss) return rtxn::l2_train(bg ? "rtxn_volrender_l2_train_ex" : "rtxn_volrender_l2_train", c, bg, stream);
+    who = reg ? "rtxn_volrender_reg_train" : "rtxn_volrender_loss_train";
+  }
+  const int batch_size = c.batch_size, num_samples_per_hit = c.num_samples_per_hit;
   RTXN_REQUIRE(batch_size >= 0, "%s: batch_size = %d < 0", who, batch_size);
   RTXN_REQUIRE(num_samples_per_hit > 0, "%s: num_samples_per_hit = %d", who, num_samples_per_hit);
   // deterministic mode: the kernels get no loss pointer (their sum is float atomics); loss.hip sums behind them
-  const bool det_loss = loss_sum && batch_size > 0 && rtxn::deterministic_mode();
-  RTXN_REQUIRE(!(det_loss && loss_active && loss->opacity_weight > 0.0f && !loss->opacity),
+  const bool det_loss = c.loss_sum && batch_size > 0 && rtxn::deterministic_mode();
+  RTXN_REQUIRE(!(det_loss && loss && loss->opacity_weight > 0.0f && !loss->opacity),
                "%s: loss->opacity is NULL: in deterministic mode the alpha term of the loss is summed from the opacities the compositor writes there",
                who);
-  RTXN_REQUIRE(!(det_loss && reg_active && reg->distortion_weight > 0.0f && !reg->distortion),
+  RTXN_REQUIRE(!(det_loss && reg && reg->distortion_weight > 0.0f && !reg->distortion),
                "%s: reg->distortion is NULL: in deterministic mode the distortion term of the loss is summed from the L_r the compositor writes there",
                who);
   RTXN_DEVICE_OR_FAIL();
   hipStream_t s = rtxn::as_stream(stream);
-  if (loss_sum && !det_loss) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
+  if (c.loss_sum && !det_loss) RTXN_HIP(rtxn::zero_words(c.loss_sum, 1, s));
   if (batch_size == 0) return RTXN_OK;
-  RTXN_REQUIRE(network_outputs && ray_hit && num_hits && indices && target && pixels && radiance_gradients, "%s: NULL buffer", who);
-  RTXN_REQUIRE(((uintptr_t)network_outputs & 15) == 0 && ((uintptr_t)radiance_gradients & 7) == 0,
+  RTXN_REQUIRE(c.network_outputs && c.ray_hit && c.num_hits && c.indices && c.target && c.pixels && c.radiance_gradients, "%s: NULL buffer", who);
+  RTXN_REQUIRE(((uintptr_t)c.network_outputs & 15) == 0 && ((uintptr_t)c.radiance_gradients & 7) == 0,
                "%s: radiance must be 16-byte and gradients 8-byte aligned", who);
-  if (!bg_active) bg = nullptr;
-  if (!loss_active) loss = nullptr;
-  if (!reg_active) reg = nullptr;
   const BgArgs a = make_bg_args(bg);
-  const LossArgs la = make_loss_args(loss, bg_active);
-  const RegArgs ra = make_reg_args(reg, loss_scale, batch_size);
+  const LossArgs la = make_loss_args(loss, bg != nullptr);
+  const RegArgs ra = make_reg_args(reg, c.loss_scale, batch_size);
   // 512 samples per step, two per lane: an even K, 8-byte-aligned step lengths and 16-byte-aligned gradients
-  const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)ray_hit & 7) == 0 && ((uintptr_t)radiance_gradients & 15) == 0;
+  const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)c.ray_hit & 7) == 0 && ((uintptr_t)c.radiance_gradients & 15) == 0;
   const dim3 grid((batch_size + 3) / 4), block(256);
-  const float4* const rad = reinterpret_cast<const float4*>(network_outputs);
-  __half* const lg = static_cast<__half*>(loss_gradients_half);
-  float* const ls = det_loss ? nullptr : loss_sum;
-  half4* const rg = static_cast<half4*>(radiance_gradients);
+  const float4* const rad = reinterpret_cast<const float4*>(c.network_outputs);
+  __half* const lg = static_cast<__half*>(c.loss_gradients_half);
+  float* const ls = det_loss ? nullptr : c.loss_sum;
+  half4* const rg = static_cast<half4*>(c.radiance_gradients);
   if (scale_dev) {
-    auto* const kernel = reg_active ? (pairs ? composite_train_multi_kernel<true, 4, true> : composite_train_kernel<true, true>)
-                                    : (pairs ? composite_train_multi_kernel<false, 4, true> : composite_train_kernel<false, true>);
-    kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, scale_dev, pixels, lg, ls, rg, a, la, ra);
+    auto* const kernel = reg ? (pairs ? composite_train_multi_kernel<true, 4, true> : composite_train_kernel<true, true>)
+                             : (pairs ? composite_train_multi_kernel<false, 4, true> : composite_train_kernel<false, true>);
+    kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, num_samples_per_hit, c.target, scale_dev, c.pixels, lg, ls, rg, a, la, ra);
   } else {
-    auto* const kernel = reg_active ? (pairs ? composite_train_multi_kernel<true, 4, false> : composite_train_kernel<true, false>)
-                                    : (pairs ? composite_train_multi_kernel<false, 4, false> : composite_train_kernel<false, false>);
-    kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels, lg, ls, rg, a, la, ra);
+    auto* const kernel = reg ? (pairs ? composite_train_multi_kernel<true, 4, false> : composite_train_kernel<true, false>)
+                             : (pairs ? composite_train_multi_kernel<false, 4, false> : composite_train_kernel<false, false>);
+    kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, num_samples_per_hit, c.target, c.loss_scale, c.pixels, lg, ls, rg, a, la, ra);
   }
   RTXN_LAUNCH_CHECK("composite_train_kernel");
-  if (det_loss) return rtxn::loss_fixed_order(pixels, target, batch_size, bg, loss, reg, loss_sum, s);
+  if (det_loss) return rtxn::loss_fixed_order(c.pixels, c.target, batch_size, bg, loss, reg, c.loss_sum, s);
   return RTXN_OK;
 }
-
-}  // namespace
 
 int rtxn::check_train_loss(const rtxn_train_loss* loss, int target_channels, int vr_mode, const char* who, bool* active) {
   *active = false;
@@ -519,8 +515,8 @@ extern "C" int rtxn_volrender_loss_train(const float* network_outputs, const flo
                                          int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
                                          void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
                                          const rtxn_train_background* bg, const rtxn_train_loss* loss, rtxn_stream_t stream) {
-  return composite_train("rtxn_volrender_loss_train", false, network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
-                         loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, bg, loss, nullptr, nullptr, stream);
+  return rtxn::composite_train("rtxn_volrender_loss_train", {network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
+                               loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients}, bg, loss, nullptr, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_reg_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
@@ -528,22 +524,22 @@ extern "C" int rtxn_volrender_reg_train(const float* network_outputs, const floa
                                         void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
                                         const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
                                         rtxn_stream_t stream) {
-  return composite_train("rtxn_volrender_reg_train", true, network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
-                         loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, bg, loss, reg, nullptr, stream);
+  return rtxn::composite_train("rtxn_volrender_reg_train", {network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
+                               loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients}, bg, loss, reg, nullptr, stream);
 }
 
-// the loss scale read from the scaler's device word; scaler == NULL: rtxn_volrender_reg_train
+// the loss scale read from the scaler's device word (loss_scale is not read); scaler == NULL: rtxn_volrender_reg_train
 extern "C" int rtxn_volrender_scaled_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
                                            int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
                                            void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
                                            const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
                                            const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
-  const char* who = "rtxn_volrender_scaled_train";
-  if (!scaler)
-    return rtxn_volrender_reg_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
-                                    loss_gradients_half, loss_sum, radiance_gradients, bg, loss, reg, stream);
-  const int rc = rtxn::check_loss_scaler(scaler, who, true);
-  if (rc != RTXN_OK) return rc;
-  return composite_train(who, true, network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, 0.0f, pixels,
-                         loss_gradients_half, loss_sum, radiance_gradients, bg, loss, reg, &scaler->state->scale, stream);
+  const char* who = scaler ? "rtxn_volrender_scaled_train" : "rtxn_volrender_reg_train";
+  if (scaler) {
+    const int rc = rtxn::check_loss_scaler(scaler, who, true);
+    if (rc != RTXN_OK) return rc;
+  }
+  return rtxn::composite_train(who, {network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
+                               scaler ? 0.0f : loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients}, bg, loss, reg,
+                               scaler ? &scaler->state->scale : nullptr, stream);
 }

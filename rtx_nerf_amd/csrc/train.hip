@@ -3994,10 +3994,16 @@ int rtxn::check_ray_gradients(const char* who, const rtxn_ray_gradients* rays, c
 }
 
 // ------------------------------------------------------------------------- a whole batch, segment count on the device
+// o: CHECKED options (rtxn::check_train_options): every struct ACTIVE or NULL; opt, ema and pose are the step's, not read here.
 // scaler (rtxn_train_gradients_scaled): the compositor reads the loss scale from its device word, b->loss_scale is not read
-static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                                const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
-                                rtxn_stream_t stream, const rtxn_ray_gradients* rays = nullptr) {
+int rtxn::train_gradients(const rtxn_train_batch* b, const rtxn::TrainOptions& o, rtxn_stream_t stream) {
+  const rtxn_sample_jitter* const jitter = o.jitter;
+  const rtxn_train_loss* const loss = o.loss;
+  const rtxn_loss_scaler* const scaler = o.scaler;
+  const rtxn_ray_gradients* const rays = o.rays;
+  if (rays)                                                    // a step finds this behind its own checks and its traversal, as it always did
+    RTXN_REQUIRE(scaler || (b->loss_scale > 0.0f && std::isfinite(b->loss_scale)),
+                 "rtxn_train_gradients_rays: batch.loss_scale = %g (ray gradients are unscaled by it)", (double)b->loss_scale);
   RTXN_REQUIRE(b && b->mlp, "rtxn_train_gradients: NULL batch or model");
   const rtxn_mlp* m = b->mlp;
   int rc = check_train(m, "rtxn_train_gradients");
@@ -4060,19 +4066,11 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   rc = train_forward_impl(m, fused ? nullptr : b->encT, cap_samples, b->workspace, b->output_half, b->radiance, dc, stream, fwd);
   if (rc != RTXN_OK) return rc;
   // launch_volrender_cuda, loss->evaluate, launch_volrender_backward_cuda (main.cu:737-767): per ray, no sample count needed
-  if (scaler) {                                                // vr_mode is RTXN_VR_NERF: the entry point saw to that
-    rc = rtxn_volrender_scaled_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, 0.0f, b->pixels,
-                                     b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, loss, reg, scaler, stream);
-    if (rc != RTXN_OK) return rc;
-  } else if (b->vr_mode == RTXN_VR_NERF) {
-    rc = reg  ? rtxn_volrender_reg_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
-                                         b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, loss, reg, stream)
-       : loss ? rtxn_volrender_loss_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
-                                          b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, loss, stream)
-         : bg ? rtxn_volrender_l2_train_ex(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale,
-                                         b->pixels, b->loss_gradients_half, b->loss_sum, b->radiance_gradients, bg, stream)
-            : rtxn_volrender_l2_train(b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, b->loss_scale, b->pixels,
-                                      b->loss_gradients_half, b->loss_sum, b->radiance_gradients, stream);
+  if (b->vr_mode == RTXN_VR_NERF) {                            // with a scaler always: the checked path saw to that
+    rc = rtxn::composite_train(scaler ? "rtxn_volrender_scaled_train" : "rtxn_volrender_reg_train",
+                               {b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, scaler ? 0.0f : b->loss_scale, b->pixels,
+                                b->loss_gradients_half, b->loss_sum, b->radiance_gradients},
+                               o.bg, loss, o.reg, scaler ? &scaler->state->scale : nullptr, stream);
     if (rc != RTXN_OK) return rc;
   } else {
     rc = rtxn_volrender_fwd(nullptr, b->radiance, b->num_stored, b->indices, b->t_vals, b->n_rays, 32, b->pixels, b->vr_mode, stream);
@@ -4121,92 +4119,47 @@ static int train_gradients_impl(const rtxn_train_batch* b, const rtxn_train_back
   return rc;
 }
 
-extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return train_gradients_impl(b, nullptr, nullptr, nullptr, nullptr, nullptr, stream); }
-
-// over a background: the one difference is the compositor (rtxn_volrender_l2_train_ex); NULL / NONE + 3 channels: the plain call
-extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
-  RTXN_REQUIRE(b, "rtxn_train_gradients_ex: NULL batch");
-  bool active = false;
-  const int rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_ex", &active);
-  if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+// ---- the gradients ladder (include/rtxn.h): every rung fills the option set its signature has and takes the one checked path
+// (rtxn::check_train_options, trainer.hip); what is NULL or switched off runs exactly what the rung without it runs.
+// _ex: over a background (the compositor is the one difference); _jitter: the sampler's jitter (RTXN_SAMPLING_JITTER_WORLD);
+// _loss: the loss of rtxn_train_loss (RTXN_VR_NERF: in the compositor, RTXN_VR_COMPAT: rtxn_loss between the two compositor
+// launches); _reg: the distortion regulariser; _scaled: the loss scale from the scaler's device word, the RTXN_VR_NERF compositor
+// alone; _rays: behind the table scatter, the gather rtxn_hashgrid_input_gradient_segments over the batch's dencT and live list
+// and the per-ray reduction.
+static int gradients_entry(rtxn::TrainRung rung, const rtxn_train_batch* b, rtxn::TrainOptions o, rtxn_stream_t stream) {
+  const int rc = rtxn::check_train_options(rung, false, nullptr, b, &o);
+  return rc != RTXN_OK ? rc : rtxn::train_gradients(b, o, stream);
 }
 
-// ... and with the sampler's jitter (RTXN_SAMPLING_JITTER_WORLD): both optional, NULL + NULL is rtxn_train_gradients
+extern "C" int rtxn_train_gradients(const rtxn_train_batch* b, rtxn_stream_t stream) { return gradients_entry(rtxn::RUNG_PLAIN, b, {}, stream); }
+
+extern "C" int rtxn_train_gradients_ex(const rtxn_train_batch* b, const rtxn_train_background* bg, rtxn_stream_t stream) {
+  return gradients_entry(rtxn::RUNG_EX, b, {bg}, stream);
+}
+
 extern "C" int rtxn_train_gradients_jitter(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                            rtxn_stream_t stream) {
-  RTXN_REQUIRE(b, "rtxn_train_gradients_jitter: NULL batch");
-  int rc = rtxn::check_sample_jitter("rtxn_train_gradients_jitter", b->sample_type, jitter, b->vr_mode);
-  if (rc != RTXN_OK) return rc;
-  bool active = false;
-  rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_jitter", &active);
-  if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, nullptr, nullptr, nullptr, stream);
+  return gradients_entry(rtxn::RUNG_JITTER, b, {bg, jitter}, stream);
 }
 
-// ... and with the loss of rtxn_train_loss: the compositor (RTXN_VR_NERF: rtxn_volrender_loss_train) or the loss launch between
-// the two compositor launches (RTXN_VR_COMPAT: rtxn_loss) is the one difference; NULL, or plain L2: rtxn_train_gradients_jitter
 extern "C" int rtxn_train_gradients_loss(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                          const rtxn_train_loss* loss, rtxn_stream_t stream) {
-  RTXN_REQUIRE(b, "rtxn_train_gradients_loss: NULL batch");
-  int rc = rtxn::check_sample_jitter("rtxn_train_gradients_loss", b->sample_type, jitter, b->vr_mode);
-  if (rc != RTXN_OK) return rc;
-  bool active = false, loss_active = false;
-  rc = rtxn::check_train_background(bg, b->vr_mode, "rtxn_train_gradients_loss", &active);
-  if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, b->vr_mode, "rtxn_train_gradients_loss", &loss_active);
-  if (rc != RTXN_OK) return rc;
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, nullptr, nullptr, stream);
-}
-
-// ... and with the distortion regulariser (rtxn_train_regularizer): the compositor (rtxn_volrender_reg_train) is the one
-// difference; NULL, or weight 0 without outputs: rtxn_train_gradients_loss
-// rtxn_train_gradients_reg and rtxn_train_gradients_scaled: with the scaler (rtxn_loss_scaler, optimizer.hip) the compositor
-// is rtxn_volrender_scaled_train, the RTXN_VR_NERF one alone
-static int train_gradients_reg(const char* who, const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                               const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
-                               rtxn_stream_t stream, const rtxn_ray_gradients* rays = nullptr) {
-  RTXN_REQUIRE(b, "%s: NULL batch", who);
-  int rc = rtxn::check_sample_jitter(who, b->sample_type, jitter, b->vr_mode);
-  if (rc != RTXN_OK) return rc;
-  bool active = false, loss_active = false, reg_active = false;
-  rc = rtxn::check_train_background(bg, b->vr_mode, who, &active);
-  if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, b->vr_mode, who, &loss_active);
-  if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_regularizer(reg, b->vr_mode, b->sample_type, who, &reg_active);
-  if (rc != RTXN_OK) return rc;
-  if (scaler) {
-    rc = rtxn::check_loss_scaler(scaler, who, true);
-    if (rc != RTXN_OK) return rc;
-    RTXN_REQUIRE(b->vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor, which reads the scale from device memory "
-                 "(vr_mode = %d: the three-launch route takes it by value)", who, b->vr_mode);
-  }
-  if (rays) {
-    rc = rtxn::check_ray_gradients(who, rays, b, reg_active ? reg : nullptr);
-    if (rc != RTXN_OK) return rc;
-    RTXN_REQUIRE(scaler || (b->loss_scale > 0.0f && std::isfinite(b->loss_scale)), "%s: batch.loss_scale = %g (ray gradients are unscaled by it)",
-                 who, (double)b->loss_scale);
-  }
-  return train_gradients_impl(b, active ? bg : nullptr, jitter, loss_active ? loss : nullptr, reg_active ? reg : nullptr, scaler, stream, rays);
+  return gradients_entry(rtxn::RUNG_LOSS, b, {bg, jitter, loss}, stream);
 }
 
 extern "C" int rtxn_train_gradients_reg(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                         const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
-  return train_gradients_reg("rtxn_train_gradients_reg", b, bg, jitter, loss, reg, nullptr, stream);
+  return gradients_entry(rtxn::RUNG_REG, b, {bg, jitter, loss, reg}, stream);
 }
 
 extern "C" int rtxn_train_gradients_scaled(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                            const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
                                            rtxn_stream_t stream) {
-  return train_gradients_reg(scaler ? "rtxn_train_gradients_scaled" : "rtxn_train_gradients_reg", b, bg, jitter, loss, reg, scaler, stream);
+  return gradients_entry(rtxn::RUNG_SCALED, b, {bg, jitter, loss, reg, nullptr, scaler}, stream);
 }
 
-// ... and with the ray gradients (rtxn_ray_gradients): behind the table scatter, the gather rtxn_hashgrid_input_gradient_segments
-// over the batch's dencT and live list and the per-ray reduction; rays == NULL: exactly rtxn_train_gradients_scaled
 extern "C" int rtxn_train_gradients_rays(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                          const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
                                          const rtxn_ray_gradients* rays, rtxn_stream_t stream) {
-  if (!rays) return rtxn_train_gradients_scaled(b, bg, jitter, loss, reg, scaler, stream);
-  return train_gradients_reg("rtxn_train_gradients_rays", b, bg, jitter, loss, reg, scaler, stream, rays);
+  return gradients_entry(rtxn::RUNG_RAYS, b, {bg, jitter, loss, reg, nullptr, scaler, nullptr, rays}, stream);
 }

@@ -121,15 +121,113 @@ static int optimizer_step(const rtxn_train_step_args* a, const rtxn_optimizer_op
   return RTXN_OK;
 }
 
-// opt: ACTIVE optimizer options (rtxn_train_step_opt, optimizer.hip) or NULL; scaler: the loss scaler (with opt) or NULL;
-// ema: the weight EMA (with opt, active or not) or NULL
-static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
-                           const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream,
-                           const rtxn_ray_gradients* rays = nullptr, const rtxn_pose_refinement* pose = nullptr) {
-  RTXN_REQUIRE(a, "rtxn_train_step: NULL arguments");
+// ---- the one checked path of the step and gradients ladders (common.h) ----------------------------------------------
+
+// The name rule: a rung reports under its own name while it holds a struct of its own -- _rays: rays or pose, _ema: the EMA,
+// _scaled: the scaler, _opt: options (have_opt: present for the options' own check, ACTIVE from then on) -- and is the rung below
+// otherwise; _reg and the rungs below it always report under their own name.
+static const char* entry_name(bool step, int rung, const rtxn::TrainOptions& o, bool have_opt) {
+  static const char* const kStep[] = {"rtxn_train_step", "rtxn_train_step_ex", "rtxn_train_step_jitter", "rtxn_train_step_loss", "rtxn_train_step_reg",
+                                      "rtxn_train_step_opt", "rtxn_train_step_scaled", "rtxn_train_step_ema", "rtxn_train_step_rays"};
+  static const char* const kGradients[] = {"rtxn_train_gradients", "rtxn_train_gradients_ex", "rtxn_train_gradients_jitter", "rtxn_train_gradients_loss",
+                                           "rtxn_train_gradients_reg", nullptr, "rtxn_train_gradients_scaled", nullptr, "rtxn_train_gradients_rays"};
+  if (rung == rtxn::RUNG_RAYS && !o.rays && !o.pose) rung = rtxn::RUNG_EMA;
+  if (rung == rtxn::RUNG_EMA && !o.ema) rung = rtxn::RUNG_SCALED;
+  if (rung == rtxn::RUNG_SCALED && !o.scaler) rung = rtxn::RUNG_OPT;
+  if (rung == rtxn::RUNG_OPT && !have_opt) rung = rtxn::RUNG_REG;
+  return (step ? kStep : kGradients)[rung];
+}
+
+// The order: the options (under the name they are present with), then NULL arguments, the EMA's and the scaler's requirements of
+// the options, then jitter, background, loss, regulariser, scaler, rays, pose.  A rung checks what its signature has: the rungs
+// below _jitter leave a missing jitter to rtxn_train_gradients, as they always did.
+int rtxn::check_train_options(rtxn::TrainRung rung, bool step, const rtxn_train_step_args* a, const rtxn_train_batch* b, rtxn::TrainOptions* o) {
+  bool opt_active = false;
+  int rc = rtxn::check_optimizer_options(o->opt, entry_name(step, rung, *o, o->opt != nullptr), true, &opt_active);
+  if (rc != RTXN_OK) return rc;
+  const char* const who = entry_name(step, rung, *o, opt_active);
+  if (step) {
+    RTXN_REQUIRE(a, "%s: NULL arguments", who);
+    b = &a->batch;
+  }
+  if (rung == rtxn::RUNG_PLAIN) return RTXN_OK;                // no struct; a NULL batch: rtxn_train_gradients' own message
+  RTXN_REQUIRE(b, "%s: NULL batch", who);
+  if (o->ema) {
+    rc = rtxn_weight_ema_check(o->ema);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(o->ema->state && o->ema->mlp_ema, "%s: ema->state = %p, ema->mlp_ema = %p", who, (void*)o->ema->state, (void*)o->ema->mlp_ema);
+    RTXN_REQUIRE(!b->grid || (o->ema->table_ema && o->ema->table_stamps),
+                 "%s: a hash grid needs ema->table_ema and ema->table_stamps (this call steps the table by the sparse rule)", who);
+    RTXN_REQUIRE(o->opt && o->opt->lr_factor && (!o->opt->skip_nonfinite || o->opt->guard),
+                 "%s: the weight EMA needs options that carry lr_factor (and guard with skip_nonfinite), with or without anything switched on", who);
+  }
+  if (o->scaler) {
+    rc = rtxn::check_loss_scaler(o->scaler, who, true);
+    if (rc != RTXN_OK) return rc;
+    if (step)
+      RTXN_REQUIRE(o->opt && o->opt->skip_nonfinite && o->opt->guard && o->opt->lr_factor,
+                   "%s: the loss scaler needs options with skip_nonfinite, guard and lr_factor: dynamic scaling implies the non-finite guard", who);
+  }
+  if (rung >= rtxn::RUNG_JITTER) {
+    rc = rtxn::check_sample_jitter(who, b->sample_type, o->jitter, b->vr_mode);
+    if (rc != RTXN_OK) return rc;
+  }
+  bool bg_active = false, loss_active = false, reg_active = false;
+  rc = rtxn::check_train_background(o->bg, b->vr_mode, who, &bg_active);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn::check_train_loss(o->loss, bg_active ? o->bg->target_channels : 3, b->vr_mode, who, &loss_active);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn::check_train_regularizer(o->reg, b->vr_mode, b->sample_type, who, &reg_active);
+  if (rc != RTXN_OK) return rc;
+  if (step && reg_active)
+    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the regulariser's t_start / t_end are written by the "
+                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
+  if (o->scaler) {
+    if (step)
+      RTXN_REQUIRE(b->vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor (batch.vr_mode = %d)", who, b->vr_mode);
+    else
+      RTXN_REQUIRE(b->vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor, which reads the scale from device memory "
+                   "(vr_mode = %d: the three-launch route takes it by value)", who, b->vr_mode);
+  }
+  if (!bg_active) o->bg = nullptr;
+  if (!loss_active) o->loss = nullptr;
+  if (!reg_active) o->reg = nullptr;
+  if (!o->ema && !opt_active) o->opt = nullptr;                // the EMA's step goes through the rate kernel, switched on or not
+  if (o->rays) {
+    rc = rtxn::check_ray_gradients(who, o->rays, b, o->reg);
+    if (rc != RTXN_OK) return rc;
+    if (step)
+      RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the ray gradients' t_start / t_end are written by the "
+                   "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
+  }
+  if (o->pose) {
+    RTXN_REQUIRE(o->rays, "%s: pose without rays: the pose gradient is formed from the ray gradients", who);
+    rc = rtxn::check_pose_refinement(o->pose, who, true);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(o->pose->drawn && a->trace.rays_d, "%s: pose->drawn = %p, trace.rays_d = %p: the pose gradient reads (image, pixel) per ray "
+                 "and the explicit rays", who, (const void*)o->pose->drawn, (const void*)a->trace.rays_d);
+  }
+  if (!step) return RTXN_OK;
+  // RANDOM without a counter of its own: the optimizer's, read by the compositor before the step is advanced; a jitter without one
+  // likewise, by the same rule
+  if (o->bg) {
+    o->own_bg = *o->bg;
+    if (o->own_bg.mode == RTXN_BG_RANDOM && !o->own_bg.step) o->own_bg.step = a->opt.step;
+    o->bg = &o->own_bg;
+  }
+  if (o->jitter) {
+    o->own_jitter = *o->jitter;
+    if (!o->own_jitter.step) o->own_jitter.step = a->opt.step;
+    o->jitter = &o->own_jitter;
+  }
+  return RTXN_OK;
+}
+
+// o: CHECKED options.  reg, rays: the write pass of the traversal stores t_start / t_end into their buffers; opt (ACTIVE, or
+// inactive under an EMA), scaler, ema: the optimizer's (optimizer_step); pose: its gradient and step, behind the optimizer.
+static int train_step_impl(const rtxn_train_step_args* a, const rtxn::TrainOptions& o, rtxn_stream_t stream) {
   const rtxn_train_batch& b = a->batch;
-  const rtxn_train_state& o = a->opt;
+  const rtxn_train_state& st = a->opt;
   RTXN_REQUIRE(b.mlp, "rtxn_train_step: batch.mlp is NULL");
   RTXN_REQUIRE(b.n_rays > 0 && (uint32_t)b.n_rays == a->trace.ray_count, "rtxn_train_step: batch.n_rays = %d, trace.ray_count = %u", b.n_rays,
                a->trace.ray_count);
@@ -137,11 +235,11 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
                "rtxn_train_step: NULL num_hits / indices / num_stored / total_segments / scan workspace");
   RTXN_REQUIRE(b.start_points && b.end_points && b.seg_view && b.segment_capacity > 0, "rtxn_train_step: NULL segment buffers or capacity %ld",
                b.segment_capacity);
-  RTXN_REQUIRE(o.mlp_master && o.mlp_params_fp16 && o.mlp_m && o.mlp_v && o.step && o.effective_lr, "rtxn_train_step: NULL optimizer state");
-  RTXN_REQUIRE(o.loss_scale_divisor > 0.0f, "rtxn_train_step: loss_scale_divisor = %g", o.loss_scale_divisor);
+  RTXN_REQUIRE(st.mlp_master && st.mlp_params_fp16 && st.mlp_m && st.mlp_v && st.step && st.effective_lr, "rtxn_train_step: NULL optimizer state");
+  RTXN_REQUIRE(st.loss_scale_divisor > 0.0f, "rtxn_train_step: loss_scale_divisor = %g", st.loss_scale_divisor);
   const bool hash = b.grid != nullptr;
   if (hash)
-    RTXN_REQUIRE(o.table_master && o.table_params_fp16 && o.table_m && o.table_v && o.table_steps && b.dtable,
+    RTXN_REQUIRE(st.table_master && st.table_params_fp16 && st.table_m && st.table_v && st.table_steps && b.dtable,
                  "rtxn_train_step: hash grid without table optimizer state / gradient");
   RTXN_DEVICE_OR_FAIL();
 
@@ -164,228 +262,82 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn_train_backg
   t.seg_view = const_cast<float*>(b.seg_view);
   t.num_stored = const_cast<int*>(b.num_stored);
   t.segment_capacity = b.segment_capacity;
-  if (reg) {                                                  // the regulariser's distances, written beside the segments
-    t.t_start = const_cast<float*>(reg->t_start);
-    t.t_end = const_cast<float*>(reg->t_end);
+  if (o.reg) {                                                // the regulariser's distances, written beside the segments
+    t.t_start = const_cast<float*>(o.reg->t_start);
+    t.t_end = const_cast<float*>(o.reg->t_end);
   }
-  if (rays) {                                                 // ... and the ray gradients': the same buffers when both are given
-    t.t_start = rays->t_start;
-    t.t_end = rays->t_end;
+  if (o.rays) {                                               // ... and the ray gradients': the same buffers when both are given
+    t.t_start = o.rays->t_start;
+    t.t_end = o.rays->t_end;
   }
   rc = rtxn_trace_grid(&t, stream);
   if (rc != RTXN_OK) return rc;
 
   // ---- sampler ... backward (main.cu:703-781), segment count read on the device ----
-  rc = rays   ? rtxn_train_gradients_rays(&b, bg, jitter, loss, reg, scaler, rays, stream)
-     : scaler ? rtxn_train_gradients_scaled(&b, bg, jitter, loss, reg, scaler, stream)
-     : reg    ? rtxn_train_gradients_reg(&b, bg, jitter, loss, reg, stream)
-     : loss   ? rtxn_train_gradients_loss(&b, bg, jitter, loss, stream)
-     : jitter ? rtxn_train_gradients_jitter(&b, bg, jitter, stream) : bg ? rtxn_train_gradients_ex(&b, bg, stream) : rtxn_train_gradients(&b, stream);
+  rc = rtxn::train_gradients(&b, o, stream);
   if (rc != RTXN_OK) return rc;
 
-  rc = optimizer_step(a, opt, scaler, ema, stream);
-  if (rc != RTXN_OK || !pose) return rc;
+  rc = optimizer_step(a, o.opt, o.scaler, o.ema, stream);
+  if (rc != RTXN_OK || !o.pose) return rc;
   // ---- the pose gradient and the pose step, behind the optimizer: they see the guard's skip word ----
-  rc = rtxn_pose_gradients(pose->drawn, a->trace.rays_d, rays->d_origin, rays->d_direction, b.n_rays, pose, stream);
+  rc = rtxn_pose_gradients(o.pose->drawn, a->trace.rays_d, o.rays->d_origin, o.rays->d_direction, b.n_rays, o.pose, stream);
   if (rc != RTXN_OK) return rc;
-  return rtxn_pose_step(pose, stream);
+  return rtxn_pose_step(o.pose, stream);
 }
 
-extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream); }
+// ---- the step ladder (include/rtxn.h): every rung fills the option set its signature has and takes the one checked path; what
+// is NULL or switched off runs exactly what the rung without it runs.  _ex: over a background; _jitter: the sampler's jitter;
+// _loss: the loss of rtxn_train_loss; _reg: the distortion regulariser; _opt: the optimizer options (optimizer.hip); _scaled: the
+// dynamic loss scale, which implies the non-finite guard; _ema: the weight EMA (the options may have nothing switched on: the
+// step goes through the rate kernel all the same, which advances the EMA's update count); _rays: the ray gradients and the pose
+// refinement (train.hip, pose.hip).
+static int step_entry(rtxn::TrainRung rung, const rtxn_train_step_args* a, rtxn::TrainOptions o, rtxn_stream_t stream) {
+  const int rc = rtxn::check_train_options(rung, true, a, nullptr, &o);
+  return rc != RTXN_OK ? rc : train_step_impl(a, o, stream);
+}
+
+extern "C" int rtxn_train_step(const rtxn_train_step_args* a, rtxn_stream_t stream) { return step_entry(rtxn::RUNG_PLAIN, a, {}, stream); }
 
 extern "C" int rtxn_train_step_ex(const rtxn_train_step_args* a, const rtxn_train_background* bg, rtxn_stream_t stream) {
-  RTXN_REQUIRE(a, "rtxn_train_step_ex: NULL arguments");
-  bool active = false;
-  const int rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_ex", &active);
-  if (rc != RTXN_OK) return rc;
-  if (!active) return train_step_impl(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-  // RANDOM without a counter of its own: the optimizer's, read by the compositor before advance_step_kernel increments it
-  rtxn_train_background own = *bg;
-  if (own.mode == RTXN_BG_RANDOM && !own.step) own.step = a->opt.step;
-  return train_step_impl(a, &own, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  return step_entry(rtxn::RUNG_EX, a, {bg}, stream);
 }
 
-// ... and with the sampler's jitter; a NULL jitter->step is the optimizer's counter too, by the same rule
 extern "C" int rtxn_train_step_jitter(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                       rtxn_stream_t stream) {
-  RTXN_REQUIRE(a, "rtxn_train_step_jitter: NULL arguments");
-  int rc = rtxn::check_sample_jitter("rtxn_train_step_jitter", a->batch.sample_type, jitter, a->batch.vr_mode);
-  if (rc != RTXN_OK) return rc;
-  bool active = false;
-  rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_jitter", &active);
-  if (rc != RTXN_OK) return rc;
-  rtxn_train_background own_bg;
-  if (active) {
-    own_bg = *bg;
-    if (own_bg.mode == RTXN_BG_RANDOM && !own_bg.step) own_bg.step = a->opt.step;
-  }
-  rtxn_sample_jitter own_jitter;
-  if (jitter) {
-    own_jitter = *jitter;
-    if (!own_jitter.step) own_jitter.step = a->opt.step;
-  }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  return step_entry(rtxn::RUNG_JITTER, a, {bg, jitter}, stream);
 }
 
-// ... and with the loss of rtxn_train_loss (rtxn_train_gradients_loss); NULL, or plain L2: rtxn_train_step_jitter
 extern "C" int rtxn_train_step_loss(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                     const rtxn_train_loss* loss, rtxn_stream_t stream) {
-  RTXN_REQUIRE(a, "rtxn_train_step_loss: NULL arguments");
-  int rc = rtxn::check_sample_jitter("rtxn_train_step_loss", a->batch.sample_type, jitter, a->batch.vr_mode);
-  if (rc != RTXN_OK) return rc;
-  bool active = false, loss_active = false;
-  rc = rtxn::check_train_background(bg, a->batch.vr_mode, "rtxn_train_step_loss", &active);
-  if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, a->batch.vr_mode, "rtxn_train_step_loss", &loss_active);
-  if (rc != RTXN_OK) return rc;
-  rtxn_train_background own_bg;
-  if (active) {
-    own_bg = *bg;
-    if (own_bg.mode == RTXN_BG_RANDOM && !own_bg.step) own_bg.step = a->opt.step;
-  }
-  rtxn_sample_jitter own_jitter;
-  if (jitter) {
-    own_jitter = *jitter;
-    if (!own_jitter.step) own_jitter.step = a->opt.step;
-  }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-// ... and with the distortion regulariser (rtxn_train_gradients_reg): the write pass of the traversal stores t_start / t_end
-// into the struct's buffers; NULL, or weight 0 without outputs: rtxn_train_step_loss
-static int train_step_reg(const char* who, const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
-                          const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
-                          const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream,
-                          const rtxn_ray_gradients* rays = nullptr, const rtxn_pose_refinement* pose = nullptr) {
-  RTXN_REQUIRE(a, "%s: NULL arguments", who);
-  if (scaler)
-    RTXN_REQUIRE(a->batch.vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor (batch.vr_mode = %d)", who, a->batch.vr_mode);
-  int rc = rtxn::check_sample_jitter(who, a->batch.sample_type, jitter, a->batch.vr_mode);
-  if (rc != RTXN_OK) return rc;
-  bool active = false, loss_active = false, reg_active = false;
-  rc = rtxn::check_train_background(bg, a->batch.vr_mode, who, &active);
-  if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_loss(loss, active ? bg->target_channels : 3, a->batch.vr_mode, who, &loss_active);
-  if (rc != RTXN_OK) return rc;
-  rc = rtxn::check_train_regularizer(reg, a->batch.vr_mode, a->batch.sample_type, who, &reg_active);
-  if (rc != RTXN_OK) return rc;
-  if (reg_active)
-    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the regulariser's t_start / t_end are written by the "
-                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
-  if (rays) {
-    rc = rtxn::check_ray_gradients(who, rays, &a->batch, reg_active ? reg : nullptr);
-    if (rc != RTXN_OK) return rc;
-    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the ray gradients' t_start / t_end are written by the "
-                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
-  }
-  if (pose) {
-    RTXN_REQUIRE(rays, "%s: pose without rays: the pose gradient is formed from the ray gradients", who);
-    rc = rtxn::check_pose_refinement(pose, who, true);
-    if (rc != RTXN_OK) return rc;
-    RTXN_REQUIRE(pose->drawn && a->trace.rays_d, "%s: pose->drawn = %p, trace.rays_d = %p: the pose gradient reads (image, pixel) per ray "
-                 "and the explicit rays", who, (const void*)pose->drawn, (const void*)a->trace.rays_d);
-  }
-  rtxn_train_background own_bg;
-  if (active) {
-    own_bg = *bg;
-    if (own_bg.mode == RTXN_BG_RANDOM && !own_bg.step) own_bg.step = a->opt.step;
-  }
-  rtxn_sample_jitter own_jitter;
-  if (jitter) {
-    own_jitter = *jitter;
-    if (!own_jitter.step) own_jitter.step = a->opt.step;
-  }
-  return train_step_impl(a, active ? &own_bg : nullptr, jitter ? &own_jitter : nullptr, loss_active ? loss : nullptr, reg_active ? reg : nullptr,
-                         opt, scaler, ema, stream, rays, pose);
+  return step_entry(rtxn::RUNG_LOSS, a, {bg, jitter, loss}, stream);
 }
 
 extern "C" int rtxn_train_step_reg(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, rtxn_stream_t stream) {
-  return train_step_reg("rtxn_train_step_reg", a, bg, jitter, loss, reg, nullptr, nullptr, nullptr, stream);
+  return step_entry(rtxn::RUNG_REG, a, {bg, jitter, loss, reg}, stream);
 }
 
-// ... and under the optimizer options (optimizer.hip); NULL, or nothing switched on: rtxn_train_step_reg
 extern "C" int rtxn_train_step_opt(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
                                    rtxn_stream_t stream) {
-  bool opt_active = false;
-  const int rc = rtxn::check_optimizer_options(opt, "rtxn_train_step_opt", true, &opt_active);
-  if (rc != RTXN_OK) return rc;
-  if (!opt_active) return rtxn_train_step_reg(a, bg, jitter, loss, reg, stream);
-  return train_step_reg("rtxn_train_step_opt", a, bg, jitter, loss, reg, opt, nullptr, nullptr, stream);
+  return step_entry(rtxn::RUNG_OPT, a, {bg, jitter, loss, reg, opt}, stream);
 }
 
-// ... and with the dynamic loss scale (rtxn_loss_scaler, optimizer.hip), which implies the non-finite guard; NULL: rtxn_train_step_opt
 extern "C" int rtxn_train_step_scaled(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                       const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
                                       const rtxn_loss_scaler* scaler, rtxn_stream_t stream) {
-  const char* who = "rtxn_train_step_scaled";
-  if (!scaler) return rtxn_train_step_opt(a, bg, jitter, loss, reg, opt, stream);
-  int rc = rtxn::check_loss_scaler(scaler, who, true);
-  if (rc != RTXN_OK) return rc;
-  bool opt_active = false;
-  rc = rtxn::check_optimizer_options(opt, who, true, &opt_active);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(opt && opt->skip_nonfinite && opt->guard && opt->lr_factor,
-               "%s: the loss scaler needs options with skip_nonfinite, guard and lr_factor: dynamic scaling implies the non-finite guard", who);
-  return train_step_reg(who, a, bg, jitter, loss, reg, opt, scaler, nullptr, stream);
+  return step_entry(rtxn::RUNG_SCALED, a, {bg, jitter, loss, reg, opt, scaler}, stream);
 }
 
-// ... and with the weight EMA (rtxn_weight_ema, optimizer.hip); NULL: rtxn_train_step_scaled.  The options may have nothing switched
-// on: the step goes through the rate kernel all the same, which advances the EMA's update count.
 extern "C" int rtxn_train_step_ema(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                    const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
                                    const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, rtxn_stream_t stream) {
-  const char* who = "rtxn_train_step_ema";
-  if (!ema) return rtxn_train_step_scaled(a, bg, jitter, loss, reg, opt, scaler, stream);
-  int rc = rtxn_weight_ema_check(ema);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(a, "%s: NULL arguments", who);
-  RTXN_REQUIRE(ema->state && ema->mlp_ema, "%s: ema->state = %p, ema->mlp_ema = %p", who, (void*)ema->state, (void*)ema->mlp_ema);
-  RTXN_REQUIRE(!a->batch.grid || (ema->table_ema && ema->table_stamps),
-               "%s: a hash grid needs ema->table_ema and ema->table_stamps (this call steps the table by the sparse rule)", who);
-  bool opt_active = false;
-  rc = rtxn::check_optimizer_options(opt, who, true, &opt_active);
-  if (rc != RTXN_OK) return rc;
-  RTXN_REQUIRE(opt && opt->lr_factor && (!opt->skip_nonfinite || opt->guard),
-               "%s: the weight EMA needs options that carry lr_factor (and guard with skip_nonfinite), with or without anything switched on", who);
-  if (scaler) {
-    rc = rtxn::check_loss_scaler(scaler, who, true);
-    if (rc != RTXN_OK) return rc;
-    RTXN_REQUIRE(opt->skip_nonfinite, "%s: the loss scaler needs options with skip_nonfinite: dynamic scaling implies the non-finite guard", who);
-  }
-  return train_step_reg(who, a, bg, jitter, loss, reg, opt, scaler, ema, stream);
+  return step_entry(rtxn::RUNG_EMA, a, {bg, jitter, loss, reg, opt, scaler, ema}, stream);
 }
 
-// ... and with the ray gradients and the pose refinement (train.hip, pose.hip); both NULL: rtxn_train_step_ema.  The other
-// structs keep the rules of the entry point that introduced them: what is NULL or switched off makes the call it always made.
 extern "C" int rtxn_train_step_rays(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
                                     const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
                                     const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
                                     const rtxn_pose_refinement* pose, rtxn_stream_t stream) {
-  const char* who = "rtxn_train_step_rays";
-  if (!rays && !pose) return rtxn_train_step_ema(a, bg, jitter, loss, reg, opt, scaler, ema, stream);
-  RTXN_REQUIRE(rays, "%s: pose without rays: the pose gradient is formed from the ray gradients", who);
-  RTXN_REQUIRE(a, "%s: NULL arguments", who);
-  int rc;
-  bool opt_active = false;
-  if (ema) {
-    rc = rtxn_weight_ema_check(ema);
-    if (rc != RTXN_OK) return rc;
-    RTXN_REQUIRE(ema->state && ema->mlp_ema, "%s: ema->state = %p, ema->mlp_ema = %p", who, (void*)ema->state, (void*)ema->mlp_ema);
-    RTXN_REQUIRE(!a->batch.grid || (ema->table_ema && ema->table_stamps),
-                 "%s: a hash grid needs ema->table_ema and ema->table_stamps (this call steps the table by the sparse rule)", who);
-  }
-  rc = rtxn::check_optimizer_options(opt, who, true, &opt_active);
-  if (rc != RTXN_OK) return rc;
-  if (ema)
-    RTXN_REQUIRE(opt && opt->lr_factor && (!opt->skip_nonfinite || opt->guard),
-                 "%s: the weight EMA needs options that carry lr_factor (and guard with skip_nonfinite), with or without anything switched on", who);
-  if (scaler) {
-    rc = rtxn::check_loss_scaler(scaler, who, true);
-    if (rc != RTXN_OK) return rc;
-    RTXN_REQUIRE(opt && opt->skip_nonfinite && opt->guard && opt->lr_factor,
-                 "%s: the loss scaler needs options with skip_nonfinite, guard and lr_factor: dynamic scaling implies the non-finite guard", who);
-  }
-  return train_step_reg(who, a, bg, jitter, loss, reg, (ema || opt_active) ? opt : nullptr, scaler, ema, stream, rays, pose);
+  return step_entry(rtxn::RUNG_RAYS, a, {bg, jitter, loss, reg, opt, scaler, ema, rays, pose}, stream);
 }

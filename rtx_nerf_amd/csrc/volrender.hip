@@ -1159,69 +1159,58 @@ extern "C" int rtxn_volrender_bwd(const float* loss_values, const void* loss_gra
   return RTXN_OK;
 }
 
-namespace {
-
-// rtxn_volrender_l2_train (bg == NULL: the plain kernels) and rtxn_volrender_l2_train_ex over an active background
-int l2_train(const char* who, const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices, int batch_size,
-             int num_samples_per_hit, const float* target, float loss_scale, float* pixels, void* loss_gradients_half, float* loss_sum,
-             void* radiance_gradients, const BgArgs* bg, rtxn_stream_t stream) {
+// rtxn_volrender_l2_train (bg == NULL: the plain kernels) and rtxn_volrender_l2_train_ex over an active background, behind
+// rtxn::composite_train (composite_train.hip), which has checked the structs and names the entry point
+int rtxn::l2_train(const char* who, const rtxn::CompositeArgs& c, const rtxn_train_background* active_bg, rtxn_stream_t stream) {
+  const int batch_size = c.batch_size, K = c.num_samples_per_hit;
   RTXN_REQUIRE(batch_size >= 0, "%s: batch_size = %d < 0", who, batch_size);
-  RTXN_REQUIRE(num_samples_per_hit > 0, "%s: num_samples_per_hit = %d", who, num_samples_per_hit);
+  RTXN_REQUIRE(K > 0, "%s: num_samples_per_hit = %d", who, K);
   RTXN_DEVICE_OR_FAIL();
   hipStream_t s = rtxn::as_stream(stream);
   // deterministic mode: the kernels get no loss pointer (their sum is float atomics, per block or per ray); loss.hip sums behind them
-  const bool det_loss = loss_sum && batch_size > 0 && rtxn::deterministic_mode();
-  if (loss_sum && !det_loss) RTXN_HIP(rtxn::zero_words(loss_sum, 1, s));
+  const bool det_loss = c.loss_sum && batch_size > 0 && rtxn::deterministic_mode();
+  if (c.loss_sum && !det_loss) RTXN_HIP(rtxn::zero_words(c.loss_sum, 1, s));
   if (batch_size == 0) return RTXN_OK;
-  RTXN_REQUIRE(network_outputs && ray_hit && num_hits && indices && target && pixels && radiance_gradients, "%s: NULL buffer", who);
-  float* const loss_out = loss_sum;
-  if (det_loss) loss_sum = nullptr;
-  RTXN_REQUIRE(((uintptr_t)network_outputs & 15) == 0 && ((uintptr_t)radiance_gradients & 7) == 0,
+  RTXN_REQUIRE(c.network_outputs && c.ray_hit && c.num_hits && c.indices && c.target && c.pixels && c.radiance_gradients, "%s: NULL buffer", who);
+  float* const loss_sum = det_loss ? nullptr : c.loss_sum;
+  RTXN_REQUIRE(((uintptr_t)c.network_outputs & 15) == 0 && ((uintptr_t)c.radiance_gradients & 7) == 0,
                "%s: radiance must be 16-byte and gradients 8-byte aligned", who);
   // 512 samples per step, two per lane: an even K, 8-byte-aligned step lengths and 16-byte-aligned gradients
-  const bool pairs = num_samples_per_hit % 2 == 0 && ((uintptr_t)ray_hit & 7) == 0 && ((uintptr_t)radiance_gradients & 15) == 0;
+  const bool pairs = K % 2 == 0 && ((uintptr_t)c.ray_hit & 7) == 0 && ((uintptr_t)c.radiance_gradients & 15) == 0;
   const dim3 grid((batch_size + 3) / 4), block(256);
-  const float4* rad = reinterpret_cast<const float4*>(network_outputs);
-  __half* lg = static_cast<__half*>(loss_gradients_half);
-  half4* out = static_cast<half4*>(radiance_gradients);
-  const int K = num_samples_per_hit;
-  if (bg) {
-    if (pairs) volrender_l2_bg_multi_kernel<4><<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out, *bg);
-    else volrender_l2_bg_kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out, *bg);
+  const float4* rad = reinterpret_cast<const float4*>(c.network_outputs);
+  __half* lg = static_cast<__half*>(c.loss_gradients_half);
+  half4* out = static_cast<half4*>(c.radiance_gradients);
+  const BgArgs bg = make_bg_args(active_bg);
+  if (active_bg) {
+    if (pairs) volrender_l2_bg_multi_kernel<4><<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, K, c.target, c.loss_scale, c.pixels, lg, loss_sum, out, bg);
+    else volrender_l2_bg_kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, K, c.target, c.loss_scale, c.pixels, lg, loss_sum, out, bg);
     RTXN_LAUNCH_CHECK("volrender_l2_bg_kernel");
   } else {
-    if (pairs) volrender_l2_fused_multi_kernel<4><<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out);
-    else volrender_l2_fused_kernel<<<grid, block, 0, s>>>(rad, ray_hit, num_hits, indices, batch_size, K, target, loss_scale, pixels, lg, loss_sum, out);
+    if (pairs) volrender_l2_fused_multi_kernel<4><<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, K, c.target, c.loss_scale, c.pixels, lg, loss_sum, out);
+    else volrender_l2_fused_kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, K, c.target, c.loss_scale, c.pixels, lg, loss_sum, out);
     RTXN_LAUNCH_CHECK("volrender_l2_fused_kernel");
   }
   if (det_loss)
-    return rtxn::l2_loss_fixed_order(pixels, target, batch_size, bg ? bg->mode : RTXN_BG_NONE, bg ? bg->color : nullptr, bg ? bg->seed : 0u,
-                                     bg ? bg->step : nullptr, bg ? bg->target_channels : 3, loss_out, s);
+    return rtxn::l2_loss_fixed_order(c.pixels, c.target, batch_size, bg.mode, active_bg ? bg.color : nullptr, bg.seed, bg.step, bg.target_channels,
+                                     c.loss_sum, s);
   return RTXN_OK;
 }
-
-}  // namespace
 
 extern "C" int rtxn_volrender_l2_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
                                        int batch_size, int num_samples_per_hit, const float* target, float loss_scale,
                                        float* pixels, void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
                                        rtxn_stream_t stream) {
-  return l2_train("rtxn_volrender_l2_train", network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
-                  pixels, loss_gradients_half, loss_sum, radiance_gradients, nullptr, stream);
+  return rtxn::composite_train("rtxn_volrender_l2_train", {network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
+                               loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients}, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_l2_train_ex(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
                                           int batch_size, int num_samples_per_hit, const float* target, float loss_scale,
                                           float* pixels, void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
                                           const rtxn_train_background* bg, rtxn_stream_t stream) {
-  bool active = false;
-  const int rc = rtxn::check_train_background(bg, RTXN_VR_NERF, "rtxn_volrender_l2_train_ex", &active);
-  if (rc != RTXN_OK) return rc;
-  const BgArgs a = make_bg_args(active ? bg : nullptr);
-  // NULL, or NONE with 3-channel targets: exactly what the plain entry point runs, under its name
-  return l2_train(active ? "rtxn_volrender_l2_train_ex" : "rtxn_volrender_l2_train", network_outputs, ray_hit, num_hits, indices, batch_size,
-                  num_samples_per_hit, target, loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients, active ? &a : nullptr,
-                  stream);
+  return rtxn::composite_train("rtxn_volrender_l2_train_ex", {network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
+                               loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients}, bg, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int rtxn_volrender_fwd_aux(const void* radiance, int radiance_layout, const float* ray_hit, const int* num_hits,

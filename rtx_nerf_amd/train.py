@@ -816,6 +816,22 @@ class Trainer:
         by every update.)"""
         self.net.set_params(self.params)
 
+    def _composite_train(self, n, targets, bg):
+        """The RTXN_VR_NERF training compositor over the first n rays, one launch: the entry point of the topmost struct this
+        trainer has (an inactive one below it falls through in the library)."""
+        batch = (self.radiance, self.t_vals, self.num_stored, self.indices, n, api.NUM_SAMPLES_PER_SEGMENT, targets)
+        out = (self.pixels[:n], self.loss_grads[:n], self.loss, self.dout)
+        if self._scaler is not None:             # the loss scale is the scaler's device word
+            api.volrender_scaled_train(*batch, self._scaler, *out, bg, self._loss, self._reg)
+        elif self._reg is not None:
+            api.volrender_reg_train(*batch, self.loss_scale, *out, bg, self._loss, self._reg)
+        elif self._loss is not None:
+            api.volrender_loss_train(*batch, self.loss_scale, *out, bg, self._loss)
+        elif bg is not None:
+            api.volrender_l2_train_ex(*batch, self.loss_scale, *out, bg)
+        else:
+            api.volrender_l2_train(*batch, self.loss_scale, *out)
+
     def gradients(self, rays_o, rays_d, targets):
         """Everything of a step up to (not including) the optimizer: traversal ... backward.  Leaves the loss-scaled
         gradient SUMS of this batch in self.dparams (MLP, tcnn layout) and self.dtable / self.dtable_h (hash grid: fp32 for the
@@ -847,21 +863,12 @@ class Trainer:
                 else:
                     self.dtable.zero_()
         self._dp_pending = None
-        if S == 0:
-            if self._scaler is not None:
-                api.volrender_scaled_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self._scaler,
-                                           self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
-            elif self._reg is not None:
-                api.volrender_reg_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                        self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
-            elif self._loss is not None and self.mode == "nerf" and self.fuse_compositor:
-                api.volrender_loss_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                         self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss)
-            elif bg is not None:          # every pixel is its background: loss and pixels, no radiance to differentiate
-                api.volrender_l2_train_ex(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                          self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg)
-            else:
+        if S == 0:                        # every pixel is its background: loss and pixels, no radiance to differentiate
+            loss_only = self._scaler is None and self._reg is None and bg is None
+            if loss_only and (self._loss is None or not (self.mode == "nerf" and self.fuse_compositor)):
                 self.loss.zero_()
+            else:
+                self._composite_train(n, targets, bg)
             if self._rays is not None:
                 self.rays_o_grad[:n].zero_()
                 self.rays_d_grad[:n].zero_()
@@ -871,21 +878,7 @@ class Trainer:
         self._forward(S, save=not self.two_pass, jitter=jit)
         if self.mode == "nerf" and self.fuse_compositor:
             with _Stage(self, "composite_fwd+l2+bwd"):   # one launch: the backward's first sweep IS the forward
-                if self._scaler is not None:             # the loss scale is the scaler's device word
-                    api.volrender_scaled_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self._scaler,
-                                               self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
-                elif self._reg is not None:
-                    api.volrender_reg_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                            self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss, self._reg)
-                elif self._loss is not None:
-                    api.volrender_loss_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                             self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg, self._loss)
-                elif bg is not None:
-                    api.volrender_l2_train_ex(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                              self.pixels[:n], self.loss_grads[:n], self.loss, self.dout, bg)
-                else:
-                    api.volrender_l2_train(self.radiance, self.t_vals, self.num_stored, self.indices, n, K, targets, self.loss_scale,
-                                           self.pixels[:n], self.loss_grads[:n], self.loss, self.dout)
+                self._composite_train(n, targets, bg)
         else:
             with _Stage(self, "composite_fwd"):
                 api.launch_volrender_cuda(None, self.radiance, self.num_stored, self.indices, self.t_vals, n, K,
@@ -973,11 +966,7 @@ class Trainer:
         gradient is cleared as it is consumed.  Capturable; nothing is read on the host.
         With the loss scaler, as rtxn_train_step_scaled: the statistics pass in place of the check, the scaler kernel in place of the
         rate kernel (grad_divisor is its D), and the Adam kernels that read the multiplier it leaves; `ls` is not read."""
-        hash_ = self.encoding == "hash"
-        lo = self.hashed_lo if hash_ else 0
-        parts = []
-        if hash_:
-            parts = [(slice(0, lo), self.dtable[:lo]), (slice(lo, None), self.dtable_h)] if self.hash_fp16 else [(slice(None), self.dtable)]
+        parts = self._table_parts()
         # one sequence for every combination: the _ema entry points with ema None are the _scaled calls, and those with scaler None
         # the _opt calls -- the same launches (rtxn_train_step_ema sequences its calls the same way)
         ema, scaler = self._ema, self._scaler
@@ -1006,11 +995,17 @@ class Trainer:
                 api.adam_step_ema(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], rates[1:2], self._opt,
                                   ema, cut(self.ema_table, sl), lr=self.lr * 10.0, eps=1e-15, weight_decay=False, **kw)
 
+    def _table_parts(self):
+        """(slice of the table, its gradient buffer): the densely stored levels from the fp32 gradient, the hashed ones from the
+        fp16 one; no hash grid: none"""
+        if self.encoding != "hash":
+            return []
+        lo = self.hashed_lo
+        return [(slice(0, lo), self.dtable[:lo]), (slice(lo, None), self.dtable_h)] if self.hash_fp16 else [(slice(None), self.dtable)]
+
     def _table_adam_sparse(self, **kw):
         """rtxn_adam_step_sparse over the table: the densely stored levels from the fp32 gradient, the hashed ones from the fp16 one"""
-        lo = self.hashed_lo
-        parts = [(slice(0, lo), self.dtable[:lo]), (slice(lo, None), self.dtable_h)] if self.hash_fp16 else [(slice(None), self.dtable)]
-        for sl, g in parts:
+        for sl, g in self._table_parts():
             if g.numel():
                 api.adam_step_sparse(self.table_master[sl], self.table[sl], g, self.table_m[sl], self.table_v[sl], self.table_steps[sl], **kw)
 
@@ -1472,18 +1467,9 @@ class Trainer:
                                    num_hits=self.num_hits, sub_rays=api.auto_sub_rays(n), sub_hits=self.sub_hits)
         a.scan_workspace = self.scan_ws.data_ptr()
         a.scan_workspace_bytes = self.scan_ws.numel() * 4
-        a.batch = api.train_batch(self.net, grid=self.hg if hash_ else None, n_dir_freqs=self.hg.n_dir_freqs if hash_ else 0,
-                                  table=self.table if hash_ else None, start_points=self.start, end_points=self.end, seg_view=self.seg_view,
-                                  num_stored=self.num_stored, indices=self.indices, total_segments=self.total, segment_capacity=cap,
-                                  n_rays=n, sample_type=self._stype(self._jitter(None)),
-                                  t_scale=self.density_scale if self.mode == "nerf" else 1.0,
-                                  vr_mode=api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT, targets=self.graph_targets,
-                                  loss_scale=self.loss_scale, encT=self.encT, dencT=self.dencT, workspace=self.ws,
-                                  output_half=self.out, radiance=self.radiance, t_vals=self.t_vals, radiance_gradients=self.dout,
-                                  pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss, dparams=self.dparams,
-                                  dtable=self.dtable if hash_ else None,
-                                  dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
-                                  live_ws=self.live_ws if self.live_segments else None, workspace_lean=self.lean,
+        a.batch = api.train_batch(self.net, **self._batch_kw(dict(start=self.start, end=self.end, seg_view=self.seg_view,
+                                                                  num_stored=self.num_stored, indices=self.indices, total=self.total,
+                                                                  targets=self.graph_targets), n, cap, self._jitter(None)),
                                   target_channels=self.graph_targets.shape[1])
         # RANDOM: step NULL = the call's own counter (entry_step) before its increment
         self._entry_bg = self._bg(None, self.graph_targets.shape[1])
@@ -1561,19 +1547,23 @@ class Trainer:
     def _captured_gradients(self, k):
         st, n, cap = self._g_sets[k], self._g_n, self._g_cap
         # no fills: the captured Adam clears every gradient as it consumes it (zero_grads), capture_step() clears them once
+        api.train_gradients(self.net, **self._batch_kw(st, n, cap, self._g_jit), skip_table_backward=self._g_split, background=self._g_bg,
+                            jitter=self._g_jit, loss=self._loss, regularizer=st["reg"], scaler=self._scaler, rays=self._rays)
+
+    def _batch_kw(self, st, n, cap, jitter):
+        """The keywords of api.train_batch (struct rtxn_train_batch) over this trainer's buffers; st: the segments, per-ray counts
+        and targets of the batch -- the trainer's own (entry_args) or one of the captured step's sets"""
         hash_ = self.encoding == "hash"
-        api.train_gradients(self.net, grid=self.hg if hash_ else None, n_dir_freqs=self.hg.n_dir_freqs if hash_ else 0,
-                            table=self.table if hash_ else None, start_points=st["start"], end_points=st["end"], seg_view=st["seg_view"],
-                            num_stored=st["num_stored"], indices=st["indices"], total_segments=st["total"], segment_capacity=cap,
-                            n_rays=n, sample_type=self._stype(self._g_jit), t_scale=self.density_scale if self.mode == "nerf" else 1.0,
-                            vr_mode=api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT, targets=st["targets"],
-                            loss_scale=self.loss_scale, encT=self.encT, dencT=self.dencT, workspace=self.ws,
-                            output_half=self.out, radiance=self.radiance, t_vals=self.t_vals, radiance_gradients=self.dout,
-                            pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss, dparams=self.dparams,
-                            dtable=self.dtable if hash_ else None, dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
-                            live_ws=self.live_ws if self.live_segments else None, skip_table_backward=self._g_split,
-                            workspace_lean=self.lean, background=self._g_bg, jitter=self._g_jit, loss=self._loss,
-                            regularizer=st["reg"], scaler=self._scaler, rays=self._rays)
+        return dict(grid=self.hg if hash_ else None, n_dir_freqs=self.hg.n_dir_freqs if hash_ else 0, table=self.table if hash_ else None,
+                    start_points=st["start"], end_points=st["end"], seg_view=st["seg_view"], num_stored=st["num_stored"],
+                    indices=st["indices"], total_segments=st["total"], segment_capacity=cap, n_rays=n, sample_type=self._stype(jitter),
+                    t_scale=self.density_scale if self.mode == "nerf" else 1.0,
+                    vr_mode=api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT, targets=st["targets"], loss_scale=self.loss_scale,
+                    encT=self.encT, dencT=self.dencT, workspace=self.ws, output_half=self.out, radiance=self.radiance, t_vals=self.t_vals,
+                    radiance_gradients=self.dout, pixels=self.pixels, loss_gradients=self.loss_grads, loss_sum=self.loss,
+                    dparams=self.dparams, dtable=self.dtable if hash_ else None,
+                    dtable_hashed_half=self.dtable_h if (hash_ and self.hash_fp16) else None,
+                    live_ws=self.live_ws if self.live_segments else None, workspace_lean=self.lean)
 
     def _captured_table_bwd(self, k):
         """the hash scatter of set k's batch over the live list the gradient graph left (its count is on the device)"""
