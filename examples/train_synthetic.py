@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end use of the harness on a NeRF-synthetic scene directory (transforms_train.json + PNG frames, the format the
 reference's loader expects at ./data/nerf_synthetic/<scene>, loader/data_loader.cpp:144): load -> device ray dataset ->
-train (hash-grid or frequency model) with periodic occupancy refresh -> held-out PSNR -> PNG of a rendered view.
+train (hash-grid or frequency model) with periodic occupancy refresh -> mean held-out PSNR and SSIM (Trainer.evaluate) -> PNG of a
+rendered view.
 No dataset ships with this image; pass --make-demo to first write a small procedural scene in the same format.
 
   python examples/train_synthetic.py --data /path/to/lego [--steps 2000] [--encoding hash]
@@ -10,7 +11,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego --loss huber --opacity-weight 0.1     (Huber, and the frames' alpha fitted)
   python examples/train_synthetic.py --data /path/to/lego --distortion-weight 0.01 --loss-scale 4096     (mip-NeRF 360's distortion loss)
   python examples/train_synthetic.py --data /path/to/lego --steps 20000 --lr-schedule cosine:20000 --weight-decay 1e-6 --skip-nonfinite
-  python examples/train_synthetic.py --data /path/to/lego --steps 20000 --ema-decay 0.99     (held-out PSNR of the live and the averaged weights)
+  python examples/train_synthetic.py --data /path/to/lego --steps 20000 --ema-decay 0.99     (held-out PSNR and SSIM of the live and the averaged weights)
   python examples/train_synthetic.py --data /path/to/lego --pose-noise 0.5,0.02 --refine-poses 1e-3     (noisy poses, refined on the device)
 """
 import argparse
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from rtx_nerf_amd import api, loader, scenes
-from rtx_nerf_amd.train import RayDataset, Trainer, camera_rays, psnr
+from rtx_nerf_amd.train import RayDataset, Trainer, camera_rays
 
 
 def make_demo(path, n_frames=16, res=64, grid=32):
@@ -104,7 +105,7 @@ def main():
                     help="skip a step whose gradients hold an Inf or a NaN instead of stepping Adam on them; the number skipped is printed")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
                     help="keep the debiased exponential moving average of the weights with this decay (Trainer(ema_decay=...), DESIGN 5.15) "
-                         "and report the held-out PSNR of the averaged weights beside the live ones")
+                         "and report the held-out PSNR and SSIM of the averaged weights (evaluate(weights='ema')) beside the live ones")
     ap.add_argument("--refine-poses", nargs="?", const=1e-3, type=float, default=None, metavar="LR",
                     help="refine a 6-DoF correction per training image on the device from the rays' gradients "
                          "(Trainer(ray_gradients=True), attach_images(refine_poses=...), DESIGN 5.16); implies --device-batches")
@@ -156,41 +157,29 @@ def main():
                  loss_scale=loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite,
                  max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay, ray_gradients=a.refine_poses is not None, **model)
     white = (1.0, 1.0, 1.0) if rgba else None
+    # the held-out frames stay on the device as they were loaded (flags=2 frames are k/255: one byte per channel holds them exactly)
+    hold_ds = loader.ImageDataset(ds.images[-n_hold:], ds.poses[-n_hold:], ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
+    hold, _ = api.ImageSet.from_dataset(hold_ds, storage="u8")
 
     def render():
         return tr.render_rays(o_t, d_t, background=white)
 
-    viewer = []
-
-    def render_ema():
-        """the held-out view from the averaged weights: a second model of the same shape set to ema_parameters(), behind the
-        live model's occupancy (render_rays itself stays on the live weights)"""
-        if not viewer:
-            viewer.append(Trainer(R, None, **model))
-        view = viewer[0]
-        mlp, table = tr.ema_parameters()
-        view.params.copy_(mlp.half())
-        view.net.set_params_training(view.params)
-        if table is not None:
-            view.table.copy_(table.half())
-        if tr.occ is not None:
-            view._set_occupancy(tr.occ.clone())
-        return view.render_rays(o_t, d_t, background=white)
+    def score(weights="live"):
+        """mean PSNR and SSIM over ALL held-out frames (Trainer.evaluate: rendered and compared on the device, an RGBA frame over
+        the white the model is trained over); one host read, of the two means"""
+        _, db, ssim = tr.evaluate(hold, weights=weights).mean(0).tolist()
+        return f"{db:.2f} dB, SSIM {ssim:.4f}"
 
     def held_out():
-        live = f"{psnr(render(), gt):.2f} dB"
-        return live if a.ema_decay is None else f"{live} live, {psnr(render_ema(), gt):.2f} dB averaged"
+        return score() if a.ema_decay is None else f"{score()} live, {score('ema')} averaged"
 
     if a.device_batches:
         tr.attach_images(images, refine_poses=None if a.refine_poses is None else dict(lr=a.refine_poses))
     g = torch.Generator(device="cuda").manual_seed(0)
     W, H = ds.image_width, ds.image_height
     o_t, d_t = camera_rays(ds.poses[-1], focal, W, H, origin_scale=0.1)
-    gt = torch.from_numpy(ds.images[-1].reshape(-1, C)).cuda()
-    if rgba:                                    # the held-out frame over white, as the model is rendered
-        gt = gt[:, 3:4] * gt[:, :3] + (1.0 - gt[:, 3:4])
     print(f"{n_rays} training rays from {train_ds.images.shape[0]} frames ({W}x{H}), {held / 1e6:.2f} MB on the device "
-          f"({'image set, batches drawn on the device' if a.device_batches else 'ray dataset'}); held-out PSNR before: {psnr(render(), gt):.2f} dB")
+          f"({'image set, batches drawn on the device' if a.device_batches else 'ray dataset'}); held-out PSNR over {n_hold} frame{'s' if n_hold > 1 else ''} before: {held_out()}")
     for it in range(a.steps):
         loss = tr.step_images(a.batch) if a.device_batches else tr.step(*rays.sample_batch(a.batch, g))
         if (it + 1) % 100 == 0:

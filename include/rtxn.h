@@ -1414,6 +1414,47 @@ typedef struct rtxn_draw_batch_args {
 } rtxn_draw_batch_args;
 int rtxn_draw_batch(const rtxn_draw_batch_args* a, rtxn_stream_t stream);
 
+/* ---- held-out evaluation: PSNR and SSIM of a rendered frame against a resident frame ----------------------
+ * Compares pred, a rendered frame float[height*width][3] in the compositor's layout (ray r = pixel (r % width, r / width), so a
+ * frame rendered at the set's width x height, focal_length and aspect_ratio lies in the set's own [height][width] order), with
+ * frame `image` of an rtxn_image_set, and leaves ONE record of three doubles {mse, psnr, ssim} in device memory.  Two kernels on
+ * `stream`, no allocation, no synchronisation, nothing read on the host: hipGraph-capturable behind rtxn_render_frame[_ex].
+ * No atomics: a block reduces its tile of the frame to two double partials in the workspace, and one block folds the partials
+ * in a fixed order -- the same inputs give the same bits on every run, with and without RTXN_METRICS_SSIM.
+ * Target: rtxn_draw_batch's rule (RTXN_IMAGE_F32 copied, RTXN_IMAGE_U8 (float)v / 255.0f); with 4 channels the straight-alpha
+ *   pixel over `background`, t_k = fmaf(a, rgb_k, (1.0f - a) * bg_k) = a rgb_k + (1 - a) bg_k in fp32 (a = 1 keeps rgb_k, a = 0
+ *   bg_k, exactly).  3 channels: background is not read.
+ * RTXN_METRICS_CLAMP: pred is first clamped to [0, 1] (what an 8-bit PNG of the frame keeps); off: pred as it is.
+ * mse  = the mean over height*width*3 of (pred - target)^2, differences and squares formed in double;
+ * psnr = 10 log10(1 / max(mse, 1e-12))     (120 dB at most; train.psnr()'s rule)
+ * ssim (RTXN_METRICS_SSIM; without the flag the slot is NaN): Wang et al. 2004 as mip-NeRF and instant-ngp evaluate it --
+ *   an 11 x 11 Gaussian window, sigma = 1.5, normalised to sum 1 and applied separably; K1 = 0.01, K2 = 0.03, L = 1
+ *   (C1 = 1e-4, C2 = 9e-4); "valid" windows only, (height - 10)(width - 10) of them, no padding; per channel the weighted
+ *   population moments and (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx^2 + sy^2 + C2)); the mean over all windows and
+ *   the three channels.  The windowed sums are fp32, taken of each image MINUS a per-tile pivot (that image's own pixel at the
+ *   centre of the 16 x 16-window tile, per channel): variances and the covariance are shift-invariant and the means get their
+ *   pivot back, so a bright flat region keeps its variance against C2 (the raw-moment form E[x^2] - m^2 loses it in fp32).
+ *   The moments and the quotient are formed in double from those sums, each first divided by the squared sum of the eleven
+ *   float weights (what rounding them left of 1).
+ * Rules (RTXN_ERR_INVALID with a message, before any device is touched): no NULL among set.images, pred, workspace, record
+ * (set.poses MAY be NULL: nothing reads it); workspace and record 8-byte aligned; set.n_images >= 1 and 0 <= image < n_images;
+ * width, height, channels, format as rtxn_draw_batch; no flag bits beyond the two; with RTXN_METRICS_SSIM width >= 11 and
+ * height >= 11; workspace_bytes >= rtxn_image_metrics_workspace_bytes(width, height) (which is 0, with a message, for a frame
+ * rtxn_draw_batch would refuse).  The kernels write nothing past that many bytes. */
+enum rtxn_metrics_flags { RTXN_METRICS_SSIM = 1, RTXN_METRICS_CLAMP = 2 };
+typedef struct rtxn_image_metrics_args {
+  rtxn_image_set set;
+  int image;             /* which frame of the set: 0 .. n_images - 1 */
+  const float* pred;     /* DEVICE float[height*width][3] */
+  float background[3];   /* under a 4-channel target */
+  int flags;             /* enum rtxn_metrics_flags */
+  void* workspace;       /* DEVICE, 8-byte aligned */
+  size_t workspace_bytes;
+  double* record;        /* DEVICE: 3 doubles {mse, psnr, ssim} */
+} rtxn_image_metrics_args;
+size_t rtxn_image_metrics_workspace_bytes(uint32_t width, uint32_t height);
+int rtxn_image_metrics(const rtxn_image_metrics_args* a, rtxn_stream_t stream);
+
 /* ---- ray gradients through the hash grid, and camera pose refinement ---------------------------------------
  * tiny-cuda-nn's dL/dinput and instant-ngp's extrinsics optimisation.  Three stages, each without atomics and in a fixed order:
  * the same bits on every run, in default and in deterministic mode.  Everything is stream-ordered and hipGraph-capturable.

@@ -184,6 +184,12 @@ class DrawBatchArgs(C.Structure):
                 ("rays_d", C.c_void_p), ("targets", C.c_void_p), ("drawn", C.c_void_p)]
 
 
+class ImageMetricsArgs(C.Structure):
+    """struct rtxn_image_metrics_args (include/rtxn.h)."""
+    _fields_ = [("set", ImageSet), ("image", C.c_int), ("pred", C.c_void_p), ("background", C.c_float * 3), ("flags", C.c_int),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("record", C.c_void_p)]
+
+
 class RayGradients(C.Structure):
     """struct rtxn_ray_gradients (include/rtxn.h)."""
     _fields_ = [("t_start", C.c_void_p), ("t_end", C.c_void_p), ("dstart", C.c_void_p), ("dend", C.c_void_p), ("d_origin", C.c_void_p),
@@ -402,6 +408,8 @@ SYMBOLS = {
     "rtxn_train_step_ema": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                  C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma), _P]),
     "rtxn_draw_batch": (_I, [C.POINTER(DrawBatchArgs), _P]),
+    "rtxn_image_metrics_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rtxn_image_metrics": (_I, [C.POINTER(ImageMetricsArgs), _P]),
     "rtxn_ray_gradients_supported": (_I, [_P, _P]),
     "rtxn_hashgrid_input_gradient_segments": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, C.POINTER(SampleJitter), _F, _P, _P, _P, _P]),
     "rtxn_ray_gradients_reduce": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),

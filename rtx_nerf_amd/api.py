@@ -1511,6 +1511,64 @@ def draw_batch_launch(args):
     check(_lib.lib().rtxn_draw_batch(C.byref(args), _stream()), "rtxn_draw_batch")
 
 
+# --------------------------------------------------------------------------- held-out evaluation
+METRICS_SSIM, METRICS_CLAMP = 1, 2         # enum rtxn_metrics_flags
+
+
+def image_metrics_workspace_bytes(width, height):
+    """rtxn_image_metrics_workspace_bytes: the bytes of partial sums rtxn_image_metrics needs for width x height frames."""
+    lib = _lib.lib()
+    need = lib.rtxn_image_metrics_workspace_bytes(int(width), int(height))
+    if need == 0:
+        msg = lib.rtxn_last_error()
+        raise _lib.RtxnError(f"rtxn_image_metrics_workspace_bytes: {msg.decode() if msg else '?'}")
+    return int(need)
+
+
+def image_metrics_workspace(image_set):
+    """A workspace for image_metrics() over image_set's frames, on the set's device (uint8, from an 8-byte aligned allocation)."""
+    return torch.empty(image_metrics_workspace_bytes(image_set.width, image_set.height), dtype=torch.uint8, device=image_set.images.device)
+
+
+def image_metrics_args(image_set, image, pred, *, background=None, ssim=True, clamp=False, record, workspace):
+    """struct rtxn_image_metrics_args over the given tensors (which the caller keeps alive): pred float32 with H*W*3 elements
+    ([H*W, 3] as the compositor writes it, or [H, W, 3]), record float64 [3], workspace from image_metrics_workspace()."""
+    n = image_set.width * image_set.height
+    if pred.numel() != 3 * n or pred.shape[-1] != 3:
+        raise _lib.RtxnError(f"image_metrics: pred of shape {tuple(pred.shape)}: [{n}, 3] or [{image_set.height}, {image_set.width}, 3]")
+    if record.numel() != 3:
+        raise _lib.RtxnError(f"image_metrics: record of shape {tuple(record.shape)}: [3]")
+    if image_set.channels == 4 and background is None:
+        raise _lib.RtxnError("image_metrics: a 4-channel image set needs background=(r, g, b) to composite its frames over")
+    a = _lib.ImageMetricsArgs()
+    a.set = image_set.c_struct()
+    a.image = int(image)
+    a.pred = _ptr(pred, torch.float32, "pred")
+    if background is not None:
+        bg = [float(v) for v in background]
+        if len(bg) != 3:
+            raise _lib.RtxnError(f"image_metrics: background {background!r}: three floats")
+        a.background[:] = bg
+    a.flags = (METRICS_SSIM if ssim else 0) | (METRICS_CLAMP if clamp else 0)
+    a.workspace, a.workspace_bytes = _ptr(workspace, torch.uint8, "workspace"), workspace.numel()
+    a.record = _ptr(record, torch.float64, "record")
+    return a
+
+
+def image_metrics(image_set, image, pred, *, background=None, ssim=True, clamp=False, record=None, workspace=None):
+    """rtxn_image_metrics: (mse, psnr, ssim) of the rendered frame `pred` against frame `image` of image_set, as a float64 device
+    tensor of 3 (`record`, or a new one), on the current stream with nothing read on the host.  background: three floats a
+    4-channel set's frames are composited over (required for one, ignored for RGB); ssim=False leaves NaN in slot 2 and takes
+    frames smaller than 11 x 11; clamp: pred is clamped to [0, 1] first, as an 8-bit PNG of it would be."""
+    if record is None:
+        record = torch.empty(3, dtype=torch.float64, device=pred.device)
+    if workspace is None:
+        workspace = image_metrics_workspace(image_set)
+    a = image_metrics_args(image_set, image, pred, background=background, ssim=ssim, clamp=clamp, record=record, workspace=workspace)
+    check(_lib.lib().rtxn_image_metrics(C.byref(a), _stream()), "rtxn_image_metrics")
+    return record
+
+
 # --------------------------------------------------------------------------- ray gradients and pose refinement
 def ray_gradients(t_start, t_end, dstart, dend, d_origin, d_direction):
     """struct rtxn_ray_gradients (include/rtxn.h) over device float32 tensors (which the struct keeps referenced): t_start, t_end

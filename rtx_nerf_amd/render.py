@@ -271,13 +271,22 @@ class RenderPipeline:
             self._create()
         return worst
 
-    def render(self, ray_begin=0, ray_count=None, out=None):
+    def _pose(self, look_at):
+        """the frame's pose: the one set_pose() wrote, or `look_at`, 16 device floats read where they lie (a row of an
+        api.ImageSet's poses, say)"""
+        if look_at is None:
+            return C.c_void_p(self.look_at.data_ptr())
+        if look_at.numel() != 16:
+            raise ValueError(f"look_at of shape {tuple(look_at.shape)}: 16 floats")
+        return api._ptr(look_at, torch.float32, "look_at")
+
+    def render(self, ray_begin=0, ray_count=None, out=None, look_at=None):
         """Enqueue one frame (or one shard of it) on the current stream; returns the
-        pixel buffer view float[ray_count, 3] (or `out`).  No host synchronisation."""
+        pixel buffer view float[ray_count, 3] (or `out`).  No host synchronisation.  look_at: see _pose()."""
         n = self.max_rays if ray_count is None else ray_count
         pixels = self.pixels[:n] if out is None else out
         self._check_overflow()
-        _lib.check(_lib.lib().rtxn_render_frame(self._h, 0, C.c_void_p(self.look_at.data_ptr()), ray_begin, n,
+        _lib.check(_lib.lib().rtxn_render_frame(self._h, 0, self._pose(look_at), ray_begin, n,
                                                 api._ptr(pixels, torch.float32, "pixels"), api._stream()), "rtxn_render_frame")
         return pixels
 
@@ -296,15 +305,15 @@ class RenderPipeline:
             o.background[:] = [float(v) for v in background]
         return o, (pixels, d if depth else None, a if opacity else None)
 
-    def render_ex(self, ray_begin=0, ray_count=None, background=None, depth=True, opacity=True, out=None):
+    def render_ex(self, ray_begin=0, ray_count=None, background=None, depth=True, opacity=True, out=None, look_at=None):
         """render() with the expected depth (sum w_i d_i, unnormalised; float[ray_count]) and the opacity (sum w_i) of every
         ray, and an optional background colour (3 floats) composited as (1 - opacity) * background (rtxn_render_frame_ex).
         Returns (pixels, depth, opacity); an output not asked for is None.  With no background the pixels are render()'s
-        bit for bit."""
+        bit for bit.  look_at: see _pose()."""
         n = self.max_rays if ray_count is None else ray_count
         o, res = self._outputs(n, background, depth, opacity, out)
         self._check_overflow()
-        _lib.check(_lib.lib().rtxn_render_frame_ex(self._h, 0, C.c_void_p(self.look_at.data_ptr()), ray_begin, n, C.byref(o),
+        _lib.check(_lib.lib().rtxn_render_frame_ex(self._h, 0, self._pose(look_at), ray_begin, n, C.byref(o),
                                                    api._stream()), "rtxn_render_frame_ex")
         return res
 

@@ -800,21 +800,86 @@ class Trainer:
                 raise RuntimeError("render_pipeline(weights='ema'): call sync_ema() first")
             net, table = self._ema_net, self._ema_table16
         if self.encoding == "hash":
-            if not api.hashmlp_supported(self.net, self.hg):
-                raise api._lib.RtxnError("render_pipeline: no fused hash-grid inference kernel for this model (built: 64 wide, <= 8 hidden "
-                                         "layers, 2 features per level, an even number of levels); use render_rays()"
-                                         + (" on a model set to ema_parameters()" if weights == "ema" else ""))
+            self._require_fused_inference(weights)
             kw.update(hashgrid=self.hg, table=table)
         pipe = render.RenderPipeline(net, self.R, width, height, focal_length, occupancy=self.occ, max_segments=max_segments,
                                      vr_mode=api.VR_NERF if nerf else api.VR_COMPAT, step_scale=self.density_scale if nerf else 1.0, **kw)
         self._pipelines = [r for r in getattr(self, "_pipelines", []) if r() is not None] + [weakref.ref(pipe)]
         return pipe
 
+    def _require_fused_inference(self, weights):
+        """render_pipeline's refusal of a hash model its fused inference kernel does not cover"""
+        if not api.hashmlp_supported(self.net, self.hg):
+            raise api._lib.RtxnError("render_pipeline: no fused hash-grid inference kernel for this model (built: 64 wide, <= 8 hidden "
+                                     "layers, 2 features per level, an even number of levels); use render_rays()"
+                                     + (" on a model set to ema_parameters()" if weights == "ema" else ""))
+
     def sync_inference_weights(self):
         """Frequency models: re-pack the fused inference kernel's weights from the current parameters (rtxn_mlp_set_params); the
         per-step update only refreshes the training layouts.  (Hash models need nothing: their one 16x16x32 packing is refreshed
         by every update.)"""
         self.net.set_params(self.params)
+
+    def evaluate(self, image_set, images=None, weights="live", background=None, ssim=True, clamp=False, out=None):
+        """Score held-out frames on the device: per frame of `images` (indices into image_set, default all of them, in that
+        order) one frame rendered on the fast inference path at the set's width, height, focal length and aspect ratio, with the
+        pose read where it lies in image_set.poses, and one rtxn_image_metrics call against the resident frame.  Returns a
+        float64 device tensor [n, 3] (`out`, or a new one) with rows (mse, psnr, ssim); average on the device (rec.mean(0)).
+        weights "live" | "ema" (ema_decay; sync_ema() is called first); frequency models get sync_inference_weights() first.
+        background: what the frames are rendered over, and what a 4-channel set's frames are composited over: None takes the
+        trainer's constant background (a "random" trainer must be given one for a 4-channel set); an RGB set with no background
+        renders as render() does.  ssim=False leaves NaN in column 2; clamp: the frame is clamped to [0, 1] first.
+        The FIRST call for a (set geometry, weights) builds and caches the render_pipeline and sizes it with calibrate() over
+        the set's poses: that reads the poses and one segment count per pose on the host, once.  Every later call only enqueues
+        work -- no tensor is read on the host -- and may be captured in a torch.cuda.graph (serial frames, no parallel branches;
+        pass `out`, or keep the returned tensor, as with any captured allocation).  update_occupancy() and refresh_occupancy()
+        reach the cached pipelines, so the scores follow the occupancy."""
+        if weights not in ("live", "ema"):
+            raise ValueError(f"evaluate: weights = {weights!r}: 'live' or 'ema'")
+        if weights == "ema" and self._ema is None:
+            raise RuntimeError("evaluate(weights='ema'): this trainer was made without ema_decay")
+        if background is None and not isinstance(self.background, str):
+            background = self.background
+        if background is not None:
+            background = tuple(float(v) for v in background)
+            if len(background) != 3:
+                raise ValueError(f"evaluate: background {background!r}: three floats")
+        if image_set.channels == 4 and background is None:
+            raise ValueError("evaluate: a 4-channel image set needs a colour to composite its frames over: this trainer's background is "
+                             + ("'random'" if self.background == "random" else "None") + ", pass background=(r, g, b)")
+        idx = list(range(image_set.n_images)) if images is None else [int(i) for i in images]
+        for i in idx:
+            if not 0 <= i < image_set.n_images:
+                raise ValueError(f"evaluate: image {i} outside [0, {image_set.n_images})")
+        if out is not None and (tuple(out.shape) != (len(idx), 3) or out.dtype != torch.float64 or not out.is_contiguous()):
+            raise ValueError(f"evaluate: out of shape {tuple(out.shape)} / {out.dtype}: contiguous float64 [{len(idx)}, 3]")
+        if self.encoding == "hash":
+            self._require_fused_inference(weights)
+        else:
+            self.sync_inference_weights()
+        if weights == "ema":
+            self.sync_ema()
+        key = (image_set.width, image_set.height, image_set.focal_length, image_set.aspect_ratio, weights)
+        cache = self.__dict__.setdefault("_eval_pipelines", {})
+        entry = cache.get(key)
+        if entry is None or (entry[0].occ is None) != (self.occ is None):    # a trainer that started dense has its occupancy now
+            cache.pop(key, None)
+            # one slot: only serial frames are rendered here; "grow": a frame that outgrows the calibrated buffers (the occupancy
+            # has filled up since) is scored truncated once, and the next eager call re-sizes the pipeline instead of raising
+            pipe = self.render_pipeline(image_set.width, image_set.height, image_set.focal_length, weights=weights,
+                                        aspect_ratio=image_set.aspect_ratio, n_slots=1, on_overflow="grow")
+            pipe.calibrate(image_set.poses.cpu().numpy())             # the one-time host read
+            entry = cache[key] = (pipe, api.image_metrics_workspace(image_set))
+        pipe, workspace = entry
+        rec = out if out is not None else torch.empty((len(idx), 3), dtype=torch.float64, device=self.dev)
+        for row, i in enumerate(idx):
+            pose = image_set.poses[i]
+            if background is not None:
+                pixels = pipe.render_ex(background=background, depth=False, opacity=False, look_at=pose)[0]
+            else:
+                pixels = pipe.render(look_at=pose)
+            api.image_metrics(image_set, i, pixels, background=background, ssim=ssim, clamp=clamp, record=rec[row], workspace=workspace)
+        return rec
 
     def _composite_train(self, n, targets, bg):
         """The RTXN_VR_NERF training compositor over the first n rays, one launch: the entry point of the topmost struct this
