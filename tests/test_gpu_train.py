@@ -530,7 +530,7 @@ def test_outputs_only_forward_against_saving_forward_and_torch_per_column_tile(g
 def test_adam_sparse_matches_oracle(gpu, oracle, half_grads):
     """rtxn_adam_step_sparse (the hash table's optimizer) against oracle.adam_step_sparse over five steps of gradients that are
     zero on a different 90 % of the entries each time: identical update counts, weights and moments to fp32 rounding of the
-    in-kernel bias correction (powf), untouched entries bit-identical to where they started; ZERO clears what it consumed."""
+    in-kernel bias correction (one exp2 per power; the oracle's is powf), untouched entries bit-identical to where they started; ZERO clears what it consumed."""
     torch = gpu
     from rtx_nerf_amd import api
     rng = np.random.default_rng(11)
