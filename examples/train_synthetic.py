@@ -13,6 +13,7 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego --steps 20000 --lr-schedule cosine:20000 --weight-decay 1e-6 --skip-nonfinite
   python examples/train_synthetic.py --data /path/to/lego --steps 20000 --ema-decay 0.99     (held-out PSNR and SSIM of the live and the averaged weights)
   python examples/train_synthetic.py --data /path/to/lego --pose-noise 0.5,0.02 --refine-poses 1e-3     (noisy poses, refined on the device)
+  python examples/train_synthetic.py --data /path/to/lego --mesh lego.ply --mesh-resolution 256 --mesh-iso 30     (triangle mesh of the density field)
 """
 import argparse
 import json
@@ -72,6 +73,10 @@ def pose_errors(poses, true_poses):
     return float(np.degrees(np.arccos(np.clip(cos, -1.0, 1.0))).mean()), float(np.linalg.norm(a[:, :3, 3] - b[:, :3, 3], axis=1).mean())
 
 
+# --mesh-iso's default: a judgement call from the sweep of DESIGN 5.19 on the --make-demo scene, not derived
+DEMO_MESH_ISO = 30.0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", required=True)
@@ -112,6 +117,13 @@ def main():
     ap.add_argument("--pose-noise", default=None, metavar="ROT_DEG,TRANS",
                     help="perturb the training poses on load by a seeded random rotation of ROT_DEG degrees and a translation of "
                          "length TRANS; the mean errors against the true poses are printed before and after training")
+    ap.add_argument("--mesh", default=None, metavar="OUT.ply",
+                    help="after training, extract the triangle mesh of {sigma * density_scale > iso} on the device "
+                         "(Trainer.extract_mesh, DESIGN 5.19) and write it as a binary PLY, in the cube's coordinates")
+    ap.add_argument("--mesh-resolution", type=int, default=128, metavar="N", help="lattice nodes per axis of --mesh")
+    ap.add_argument("--mesh-iso", default=str(DEMO_MESH_ISO), metavar="V[,V...]",
+                    help="iso value of --mesh, an extinction per unit length of the cube; the default is a judgement call from a sweep on "
+                         "the --make-demo scene (DESIGN 5.19), not a derived number.  Several values: one OUT.<V>.ply each, and the sweep's table")
     a = ap.parse_args()
     if a.refine_poses is not None:
         a.device_batches = True
@@ -204,6 +216,18 @@ def main():
     img = render().reshape(H, W, 3).cpu().numpy()
     loader.write_png(a.out, img)
     print("wrote", a.out)
+    if a.mesh:
+        isos = [float(v) for v in a.mesh_iso.split(",")]
+        for iso in isos:
+            v, t, nrm = tr.extract_mesh(a.mesh_resolution, iso=iso, weights="live" if a.ema_decay is None else "ema")
+            path = a.mesh if len(isos) == 1 else f"{os.path.splitext(a.mesh)[0]}.{iso:g}.ply"
+            api.write_ply(path, v, t, nrm)
+            # closed: every undirected edge belongs to two triangles (an open one ends on a face of the cube)
+            e = torch.sort(torch.cat([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]]).long(), dim=1).values
+            _, per_edge = torch.unique(e[:, 0] * max(v.shape[0], 1) + e[:, 1], return_counts=True)
+            closed = bool((per_edge == 2).all().item())
+            print(f"mesh at iso {iso:g}, {a.mesh_resolution}^3 nodes: {v.shape[0]} vertices, {t.shape[0]} triangles, "
+                  f"{'closed' if closed else 'open'}; wrote {path}")
 
 
 if __name__ == "__main__":

@@ -426,6 +426,86 @@ int rtxn_occupancy_refresh_supported(const rtxn_mlp* m, const rtxn_hashgrid* g, 
 size_t rtxn_occupancy_refresh_workspace_bytes(int grid_res, long runs_per_pass);
 int rtxn_occupancy_refresh(const rtxn_occupancy_refresh_args* args, rtxn_stream_t stream);
 
+/* ---- mesh extraction: sigma on a lattice, and its isosurface -------------------------------------------------------
+ * Not in the reference.  Two entries, both on `stream` without a synchronisation, a host read, an allocation or an atomic:
+ * hipGraph-capturable, and the same bytes on every run.
+ *
+ * rtxn_density_lattice: sigma of the model at the n_x * n_y * n_z NODES of a regular lattice over the box [lo, hi] (lo < hi, both
+ * inside [-1, 1]^3, n_c in [2, 1024]), through the fused inference kernels: the occupancy refresh's evaluation without the
+ * fold, the jitter and the hierarchy.  Nodes (x, y, 32k .. 32k+31) form a RUN, handed to the segment kernels as one
+ * pseudo-segment whose 32 REGULAR samples are the nodes; NK = ceil(n_z/32) runs per row, run g = (x*n_y + y)*NK + k, samples
+ * of a tail run beyond n_z are shaded and dropped; seg_view = (0, 0).  float32, each operation rounded on its own, in this order:
+ *   h_c = (hi_c - lo_c) / (float)(n_c - 1);   P_c(i) = lo_c + (float)i * h_c;
+ *   start = (P_x(x), P_y(y), P_z(32k));   end = (start_x, start_y, start_z + 32.0f * h_z);
+ *   density[(x*n_y + y)*n_z + z] = s * scale,   s = (float) of the half sigma of sample z - 32k, NaN taken as 0.
+ * Hash models (grid != NULL) go through rtxn_hashmlp_forward_segments(RTXN_SAMPLING_REGULAR), Composite-Frequency models
+ * through rtxn_mlp_forward_segments_compact.  The runs are shaded runs_per_pass at a time through ONE caller-provided
+ * workspace of rtxn_density_lattice_workspace_bytes(n, runs_per_pass) bytes (256-byte aligned; 0 with a message for bad
+ * arguments): 32 B of segment records + 256 B of radiance per run of a pass.  Results are bit-identical for every
+ * runs_per_pass.  Support is rtxn_occupancy_refresh_supported's rule, otherwise RTXN_ERR_UNSUPPORTED; rtxn_mlp_set_params
+ * must have run since the last rtxn_mlp_set_params_training of a frequency model (the inference kernels' rule). */
+typedef struct rtxn_density_lattice_args {
+  const rtxn_mlp* mlp;
+  const rtxn_hashgrid* grid;        /* NULL: Composite-Frequency model */
+  int n_dir_freqs;                  /* hash grid only */
+  const void* table_fp16;           /* hash grid only: half[rtxn_hashgrid_n_params] */
+  int n[3];                         /* nodes per axis, each in [2, 1024] */
+  float lo[3];                      /* lo < hi, both inside [-1, 1]^3 */
+  float hi[3];
+  float scale;                      /* finite; a trainer passes its density scale */
+  float* density;                   /* DEVICE float[n_x*n_y*n_z], index (x*n_y + y)*n_z + z */
+  void* workspace;
+  size_t workspace_bytes;
+  long runs_per_pass;               /* >= 1; n_x*n_y*ceil(n_z/32) shades the lattice in one pass */
+} rtxn_density_lattice_args;
+size_t rtxn_density_lattice_workspace_bytes(const int* n, long runs_per_pass);
+int rtxn_density_lattice(const rtxn_density_lattice_args* args, rtxn_stream_t stream);
+
+/* rtxn_isosurface: the indexed triangle mesh of {density > iso} over ANY device float lattice laid out as above (n_c in
+ * [2, 1024], lo < hi finite, iso finite), by MARCHING TETRAHEDRA.  Every lattice cube is cut into the 6 tetrahedra of the Kuhn
+ * triangulation along its (0,0,0)-(1,1,1) diagonal: for the axis permutation pi in lexicographic order (xyz, xzy, yxz, yzx,
+ * zxy, zyx) the tet is v0 = (0,0,0), v1 = v0 + e_pi1, v2 = v1 + e_pi2, v3 = (1,1,1).  The split is translation invariant, so
+ * neighbouring cubes agree on every shared face diagonal, and every tet edge leaves its lower node along one of 7 edge types,
+ * d in {+x, +y, +z, +x+y, +y+z, +x+z, +x+y+z} in this order: each edge has ONE owner (node, type), its vertex is computed
+ * once, and no cracks appear.
+ *   Values are sanitised when read: NaN -> 0.0f, +-Inf -> +-FLT_MAX.   inside(v) = v > iso.
+ *   An owned edge from node i (value a) to node i + d (value b) with inside(a) != inside(b) gets one vertex, float32, each
+ *   operation rounded on its own:  t = (iso - a) / (b - a), a NaN or t < 0 -> 0, t > 1 -> 1;
+ *                                  p_c = P_c(i_c) + t * ((float)d_c * h_c)      (h_c, P_c as above): finite for any input.
+ *   Cases, mask bit k = inside(v_k): one vertex a alone on its side gives the triangle (a o0, a o1, a o2), the others ascending;
+ *   two inside a < b and two outside c < d give (ac, ad, bd) and (ac, bd, bc); in each triangle the 2nd and 3rd entry are
+ *   swapped if the normal of the edge midpoints does not point from the inside vertices' centroid to the outside vertices':
+ *   triangles wind counter-clockwise seen from the side of LOWER density.  Degenerate triangles (a node equal to iso) are kept.
+ *   tools/gen_tet_table.py is the definition of the table the kernel includes.
+ *   Order: vertex ids in node order (x, y, z), then edge type; triangles in cube order (x, y, z), then tet, then table order.
+ *   The output is a pure function of the input.
+ *   normals (optional): g = the gradient of the sanitised lattice at a node -- per axis (v[i+1] - v[i-1]) / (2 h_c), at the
+ *   boundary (v[1] - v[0]) / h_c and (v[n-1] - v[n-2]) / h_c -- evaluated in double at both end nodes;
+ *   normal = -(g_a + t (g_b - g_a)) normalised, (0,0,0) for a zero gradient; finite for any input.
+ * counts = {n_vertices, n_triangles, overflow}: the TRUE totals are always written (a total above INT_MAX is reported as
+ * INT_MAX); only entries with an index below the capacity are written to the arrays, overflow = 1 if either total exceeds its
+ * capacity, and triangles keep their true vertex ids in that case.  A NULL array has capacity 0: with vertices == triangles ==
+ * NULL the call only counts.  Workspace: rtxn_isosurface_workspace_bytes(n) bytes (256-byte aligned; 0 with a message for bad
+ * arguments): 4 B per node, 16 B per row (x, y) and 32 KB.  Argument errors are RTXN_ERR_INVALID with a message naming the field
+ * before any device is touched. */
+typedef struct rtxn_isosurface_args {
+  const float* density;             /* DEVICE float[n_x*n_y*n_z], index (x*n_y + y)*n_z + z */
+  int n[3];
+  float lo[3];                      /* position of node (0, 0, 0) */
+  float hi[3];                      /* position of node (n_x-1, n_y-1, n_z-1) */
+  float iso;
+  float* vertices;                  /* DEVICE float[max_vertices][3], or NULL */
+  float* normals;                   /* DEVICE float[max_vertices][3], or NULL */
+  int* triangles;                   /* DEVICE int[max_triangles][3], or NULL */
+  int max_vertices;
+  int max_triangles;
+  int* counts;                      /* DEVICE int[3] */
+  void* workspace;
+  size_t workspace_bytes;
+} rtxn_isosurface_args;
+size_t rtxn_isosurface_workspace_bytes(const int* n);
+int rtxn_isosurface(const rtxn_isosurface_args* args, rtxn_stream_t stream);
+
 /* ---- one frame behind one call ------------------------------------------------------------------------------------
  * The per-image host sequence of the reference -- fill Params and optixLaunch (main.cu:473-508), copy every traversal
  * buffer to the host and re-pack it (:510-543, :646-673), thrust compaction (:631-637), launchSampler (:704),

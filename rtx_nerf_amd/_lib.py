@@ -245,6 +245,20 @@ class OccupancyRefreshArgs(C.Structure):
                 ("workspace_bytes", C.c_size_t), ("runs_per_pass", C.c_long)]
 
 
+class DensityLatticeArgs(C.Structure):
+    """struct rtxn_density_lattice_args (include/rtxn.h)."""
+    _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("n_dir_freqs", C.c_int), ("table_fp16", C.c_void_p),
+                ("n", C.c_int * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("scale", C.c_float), ("density", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("runs_per_pass", C.c_long)]
+
+
+class IsosurfaceArgs(C.Structure):
+    """struct rtxn_isosurface_args (include/rtxn.h)."""
+    _fields_ = [("density", C.c_void_p), ("n", C.c_int * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("iso", C.c_float),
+                ("vertices", C.c_void_p), ("normals", C.c_void_p), ("triangles", C.c_void_p), ("max_vertices", C.c_int),
+                ("max_triangles", C.c_int), ("counts", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/rtxn.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
 SYMBOLS = {
@@ -283,6 +297,10 @@ SYMBOLS = {
     "rtxn_occupancy_refresh_supported": (_I, [_P, _P, _I]),
     "rtxn_occupancy_refresh_workspace_bytes": (C.c_size_t, [_I, _L]),
     "rtxn_occupancy_refresh": (_I, [C.POINTER(OccupancyRefreshArgs), _P]),
+    "rtxn_density_lattice_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int), _L]),
+    "rtxn_density_lattice": (_I, [C.POINTER(DensityLatticeArgs), _P]),
+    "rtxn_isosurface_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int)]),
+    "rtxn_isosurface": (_I, [C.POINTER(IsosurfaceArgs), _P]),
     "rtxn_render_workspace_bytes": (C.c_size_t, [C.POINTER(RenderConfig)]),
     "rtxn_render_create": (_I, [C.POINTER(RenderConfig), _P, C.c_size_t, C.POINTER(_P)]),
     "rtxn_render_destroy": (_I, [_P]),

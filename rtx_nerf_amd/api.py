@@ -194,6 +194,151 @@ def occupancy_refresh(net, *, grid=None, table=None, grid_res, density, decay, t
     check(_lib.lib().rtxn_occupancy_refresh(C.byref(a), _stream()), "rtxn_occupancy_refresh")
 
 
+# --------------------------------------------------------------------------- mesh extraction
+def _box(who, aabb):
+    try:
+        lo, hi = [tuple(float(v) for v in b) for b in aabb]
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise _lib.RtxnError(f"{who}: aabb = {aabb!r}: ((lo_x, lo_y, lo_z), (hi_x, hi_y, hi_z))") from None
+    return lo, hi
+
+
+def density_lattice_runs(n):
+    """Runs of 32 z-nodes in a lattice of n = (n_x, n_y, n_z) nodes: the runs_per_pass that shades it in one pass."""
+    return n[0] * n[1] * ((n[2] + NUM_SAMPLES_PER_SEGMENT - 1) // NUM_SAMPLES_PER_SEGMENT)
+
+
+def density_lattice_workspace(n, runs_per_pass, device="cuda"):
+    """The workspace of density_lattice for passes of runs_per_pass runs (rtxn_density_lattice_workspace_bytes)."""
+    nbytes = int(_lib.lib().rtxn_density_lattice_workspace_bytes((C.c_int * 3)(*[int(v) for v in n]), int(runs_per_pass)))
+    if nbytes == 0:
+        check(1, "rtxn_density_lattice_workspace_bytes")
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def density_lattice(net, *, grid=None, table=None, resolution, aabb=((-1, -1, -1), (1, 1, 1)), scale=1.0, out=None, workspace=None,
+                    runs_per_pass=None):
+    """rtxn_density_lattice: sigma * scale of the model at the nodes of a regular lattice over aabb = (lo, hi) inside [-1, 1]^3,
+    through the fused inference kernels.  resolution: nodes per axis, an int or (n_x, n_y, n_z), each in [2, 1024].  Returns
+    float32 [n_x, n_y, n_z] (`out`, or a new tensor).  runs_per_pass: runs of 32 z-nodes shaded per pass (default: the lattice
+    in one pass up to 65536 runs); the result does not depend on it.  With out and workspace given the call only enqueues:
+    no host read, capturable."""
+    n = (int(resolution),) * 3 if np.isscalar(resolution) else tuple(int(v) for v in resolution)
+    if len(n) != 3:
+        raise _lib.RtxnError(f"density_lattice: resolution = {resolution!r}: an int or three")
+    lo, hi = _box("density_lattice", aabb)
+    runs = density_lattice_runs(n)
+    P = max(1, min(runs, int(runs_per_pass) if runs_per_pass else 1 << 16))
+    a = _lib.DensityLatticeArgs()
+    a.mlp, a.grid = net._h, (grid._h if grid is not None else None)
+    a.n_dir_freqs = int(grid.n_dir_freqs) if grid is not None else 0
+    a.table_fp16 = _ptr(table, torch.float16, "table")
+    a.n, a.lo, a.hi, a.scale = (C.c_int * 3)(*n), (C.c_float * 3)(*lo), (C.c_float * 3)(*hi), float(scale)
+    a.runs_per_pass = P
+    if grid is not None and table is not None and table.numel() < grid.n_params():
+        raise _lib.RtxnError(f"density_lattice: table holds {table.numel()} parameters, the grid has {grid.n_params()}")
+    if out is not None and out.numel() != n[0] * n[1] * n[2]:
+        raise _lib.RtxnError(f"density_lattice: out holds {out.numel()} elements, the lattice has {n[0] * n[1] * n[2]}")
+    if all(2 <= v <= 1024 for v in n):                        # otherwise the library names the field
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device="cuda")
+        if workspace is None:
+            workspace = density_lattice_workspace(n, P, device=out.device)
+    a.density = _ptr(out, torch.float32, "out")
+    a.workspace = _ptr(workspace, None, "workspace")
+    a.workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    check(_lib.lib().rtxn_density_lattice(C.byref(a), _stream()), "rtxn_density_lattice")
+    return out.view(n)
+
+
+def isosurface_workspace(n, device="cuda"):
+    """The workspace of isosurface for a lattice of n = (n_x, n_y, n_z) nodes (rtxn_isosurface_workspace_bytes)."""
+    nbytes = int(_lib.lib().rtxn_isosurface_workspace_bytes((C.c_int * 3)(*[int(v) for v in n])))
+    if nbytes == 0:
+        check(1, "rtxn_isosurface_workspace_bytes")
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def isosurface(density, iso, aabb, *, normals=True, max_vertices=None, max_triangles=None, counts=None, vertices=None, triangles=None,
+               normals_out=None, workspace=None):
+    """rtxn_isosurface: the indexed triangle mesh of {density > iso} by marching tetrahedra.  density: float32 [n_x, n_y, n_z]
+    on the device; aabb = (lo, hi): the positions of its first and last node.  Returns (vertices float32[V, 3], triangles
+    int32[T, 3], normals float32[V, 3] | None, counts int32[3] = (n_vertices, n_triangles, overflow) on the device); triangles
+    wind counter-clockwise seen from the side of lower density, normals point there.
+    With no capacities given the call counts first, reads the two totals on the host and allocates exactly.  With max_vertices
+    and max_triangles given it only enqueues -- no host read, capturable once counts, vertices, triangles, normals_out and
+    workspace are given too: the arrays come back at full capacity, entries past counts[0] / counts[1] are not written, and
+    counts[2] = 1 says a capacity was too small (the totals are still the true ones)."""
+    if density.dim() != 3:
+        raise _lib.RtxnError(f"isosurface: density of shape {tuple(density.shape)}: [n_x, n_y, n_z]")
+    n = tuple(int(v) for v in density.shape)
+    lo, hi = _box("isosurface", aabb)
+    dev = density.device
+    if (max_vertices is None) != (max_triangles is None):
+        raise _lib.RtxnError("isosurface: give both max_vertices and max_triangles, or neither")
+    if workspace is None and all(2 <= v <= 1024 for v in n):
+        workspace = isosurface_workspace(n, device=dev)
+    if counts is None:
+        counts = torch.empty(3, dtype=torch.int32, device=dev)
+    a = _lib.IsosurfaceArgs()
+    a.density = _ptr(density, torch.float32, "density")
+    a.n, a.lo, a.hi, a.iso = (C.c_int * 3)(*n), (C.c_float * 3)(*lo), (C.c_float * 3)(*hi), float(iso)
+    a.counts = _ptr(counts, torch.int32, "counts")
+    a.workspace = _ptr(workspace, None, "workspace")
+    a.workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    if counts.numel() < 3:
+        raise _lib.RtxnError(f"isosurface: counts holds {counts.numel()} elements, 3 needed")
+    if max_vertices is None:
+        check(_lib.lib().rtxn_isosurface(C.byref(a), _stream()), "rtxn_isosurface")        # vertices == triangles == NULL: counts only
+        max_vertices, max_triangles = (int(v) for v in counts[:2].tolist())
+        vertices = triangles = normals_out = None
+    max_vertices, max_triangles = int(max_vertices), int(max_triangles)
+    if vertices is None:
+        vertices = torch.empty((max(max_vertices, 0), 3), dtype=torch.float32, device=dev)
+    if triangles is None:
+        triangles = torch.empty((max(max_triangles, 0), 3), dtype=torch.int32, device=dev)
+    if normals and normals_out is None:
+        normals_out = torch.empty((max(max_vertices, 0), 3), dtype=torch.float32, device=dev)
+    if not normals:
+        normals_out = None
+    for nm, t, need in (("vertices", vertices, 3 * max_vertices), ("normals_out", normals_out, 3 * max_vertices),
+                        ("triangles", triangles, 3 * max_triangles)):
+        if t is not None and t.numel() < need:
+            raise _lib.RtxnError(f"isosurface: {nm} holds {t.numel()} elements, {need} needed")
+    a.vertices, a.normals = _ptr(vertices, torch.float32, "vertices"), _ptr(normals_out, torch.float32, "normals_out")
+    a.triangles = _ptr(triangles, torch.int32, "triangles")
+    a.max_vertices, a.max_triangles = max_vertices, max_triangles
+    check(_lib.lib().rtxn_isosurface(C.byref(a), _stream()), "rtxn_isosurface")
+    return vertices, triangles, normals_out, counts
+
+
+def write_ply(path, vertices, triangles, normals=None):
+    """A binary little-endian PLY of an indexed triangle mesh: vertices [V, 3] (x y z), optional normals [V, 3] (nx ny nz) as
+    float32, faces as uchar 3 + three int32.  Tensors are copied to the host; numpy arrays are taken as they are."""
+    def host(t, dtype):
+        return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=dtype).reshape(-1, 3)
+    v, f = host(vertices, "<f4"), host(triangles, "<i4")
+    cols = [v]
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        nrm = host(normals, "<f4")
+        if nrm.shape != v.shape:
+            raise ValueError(f"write_ply: {nrm.shape[0]} normals for {v.shape[0]} vertices")
+        cols.append(nrm)
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"write_ply: a triangle names vertex {int(f.max() if f.max() >= v.shape[0] else f.min())} of {v.shape[0]}")
+    faces = np.empty(f.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    faces["n"], faces["v"] = 3, f
+    with open(path, "wb") as out:
+        out.write((f"ply\nformat binary_little_endian 1.0\ncomment rtx_nerf_amd isosurface\nelement vertex {v.shape[0]}\n{props}"
+                   f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii"))
+        out.write(np.ascontiguousarray(np.concatenate(cols, axis=1)).tobytes())
+        out.write(faces.tobytes())
+
+
 # --------------------------------------------------------------------------- CSR compaction
 def scan_hits(num_hits, indices=None, total=None, workspace=None):
     """thrust::reduce + thrust::exclusive_scan (main.cu:631-637); total stays on the device."""

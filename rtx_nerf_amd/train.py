@@ -1849,6 +1849,47 @@ class Trainer:
             raise RuntimeError("occupancy_stats: call refresh_occupancy() first")
         return int(self._occ_out[0].item()) / float(self.R ** 3), float(self._occ_out[1].item())
 
+    # ------------------------------------------------------------------------------------------------ mesh extraction
+    @torch.no_grad()
+    def density_lattice(self, resolution=128, aabb=None, weights="live", out=None):
+        """sigma * density_scale of the model at the nodes of a regular lattice (api.density_lattice): float32
+        [n_x, n_y, n_z] over aabb = (lo, hi) inside the cube (default: all of it), from the live weights or, weights="ema", from
+        the averaged ones (sync_ema() is called first, as by evaluate()).  Frequency models re-pack their inference weights first
+        (sync_inference_weights)."""
+        if weights not in ("live", "ema"):
+            raise ValueError(f"density_lattice: weights = {weights!r}: 'live' or 'ema'")
+        if weights == "ema" and self._ema is None:
+            raise RuntimeError("density_lattice(weights='ema'): this trainer was made without ema_decay")
+        if not api.occupancy_refresh_supported(self.net, self.hg):
+            raise api._lib.RtxnError("extract_mesh: no fused inference kernel for this model (built: frequency models, and hash "
+                                     "models 64 wide with <= 8 hidden layers, 2 features per level and an even number of levels); "
+                                     "use update_occupancy(), which evaluates the cells through the training path")
+        if self.encoding != "hash":
+            self.sync_inference_weights()
+        net, table = self.net, (self.table if self.encoding == "hash" else None)
+        if weights == "ema":
+            self.sync_ema()
+            net, table = self._ema_net, (self._ema_table16 if self.encoding == "hash" else None)
+        return api.density_lattice(net, grid=self.hg, table=table, resolution=resolution,
+                                   aabb=((-1.0,) * 3, (1.0,) * 3) if aabb is None else aabb, scale=self.density_scale, out=out)
+
+    @torch.no_grad()
+    def extract_mesh(self, resolution=128, *, iso, aabb=None, weights="live", normals=True):
+        """The triangle mesh of {sigma * density_scale > iso}: density_lattice() at `resolution` nodes per axis (an int or three)
+        and api.isosurface() over it (marching tetrahedra on the device).  Returns (vertices float32[V, 3],
+        triangles int32[T, 3], normals float32[V, 3] | None) on the device; api.write_ply() stores them.
+        iso has no default: it is an extinction per unit length of the cube's coordinates, sigma * density_scale, the quantity the
+        compositor integrates -- a surface at iso is where a ray loses a fraction 1 - exp(-iso * d) over a length d.
+        Vertices are in the CUBE's coordinates, [-1, 1]^3, the ones start_points and the occupancy grid use: the loader's camera
+        ORIGINS are divided by 10 on their way in (origin_scale 0.1, quirk Q2), so a vertex p lies at 10 p in the units of the
+        poses' translations; rotations are unchanged.  Triangles wind counter-clockwise seen from outside (lower density), and
+        normals point there.  Counts once, reads the two totals on the host and allocates exactly; raises the refusal of
+        refresh_occupancy() for a model without a fused inference kernel."""
+        box = ((-1.0,) * 3, (1.0,) * 3) if aabb is None else aabb
+        lattice = self.density_lattice(resolution, box, weights)
+        v, t, nrm, _ = api.isosurface(lattice, iso, box, normals=normals)
+        return v, t, nrm
+
     def _set_occupancy(self, occ):
         """Install a new occupancy bitfield.  The four traversal inputs (fine bits, 4^3 mip, bricks, 16^3 mip) keep their
         ADDRESSES once they exist: capture_step() bakes those device pointers into the traversal nodes of its graphs, so the
