@@ -152,6 +152,12 @@ static int run_frame(int argc, char** argv) {
   ws_bytes = rtxn_render_workspace_bytes(&cfg);
   HIP_CHECK(hipMalloc(&d_ws, ws_bytes));
   RTXN_CHECK(rtxn_render_create(&cfg, d_ws, ws_bytes, &renderer));
+  // per-ray shading: layer 0's direction product once per ray instead of once per segment (same pixels); a second workspace
+  void* d_ray_ws = nullptr;
+  if (const size_t ray_bytes = rtxn_render_ray_workspace_bytes(&cfg)) {
+    HIP_CHECK(hipMalloc(&d_ray_ws, ray_bytes));
+    RTXN_CHECK(rtxn_render_set_ray_workspace(renderer, d_ray_ws, ray_bytes));
+  }
 
   const size_t n_rays = (size_t)width * height;
   float* d_pixels;

@@ -310,6 +310,28 @@ int rtxn_mlp_forward_segments_compact(const rtxn_mlp* m, const float* start_poin
                                       void* radiance_half4, rtxn_stream_t stream);
 int rtxn_volrender_fwd_compact(const void* radiance_half4, const int* num_hits, const int* indices, int batch_size,
                                int num_samples_per_hit, float* pixels, rtxn_stream_t stream);
+
+/* The per-ray form of the two segment entries above (64- and 128-wide Composite-Frequency models:
+ * rtxn_mlp_ray_direction_bias_supported; others RTXN_ERR_UNSUPPORTED).  A segment's view direction is its ray's, so the
+ * direction part of the first layer -- W values, the same for every sample of every segment of a ray -- is formed once per
+ * ray and the segment kernel starts the first layer from it:
+ *   rtxn_mlp_ray_direction_bias   ray_bias float[n_rays][W] (16-byte aligned) from viewing_direction float2[n_rays], as
+ *                                 rtxn_trace_grid writes it; rows of rays with num_hits[ray] <= 0 are left untouched.  No host
+ *                                 read: capturable.  Must be called again after rtxn_mlp_set_params.
+ *   rtxn_mlp_forward_segments_rays[_compact]   as rtxn_mlp_forward_segments[_compact] with seg_ray (int per segment:
+ *                                 rtxn_trace_params.seg_ray, the row of ray_bias; read clamped to n_rays - 1) and ray_bias in
+ *                                 place of seg_view.
+ * Outputs are bit-identical to the seg_view entries given seg_view[k] == viewing_direction[seg_ray[k]]: the same encoder, the
+ * same MFMA instruction and the same k order form the same W values. */
+int rtxn_mlp_ray_direction_bias_supported(const rtxn_mlp* m);
+int rtxn_mlp_ray_direction_bias(const rtxn_mlp* m, const float* viewing_direction, const int* num_hits, int n_rays,
+                                float* ray_bias, rtxn_stream_t stream);
+int rtxn_mlp_forward_segments_rays(const rtxn_mlp* m, const float* start_points, const float* end_points, const int* seg_ray,
+                                   const float* ray_bias, int n_rays, const int* total_segments, long max_segments,
+                                   float* radiance, float* t_vals, rtxn_stream_t stream);
+int rtxn_mlp_forward_segments_rays_compact(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                           const int* seg_ray, const float* ray_bias, int n_rays, const int* total_segments,
+                                           long max_segments, void* radiance_half4, rtxn_stream_t stream);
 /* The same hand-over for RTXN_VR_NERF (midpoint samples, exclusive transmittance): every sample of a segment has the same
  * world-space step |end - start| / K (x density scale), so the compositor takes ONE float per segment (segment_step[P], written
  * by rtxn_hashmlp_forward_segments) instead of launch_volrender_cuda's ray_hit[P*K].  Pixels bit-identical to
@@ -637,6 +659,21 @@ int rtxn_render_slot_buffers(rtxn_render* r, int slot, const int** num_hits, con
                              const int** total_segments, const float** start_points, const float** end_points,
                              const float** seg_view, const void** radiance, const float** t_vals, const float** segment_step,
                              const float** viewing_direction);
+/* Per-ray shading of the frequency model's frame (rtxn_mlp_forward_segments_rays*): with a RAY WORKSPACE set, every frame entry
+ * -- serial, pipelined, captured -- also has the write pass store each segment's slot-local ray (rtxn_trace_params.seg_ray),
+ * forms layer 0's direction product once per ray with a hit right behind the counting pass, on the stream the traversal runs
+ * on (rtxn_mlp_ray_direction_bias), and shades from that table: the same radiance and pixels bit for bit, 1.6 % fewer MFMAs
+ * and 6 % fewer LDS reads in the kernel that is the frame.  The table is per slot and lives as long as the slot's segments.
+ * The workspace is the caller's (256-byte aligned), per slot int[max_segments] + float[max_rays][n_neurons] -- dense over the
+ * rays, 512 B per ray of a 128-wide model, of which only rows of rays with a hit are written or read;
+ * rtxn_render_ray_workspace_bytes is 0 (and says nothing) for models without per-ray kernels: hash-grid and 256-wide ones.
+ * rtxn_render_set_ray_workspace synchronises the device; workspace == NULL turns per-ray shading off again.  The main
+ * workspace, the termination rounds (which gather seg_view) and the public segment entries are unchanged.  A pipelined frame
+ * that follows rtxn_mlp_set_params* has its traversal wait for `stream` once: the table is built from the packed weights.
+ * rtxn_render_ray_buffers: the slot's two buffers for inspection, NULL without a ray workspace. */
+size_t rtxn_render_ray_workspace_bytes(const rtxn_render_config* cfg);
+int rtxn_render_set_ray_workspace(rtxn_render* r, void* workspace, size_t workspace_bytes);
+int rtxn_render_ray_buffers(rtxn_render* r, int slot, const int** seg_ray, const float** ray_bias);
 
 /* ---- early termination of the frame entry --------------------------------------------------------------------------
  * Not in the reference, whose loop shades every sample of every ray (main.cu:703-737).  With a termination set,

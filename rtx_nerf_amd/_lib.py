@@ -289,6 +289,10 @@ SYMBOLS = {
     "rtxn_mlp_forward_radiance": (_I, [_P, _P, _P, _L, _P]),
     "rtxn_mlp_forward_segments": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _P]),
     "rtxn_mlp_forward_segments_compact": (_I, [_P, _P, _P, _P, _P, _L, _P, _P]),
+    "rtxn_mlp_ray_direction_bias_supported": (_I, [_P]),
+    "rtxn_mlp_ray_direction_bias": (_I, [_P, _P, _P, _I, _P, _P]),
+    "rtxn_mlp_forward_segments_rays": (_I, [_P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P]),
+    "rtxn_mlp_forward_segments_rays_compact": (_I, [_P, _P, _P, _P, _P, _I, _P, _L, _P, _P]),
     "rtxn_volrender_fwd_compact": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "rtxn_volrender_fwd_compact_nerf": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "rtxn_volrender_fwd_aux": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
@@ -314,6 +318,9 @@ SYMBOLS = {
     "rtxn_render_drain": (_I, [_P, _P]),
     "rtxn_render_status": (_I, [_P, _I, C.POINTER(RenderStats)]),
     "rtxn_render_slot_buffers": (_I, [_P, _I] + [C.POINTER(_P)] * 11),
+    "rtxn_render_ray_workspace_bytes": (C.c_size_t, [C.POINTER(RenderConfig)]),
+    "rtxn_render_set_ray_workspace": (_I, [_P, _P, C.c_size_t]),
+    "rtxn_render_ray_buffers": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P)]),
     "rtxn_render_termination_workspace_bytes": (C.c_size_t, [C.POINTER(RenderConfig), C.POINTER(RenderTermination)]),
     "rtxn_render_set_termination": (_I, [_P, C.POINTER(RenderTermination), _P, C.c_size_t]),
     "rtxn_render_termination_status": (_I, [_P, _I, C.POINTER(RenderTerminationStats)]),

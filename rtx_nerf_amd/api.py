@@ -647,6 +647,43 @@ def _net_forward_segments_compact(self, start_points, end_points, seg_view, tota
 Network.forward_segments_compact = _net_forward_segments_compact
 
 
+def _net_ray_direction_bias_supported(self):
+    """True for the models whose segment kernels have the per-ray form (64 / 128 wide, Composite-Frequency)."""
+    return bool(_lib.lib().rtxn_mlp_ray_direction_bias_supported(self._h))
+
+
+def _net_ray_direction_bias(self, viewing_direction, num_hits, ray_bias):
+    """Layer 0's direction product of every ray that hit: ray_bias float[n_rays, n_neurons] (rtxn_mlp_ray_direction_bias)."""
+    n = int(num_hits.numel())
+    check(_lib.lib().rtxn_mlp_ray_direction_bias(
+        self._h, _ptr(viewing_direction, torch.float32, "viewing_direction"), _ptr(num_hits, torch.int32, "num_hits"), n,
+        _ptr(ray_bias, torch.float32, "ray_bias"), _stream()), "rtxn_mlp_ray_direction_bias")
+    return ray_bias
+
+
+def _net_forward_segments_rays(self, start_points, end_points, seg_ray, ray_bias, total_segments, max_segments, radiance,
+                               t_vals=None):
+    """forward_segments (float32 radiance) or forward_segments_compact (float16) with the segments' ray index and the rays'
+    table of ray_direction_bias() in place of seg_view."""
+    n_rays = int(ray_bias.shape[0])
+    args = (self._h, _ptr(start_points, torch.float32, "start_points"), _ptr(end_points, torch.float32, "end_points"),
+            _ptr(seg_ray, torch.int32, "seg_ray"), _ptr(ray_bias, torch.float32, "ray_bias"), n_rays,
+            _ptr(total_segments, torch.int32, "total_segments"), max_segments)
+    if radiance.dtype == torch.float16:
+        check(_lib.lib().rtxn_mlp_forward_segments_rays_compact(*args, _ptr(radiance, torch.float16, "radiance_half4"), _stream()),
+              "rtxn_mlp_forward_segments_rays_compact")
+    else:
+        check(_lib.lib().rtxn_mlp_forward_segments_rays(*args, _ptr(radiance, torch.float32, "radiance"),
+                                                        _ptr(t_vals, torch.float32, "t_vals"), _stream()),
+              "rtxn_mlp_forward_segments_rays")
+    return radiance
+
+
+Network.ray_direction_bias_supported = _net_ray_direction_bias_supported
+Network.ray_direction_bias = _net_ray_direction_bias
+Network.forward_segments_rays = _net_forward_segments_rays
+
+
 def volrender_compact(radiance_half4, num_hits, indices, batch_size, num_samples_per_hit, pixels):
     """RTXN_VR_COMPAT compositing of half[N, 4] radiance with the implicit REGULAR t_vals (i + 1) / K."""
     check(_lib.lib().rtxn_volrender_fwd_compact(_ptr(radiance_half4, torch.float16, "radiance_half4"),

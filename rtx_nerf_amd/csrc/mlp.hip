@@ -53,6 +53,8 @@ namespace {
 // Build-time knobs of the inference kernels (defaults are the measured best):
 //   RTXN_SHARE_DIR 1: segment input computes a segment's direction features and their layer-0 product once per segment
 //                     (mlp_fwd16_kernel: rtxn::dir_bias16; the 256-wide kernel: the features only, DirShare16)
+//                     and the frame forms that product once per RAY (ray_dir_bias_kernel, IN_MODE 2 of mlp_fwd16_kernel);
+//                     0: neither -- no per-ray kernels are built and rtxn_mlp_ray_direction_bias_supported says so
 //   RTXN_PIPE16 depth of the A-fragment register ring                        -- mlp_internal.h
 //   RTXN_STAMPS diagnostic build: per-stage s_memtime stamps of block 0 (tools/probe/stamps.py); never in the shipped library
 #ifndef RTXN_SHARE_DIR
@@ -67,16 +69,21 @@ struct FwdArgs {
   // IN_MODE 0
   const float* input;
   long n;
-  // IN_MODE 1
+  // IN_MODE 1, 2
   const float* start;
   const float* end;
-  const float* seg_view;
+  const float* seg_view;   // IN_MODE 1
   const int* total_segments;
   long max_segments;
   // outputs
   _Float16* out_half;  // [n][16] (OUT_MODE 0) or [n][4] (OUT_MODE 3)
   float4* radiance;    // [n]
-  float* t_vals;       // [n] or NULL (IN_MODE 1 only)
+  float* t_vals;       // [n] or NULL (IN_MODE 1, 2 only)
+  // IN_MODE 2: the segments' rays and the rays' layer-0 direction products (ray_dir_bias_kernel).  Behind everything else: the
+  // kernels of the other modes keep the argument offsets, and with them the scalar register allocation, they were tuned with.
+  const int* seg_ray;
+  const float* ray_bias;   // float[n_rays][W]
+  int n_rays;
 };
 
 // ---------------------------------------------------------------------------
@@ -421,17 +428,37 @@ __device__ unsigned g_stamps[8 * kStampTiles * kStampSlots];
 #define RTXN_STAMP(k)
 #endif
 
+// The position k-steps of layer 0 alone, densely: fragment (rt, kk) of the LDS image is chunk rt * KS0 + KSD + kk of the
+// packed layer (IN_MODE 2 of mlp_fwd16_kernel, whose direction k-steps were multiplied per ray).  One fragment per wave per round.
+template <int RT, int KS0, int KSD, int KSP, int THREADS>
+__device__ __forceinline__ void stage_layer0_position(const uint8_t* __restrict__ g, uint8_t* lds_buf, int tid) {
+  constexpr int NF = RT * KSP, WAVES = THREADS / 64;
+  static_assert(NF % WAVES == 0, "whole rounds");
+#pragma unroll
+  for (int i = 0; i < NF / WAVES; ++i) {
+    const int f = i * WAVES + (tid >> 6);
+    const uint8_t* src = g + ((f / KSP) * KS0 + KSD + f % KSP) * 1024 + (tid & 63) * 16;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)(lds_buf + f * 1024), 16, 0, 0);
+  }
+}
+
+// IN_MODE 0: samples float[n][5]; 1: packed segments with seg_view (the direction product once per segment, dir_bias16);
+// 2: packed segments with their ray index and the per-ray table of that product (ray_dir_bias_kernel).
 // OUT_MODE 0: half[n][16]; 1: float4 radiance (+ t_vals); 3: compact half4.
 template <int W, int PD, int PF, int DD, int DF, int IN_MODE, int OUT_MODE>
 __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
   static_assert(RTXN_NW == 8, "8-wave blocks");
+  static_assert(IN_MODE >= 0 && IN_MODE <= 2, "input modes: samples, segments, segments with per-ray direction bias");
   static_assert(OUT_MODE == 0 || OUT_MODE == 1 || OUT_MODE == 3, "output modes: half16, radiance, compact half4");
+  constexpr bool SEG = IN_MODE != 0, RAYB = IN_MODE == 2;
   constexpr int CT = 4, THREADS = 512;
   constexpr int TILE = 512, TILE_SEGS = 16;             // samples / segments per block per iteration
   using ES = EncSpec16<PD, PF, DD, DF>;
   constexpr int RT = W / 16, KS = W / 32, KS0 = ES::k0 / 32;
   constexpr int NB = KS0 > KS ? KS0 : KS;
-  constexpr int L0_BYTES = KS0 * RT * 1024, HID_BYTES = KS * RT * 1024, OUT_BYTES = 4 * KS * 1024;
+  constexpr int L0_PACKED = KS0 * RT * 1024;            // layer 0 in the packed buffer; in LDS: all of it, or its position k-steps
+  constexpr int L0_BYTES = (RAYB ? ES::KSP : KS0) * RT * 1024, HID_BYTES = KS * RT * 1024, OUT_BYTES = 4 * KS * 1024;
   constexpr int RES_BYTES = L0_BYTES + OUT_BYTES;       // [layer 0 | output layer x 4 rotations | 3 x HID_BYTES]
   constexpr bool ROT = OUT_MODE != 0;                   // 4-output epilogue: column tile v's outputs land in lane group v
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -446,7 +473,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
   // and fetch decision through VCC and the staging jobs behind vector branches (measured: +35 % VALU instructions).
   long total_seg = 0;
   int n_tiles;
-  if (IN_MODE == 1) {
+  if (SEG) {
     total_seg = *a.total_segments;
     if (total_seg > a.max_segments) total_seg = a.max_segments;
     n_tiles = (int)((total_seg + TILE_SEGS - 1) / TILE_SEGS);
@@ -458,10 +485,11 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
   if ((int)blockIdx.x >= n_tiles) return;
 
   const int n_layers = a.n_hidden + 1;
-  auto layer_off = [&](int l) -> unsigned { return l == 0 ? 0u : (unsigned)L0_BYTES + (unsigned)(l - 1) * HID_BYTES; };
+  auto layer_off = [&](int l) -> unsigned { return l == 0 ? 0u : (unsigned)L0_PACKED + (unsigned)(l - 1) * HID_BYTES; };
   const int grp = wave_u >> 2;              // 0: leading wave group, 1: one stage behind (file header)
   const int n_hid = n_layers - 2;
-  stage<L0_BYTES, THREADS>(a.packed, smem, tid);
+  if constexpr (RAYB) stage_layer0_position<RT, KS0, ES::KSD, ES::KSP, THREADS>(a.packed, smem, tid);
+  else stage<L0_BYTES, THREADS>(a.packed, smem, tid);
   stage<OUT_BYTES, THREADS>(a.packed + layer_off(n_layers - 1), smem + L0_BYTES, tid);
   int qs = 0;                               // hidden stages this wave has begun (ring slot = qs % 3)
 
@@ -471,7 +499,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
                               0.5f * (float)(1u << pos16_start(2, g))};
   float xq[CT][5];                          // inputs of the lane's four samples, already scaled for its lane group
   auto sample_of = [&](int tile, int ct, bool& valid) -> long {
-    if (IN_MODE == 1) {
+    if (SEG) {
       const long seg = (long)tile * TILE_SEGS + wave_u * 2 + (ct >> 1);
       valid = seg < total_seg;
       return seg * 32 + 16 * (ct & 1) + c;
@@ -488,11 +516,12 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
   // element right behind the loads -- register tuples versus loop phis -- and the copies waited for the data all the same.)
   typedef float f3v __attribute__((ext_vector_type(3)));
   typedef float f2v __attribute__((ext_vector_type(2)));
-  f3v raw_s[CT / 2], raw_e[CT / 2];         // segments: start, end, view of the wave's two
+  f3v raw_s[CT / 2], raw_e[CT / 2];         // segments: start, end and view (or ray) of the wave's two
   f2v raw_v[CT / 2];
-  float raw_x[IN_MODE == 1 ? 1 : CT][5];    // samples: x[5] of the lane's four
+  int raw_r[CT / 2];
+  float raw_x[SEG ? 1 : CT][5];    // samples: x[5] of the lane's four
   auto fetch_inputs = [&](int tile) {
-    if (IN_MODE == 1) {
+    if (SEG) {
 #pragma unroll
       for (int sgi = 0; sgi < CT / 2; ++sgi) {
         bool valid_in;
@@ -500,7 +529,8 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
         const long sg = valid_in ? (samp_in >> 5) : 0;
         __builtin_memcpy(&raw_s[sgi], a.start + 3 * sg, 12);
         __builtin_memcpy(&raw_e[sgi], a.end + 3 * sg, 12);
-        __builtin_memcpy(&raw_v[sgi], a.seg_view + 2 * sg, 8);
+        if constexpr (RAYB) raw_r[sgi] = a.seg_ray[sg];
+        else __builtin_memcpy(&raw_v[sgi], a.seg_view + 2 * sg, 8);
       }
     } else {
 #pragma unroll
@@ -516,7 +546,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
   auto form_inputs = [&]() {
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      if (IN_MODE == 1) {
+      if (SEG) {
         const int sgi = ct >> 1;
         const float t = (float)(16 * (ct & 1) + c) * (1.0f / 32);
 #pragma unroll
@@ -524,8 +554,8 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
           const float og = raw_s[sgi][k];
           xq[ct][k] = fmaf(t, raw_e[sgi][k] - og, og) * pos_scale[k];   // REGULAR sample, sampler.cu:52-66; exact scaling
         }
-        xq[ct][3] = raw_v[sgi][0] * dir_scale;
-        xq[ct][4] = raw_v[sgi][1] * dir_scale;
+        xq[ct][3] = RAYB ? 0.0f : raw_v[sgi][0] * dir_scale;     // per-ray form: the direction never enters the kernel
+        xq[ct][4] = RAYB ? 0.0f : raw_v[sgi][1] * dir_scale;
       } else {
 #pragma unroll
         for (int k = 0; k < 5; ++k) xq[ct][k] = raw_x[ct][k] * (k < PD ? pos_scale[k < PD ? k : 0] : dir_scale);
@@ -548,7 +578,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
     const bool more = tile + tile_step < n_tiles;       // this block has another tile after this one
     RTXN_STAMP(0);
     form_inputs();
-    if (IN_MODE == 1 && OUT_MODE == 1 && a.t_vals) {
+    if (SEG && OUT_MODE == 1 && a.t_vals) {
       // REGULAR t_vals (sampler.cu:65: post-increment) of the wave's 64 samples, one per lane: lane l is sample l of the two
       // segments.  The lane index goes through an empty asm so that the per-lane address is formed here, not hoisted out of
       // the tile loop and carried in VGPRs through layer 0's register peak (it was, and got spilled).
@@ -558,10 +588,17 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
       if (seg < total_seg) a.t_vals[seg * 32 + (lane_t & 31)] = (float)((lane_t & 31) + 1) * (1.0f / 32);
     }
     // Segment input: layer 0's direction k-steps once per segment (dir_bias16), the position k-steps per sample from there.
-    constexpr bool BIAS = RTXN_SHARE_DIR && IN_MODE == 1;
+    // Per-ray form: the product comes from the table, segment c & 1's rows for column c as dir_bias16 would leave them.  Loaded
+    // here, an encode ahead of its first reader; the ray index came in with the records, one tile ahead.
+    constexpr bool BIAS = (RTXN_SHARE_DIR && SEG) || RAYB;
+    rtxn::floatx4 bias[BIAS ? RT : 1];
+    if constexpr (RAYB) {
+      const unsigned ray = min((unsigned)((c & 1) ? raw_r[1] : raw_r[0]), (unsigned)(a.n_rays - 1));
+      rtxn::load_ray_bias<RT>(a.ray_bias + (size_t)ray * W + 4 * g, bias);
+    }
     int dirs[CT / 2][DirShare16<PD, PF, DD, DF>::n_dwords];
     half8 bd[ES::KSD];
-    if constexpr (BIAS) encode_direction_pair<ES, PD, DD, CT>(xq, c, bd);
+    if constexpr (BIAS && !RAYB) encode_direction_pair<ES, PD, DD, CT>(xq, c, bd);
     half8 bf[NB][CT], bg[NB][CT];
     rtxn::floatx4 acc2[2][CT];
     rtxn::StageJob sj;
@@ -632,7 +669,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
         long samp;
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));   // form the store address HERE (see t_vals above): not a loop invariant to carry around
-        if (IN_MODE == 1) {
+        if (SEG) {
           const long seg = (long)tile * TILE_SEGS + wave_u * 2 + (lane_e >> 5);
           valid = seg < total_seg;
           samp = seg * 32 + (lane_e & 31);
@@ -654,8 +691,10 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
       RTXN_STAMP(1);
       const uint8_t* w = begin_stage(0);
       RTXN_STAMP(2);
-      if constexpr (BIAS) {
-        rtxn::floatx4 bias[RT];
+      if constexpr (RAYB) {
+        rtxn::ray_bias_settle<RT>(bias);
+        rtxn::pipe_layer16<RT, ES::KSP, NB, CT, false, ES::KSP, 0, true>(w, sj, bf, bg, acc2, wave_u, lane, bias);
+      } else if constexpr (BIAS) {
         rtxn::dir_bias16<RT, ES::KSD, KS0>(w, bd, bias, lane);
         rtxn::pipe_layer16<RT, ES::KSP, NB, CT, false, KS0, ES::KSD, true>(w, sj, bf, bg, acc2, wave_u, lane, bias);
       } else {
@@ -694,6 +733,50 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd16_kernel(FwdArgs a) {
     for (int i = lane; i < kStampTiles * kStampSlots; i += 64)
       g_stamps[wave_u * kStampTiles * kStampSlots + i] = stamp_lds[wave_u * kStampTiles * kStampSlots + i];
 #endif
+}
+
+// Layer 0's direction product once per RAY (the table IN_MODE 2 reads): a wave takes 16 rays as the 16 columns of its MFMAs.
+// Everything is what the segment kernel does for a segment -- encode_direction_pair's fragments (the ray's own view in every
+// column), v_mfma_f32_16x16x32_f16 over the KSD direction k-steps from a zero C, in k order -- so the 4 values lane (c, g)
+// holds of row tile rt are bit for bit dir_bias16's, and they are stored as that register image: bias[ray c][16 rt + 4 g + e].
+// A fragments come straight from the packed layer (L2; 16-32 KiB shared by every wave).  Rays without a hit are not written
+// (nothing reads them) and a wave none of whose rays hit leaves at once: 12 % of the bench frame's rays hit.
+template <int W, int PD, int PF, int DD, int DF>
+__global__ __launch_bounds__(256) void ray_dir_bias_kernel(const uint8_t* __restrict__ packed, const float* __restrict__ view_dirs,
+                                                           const int* __restrict__ num_hits, int n_rays, float* __restrict__ bias) {
+  using ES = EncSpec16<PD, PF, DD, DF>;
+  constexpr int RT = W / 16, KS0 = ES::k0 / 32, KSD = ES::KSD;
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const long ray = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + c;
+  const bool live = ray < n_rays && num_hits[ray] > 0;
+  if (__ballot(live) == 0) return;
+  const long src = ray < n_rays ? ray : 0;
+  const float dir_scale = 0.5f * (float)(1u << (ES::FBD * g));
+  rtxn::int4v t[KSD];
+#pragma unroll
+  for (int kk = 0; kk < KSD; ++kk)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int D = 4 * kk + e;
+      t[kk][e] = (D >= ES::ND && D < ES::ND + ES::NPADW) ? 0x3c003c00 : 0;
+    }
+#pragma unroll
+  for (int dd = 0; dd < DD; ++dd) {
+    int d[3];
+    octave_unit<ES::FBD>(view_dirs[2 * src + dd] * dir_scale, d);
+#pragma unroll
+    for (int k = 0; k < ES::FBD; ++k) t[(dd * ES::FBD + k) / 4][(dd * ES::FBD + k) % 4] = d[k];
+  }
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    rtxn::floatx4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int kk = 0; kk < KSD; ++kk) {
+      const half8 af = *reinterpret_cast<const half8*>(packed + ((rt * KS0 + kk) * 64 + lane) * 16);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, __builtin_bit_cast(half8, t[kk]), acc, 0, 0, 0);
+    }
+    if (live) *reinterpret_cast<rtxn::floatx4*>(bias + ray * W + 16 * rt + 4 * g) = acc;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -957,12 +1040,15 @@ __global__ __launch_bounds__(kThreads256, 2) void mlp_fwd256x16_kernel(FwdArgs a
 // host side
 // ---------------------------------------------------------------------------
 typedef void (*fwd_fn)(FwdArgs);
+typedef void (*ray_bias_fn)(const uint8_t*, const float*, const int*, int, float*);
 
 struct Variant {
   int W, PD, PF, DD, DF;
-  fwd_fn fn[2][4];    // [IN_MODE][OUT_MODE]: OUT_MODE 0 half[n][16], 1 float4 radiance (+ t_vals), 3 compact half4 (IN_MODE 1 only)
+  fwd_fn fn[3][4];    // [IN_MODE][OUT_MODE]: OUT_MODE 0 half[n][16], 1 float4 radiance (+ t_vals), 3 compact half4 (IN_MODE 1, 2 only)
+  ray_bias_fn ray_bias;   // the table IN_MODE 2 reads; NULL: this variant has no per-ray form
   int k0;             // first-layer K as staged
   size_t lds;
+  size_t lds_ray;     // IN_MODE 2: layer 0's direction k-steps are not staged
   int threads;        // block size
   int blocks_per_cu;  // persistent grid = CUs x this
   int tile;           // samples per block per iteration (segments: tile / 32)
@@ -980,9 +1066,15 @@ Variant make_variant() {
   v.fn[1][0] = mlp_fwd16_kernel<W, PD, PF, DD, DF, 1, 0>;
   v.fn[1][1] = mlp_fwd16_kernel<W, PD, PF, DD, DF, 1, 1>;
   v.fn[1][3] = mlp_fwd16_kernel<W, PD, PF, DD, DF, 1, 3>;
+#if RTXN_SHARE_DIR
+  v.fn[2][1] = mlp_fwd16_kernel<W, PD, PF, DD, DF, 2, 1>;
+  v.fn[2][3] = mlp_fwd16_kernel<W, PD, PF, DD, DF, 2, 3>;
+  v.ray_bias = ray_dir_bias_kernel<W, PD, PF, DD, DF>;
+#endif
   v.k0 = ES::k0;
   // [layer 0 | output layer x 4 rotations | 3 ring slots of one hidden layer]
   v.lds = (size_t)(ES::k0 / 32) * (W / 16) * 1024 + 4 * (size_t)(W / 32) * 1024 + 3 * (size_t)(W / 32) * (W / 16) * 1024;
+  v.lds_ray = v.lds - (size_t)ES::KSD * (W / 16) * 1024;
   v.threads = 512;
   v.blocks_per_cu = 1;
   v.tile = 512;
@@ -1045,7 +1137,7 @@ struct Pcg32 {
 // n_units: samples (in_mode 0) or segments (in_mode 1) the launch may have to cover
 int launch_fwd(const rtxn_mlp* m, FwdArgs& a, int in_mode, int out_mode, long n_units, hipStream_t s) {
   const Variant& v = variants()[m->variant];
-  const long per_tile = in_mode == 1 ? v.tile / 32 : v.tile;
+  const long per_tile = in_mode != 0 ? v.tile / 32 : v.tile;
   const long n_tiles = (n_units + per_tile - 1) / per_tile;
   a.packed = static_cast<const uint8_t*>(m->packed);
   a.n_hidden = m->cfg.n_hidden_layers;
@@ -1058,8 +1150,9 @@ int launch_fwd(const rtxn_mlp* m, FwdArgs& a, int in_mode, int out_mode, long n_
   if (grid < 1) grid = 1;
   fwd_fn fn = v.fn[in_mode][out_mode];
   if (!fn) { rtxn::set_error("mlp forward: no kernel for input mode %d / output mode %d", in_mode, out_mode); return RTXN_ERR_UNSUPPORTED; }
-  RTXN_HIP(rtxn::set_lds_once(reinterpret_cast<const void*>(fn), v.lds));
-  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)v.threads), v.lds, s, a);
+  const size_t lds = in_mode == 2 ? v.lds_ray : v.lds;
+  RTXN_HIP(rtxn::set_lds_once(reinterpret_cast<const void*>(fn), lds));
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)v.threads), lds, s, a);
   RTXN_LAUNCH_CHECK("mlp_fwd16_kernel");
   return RTXN_OK;
 }
@@ -1174,6 +1267,7 @@ static int set_params_impl(rtxn_mlp* m, const void* params_fp16, rtxn_stream_t s
   RTXN_DEVICE_OR_FAIL();
   // training-only update: the inference packing is neither allocated nor refreshed, and says so (check_ready)
   m->inference_ready = 0;
+  m->params_version++;
   if (!m->packed_train) RTXN_HIP(hipMalloc(&m->packed_train, m->packed_train_bytes));
   if (!m->packed_t) RTXN_HIP(hipMalloc(&m->packed_t, m->packed_t_bytes));
   void* dst[3] = {nullptr, m->packed_train, m->packed_t};
@@ -1295,6 +1389,83 @@ extern "C" int rtxn_mlp_forward_segments_compact(const rtxn_mlp* m, const float*
   a.max_segments = max_segments;
   a.out_half = static_cast<_Float16*>(radiance_half4);
   return launch_fwd(m, a, 1, 3, max_segments, rtxn::as_stream(stream));
+}
+
+// ---- the per-ray form: layer 0's direction product from a table over the rays ----
+extern "C" int rtxn_mlp_ray_direction_bias_supported(const rtxn_mlp* m) {
+  return m && m->variant >= 0 && variants()[m->variant].ray_bias ? 1 : 0;
+}
+
+static int check_ray_form(const rtxn_mlp* m, const char* who) {
+  if (m && m->variant >= 0 && !variants()[m->variant].ray_bias) {
+    rtxn::set_error("%s: no per-ray kernel for this model (64/128 wide only; see rtxn_mlp_ray_direction_bias_supported)", who);
+    return RTXN_ERR_UNSUPPORTED;
+  }
+  return check_ready(m, who);
+}
+
+extern "C" int rtxn_mlp_ray_direction_bias(const rtxn_mlp* m, const float* viewing_direction, const int* num_hits, int n_rays,
+                                           float* ray_bias, rtxn_stream_t stream) {
+  int rc = check_ray_form(m, "rtxn_mlp_ray_direction_bias");
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(n_rays >= 0, "rtxn_mlp_ray_direction_bias: n_rays = %d < 0", n_rays);
+  RTXN_DEVICE_OR_FAIL();
+  if (n_rays == 0) return RTXN_OK;
+  RTXN_REQUIRE(viewing_direction && num_hits && ray_bias, "rtxn_mlp_ray_direction_bias: NULL buffer");
+  RTXN_REQUIRE(((uintptr_t)ray_bias & 15) == 0, "rtxn_mlp_ray_direction_bias: ray_bias must be 16-byte aligned");
+  const Variant& v = variants()[m->variant];
+  const unsigned blocks = (unsigned)(((long)n_rays + 63) / 64);      // 4 waves x 16 rays
+  hipLaunchKernelGGL(v.ray_bias, dim3(blocks), dim3(256), 0, rtxn::as_stream(stream), static_cast<const uint8_t*>(m->packed),
+                     viewing_direction, num_hits, n_rays, ray_bias);
+  RTXN_LAUNCH_CHECK("ray_dir_bias_kernel");
+  return RTXN_OK;
+}
+
+static int forward_segments_rays(const rtxn_mlp* m, const char* who, const float* start_points, const float* end_points,
+                                 const int* seg_ray, const float* ray_bias, int n_rays, const int* total_segments, long max_segments,
+                                 float* radiance, float* t_vals, void* radiance_half4, rtxn_stream_t stream) {
+  int rc = check_ray_form(m, who);
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(max_segments >= 0, "%s: max_segments = %ld < 0", who, max_segments);
+  RTXN_REQUIRE(n_rays >= 0, "%s: n_rays = %d < 0", who, n_rays);
+  RTXN_DEVICE_OR_FAIL();
+  if (max_segments == 0) return RTXN_OK;
+  RTXN_REQUIRE(n_rays > 0, "%s: segments without rays (n_rays = 0)", who);
+  RTXN_REQUIRE(start_points && end_points && seg_ray && ray_bias && total_segments && (radiance || radiance_half4), "%s: NULL buffer", who);
+  RTXN_REQUIRE(((uintptr_t)ray_bias & 15) == 0, "%s: ray_bias must be 16-byte aligned", who);
+  RTXN_REQUIRE(((uintptr_t)radiance & 15) == 0 && ((uintptr_t)radiance_half4 & 7) == 0, "%s: radiance must be %d-byte aligned", who,
+               radiance ? 16 : 8);
+  FwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.start = start_points;
+  a.end = end_points;
+  a.seg_ray = seg_ray;
+  a.ray_bias = ray_bias;
+  a.n_rays = n_rays;
+  a.total_segments = total_segments;
+  a.max_segments = max_segments;
+  a.radiance = reinterpret_cast<float4*>(radiance);
+  a.t_vals = t_vals;
+  a.out_half = static_cast<_Float16*>(radiance_half4);
+  return launch_fwd(m, a, 2, radiance ? 1 : 3, max_segments, rtxn::as_stream(stream));
+}
+
+extern "C" int rtxn_mlp_forward_segments_rays(const rtxn_mlp* m, const float* start_points, const float* end_points, const int* seg_ray,
+                                              const float* ray_bias, int n_rays, const int* total_segments, long max_segments,
+                                              float* radiance, float* t_vals, rtxn_stream_t stream) {
+  const char* who = "rtxn_mlp_forward_segments_rays";
+  RTXN_REQUIRE(radiance != nullptr || max_segments <= 0, "%s: NULL buffer", who);
+  return forward_segments_rays(m, who, start_points, end_points, seg_ray, ray_bias, n_rays, total_segments, max_segments, radiance, t_vals,
+                               nullptr, stream);
+}
+
+extern "C" int rtxn_mlp_forward_segments_rays_compact(const rtxn_mlp* m, const float* start_points, const float* end_points,
+                                                      const int* seg_ray, const float* ray_bias, int n_rays, const int* total_segments,
+                                                      long max_segments, void* radiance_half4, rtxn_stream_t stream) {
+  const char* who = "rtxn_mlp_forward_segments_rays_compact";
+  RTXN_REQUIRE(radiance_half4 != nullptr || max_segments <= 0, "%s: NULL buffer", who);
+  return forward_segments_rays(m, who, start_points, end_points, seg_ray, ray_bias, n_rays, total_segments, max_segments, nullptr, nullptr,
+                               radiance_half4, stream);
 }
 
 #ifdef RTXN_STAMPS

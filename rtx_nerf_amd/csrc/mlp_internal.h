@@ -24,6 +24,7 @@ struct rtxn_mlp {
   size_t packed_train_bytes;
   void* packed_t;     // training backward: A fragments of the TRANSPOSED layers (dA = W^T dZ)
   size_t packed_t_bytes;
+  long params_version; // counts rtxn_mlp_set_params*: what was derived from the packed weights (the renderer's per-ray table) is stale
   int inference_ready; // the fused inference kernels' packings (packed / packed16) hold the CURRENT parameters: set by
                        // rtxn_mlp_set_params, cleared by rtxn_mlp_set_params_training (which re-packs the training layouts only)
 };
@@ -463,8 +464,8 @@ struct PipeStep16 {
     if constexpr (BZ) {
       static_assert(CT == 4, "two segments per wave");
       // as asm: __builtin_amdgcn_mov_dpp on the four elements of a vector came out as ONE DPP of element 0 copied to all four
-      // (this toolchain).  The source is an asm MFMA result: its wait states are dir_bias16's (row tiles 0, 1) or a row tile
-      // of this pipeline (the others).
+      // (this toolchain).  The source is an asm MFMA result -- its wait states are dir_bias16's (row tiles 0, 1) or a row tile
+      // of this pipeline (the others) -- or, in the per-ray form, a global load that ray_bias_settle has waited for.
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float s0, s1;
@@ -577,6 +578,29 @@ __device__ __forceinline__ void dir_bias16(const uint8_t* lds_buf, const half8 (
   DirBias16<RT, KSD, KS0, 0>::run(addr, bd, bias, ring);
   // row tiles 0 and 1 are read first, possibly only one pair of MFMAs after their last write: their wait states, through them
   asm volatile("s_nop 15\n\ts_nop 7" : "+v"(bias[0]), "+v"(bias[1]));
+}
+
+// The per-ray form of the same bias (IN_MODE 2 of mlp_fwd16_kernel): a segment's direction is its ray's, so the product is
+// formed once per RAY by ray_dir_bias_kernel and kept in a table float[ray][16 rt + 4 g + e] -- the register image dir_bias16
+// leaves.  Lane (c, g) loads segment c & 1's four rows of every row tile (RT 16-byte loads, L2 hits: a ray's ~40 segments are
+// neighbours in the packed order) at the top of its tile and meets them after stage 0's barrier, an encode later.
+template <int RT>
+__device__ __forceinline__ void load_ray_bias(const float* __restrict__ row, floatx4 (&bias)[RT]) {
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) bias[rt] = *reinterpret_cast<const floatx4*>(row + 16 * rt);
+}
+// The DPP copies of PipeStep16 are asm: what they read must have LANDED, and hipcc's own vmcnt bookkeeping ends at an asm
+// statement it cannot see into.  The wait is spent here, explicitly, and the values go THROUGH the statement ("+v", as in
+// mfma_results_settle): nothing that reads them can be scheduled above it.  vmcnt(0) also covers the weight staging, which
+// stage 0's barrier has just waited for anyway.
+template <int RT>
+__device__ __forceinline__ void ray_bias_settle(floatx4 (&bias)[RT]) {
+  static_assert(RT == 4 || RT == 8, "operand lists written for 64- and 128-wide layers");
+  if constexpr (RT == 4)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(bias[0]), "+v"(bias[1]), "+v"(bias[2]), "+v"(bias[3]));
+  else
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(bias[0]), "+v"(bias[1]), "+v"(bias[2]), "+v"(bias[3]), "+v"(bias[4]), "+v"(bias[5]), "+v"(bias[6]), "+v"(bias[7]));
 }
 
 // The same 16x16x32 pipeline over one CHUNK of a streamed layer (the 256-wide kernel: a layer is 128 KiB of fragments and goes

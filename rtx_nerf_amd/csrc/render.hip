@@ -40,6 +40,8 @@ struct Slot {
   float* start;
   float* end;
   float* seg_view;
+  int* seg_ray;       // int[m] and float[n][W], in the caller's ray workspace (rtxn_render_set_ray_workspace): the per-ray direction
+  float* ray_bias;    // product; written by geometry(), lives with the slot's segments (shade, a re-shade, two slots in flight)
   void* radiance;     // half4[m*32] (compact) or float4[m*32]
   float* t_vals;      // float[m*32]: RTXN_RENDER_FLOAT4 only
   float* seg_step;    // float[m]: compact RTXN_VR_NERF only
@@ -84,6 +86,8 @@ struct rtxn_render {
   uint32_t max_rays;
   int sub_rays;
   bool compact, hash;
+  bool ray_bias;        // shade through rtxn_mlp_forward_segments_rays*: a ray workspace has been set
+  long params_seen;     // rtxn_mlp.params_version at the last pipelined frame: see frame_async
   Slot slots[kMaxSlots];
   int n_slots;
   uint32_t* coarse;
@@ -141,6 +145,8 @@ int validate(const rtxn_render_config* c, const char* who) {
 
 uint32_t max_rays_of(const rtxn_render_config* c) { return c->max_rays ? c->max_rays : c->width * c->height; }
 
+bool ray_bias_of(const rtxn_render_config* c) { return !c->grid && rtxn_mlp_ray_direction_bias_supported(c->mlp); }
+
 // Lay the renderer's buffers out in the workspace (r == nullptr: measure only).
 size_t layout(const rtxn_render_config* c, uint8_t* base, rtxn_render* r) {
   Carver cv{base, 0};
@@ -187,6 +193,19 @@ size_t layout(const rtxn_render_config* c, uint8_t* base, rtxn_render* r) {
       s.t_end = cv.take<float>(m);
     }
     if (r) r->slots[i] = s;
+  }
+  return cv.off;
+}
+
+// The ray workspace (r == nullptr: measure only): per slot the segments' ray index and the table of the rays' layer-0 direction
+// products, dense over the rays -- only the rows of rays with a hit are ever written or read.
+size_t ray_layout(const rtxn_render_config* c, uint8_t* base, rtxn_render* r) {
+  Carver cv{base, 0};
+  const size_t n = max_rays_of(c), m = (size_t)c->max_segments;
+  for (int i = 0; i < c->n_slots; ++i) {
+    int* seg_ray = cv.take<int>(m);
+    float* ray_bias = cv.take<float>(n * (size_t)c->mlp->cfg.n_neurons);
+    if (r) { r->slots[i].seg_ray = seg_ray; r->slots[i].ray_bias = ray_bias; }
   }
   return cv.off;
 }
@@ -286,6 +305,7 @@ void trace_params(const rtxn_render* r, const Slot& g, uint32_t ray_begin, uint3
     p.start_points = g.start;
     p.end_points = g.end;
     p.seg_view = g.seg_view;
+    p.seg_ray = g.seg_ray;       // NULL unless the frame shades per ray
     p.t_start = g.t_start;       // NULL without RTXN_RENDER_AUX
     p.t_end = g.t_end;
     p.num_stored = g.num_stored;
@@ -340,6 +360,11 @@ int geometry(rtxn_render* r, Slot& g, const float* look_at, bool pose_on_host, u
   trace_params(r, g, ray_begin, n, false, p);
   int rc = rtxn_trace_grid(&p, s);
   if (rc != RTXN_OK) return rc;
+  // the rays' direction products need the count pass only (view_dirs, num_hits): the slot's table is rewritten with its rays
+  if (r->ray_bias) {
+    rc = rtxn_mlp_ray_direction_bias(r->cfg.mlp, g.view_dirs, g.num_hits, (int)n, g.ray_bias, s);
+    if (rc != RTXN_OK) return rc;
+  }
   rc = rtxn_scan_hits(g.num_hits, g.indices, g.total, (int)n, g.scan_ws, r->scan_ws_bytes, s);
   if (rc != RTXN_OK) return rc;
   trace_params(r, g, ray_begin, n, true, p);
@@ -365,6 +390,13 @@ int shade(rtxn_render* r, Slot& g, hipStream_t s) {
   if (r->hash)
     return rtxn_hashmlp_forward_segments(c.mlp, c.grid, c.n_dir_freqs, c.table_fp16, g.start, g.end, g.seg_view, g.total, c.max_segments,
                                          c.sample_type, c.step_scale, g.radiance, g.seg_step, s);
+  if (r->ray_bias) {
+    if (r->compact)
+      return rtxn_mlp_forward_segments_rays_compact(c.mlp, g.start, g.end, g.seg_ray, g.ray_bias, (int)r->max_rays, g.total, c.max_segments,
+                                                    g.radiance, s);
+    return rtxn_mlp_forward_segments_rays(c.mlp, g.start, g.end, g.seg_ray, g.ray_bias, (int)r->max_rays, g.total, c.max_segments,
+                                          static_cast<float*>(g.radiance), g.t_vals, s);
+  }
   if (r->compact) return rtxn_mlp_forward_segments_compact(c.mlp, g.start, g.end, g.seg_view, g.total, c.max_segments, g.radiance, s);
   return rtxn_mlp_forward_segments(c.mlp, g.start, g.end, g.seg_view, g.total, c.max_segments, static_cast<float*>(g.radiance), g.t_vals, s);
 }
@@ -634,7 +666,11 @@ int frame_async(rtxn_render* r, const float* look_at, bool pose_on_host, uint32_
   Slot& g = r->slots[b];
   harvest(r, g, false);                                   // the frame that used this slot n_slots frames ago
   if (g.used) RTXN_HIP(hipStreamWaitEvent(r->geo, g.ev_comp, 0));
-  const bool ordered = !g.used || !(r->stable_inputs || pose_on_host);
+  // The per-ray table is formed from the model's packed weights ON THE TRAVERSAL STREAM.  Weights set since the last frame were
+  // packed on a caller stream -- `stream`, by this entry's ordering rule -- so that frame's traversal waits for it like a first use.
+  const bool new_params = r->ray_bias && r->cfg.mlp->params_version != r->params_seen;
+  r->params_seen = r->cfg.mlp->params_version;
+  const bool ordered = !g.used || new_params || !(r->stable_inputs || pose_on_host);
   if (ordered) {
     RTXN_HIP(hipEventRecord(r->ev_tmp[0], main_s));
     RTXN_HIP(hipStreamWaitEvent(r->geo, r->ev_tmp[0], 0));
@@ -751,6 +787,39 @@ extern "C" int rtxn_render_slot_buffers(rtxn_render* r, int slot, const int** nu
   if (t_vals) *t_vals = g.t_vals;
   if (segment_step) *segment_step = g.seg_step;
   if (viewing_direction) *viewing_direction = g.view_dirs;
+  return RTXN_OK;
+}
+
+extern "C" size_t rtxn_render_ray_workspace_bytes(const rtxn_render_config* cfg) {
+  if (validate(cfg, "rtxn_render_ray_workspace_bytes") != RTXN_OK) return 0;
+  return ray_bias_of(cfg) ? ray_layout(cfg, nullptr, nullptr) : 0;
+}
+
+extern "C" int rtxn_render_set_ray_workspace(rtxn_render* r, void* workspace, size_t bytes) {
+  const char* who = "rtxn_render_set_ray_workspace";
+  RTXN_REQUIRE(r != nullptr, "%s: NULL renderer", who);
+  if (workspace && !ray_bias_of(&r->cfg)) {
+    rtxn::set_error("%s: this renderer's model has no per-ray kernels (rtxn_render_ray_workspace_bytes is 0)", who);
+    return RTXN_ERR_UNSUPPORTED;
+  }
+  const size_t need = workspace ? ray_layout(&r->cfg, nullptr, nullptr) : 0;
+  RTXN_REQUIRE(((uintptr_t)workspace & (kAlign - 1)) == 0, "%s: workspace not %zu-byte aligned", who, kAlign);
+  RTXN_REQUIRE(bytes >= need, "%s: workspace holds %zu bytes, rtxn_render_ray_workspace_bytes says %zu", who, bytes, need);
+  RTXN_DEVICE_OR_FAIL();
+  RTXN_HIP(hipDeviceSynchronize());          // frames in flight may still shade from the previous workspace
+  r->ray_bias = false;
+  for (int i = 0; i < r->n_slots; ++i) r->slots[i].seg_ray = nullptr, r->slots[i].ray_bias = nullptr;
+  if (!workspace) return RTXN_OK;            // off: frames shade through seg_view again
+  ray_layout(&r->cfg, static_cast<uint8_t*>(workspace), r);
+  r->ray_bias = true;
+  return RTXN_OK;
+}
+
+extern "C" int rtxn_render_ray_buffers(rtxn_render* r, int slot, const int** seg_ray, const float** ray_bias) {
+  RTXN_REQUIRE(r != nullptr, "rtxn_render_ray_buffers: NULL renderer");
+  RTXN_REQUIRE(slot >= 0 && slot < r->n_slots, "rtxn_render_ray_buffers: slot %d out of [0,%d)", slot, r->n_slots);
+  if (seg_ray) *seg_ray = r->slots[slot].seg_ray;
+  if (ray_bias) *ray_bias = r->slots[slot].ray_bias;
   return RTXN_OK;
 }
 

@@ -31,7 +31,7 @@ class RenderPipeline:
                  max_rays=None, max_segments=None, trace_mode=api.TRACE_DDA, vr_mode=api.VR_COMPAT,
                  device="cuda", window=(0, 0), step_scale=1.0, sub_rays=None, compact=None, on_overflow="raise",
                  hashgrid=None, table=None, sample_type=None, n_slots=None, stable_inputs=False, aux=False,
-                 min_transmittance=None, first_round_segments=4, termination_rounds=5):
+                 min_transmittance=None, first_round_segments=4, termination_rounds=5, per_ray=True):
         self.net = network
         self.hg, self.table = hashgrid, table
         if (hashgrid is None) != (table is None):
@@ -95,7 +95,10 @@ class RenderPipeline:
         # min_transmittance (depth: times the largest sample distance).  None = off: the plain frame.
         self.min_transmittance = None if min_transmittance is None else float(min_transmittance)
         self.first_round_segments, self.termination_rounds = int(first_round_segments), int(termination_rounds)
+        # per_ray=False: keep the per-segment direction product (the seg_view entries) where the model has per-ray kernels too
+        self.per_ray = bool(per_ray)
         self._term_ws = None
+        self._ray_ws = None
         self._h = None
         self._comp_stream = None
         self._create()
@@ -143,8 +146,16 @@ class RenderPipeline:
         _lib.check(lib.rtxn_render_create(C.byref(cfg), C.c_void_p(self._ws.data_ptr()), need, C.byref(h)), "rtxn_render_create")
         self._h = h
         self._seen_overflows = 0
+        # per-ray shading (rtxn_render_set_ray_workspace): wherever the model has the kernels, in a second tensor of the same
+        # lifetime -- each segment's ray and, per slot, the table of layer 0's direction product over the rays
+        self._ray_ws = None
+        ray_need = lib.rtxn_render_ray_workspace_bytes(C.byref(cfg)) if self.per_ray else 0
+        if ray_need:
+            self._ray_ws = torch.empty(ray_need, dtype=torch.uint8, device=self.dev)
+            _lib.check(lib.rtxn_render_set_ray_workspace(h, C.c_void_p(self._ray_ws.data_ptr()), ray_need), "rtxn_render_set_ray_workspace")
         self._slots = [self._slot_views(i) for i in range(self.n_slots)]
-        for f in ("num_hits", "num_hits_c", "indices", "total", "start", "end", "seg_view", "radiance", "t_vals", "seg_step", "view_dirs"):
+        for f in ("num_hits", "num_hits_c", "indices", "total", "start", "end", "seg_view", "radiance", "t_vals", "seg_step", "view_dirs", "seg_ray",
+                  "ray_bias"):
             setattr(self, f, getattr(self._slots[0], f))
         self._term_ws = None
         if self.min_transmittance is not None:
@@ -194,10 +205,10 @@ class RenderPipeline:
         _lib.check(_lib.lib().rtxn_render_slot_buffers(self._h, i, *[C.byref(p) for p in ptrs]), "rtxn_render_slot_buffers")
         base, n, m, K = self._ws.data_ptr(), self.max_rays, self.max_segments, api.NUM_SAMPLES_PER_SEGMENT
 
-        def view(p, count, dtype, shape):
-            off = p.value - base
+        def view(p, count, dtype, shape, ws=None, origin=None):
+            off = p.value - (base if origin is None else origin)
             nbytes = count * torch.empty((), dtype=dtype).element_size()
-            return self._ws[off:off + nbytes].view(dtype).view(shape)
+            return (self._ws if ws is None else ws)[off:off + nbytes].view(dtype).view(shape)
 
         g = SimpleNamespace()
         g.num_hits = view(ptrs[0], n, torch.int32, (n,))
@@ -212,6 +223,15 @@ class RenderPipeline:
         g.t_vals = view(ptrs[8], m * K, torch.float32, (m * K,)) if ptrs[8].value else None
         g.seg_step = view(ptrs[9], m, torch.float32, (m,)) if ptrs[9].value else None
         g.view_dirs = view(ptrs[10], 2 * n, torch.float32, (n, 2))
+        # per-ray shading (rtxn_mlp_forward_segments_rays): each segment's ray and the rays' table of layer 0's direction
+        # product, in the ray workspace; None where the frame shades through seg_view
+        rp = [C.c_void_p(), C.c_void_p()]
+        _lib.check(_lib.lib().rtxn_render_ray_buffers(self._h, i, C.byref(rp[0]), C.byref(rp[1])), "rtxn_render_ray_buffers")
+        g.seg_ray = g.ray_bias = None
+        if rp[0].value:
+            Wn, rbase = self.net.cfg.n_neurons, self._ray_ws.data_ptr()
+            g.seg_ray = view(rp[0], m, torch.int32, (m,), self._ray_ws, rbase)
+            g.ray_bias = view(rp[1], n * Wn, torch.float32, (n, Wn), self._ray_ws, rbase)
         return g
 
     def _status(self, wait=False):
@@ -411,6 +431,8 @@ class RenderPipeline:
         if self.hg is not None:
             api.hashmlp_forward_segments(self.net, self.hg, self.table, g.start, g.end, g.seg_view, g.total, self.max_segments,
                                          g.radiance, self.sample_type, self.step_scale, g.seg_step)
+        elif self.compact and g.ray_bias is not None:
+            self.net.forward_segments_rays(g.start, g.end, g.seg_ray, g.ray_bias, g.total, self.max_segments, g.radiance)
         elif self.compact:
             self.net.forward_segments_compact(g.start, g.end, g.seg_view, g.total, self.max_segments, g.radiance)
         else:
