@@ -14,6 +14,8 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego --steps 20000 --ema-decay 0.99     (held-out PSNR and SSIM of the live and the averaged weights)
   python examples/train_synthetic.py --data /path/to/lego --pose-noise 0.5,0.02 --refine-poses 1e-3     (noisy poses, refined on the device)
   python examples/train_synthetic.py --data /path/to/lego --mesh lego.ply --mesh-resolution 256 --mesh-iso 30     (triangle mesh of the density field)
+  python examples/train_synthetic.py --make-demo /tmp/lens --lens opencv:-0.3,0.1,0,0.001,-0.001 --data /tmp/lens     (a demo scene seen through a lens,
+      trained and scored with the cameras its transforms_train.json describes; add --assume-pinhole to train the same frames without them)
 """
 import argparse
 import json
@@ -30,23 +32,52 @@ from rtx_nerf_amd import api, loader, scenes
 from rtx_nerf_amd.train import RayDataset, Trainer, camera_rays
 
 
-def make_demo(path, n_frames=16, res=64, grid=32):
-    """Writes transforms_train.json + PNGs rendered from the analytic teacher field of tools/train_demo.py."""
+def parse_lens(spec):
+    """MODEL:c1,c2,... -> (model, coefficient keywords of api.camera_params): opencv takes k1, k2, k3, p1, p2, opencv_fisheye
+    k1, k2, k3, k4; missing ones are 0"""
+    model, _, rest = spec.partition(":")
+    names = {"opencv": ("k1", "k2", "k3", "p1", "p2"), "opencv_fisheye": ("k1", "k2", "k3", "k4"), "pinhole": ()}
+    if model not in names:
+        sys.exit(f"--lens {spec}: model one of {sorted(names)}")
+    vals = [float(v) for v in rest.split(",") if v.strip()]
+    if len(vals) > len(names[model]):
+        sys.exit(f"--lens {spec}: {model} takes {', '.join(names[model])}")
+    return model, dict(zip(names[model], vals))
+
+
+def lens_rays(model, row, pose, res):
+    """the frame's rays through the lens, from the float64 restatement the tests hold the device to (tests/_camera_float64.py)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _camera_float64 as F
+    o, d = F.camera_rays(F.MODELS[model], np.asarray(row, np.float32), np.asarray(pose, np.float32).reshape(16), res, res)
+    return torch.from_numpy(o.astype(np.float32)).cuda(), torch.from_numpy(d.astype(np.float32)).cuda()
+
+
+def make_demo(path, n_frames=16, res=64, grid=32, lens=None):
+    """Writes transforms_train.json + PNGs rendered from the analytic teacher field of tools/train_demo.py.  lens: (model,
+    coefficients) of parse_lens -- the frames are then rendered through that lens (a centred camera of the same focal length)
+    and the JSON carries its intrinsics in the instant-ngp / nerfstudio keys."""
     from train_demo import teacher_field
     os.makedirs(os.path.join(path, "train"), exist_ok=True)
     occ = torch.from_numpy(scenes.pack_occupancy(scenes.sphere_density(grid, 0.72)).view(np.int32).copy()).cuda()
     tr = Trainer(grid, occ, encoding="freq", n_neurons=64, n_hidden_layers=2, batch_rays=res * res, max_segments=res * res * 40,
                  density_scale=150.0)
     focal = scenes.lego_focal_length(True)
-    frames = []
+    frames, intrinsics = [], {}
+    if lens is not None:
+        model, coeffs = lens
+        f_px = focal * res / 2
+        row = api.camera_params(f_px, f_px, res / 2, res / 2, **coeffs)
+        api.camera_set(model, row, width=res, height=res, device="cpu")           # refuses a lens that is not invertible over the frame
+        intrinsics = dict(camera_model=model.upper(), fl_x=f_px, fl_y=f_px, cx=res / 2, cy=res / 2, w=res, h=res, **coeffs)
     for i in range(n_frames):
         pose = scenes.pose_spherical(360.0 * i / n_frames, -20.0 - 20.0 * (i % 3), origin_scale=10.0)
-        o, d = camera_rays(pose, focal, res, res)
+        o, d = camera_rays(pose, focal, res, res) if lens is None else lens_rays(model, row, pose, res)
         img = tr.render_rays(o, d, radiance_fn=teacher_field).reshape(res, res, 3).cpu().numpy()
         loader.write_png(os.path.join(path, "train", f"r_{i}.png"), img)
         frames.append({"file_path": f"./train/r_{i}", "rotation": 0.0, "transform_matrix": pose.tolist()})
     with open(os.path.join(path, "transforms_train.json"), "w") as f:
-        json.dump({"camera_angle_x": scenes.LEGO_CAMERA_ANGLE_X, "frames": frames}, f)
+        json.dump({"camera_angle_x": scenes.LEGO_CAMERA_ANGLE_X, **intrinsics, "frames": frames}, f)
     return path
 
 
@@ -124,7 +155,24 @@ def main():
     ap.add_argument("--mesh-iso", default=str(DEMO_MESH_ISO), metavar="V[,V...]",
                     help="iso value of --mesh, an extinction per unit length of the cube; the default is a judgement call from a sweep on "
                          "the --make-demo scene (DESIGN 5.19), not a derived number.  Several values: one OUT.<V>.ply each, and the sweep's table")
+    ap.add_argument("--lens", default=None, metavar="MODEL:k1,k2,...",
+                    help="--make-demo renders its frames through this lens (opencv: k1,k2,k3,p1,p2; opencv_fisheye: k1,k2,k3,k4) and writes "
+                         "its intrinsics into transforms_train.json (DESIGN 5.20)")
+    ap.add_argument("--assume-pinhole", action="store_true",
+                    help="ignore the intrinsics in transforms_train.json and train and score under the centred pinhole of camera_angle_x")
     a = ap.parse_args()
+    json_path = os.path.join(a.data, "transforms_train.json")
+    if a.make_demo:
+        torch.cuda.set_device(0)
+        make_demo(a.make_demo, lens=parse_lens(a.lens) if a.lens else None)
+    elif a.lens:
+        sys.exit("--lens describes the scene --make-demo writes; a loaded scene's cameras come from its transforms_train.json")
+    # a scene whose JSON carries intrinsics (fl_x ...) is trained and scored with them: batches drawn on the device through the cameras
+    with open(json_path) as f:
+        top = json.load(f)
+    use_cameras = not a.assume_pinhole and ("fl_x" in top or any("fl_x" in fr for fr in top.get("frames", [])))
+    if use_cameras:
+        a.device_batches = True
     if a.refine_poses is not None:
         a.device_batches = True
         if a.encoding != "hash":
@@ -134,8 +182,6 @@ def main():
     if schedule and schedule.startswith("cosine:"):
         schedule = dict(kind="cosine", decay_steps=int(schedule.split(":", 1)[1]), ratio=0.01)
     torch.cuda.set_device(0)
-    if a.make_demo:
-        make_demo(a.make_demo)
     # flags=2: keep the PNGs' sRGB values (the reference's stbi_loadf applies a 2.2 gamma, Q11); corrected focal (Q1);
     # origin/10 as in the reference (Q2) so that Blender's radius-4 cameras sit just outside the unit grid
     rgba = a.opacity_weight > 0.0
@@ -151,10 +197,19 @@ def main():
     if a.pose_noise:
         rot_deg, trans = (float(v) for v in a.pose_noise.split(","))
         train_poses = perturb_poses(true_poses, rot_deg, trans, seed=0)
+    cams_train = cams_hold = None
+    if use_cameras:
+        model, P = loader.read_cameras(json_path, ds.image_width, ds.image_height)
+        if P.shape[0] == 1:
+            cams_train = cams_hold = api.camera_set(model, P, width=ds.image_width, height=ds.image_height)
+        else:                  # one camera per frame: the held-out frames are the last n_hold
+            cams_train = api.camera_set(model, P[:-n_hold], width=ds.image_width, height=ds.image_height)
+            cams_hold = api.camera_set(model, P[-n_hold:], width=ds.image_width, height=ds.image_height)
+        print(f"cameras: {model}, {P.shape[0]} in {json_path}" + ("" if P.shape[0] > 1 else " (shared by every frame)"))
     train_ds = loader.ImageDataset(ds.images[:-n_hold], train_poses.reshape(ds.poses[:-n_hold].shape), ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
     if a.device_batches:
         # flags=2 frames are k/255: one byte per channel holds them exactly
-        images, focal = api.ImageSet.from_dataset(train_ds, storage="u8")
+        images, focal = api.ImageSet.from_dataset(train_ds, storage="u8", cameras=cams_train)
         n_rays, held = images.n_images * images.width * images.height, images.nbytes()
     else:
         rays, focal = RayDataset.from_images(train_ds, origin_scale=0.1)
@@ -171,7 +226,7 @@ def main():
     white = (1.0, 1.0, 1.0) if rgba else None
     # the held-out frames stay on the device as they were loaded (flags=2 frames are k/255: one byte per channel holds them exactly)
     hold_ds = loader.ImageDataset(ds.images[-n_hold:], ds.poses[-n_hold:], ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
-    hold, _ = api.ImageSet.from_dataset(hold_ds, storage="u8")
+    hold, _ = api.ImageSet.from_dataset(hold_ds, storage="u8", cameras=cams_hold)
 
     def render():
         return tr.render_rays(o_t, d_t, background=white)
@@ -189,7 +244,10 @@ def main():
         tr.attach_images(images, refine_poses=None if a.refine_poses is None else dict(lr=a.refine_poses))
     g = torch.Generator(device="cuda").manual_seed(0)
     W, H = ds.image_width, ds.image_height
-    o_t, d_t = camera_rays(ds.poses[-1], focal, W, H, origin_scale=0.1)
+    if use_cameras:
+        o_t, d_t = api.camera_rays(cams_hold, cams_hold.n_cameras - 1, hold.poses[-1], W, H)
+    else:
+        o_t, d_t = camera_rays(ds.poses[-1], focal, W, H, origin_scale=0.1)
     print(f"{n_rays} training rays from {train_ds.images.shape[0]} frames ({W}x{H}), {held / 1e6:.2f} MB on the device "
           f"({'image set, batches drawn on the device' if a.device_batches else 'ray dataset'}); held-out PSNR over {n_hold} frame{'s' if n_hold > 1 else ''} before: {held_out()}")
     for it in range(a.steps):

@@ -1672,6 +1672,63 @@ int rtxn_train_step_rays(const rtxn_train_step_args* args, const rtxn_train_back
                          const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
                          const rtxn_pose_refinement* pose, rtxn_stream_t stream);
 
+/* ---- camera models: per-image intrinsics and lens distortion ------------------------------------------------
+ * A ray GENERATOR in front of the stages that walk explicit rays (rtxn_trace_params.rays_o / rays_d): COLMAP's, instant-ngp's and
+ * nerfstudio's fl_x, fl_y, cx, cy, k1.., p1, p2.  One model per set; one camera for every image (n_cameras == 1) or one per
+ * image.  The parameters live in DEVICE memory, twelve floats per camera:
+ *   fx, fy, cx, cy (pixels of the width x height frame), k1, k2, k3, k4, p1, p2, 0, 0.
+ * The ray of pixel (px, py) of camera c under the row-major pose la, all in fp32, no contraction:
+ *   xd = ((float)px + 0.5f - cx) / fx,   yd = ((float)py + 0.5f - cy) / fy
+ *       (the pixel centre and the axes of the pinhole launch: +x along pose column 0 with px, +y along column 1 with py);
+ *   RTXN_CAMERA_PINHOLE         q = (xd, yd, -1).
+ *   RTXN_CAMERA_OPENCV          q = (x, y, -1) with (x, y) the solution of
+ *       xd = x (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p1 x y + p2 (r2 + 2 x^2),
+ *       yd = y (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p2 x y + p1 (r2 + 2 y^2),      r2 = x^2 + y^2   (k4 is not read)
+ *     by Newton's method on the analytic 2 x 2 Jacobian from (xd, yd): exactly 8 iterations, no data-dependent exit; an
+ *     iteration whose determinant is zero or not finite leaves (x, y) as it is.
+ *   RTXN_CAMERA_OPENCV_FISHEYE  thd = sqrt(xd^2 + yd^2); th the solution of thd = th (1 + k1 th^2 + k2 th^4 + k3 th^6 + k4 th^8)
+ *     by Newton from th = thd, 8 iterations under the same rule (the derivative in the determinant's place);
+ *     q = (sin(th) xd / thd, sin(th) yd / thd, -cos(th)); thd < 1e-8: q = (xd, yd, -1).   (p1, p2 are not read)
+ *   d = normalise(fmaf(la[4k+2], q2, fmaf(la[4k], q0, la[4k+1] q1)))_k=0..2,   o_k = la[4k+3] / 10   (the pinhole launch's origin).
+ * There is no per-ray validity flag: the parameters must be invertible over the frame, which is the caller's to establish
+ * (rtx_nerf_amd.api.camera_set checks it on the host).  Nothing here refines the parameters; they are only read.
+ * rtxn_camera_set_check: host only.  RTXN_ERR_INVALID with a message for a NULL set, an unknown model, n_cameras outside
+ *   {1, n_images} or NULL params.
+ * rtxn_camera_rays: the rays of launch pixels [ray_begin, ray_begin + ray_count) of a width x height frame of camera `camera`
+ *   under look_at (DEVICE, 16 floats), written AT THEIR LAUNCH INDEX into rays_o / rays_d, float[width*height][3] each -- the
+ *   layout rtxn_trace_params reads explicit rays in.  Elements outside the window are not touched.  One kernel on `stream`, no
+ *   allocation, no synchronisation: capturable.  Rules (RTXN_ERR_INVALID, before a device is touched): the set's own (any
+ *   n_cameras >= 1), 0 <= camera < n_cameras, no NULL among look_at, rays_o, rays_d, width, height >= 1 and
+ *   width*height <= 2^31 - 1, the window inside the frame.  ray_count == 0 does nothing.
+ * rtxn_draw_batch_cameras: rtxn_draw_batch with the ray of the drawn pixel taken from the camera set -- the same hash sequence,
+ *   so the same (seed, step, r) picks the same (image, pixel) and copies the same target bits; the ray is the one
+ *   rtxn_camera_rays writes for that pixel with camera `image` (camera 0 when n_cameras == 1) and look_at = poses[image], bit
+ *   for bit.  set.focal_length and set.aspect_ratio are not read.  Rules: rtxn_draw_batch's, then rtxn_camera_set_check's
+ *   against set.n_images. */
+enum rtxn_camera_model { RTXN_CAMERA_PINHOLE = 0, RTXN_CAMERA_OPENCV = 1, RTXN_CAMERA_OPENCV_FISHEYE = 2 };
+enum { RTXN_CAMERA_PARAMS = 12 };
+typedef struct rtxn_camera_set {
+  int model;             /* enum rtxn_camera_model: one model per set */
+  int n_cameras;         /* 1 (shared by every image) or n_images */
+  const float* params;   /* DEVICE float[n_cameras][12]: fx, fy, cx, cy (pixels), k1, k2, k3, k4, p1, p2, 0, 0 */
+} rtxn_camera_set;
+int rtxn_camera_set_check(const rtxn_camera_set* cameras, int n_images);
+int rtxn_camera_rays(const rtxn_camera_set* cameras, int camera, const float* look_at, uint32_t width, uint32_t height,
+                     uint32_t ray_begin, uint32_t ray_count, float* rays_o, float* rays_d, rtxn_stream_t stream);
+int rtxn_draw_batch_cameras(const rtxn_draw_batch_args* a, const rtxn_camera_set* cameras, rtxn_stream_t stream);
+/* The serial frame of rtxn_render_frame_ex over the CALLER'S rays instead of a pose: rays_o, rays_d DEVICE
+ * float[cfg.width*cfg.height][3], indexed by launch ray (what rtxn_camera_rays writes), so windows and the configured interleave
+ * select rays as they do for a pose; cfg.focal_length / aspect_ratio and the slot's pose are not read.  The traversal runs with
+ * look_at = NULL and the two pointers; every stage behind it -- the per-ray direction product, the fused kernels, the compositor
+ * with depth, opacity and background, early termination, the overflow accounting -- is the pose frame's, and none of them reads
+ * the pose.  rays_d must be unit vectors, as for rtxn_trace_grid.  The rays are read on `stream` by both traversal passes: they
+ * must stay untouched until the frame has run.  Capturable.  There is no pipelined (_async) form over rays.
+ * rtxn_render_count_segments_rays: rtxn_render_count_segments over the same rays (synchronises `stream`). */
+int rtxn_render_frame_rays(rtxn_render* r, int slot, const float* rays_o, const float* rays_d, uint32_t ray_begin,
+                           uint32_t ray_count, const rtxn_render_outputs* outputs, rtxn_stream_t stream);
+int rtxn_render_count_segments_rays(rtxn_render* r, const float* rays_o, const float* rays_d, uint32_t ray_begin,
+                                    uint32_t ray_count, long* segments, rtxn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

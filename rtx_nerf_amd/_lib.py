@@ -184,6 +184,11 @@ class DrawBatchArgs(C.Structure):
                 ("rays_d", C.c_void_p), ("targets", C.c_void_p), ("drawn", C.c_void_p)]
 
 
+class CameraSet(C.Structure):
+    """struct rtxn_camera_set (include/rtxn.h)."""
+    _fields_ = [("model", C.c_int), ("n_cameras", C.c_int), ("params", C.c_void_p)]
+
+
 class ImageMetricsArgs(C.Structure):
     """struct rtxn_image_metrics_args (include/rtxn.h)."""
     _fields_ = [("set", ImageSet), ("image", C.c_int), ("pred", C.c_void_p), ("background", C.c_float * 3), ("flags", C.c_int),
@@ -447,6 +452,11 @@ SYMBOLS = {
     "rtxn_train_step_rays": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                   C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma),
                                   C.POINTER(RayGradients), C.POINTER(PoseRefinement), _P]),
+    "rtxn_camera_set_check": (_I, [C.POINTER(CameraSet), _I]),
+    "rtxn_camera_rays": (_I, [C.POINTER(CameraSet), _I, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "rtxn_draw_batch_cameras": (_I, [C.POINTER(DrawBatchArgs), C.POINTER(CameraSet), _P]),
+    "rtxn_render_frame_rays": (_I, [_P, _I, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(RenderOutputs), _P]),
+    "rtxn_render_count_segments_rays": (_I, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_long), _P]),
     "rtxn_load_images_json": (_I, [C.c_char_p, C.c_char_p, _I, C.POINTER(ImageDataset)]),
     "rtxn_free_image_dataset": (None, [C.POINTER(ImageDataset)]),
     "rtxn_load_llff": (_I, [C.c_char_p, _I, _I, C.POINTER(ImageDataset), C.POINTER(C.POINTER(C.c_float))]),

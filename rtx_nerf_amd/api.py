@@ -1611,9 +1611,11 @@ class ImageSet:
     """struct rtxn_image_set (include/rtxn.h) over resident training frames: `images` a device tensor [N, H, W, C] (C = 3 or 4),
     float32 or uint8 (v / 255 on read), `poses` [N, 16] or [N, 4, 4] float32 on the same device, one pinhole camera
     (focal_length and aspect_ratio as rtxn_trace_params; aspect_ratio defaults to W / H) for all of them.  A thin holder: it keeps the two tensors
-    alive and hands draw_batch() their pointers."""
+    alive and hands draw_batch() their pointers.  cameras: a CameraSet (camera_set()) of 1 or N cameras on the images' device,
+    kept alive here; batches drawn from the set and frames evaluated against it then take their rays from it, and focal_length
+    may be omitted (it is not read)."""
 
-    def __init__(self, images, poses, focal_length, aspect_ratio=None):
+    def __init__(self, images, poses, focal_length=None, aspect_ratio=None, cameras=None):
         if images.dim() != 4 or images.shape[-1] not in (3, 4) or images.dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"ImageSet: images of shape {tuple(images.shape)} / {images.dtype}: [N, H, W, 3 | 4], float32 or uint8")
         n, h, w, c = (int(v) for v in images.shape)
@@ -1623,19 +1625,29 @@ class ImageSet:
             raise ValueError(f"ImageSet: poses of shape {tuple(poses.shape)} / {poses.dtype}: float32 [{n}, 16] or [{n}, 4, 4]")
         if poses.device != images.device:
             raise ValueError(f"ImageSet: images on {images.device}, poses on {poses.device}")
+        if cameras is None and focal_length is None:
+            raise ValueError("ImageSet: focal_length is required without cameras")
+        if cameras is not None:
+            if not isinstance(cameras, CameraSet) or cameras.n_cameras not in (1, n):
+                raise ValueError(f"ImageSet: cameras must be a CameraSet of 1 or {n} cameras")
+            if cameras.params.device != images.device:
+                raise ValueError(f"ImageSet: images on {images.device}, cameras on {cameras.params.device}")
+            cameras.check_invertible(w, h)
         self.images, self.poses = images.contiguous(), poses.reshape(n, 16).contiguous()
         self.n_images, self.height, self.width, self.channels = n, h, w, c
         self.format = IMAGE_U8 if images.dtype == torch.uint8 else IMAGE_F32
-        self.focal_length = float(focal_length)
+        self.cameras = cameras
+        self.focal_length = None if focal_length is None else float(focal_length)
         self.aspect_ratio = float(aspect_ratio) if aspect_ratio is not None else w / h
 
     @classmethod
-    def from_dataset(cls, dataset, corrected_focal=True, storage="u8", device="cuda"):
+    def from_dataset(cls, dataset, corrected_focal=True, storage="u8", device="cuda", cameras=None):
         """dataset: rtx_nerf_amd.loader.ImageDataset; the focal rule is RayDataset.from_images' (corrected_focal:
         1/tan(camera_angle_x/2) instead of the reference's 1/tan(0.5*focal_px), quirk Q1).  storage "f32" keeps the loader's
         floats; "u8" quantises them ONCE on the host with round(v * 255) -- a quarter of the memory, and exact (the drawn
         v / 255 is the loader's float, bit for bit) for datasets loaded with flags bit 1 (v / 255, no gamma), whose values are
-        k / 255 already; gamma-linearised frames (flags 0) are rounded to the nearest 1/255.  Returns (image_set, focal)."""
+        k / 255 already; gamma-linearised frames (flags 0) are rounded to the nearest 1/255.  cameras: as ImageSet's.
+        Returns (image_set, focal)."""
         import math
         import numpy as np
         if storage not in ("u8", "f32"):
@@ -1650,7 +1662,7 @@ class ImageSet:
         if storage == "u8":
             img = np.clip(np.rint(img * np.float32(255.0)), 0, 255).astype(np.uint8)
         poses = np.ascontiguousarray(dataset.poses, dtype=np.float32).reshape(-1, 16)
-        return cls(torch.from_numpy(img).to(device), torch.from_numpy(poses).to(device), focal), focal
+        return cls(torch.from_numpy(img).to(device), torch.from_numpy(poses).to(device), focal, cameras=cameras), focal
 
     def nbytes(self):
         """bytes held on the device"""
@@ -1660,13 +1672,19 @@ class ImageSet:
         s = _lib.ImageSet()
         s.images, s.poses = _ptr(self.images, name="images"), _ptr(self.poses, torch.float32, "poses")
         s.n_images, s.width, s.height, s.channels, s.format = self.n_images, self.width, self.height, self.channels, self.format
-        s.focal_length, s.aspect_ratio = self.focal_length, self.aspect_ratio
+        s.focal_length, s.aspect_ratio = (0.0 if self.focal_length is None else self.focal_length), self.aspect_ratio
         return s
 
+    def camera_of(self, image):
+        """the index into self.cameras of frame `image`"""
+        return 0 if self.cameras.n_cameras == 1 else int(image)
 
-def draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None):
+
+def draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None, cameras=None):
     """struct rtxn_draw_batch_args over the given tensors (which the caller keeps alive): rays_o, rays_d float32 [>= n, 3],
-    targets float32 [>= n, channels], drawn int32 [>= n, 2] or None, step a device int32 tensor or None (0)."""
+    targets float32 [>= n, channels], drawn int32 [>= n, 2] or None, step a device int32 tensor or None (0).  cameras: a
+    CameraSet, default the image set's own (None: the set's pinhole); the struct keeps it, and draw_batch_launch() then draws
+    through rtxn_draw_batch_cameras."""
     n, C_ = int(n), image_set.channels
     for t, w, nm in ((rays_o, 3, "rays_o"), (rays_d, 3, "rays_d"), (targets, C_, "targets"), (drawn, 2, "drawn")):
         if t is not None and (t.dim() != 2 or t.shape[1] != w or t.shape[0] < n):
@@ -1678,19 +1696,185 @@ def draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn=Non
     a.rays_o, a.rays_d = _ptr(rays_o, torch.float32, "rays_o"), _ptr(rays_d, torch.float32, "rays_d")
     a.targets = _ptr(targets, torch.float32, "targets")
     a.drawn = _ptr(drawn, torch.int32, "drawn")
+    cameras = image_set.cameras if cameras is None else cameras
+    if cameras is not None and cameras is not image_set.cameras:
+        cameras.check_invertible(image_set.width, image_set.height)
+    a._cameras = cameras
+    a._camera_struct = cameras.c_struct() if cameras is not None else None
     return a
 
 
-def draw_batch(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None):
+def draw_batch(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None, cameras=None):
     """rtxn_draw_batch: batch number `step` (device int32 tensor, None: 0) of the sequence `seed` keys, n rays drawn from
-    image_set into rays_o / rays_d / targets on the current stream; drawn (int32 [n, 2], optional) receives (image, y*W + x)."""
-    a = draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn)
-    check(_lib.lib().rtxn_draw_batch(C.byref(a), _stream()), "rtxn_draw_batch")
+    image_set into rays_o / rays_d / targets on the current stream; drawn (int32 [n, 2], optional) receives (image, y*W + x).
+    With cameras (a CameraSet; default the image set's own) rtxn_draw_batch_cameras: the same (image, pixel) and target bits, the
+    ray from image's camera."""
+    draw_batch_launch(draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn, cameras))
 
 
 def draw_batch_launch(args):
-    """rtxn_draw_batch over a struct draw_batch_args() built earlier (its tensors still alive), on the current stream."""
-    check(_lib.lib().rtxn_draw_batch(C.byref(args), _stream()), "rtxn_draw_batch")
+    """rtxn_draw_batch[_cameras] over a struct draw_batch_args() built earlier (its tensors still alive), on the current stream."""
+    cams = getattr(args, "_camera_struct", None)
+    if cams is not None:
+        check(_lib.lib().rtxn_draw_batch_cameras(C.byref(args), C.byref(cams), _stream()), "rtxn_draw_batch_cameras")
+    else:
+        check(_lib.lib().rtxn_draw_batch(C.byref(args), _stream()), "rtxn_draw_batch")
+
+
+# --------------------------------------------------------------------------- camera models
+CAMERA_PINHOLE, CAMERA_OPENCV, CAMERA_OPENCV_FISHEYE = 0, 1, 2      # enum rtxn_camera_model
+CAMERA_MODELS = {"pinhole": CAMERA_PINHOLE, "opencv": CAMERA_OPENCV, "opencv_fisheye": CAMERA_OPENCV_FISHEYE}
+CAMERA_PARAMS = 12
+
+
+def camera_params(fx, fy, cx, cy, k1=0.0, k2=0.0, k3=0.0, k4=0.0, p1=0.0, p2=0.0):
+    """One camera's row of twelve floats: fx, fy, cx, cy in pixels, then k1, k2, k3, k4, p1, p2, 0, 0 (include/rtxn.h)."""
+    return [float(fx), float(fy), float(cx), float(cy), float(k1), float(k2), float(k3), float(k4), float(p1), float(p2), 0.0, 0.0]
+
+
+def _camera_residual(model, P, xd, yd):
+    """Host float64: the Newton solve of the device function run to convergence (50 iterations) for the rows P [n, 12] at the
+    distorted positions xd, yd [n, m].  Returns (residual, det) [n, m]: |distort(solution) - (xd, yd)|_inf and the Jacobian
+    determinant (fisheye: the derivative) at the solution."""
+    k1, k2, k3, k4, p1, p2 = (P[:, i:i + 1] for i in (4, 5, 6, 7, 8, 9))
+    with np.errstate(all="ignore"):
+        if model == CAMERA_OPENCV:
+            def f(x, y):
+                r2 = x * x + y * y
+                rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+                drad = k1 + r2 * (2 * k2 + r2 * 3 * k3)
+                fx_ = x * rad + 2 * p1 * x * y + p2 * (r2 + 2 * x * x) - xd
+                fy_ = y * rad + 2 * p2 * x * y + p1 * (r2 + 2 * y * y) - yd
+                j11 = rad + 2 * x * x * drad + 2 * p1 * y + 6 * p2 * x
+                j22 = rad + 2 * y * y * drad + 2 * p2 * x + 6 * p1 * y
+                j12 = 2 * x * y * drad + 2 * (p1 * x + p2 * y)
+                return fx_, fy_, j11, j12, j22
+            x, y = xd.copy(), yd.copy()
+            for _ in range(50):
+                fx_, fy_, j11, j12, j22 = f(x, y)
+                det = j11 * j22 - j12 * j12
+                ok = np.isfinite(det) & (det != 0)
+                safe = np.where(ok, det, 1.0)
+                x = np.where(ok, x - (j22 * fx_ - j12 * fy_) / safe, x)
+                y = np.where(ok, y - (j11 * fy_ - j12 * fx_) / safe, y)
+            fx_, fy_, j11, j12, j22 = f(x, y)
+            return np.maximum(np.abs(fx_), np.abs(fy_)), j11 * j22 - j12 * j12
+        thd = np.hypot(xd, yd)
+
+        def g(th):
+            t2 = th * th
+            poly = 1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4)))
+            dpoly = 1 + t2 * (3 * k1 + t2 * (5 * k2 + t2 * (7 * k3 + t2 * 9 * k4)))
+            return th * poly - thd, dpoly
+        th = thd.copy()
+        for _ in range(50):
+            f_, d_ = g(th)
+            ok = np.isfinite(d_) & (d_ != 0)
+            th = np.where(ok, th - f_ / np.where(ok, d_, 1.0), th)
+        f_, d_ = g(th)
+        return np.abs(f_), d_
+
+
+class CameraSet:
+    """struct rtxn_camera_set (include/rtxn.h) over a float32 [n, 12] tensor of camera rows (camera_params()): one model for
+    the set, n = 1 (shared by every image) or one camera per image.  A thin holder: it keeps the tensor alive and hands the
+    library its pointer.  Build it with camera_set()."""
+
+    def __init__(self, model, params):
+        self.model, self.params = int(model), params
+        self.n_cameras = int(params.shape[0])
+        self._host = params.detach().cpu().numpy().astype(np.float64)
+        self._checked = set()
+
+    def check_invertible(self, width, height):
+        """ValueError unless every camera of the set is invertible over a width x height frame: on the host, in float64, at a
+        33 x 33 lattice of pixel positions spanning the frame's corners ([0, width] x [0, height]) the Newton solve of the device
+        function, run to convergence, must reproduce the position (residual <= 1e-9) with a positive Jacobian determinant at
+        the solution.  Uses the parameters as they were when the set was built."""
+        key = (int(width), int(height))
+        if key in self._checked:
+            return
+        P = self._host
+        bad = ~(np.isfinite(P).all(1) & (P[:, 0] > 0) & (P[:, 1] > 0))
+        if bad.any():
+            c = int(np.argmax(bad))
+            raise ValueError(f"camera_set: camera {c}: fx = {P[c, 0]}, fy = {P[c, 1]} must be positive and every parameter finite")
+        if self.model != CAMERA_PINHOLE:
+            px, py = np.meshgrid(np.linspace(0.0, float(width), 33), np.linspace(0.0, float(height), 33))
+            px, py = px.reshape(1, -1), py.reshape(1, -1)
+            xd, yd = (px - P[:, 2:3]) / P[:, 0:1], (py - P[:, 3:4]) / P[:, 1:2]
+            res, det = _camera_residual(self.model, P, xd, yd)
+            bad = ~((res <= 1e-9) & (det > 0))
+            if bad.any():
+                c, j = (int(v) for v in np.argwhere(bad)[0])
+                name = [k for k, v in CAMERA_MODELS.items() if v == self.model][0]
+                raise ValueError(f"camera_set: camera {c} ({name}) is not invertible over the {width} x {height} frame: at pixel "
+                                 f"({px[0, j]:.2f}, {py[0, j]:.2f}) the float64 solve leaves a residual of {res[c, j]:.3g} with "
+                                 f"Jacobian determinant {det[c, j]:.3g}")
+        self._checked.add(key)
+
+    def c_struct(self):
+        s = _lib.CameraSet()
+        s.model, s.n_cameras = self.model, self.n_cameras
+        s.params = _ptr(self.params, torch.float32, "camera params")
+        return s
+
+
+def camera_set(model, params, width=None, height=None, device="cuda"):
+    """A CameraSet: model "pinhole" | "opencv" | "opencv_fisheye"; params a float32 [n, 12] (or [12]) array or tensor of
+    camera_params() rows, moved to `device`.
+    DOMAIN.  The device function has no per-ray validity flag: it runs 8 Newton steps whatever they do.  So parameters that are
+    not invertible over the frame are refused here, on the host (CameraSet.check_invertible: a 33 x 33 lattice over
+    [0, width] x [0, height]; ValueError naming the camera and the pixel).  width, height: the frame; without them the frame
+    is taken as [0, 2 cx] x [0, 2 cy] per camera (a principal point at the centre), and api.ImageSet(cameras=) checks again
+    with its own size.  Pixels outside the checked frame are outside the contract."""
+    if model not in CAMERA_MODELS:
+        raise ValueError(f"camera_set: model {model!r}: one of {sorted(CAMERA_MODELS)}")
+    t = torch.as_tensor(np.asarray(params.detach().cpu() if isinstance(params, torch.Tensor) else params, dtype=np.float32))
+    if t.dim() == 1:
+        t = t.reshape(1, -1)
+    if t.dim() != 2 or t.shape[1] != CAMERA_PARAMS or t.shape[0] < 1:
+        raise ValueError(f"camera_set: params of shape {tuple(t.shape)}: [n, {CAMERA_PARAMS}] or [{CAMERA_PARAMS}]")
+    cs = CameraSet(CAMERA_MODELS[model], t.contiguous().to(device))
+    if width is not None and height is not None:
+        cs.check_invertible(width, height)
+    else:
+        for c in range(cs.n_cameras):
+            one = CameraSet(cs.model, t[c:c + 1])
+            try:
+                one.check_invertible(2.0 * float(t[c, 2]), 2.0 * float(t[c, 3]))
+            except ValueError as e:
+                raise ValueError(str(e).replace("camera 0", f"camera {c}", 1)) from None
+    return cs
+
+
+def camera_set_check(cameras, n_images):
+    """rtxn_camera_set_check: the library's own rules (model, n_cameras in {1, n_images}, params), host only."""
+    s = cameras.c_struct() if isinstance(cameras, CameraSet) else cameras
+    check(_lib.lib().rtxn_camera_set_check(C.byref(s), int(n_images)), "rtxn_camera_set_check")
+
+
+def camera_rays(cameras, camera, look_at, width, height, ray_begin=0, ray_count=None, rays_o=None, rays_d=None):
+    """rtxn_camera_rays: the rays of launch pixels [ray_begin, ray_begin + ray_count) of a width x height frame of camera
+    `camera` under look_at (16 device floats), written at their launch index into rays_o / rays_d (float32 [width*height, 3];
+    new ones when None -- elements outside the window are then uninitialised).  One kernel on the current stream.
+    Returns (rays_o, rays_d)."""
+    n = int(width) * int(height)
+    if look_at.numel() != 16:
+        raise _lib.RtxnError(f"camera_rays: look_at of shape {tuple(look_at.shape)}: 16 floats")
+    if rays_o is None:
+        rays_o = torch.empty((n, 3), device=look_at.device)
+    if rays_d is None:
+        rays_d = torch.empty((n, 3), device=look_at.device)
+    for t, nm in ((rays_o, "rays_o"), (rays_d, "rays_d")):
+        if t.numel() < 3 * n:
+            raise _lib.RtxnError(f"camera_rays: {nm} of shape {tuple(t.shape)}: [{n}, 3]")
+    s = cameras.c_struct()
+    check(_lib.lib().rtxn_camera_rays(C.byref(s), int(camera), _ptr(look_at, torch.float32, "look_at"), int(width), int(height),
+                                      int(ray_begin), n - int(ray_begin) if ray_count is None else int(ray_count),
+                                      _ptr(rays_o, torch.float32, "rays_o"), _ptr(rays_d, torch.float32, "rays_d"), _stream()),
+          "rtxn_camera_rays")
+    return rays_o, rays_d
 
 
 # --------------------------------------------------------------------------- held-out evaluation

@@ -278,10 +278,22 @@ int check_window(const rtxn_render* r, uint32_t ray_begin, uint32_t& ray_count, 
   return RTXN_OK;
 }
 
-void trace_params(const rtxn_render* r, const Slot& g, uint32_t ray_begin, uint32_t ray_count, bool write, rtxn_trace_params& p) {
+// What a frame's traversal takes its rays from: a pose (copied into the slot first) or the caller's explicit rays
+// (rtxn_render_frame_rays: float3[width*height] by launch ray).  Nothing behind the traversal reads either.
+struct RaySource {
+  const float* look_at;
+  bool pose_on_host;
+  const float* rays_o;
+  const float* rays_d;
+};
+
+void trace_params(const rtxn_render* r, const Slot& g, uint32_t ray_begin, uint32_t ray_count, bool write, rtxn_trace_params& p,
+                  const float* rays_o = nullptr, const float* rays_d = nullptr) {
   const rtxn_render_config& c = r->cfg;
   memset(&p, 0, sizeof(p));
-  p.look_at = g.look_at;
+  p.look_at = rays_o ? nullptr : g.look_at;
+  p.rays_o = rays_o;
+  p.rays_d = rays_d;
   p.focal_length = c.focal_length;
   p.aspect_ratio = c.aspect_ratio;
   p.width = c.width;
@@ -350,14 +362,16 @@ bool capturing(hipStream_t s) {
 }
 
 // count -> scan -> write of one frame into slot g
-int geometry(rtxn_render* r, Slot& g, const float* look_at, bool pose_on_host, uint32_t ray_begin, uint32_t n, hipStream_t s) {
-  RTXN_HIP(hipMemcpyAsync(g.look_at, look_at, 16 * sizeof(float), pose_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-  if (pose_on_host) {
-    RTXN_HIP(hipEventRecord(g.ev_pose, s));
-    g.pose_pending = true;
+int geometry(rtxn_render* r, Slot& g, const RaySource& src, uint32_t ray_begin, uint32_t n, hipStream_t s) {
+  if (src.look_at) {
+    RTXN_HIP(hipMemcpyAsync(g.look_at, src.look_at, 16 * sizeof(float), src.pose_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    if (src.pose_on_host) {
+      RTXN_HIP(hipEventRecord(g.ev_pose, s));
+      g.pose_pending = true;
+    }
   }
   rtxn_trace_params p;
-  trace_params(r, g, ray_begin, n, false, p);
+  trace_params(r, g, ray_begin, n, false, p, src.rays_o, src.rays_d);
   int rc = rtxn_trace_grid(&p, s);
   if (rc != RTXN_OK) return rc;
   // the rays' direction products need the count pass only (view_dirs, num_hits): the slot's table is rewritten with its rays
@@ -367,7 +381,7 @@ int geometry(rtxn_render* r, Slot& g, const float* look_at, bool pose_on_host, u
   }
   rc = rtxn_scan_hits(g.num_hits, g.indices, g.total, (int)n, g.scan_ws, r->scan_ws_bytes, s);
   if (rc != RTXN_OK) return rc;
-  trace_params(r, g, ray_begin, n, true, p);
+  trace_params(r, g, ray_begin, n, true, p, src.rays_o, src.rays_d);
   rc = rtxn_trace_grid(&p, s);
   if (rc != RTXN_OK) return rc;
   // 16 bytes of counters to pinned memory: what a later call's overflow check reads.  Under stream capture the kernel and the
@@ -555,6 +569,27 @@ extern "C" int rtxn_render_count_segments(rtxn_render* r, const float* look_at, 
   return RTXN_OK;
 }
 
+extern "C" int rtxn_render_count_segments_rays(rtxn_render* r, const float* rays_o, const float* rays_d, uint32_t ray_begin,
+                                               uint32_t ray_count, long* segments, rtxn_stream_t stream) {
+  RTXN_REQUIRE(r && rays_o && rays_d && segments, "rtxn_render_count_segments_rays: NULL argument");
+  int rc = check_window(r, ray_begin, ray_count, "rtxn_render_count_segments_rays");
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  hipStream_t s = rtxn::as_stream(stream);
+  Slot& g = r->slots[0];
+  rtxn_trace_params p;
+  trace_params(r, g, ray_begin, ray_count, false, p, rays_o, rays_d);
+  rc = rtxn_trace_grid(&p, s);
+  if (rc != RTXN_OK) return rc;
+  rc = rtxn_scan_hits(g.num_hits, g.indices, g.total, (int)ray_count, g.scan_ws, r->scan_ws_bytes, s);
+  if (rc != RTXN_OK) return rc;
+  int total = 0;
+  RTXN_HIP(hipMemcpyAsync(&total, g.total, sizeof(int), hipMemcpyDeviceToHost, s));
+  RTXN_HIP(hipStreamSynchronize(s));
+  *segments = total;
+  return RTXN_OK;
+}
+
 namespace {
 
 // The frame with early termination: after the geometry, N rounds of   scan -> gather -> MLP on the round scratch -> resume
@@ -599,11 +634,11 @@ int frame_terminated(rtxn_render* r, int slot, uint32_t n, const rtxn_render_out
   return rtxn::term_account(b, t.n_rounds, g.total, (int)c_max_segments(r), s);
 }
 
-int frame_serial(rtxn_render* r, int slot, const float* look_at, uint32_t ray_begin, uint32_t ray_count, const rtxn_render_outputs& o,
+int frame_serial(rtxn_render* r, int slot, const RaySource& src, uint32_t ray_begin, uint32_t ray_count, const rtxn_render_outputs& o,
                  hipStream_t s) {
   Slot& g = r->slots[slot];
   if (!capturing(s)) harvest(r, g, false);
-  int rc = geometry(r, g, look_at, false, ray_begin, ray_count, s);
+  int rc = geometry(r, g, src, ray_begin, ray_count, s);
   if (rc != RTXN_OK) return rc;
   if (r->term.on) return frame_terminated(r, slot, ray_count, o, s);
   rc = shade(r, g, s);
@@ -627,7 +662,7 @@ extern "C" int rtxn_render_frame(rtxn_render* r, int slot, const float* look_at,
   int rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame");
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
-  return frame_serial(r, slot, look_at, ray_begin, ray_count, pixels_only(pixels), rtxn::as_stream(stream));
+  return frame_serial(r, slot, RaySource{look_at, false, nullptr, nullptr}, ray_begin, ray_count, pixels_only(pixels), rtxn::as_stream(stream));
 }
 
 extern "C" int rtxn_render_frame_ex(rtxn_render* r, int slot, const float* look_at, uint32_t ray_begin, uint32_t ray_count,
@@ -639,7 +674,19 @@ extern "C" int rtxn_render_frame_ex(rtxn_render* r, int slot, const float* look_
   rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame_ex");
   if (rc != RTXN_OK) return rc;
   RTXN_DEVICE_OR_FAIL();
-  return frame_serial(r, slot, look_at, ray_begin, ray_count, *outputs, rtxn::as_stream(stream));
+  return frame_serial(r, slot, RaySource{look_at, false, nullptr, nullptr}, ray_begin, ray_count, *outputs, rtxn::as_stream(stream));
+}
+
+extern "C" int rtxn_render_frame_rays(rtxn_render* r, int slot, const float* rays_o, const float* rays_d, uint32_t ray_begin,
+                                      uint32_t ray_count, const rtxn_render_outputs* outputs, rtxn_stream_t stream) {
+  RTXN_REQUIRE(r && rays_o && rays_d, "rtxn_render_frame_rays: NULL argument");
+  int rc = check_outputs(r, outputs, "rtxn_render_frame_rays");
+  if (rc != RTXN_OK) return rc;
+  RTXN_REQUIRE(slot >= 0 && slot < r->n_slots, "rtxn_render_frame_rays: slot %d out of [0,%d)", slot, r->n_slots);
+  rc = check_window(r, ray_begin, ray_count, "rtxn_render_frame_rays");
+  if (rc != RTXN_OK) return rc;
+  RTXN_DEVICE_OR_FAIL();
+  return frame_serial(r, slot, RaySource{nullptr, false, rays_o, rays_d}, ray_begin, ray_count, *outputs, rtxn::as_stream(stream));
 }
 
 namespace {
@@ -684,7 +731,7 @@ int frame_async(rtxn_render* r, const float* look_at, bool pose_on_host, uint32_
     memcpy(g.pose_host, look_at, 16 * sizeof(float));
     look_at = g.pose_host;
   }
-  int rc = geometry(r, g, look_at, pose_on_host, ray_begin, ray_count, r->geo);
+  int rc = geometry(r, g, RaySource{look_at, pose_on_host, nullptr, nullptr}, ray_begin, ray_count, r->geo);
   if (rc != RTXN_OK) return rc;
   RTXN_HIP(hipEventRecord(g.ev_geo, r->geo));
   RTXN_HIP(hipStreamWaitEvent(main_s, g.ev_geo, 0));

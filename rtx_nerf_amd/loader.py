@@ -84,6 +84,59 @@ def load_data(scene_type, name, root="./data", flags=0, llff_factor=8):
     return load_llff_data(f"{root}/nerf_llff_data/{filename}", llff_factor, flags)
 
 
+_CAMERA_KEYS = ("camera_model", "is_fisheye", "fl_x", "fl_y", "cx", "cy", "k1", "k2", "k3", "k4", "p1", "p2", "w", "h", "camera_angle_x")
+_CAMERA_MODEL_NAMES = {"PINHOLE": "pinhole", "SIMPLE_PINHOLE": "pinhole", "OPENCV": "opencv", "OPENCV_FISHEYE": "opencv_fisheye"}
+
+
+def read_cameras(json_path, width, height):
+    """The intrinsics of an instant-ngp / nerfstudio transforms.json for frames loaded at width x height: (model, params), model
+    "pinhole" | "opencv" | "opencv_fisheye" and params float32 [n, 12] rows of api.camera_params() -- what api.camera_set() takes.
+    Keys camera_model, fl_x, fl_y, cx, cy, k1..k4, p1, p2, w, h, read at the top level and, where a frame carries its own, per
+    frame (a frame's key wins): n = 1 when no frame does, else one row per frame in file order.  fl_y defaults to fl_x, cx / cy to
+    w / 2, h / 2, w / h to width / height; intrinsics given for w x h are rescaled to the loaded size (fx, cx by width / w;
+    fy, cy by height / h); distortion coefficients act on normalised coordinates and are kept.  Without camera_model:
+    opencv_fisheye with instant-ngp's is_fisheye, opencv with any non-zero coefficient, else pinhole; the set has ONE model, so
+    frames that disagree are refused.  Without fl_x: a centred pinhole from camera_angle_x, the HORIZONTAL field of view,
+    fx = fy = width / (2 tan(camera_angle_x / 2)).  cy counts rows of the frame as it is stored; the pose convention is the
+    caller's (include/rtxn.h: +y along pose column 1 with py).  Host only; the C loader is not involved."""
+    import json
+    import math
+    with open(json_path) as f:
+        top = json.load(f)
+    frames = top.get("frames") or []
+    per_frame = any(k in fr for fr in frames for k in _CAMERA_KEYS)
+    rows, models = [], set()
+    for fr in (frames if per_frame else [{}]):
+        g = {k: top[k] for k in _CAMERA_KEYS if k in top}
+        g.update({k: fr[k] for k in _CAMERA_KEYS if k in fr})
+        w, h = float(g.get("w", width)), float(g.get("h", height))
+        sx, sy = float(width) / w, float(height) / h
+        if "fl_x" in g:
+            fx, fy = float(g["fl_x"]) * sx, float(g.get("fl_y", g["fl_x"])) * sy
+        elif "camera_angle_x" in g:
+            fx = fy = 0.5 * float(width) / math.tan(0.5 * float(g["camera_angle_x"]))
+        else:
+            raise ValueError(f"read_cameras: {json_path}: neither fl_x nor camera_angle_x")
+        cx, cy = float(g.get("cx", 0.5 * w)) * sx, float(g.get("cy", 0.5 * h)) * sy
+        k = {n: float(g.get(n, 0.0)) for n in ("k1", "k2", "k3", "k4", "p1", "p2")}
+        if "camera_model" in g:
+            name = str(g["camera_model"]).upper()
+            if name not in _CAMERA_MODEL_NAMES:
+                raise ValueError(f"read_cameras: {json_path}: camera_model {g['camera_model']!r}: one of {sorted(_CAMERA_MODEL_NAMES)}")
+            model = _CAMERA_MODEL_NAMES[name]
+        elif g.get("is_fisheye"):
+            model = "opencv_fisheye"
+        else:
+            model = "opencv" if any(k.values()) else "pinhole"
+        models.add(model)
+        rows.append([fx, fy, cx, cy, k["k1"], k["k2"], k["k3"], k["k4"], k["p1"], k["p2"], 0.0, 0.0])
+    if models == {"pinhole", "opencv"}:        # frames without coefficients under a distorted set: opencv with zeros is the pinhole
+        models = {"opencv"}
+    if len(models) != 1:
+        raise ValueError(f"read_cameras: {json_path}: frames of different camera models {sorted(models)}: one model per set")
+    return models.pop(), np.asarray(rows, dtype=np.float32)
+
+
 def write_png(path, rgb_float):
     """Rendered frame float[H,W,3] in [0,1] -> 8-bit PNG (stb_image_write's unused role, main.cu:19-21)."""
     img = np.ascontiguousarray(np.rint(np.clip(rgb_float, 0.0, 1.0) * 255.0).astype(np.uint8))

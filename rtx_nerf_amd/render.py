@@ -99,6 +99,7 @@ class RenderPipeline:
         self.per_ray = bool(per_ray)
         self._term_ws = None
         self._ray_ws = None
+        self._cam_rays = None      # render_camera(): the frame's explicit rays, float32 [W*H, 3] x 2, made on first use
         self._h = None
         self._comp_stream = None
         self._create()
@@ -278,11 +279,24 @@ class RenderPipeline:
                                                          api._stream()), "rtxn_render_count_segments")
         return int(out.value)
 
-    def calibrate(self, poses, ray_begin=0, ray_count=None, margin=1.10):
-        """Size the segment buffers for a set of poses (outside any timed region)."""
+    def count_segments_rays(self, rays_o, rays_d, ray_begin=0, ray_count=None):
+        """count_segments() over explicit rays (rtxn_render_count_segments_rays); rays as render_rays() takes them."""
+        n = self.max_rays if ray_count is None else ray_count
+        out = C.c_long(0)
+        _lib.check(_lib.lib().rtxn_render_count_segments_rays(self._h, *self._rays(rays_o, rays_d), ray_begin, n, C.byref(out),
+                                                              api._stream()), "rtxn_render_count_segments_rays")
+        return int(out.value)
+
+    def calibrate(self, poses, ray_begin=0, ray_count=None, margin=1.10, cameras=None):
+        """Size the segment buffers for a set of poses (outside any timed region).  cameras: an api.CameraSet of one camera or
+        one per pose: pose i is counted over the rays of its camera (rtxn_render_count_segments_rays)."""
         worst = 0
-        for p in poses:
+        for i, p in enumerate(poses):
             self.set_pose(p)
+            if cameras is not None:
+                rays = self._camera_rays(cameras, 0 if cameras.n_cameras == 1 else i, None)
+                worst = max(worst, self.count_segments_rays(*rays, ray_begin, ray_count))
+                continue
             worst = max(worst, self.count_segments(ray_begin, ray_count))
         need = int(worst * margin) + 1024
         if need > self.max_segments or need < self.max_segments // 2:
@@ -336,6 +350,44 @@ class RenderPipeline:
         _lib.check(_lib.lib().rtxn_render_frame_ex(self._h, 0, self._pose(look_at), ray_begin, n, C.byref(o),
                                                    api._stream()), "rtxn_render_frame_ex")
         return res
+
+    def _rays(self, rays_o, rays_d):
+        n = self.W * self.H
+        for t, nm in ((rays_o, "rays_o"), (rays_d, "rays_d")):
+            if t.numel() != 3 * n or t.shape[-1] != 3:
+                raise ValueError(f"{nm} of shape {tuple(t.shape)}: [{n}, 3], one ray per pixel of the {self.W} x {self.H} launch")
+        return api._ptr(rays_o, torch.float32, "rays_o"), api._ptr(rays_d, torch.float32, "rays_d")
+
+    def render_rays(self, rays_o, rays_d, ray_begin=0, ray_count=None, background=None, depth=False, opacity=False, out=None):
+        """render_ex() over the CALLER'S rays (rtxn_render_frame_rays): rays_o, rays_d float32 [W*H, 3] on the device, indexed by
+        launch ray (what api.camera_rays writes), rays_d unit vectors; the pipeline's focal length and pose are not read.  The
+        window and the configured interleave select rays as they do for a pose.  Returns (pixels, depth, opacity), an output
+        not asked for None; with nothing but pixels asked for, the plain compositor runs.  The rays must stay untouched until
+        the frame has run.  Capturable."""
+        n = self.max_rays if ray_count is None else ray_count
+        o, res = self._outputs(n, background, depth, opacity, out)
+        self._check_overflow()
+        _lib.check(_lib.lib().rtxn_render_frame_rays(self._h, 0, *self._rays(rays_o, rays_d), ray_begin, n, C.byref(o), api._stream()),
+                   "rtxn_render_frame_rays")
+        return res
+
+    def _camera_rays(self, cameras, camera, look_at, ray_begin=0, ray_count=None):
+        """enqueue: the frame's rays under `cameras[camera]` and the pose (_pose()) into the pipeline's own buffers"""
+        if self._cam_rays is None:
+            self._cam_rays = (torch.empty((self.W * self.H, 3), device=self.dev), torch.empty((self.W * self.H, 3), device=self.dev))
+        pose = self.look_at if look_at is None else look_at
+        if ray_count is None or self.window[0]:          # an interleaved window reaches past [ray_begin, ray_begin + ray_count)
+            ray_begin, ray_count = 0, None
+        return api.camera_rays(cameras, camera, pose, self.W, self.H, ray_begin, ray_count, *self._cam_rays)
+
+    def render_camera(self, cameras, camera, look_at=None, ray_begin=0, ray_count=None, background=None, depth=False, opacity=False,
+                      out=None):
+        """One frame of camera `camera` of an api.CameraSet under look_at (16 device floats; None: set_pose()'s): rtxn_camera_rays
+        into two [W*H, 3] buffers the pipeline owns (allocated on the first call -- make that one outside a graph capture), then
+        render_rays() over them.  Two launches more than a pose frame, nothing on the host; capturable.  One frame at a time per
+        pipeline: the next call rewrites the rays."""
+        rays = self._camera_rays(cameras, camera, look_at, ray_begin, ray_count)
+        return self.render_rays(*rays, ray_begin, ray_count, background, depth, opacity, out)
 
     def finish(self):
         """Wait for every enqueued frame and apply the overflow policy to all of them (raises under "raise")."""

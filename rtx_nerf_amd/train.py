@@ -546,6 +546,8 @@ class Trainer:
         self.draw_count mirrors it on the host (checkpoints keep it); self.drawn holds (image, y*W + x) of the last draw.
         A graph captured with draw=True and the struct of entry_args(draw=True) hold the counter's, the frames' and the
         poses' addresses, so once either exists another set cannot be attached: build a new Trainer for it.
+        A set with cameras (api.ImageSet(cameras=)) draws every batch through rtxn_draw_batch_cameras on all three
+        paths -- same (image, pixel) and targets, the ray from the image's camera -- and the address rule covers its camera tensor.
         refine_poses: None, True, or a dict of lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-15 (a trainer built with ray_gradients=True;
         DESIGN 5.16; librtxn: rtxn_pose_refinement): a 6-DoF correction (omega, tau) per image, optimised on the device inside
         step_images(), step_captured() (capture_step(draw=True)) and step_entry() (entry_args(draw=True)) behind the optimizer, by
@@ -823,7 +825,9 @@ class Trainer:
     def evaluate(self, image_set, images=None, weights="live", background=None, ssim=True, clamp=False, out=None):
         """Score held-out frames on the device: per frame of `images` (indices into image_set, default all of them, in that
         order) one frame rendered on the fast inference path at the set's width, height, focal length and aspect ratio, with the
-        pose read where it lies in image_set.poses, and one rtxn_image_metrics call against the resident frame.  Returns a
+        pose read where it lies in image_set.poses, and one rtxn_image_metrics call against the resident frame.  A set with
+        cameras (api.ImageSet(cameras=)) renders each frame through that image's camera instead (RenderPipeline.render_camera;
+        the set's focal length is not read, and the cached pipeline is keyed on the camera tensor as well).  Returns a
         float64 device tensor [n, 3] (`out`, or a new one) with rows (mse, psnr, ssim); average on the device (rec.mean(0)).
         weights "live" | "ema" (ema_decay; sync_ema() is called first); frequency models get sync_inference_weights() first.
         background: what the frames are rendered over, and what a 4-channel set's frames are composited over: None takes the
@@ -859,22 +863,27 @@ class Trainer:
             self.sync_inference_weights()
         if weights == "ema":
             self.sync_ema()
+        cams = getattr(image_set, "cameras", None)
         key = (image_set.width, image_set.height, image_set.focal_length, image_set.aspect_ratio, weights)
+        if cams is not None:           # the camera tensor's identity: a graph captured over it keeps its address
+            key += (cams.model, cams.n_cameras, cams.params.data_ptr())
         cache = self.__dict__.setdefault("_eval_pipelines", {})
         entry = cache.get(key)
         if entry is None or (entry[0].occ is None) != (self.occ is None):    # a trainer that started dense has its occupancy now
             cache.pop(key, None)
             # one slot: only serial frames are rendered here; "grow": a frame that outgrows the calibrated buffers (the occupancy
             # has filled up since) is scored truncated once, and the next eager call re-sizes the pipeline instead of raising
-            pipe = self.render_pipeline(image_set.width, image_set.height, image_set.focal_length, weights=weights,
-                                        aspect_ratio=image_set.aspect_ratio, n_slots=1, on_overflow="grow")
-            pipe.calibrate(image_set.poses.cpu().numpy())             # the one-time host read
+            pipe = self.render_pipeline(image_set.width, image_set.height, 1.0 if image_set.focal_length is None else image_set.focal_length,
+                                        weights=weights, aspect_ratio=image_set.aspect_ratio, n_slots=1, on_overflow="grow")
+            pipe.calibrate(image_set.poses.cpu().numpy(), cameras=cams)             # the one-time host read
             entry = cache[key] = (pipe, api.image_metrics_workspace(image_set))
         pipe, workspace = entry
         rec = out if out is not None else torch.empty((len(idx), 3), dtype=torch.float64, device=self.dev)
         for row, i in enumerate(idx):
             pose = image_set.poses[i]
-            if background is not None:
+            if cams is not None:           # the frame of that image's camera: rtxn_camera_rays + rtxn_render_frame_rays
+                pixels = pipe.render_camera(cams, image_set.camera_of(i), pose, background=background)[0]
+            elif background is not None:
                 pixels = pipe.render_ex(background=background, depth=False, opacity=False, look_at=pose)[0]
             else:
                 pixels = pipe.render(look_at=pose)
