@@ -13,6 +13,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _compositor_float64 import distortion_pairwise      # noqa: E402  (the pairwise double sum and its gradient, float64)
 
 B_RAYS, LS = 777, 128.0
 LAMBDA_D = 10.0                                         # with loss scale 128: the term is of the colour term's size
@@ -108,7 +110,8 @@ _REFS = {}
 def reference(torch, K, case, t_scale=1.0):
     """float64, made once per (K, case, t_scale): c (radiance with autograd), w, pixels, A, depth = sum w m, L_r = the PAIRWISE
     double sum sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i with delta_i = (t_end - t_start) / K as include/rtxn.h
-    defines it (the compositor's step length where t_scale = 1, to an ulp), and q = dL_r/dw by autograd of that sum."""
+    defines it (the compositor's step length where t_scale = 1, to an ulp), and q = dL_r/dw of that sum -- both stated once, in
+    tests/_compositor_float64.py (distortion_pairwise; tests/test_compositor_float64_reference.py holds its q to autograd)."""
     key = (K, case, t_scale)
     if key not in _REFS:
         nh, idx, P, rad, step, ts, te, tgt, bg_np = case_inputs(K, case, t_scale)
@@ -131,14 +134,13 @@ def reference(torch, K, case, t_scale=1.0):
         depth = torch.zeros(B, dtype=torch.float64).index_add(0, ray, w.detach() * m)
         L = np.zeros(B)
         q = torch.zeros_like(m)
+        w_np, m_np, width_np = w.detach().numpy(), m.numpy(), width.numpy()
         for r in range(B):
             if nh[r] == 0:
                 continue
             s = slice(int(start[r]), int(start[r]) + int(nh[r]) * K)
-            wr = w.detach()[s].clone().requires_grad_(True)
-            Lr = (wr[:, None] * wr[None, :] * (m[s][:, None] - m[s][None, :]).abs()).sum() + (wr * wr * width[s]).sum() / 3.0
-            q[s], = torch.autograd.grad(Lr, wr)
-            L[r] = float(Lr.detach())
+            L[r], q_r = distortion_pairwise(w_np[s], m_np[s], width_np[s])
+            q[s] = torch.from_numpy(q_r)
         _REFS[key] = (c, w, pix, A, depth.numpy(), L, q, m.numpy())
     return _REFS[key]
 
