@@ -16,6 +16,8 @@ No dataset ships with this image; pass --make-demo to first write a small proced
   python examples/train_synthetic.py --data /path/to/lego --mesh lego.ply --mesh-resolution 256 --mesh-iso 30     (triangle mesh of the density field)
   python examples/train_synthetic.py --make-demo /tmp/lens --lens opencv:-0.3,0.1,0,0.001,-0.001 --data /tmp/lens     (a demo scene seen through a lens,
       trained and scored with the cameras its transforms_train.json describes; add --assume-pinhole to train the same frames without them)
+  python examples/train_synthetic.py --make-demo /tmp/lens --lens opencv:-0.3,0.1,0,0.001,-0.001 --data /tmp/lens \
+      --intrinsics-noise focal=0.03,center=1.5 --refine-cameras     (wrong focal length and principal point on load, refined on the device)
 """
 import argparse
 import json
@@ -97,6 +99,35 @@ def perturb_poses(poses, rot_deg, trans, seed=0):
     return out.astype(np.float32)
 
 
+def parse_groups(spec, names, what):
+    """'a=1,b=2' -> {a: 1.0, b: 2.0} over the given names"""
+    out = {}
+    for part in (p for p in spec.split(",") if p.strip()):
+        k, _, v = part.partition("=")
+        if k.strip() not in names or not v:
+            sys.exit(f"{what} {spec}: entries NAME=VALUE with NAME one of {', '.join(names)}")
+        out[k.strip()] = float(v)
+    return out
+
+
+def perturb_cameras(P, focal, center, seed=0):
+    """[n, 12] camera rows with fx and fy each scaled by a seeded factor of exp(+-focal) and the principal point moved by
+    `center` pixels in a seeded direction"""
+    rng = np.random.default_rng(seed)
+    out = np.array(P, np.float64)
+    for row in out:
+        row[:2] *= np.exp(focal * rng.choice([-1.0, 1.0], 2))
+        step = rng.standard_normal(2)
+        row[2:4] += step / np.linalg.norm(step) * center
+    return out.astype(np.float32)
+
+
+def camera_errors(P, true_P):
+    """(mean |log(f / f_true)| over fx and fy, mean principal-point distance in pixels) between two sets of rows"""
+    a, b = np.asarray(P, np.float64).reshape(-1, 12), np.asarray(true_P, np.float64).reshape(-1, 12)
+    return float(np.abs(np.log(a[:, :2] / b[:, :2])).mean()), float(np.linalg.norm(a[:, 2:4] - b[:, 2:4], axis=1).mean())
+
+
 def pose_errors(poses, true_poses):
     """(mean rotation angle in degrees, mean translation distance) between two sets of [N, 4, 4] poses"""
     a, b = np.asarray(poses, np.float64).reshape(-1, 4, 4), np.asarray(true_poses, np.float64).reshape(-1, 4, 4)
@@ -160,6 +191,12 @@ def main():
                          "its intrinsics into transforms_train.json (DESIGN 5.20)")
     ap.add_argument("--assume-pinhole", action="store_true",
                     help="ignore the intrinsics in transforms_train.json and train and score under the centred pinhole of camera_angle_x")
+    ap.add_argument("--intrinsics-noise", default=None, metavar="focal=F,center=C",
+                    help="perturb the training cameras on load: fx and fy by a seeded factor exp(+-F), the principal point by C pixels in "
+                         "a seeded direction; the errors against the file's cameras are printed before and after training")
+    ap.add_argument("--refine-cameras", nargs="?", const="", default=None, metavar="focal=LR,center=LR,distortion=LR",
+                    help="refine the cameras' intrinsics on the device beside the weights (attach_images(refine_cameras=...), DESIGN 5.21); "
+                         "rates per group, 0 freezes one, defaults api.CAMERA_REFINE_DEFAULTS; needs a scene with cameras and --encoding hash")
     a = ap.parse_args()
     json_path = os.path.join(a.data, "transforms_train.json")
     if a.make_demo:
@@ -177,6 +214,15 @@ def main():
         a.device_batches = True
         if a.encoding != "hash":
             sys.exit("--refine-poses needs --encoding hash (ray gradients go through the hash grid)")
+    refine_cameras = None
+    if a.refine_cameras is not None or a.intrinsics_noise:
+        if not use_cameras:
+            sys.exit("--refine-cameras / --intrinsics-noise need a scene whose transforms_train.json carries intrinsics (--make-demo --lens ...)")
+    if a.refine_cameras is not None:
+        if a.encoding != "hash":
+            sys.exit("--refine-cameras needs --encoding hash (ray gradients go through the hash grid)")
+        rates = parse_groups(a.refine_cameras, ("focal", "center", "distortion"), "--refine-cameras")
+        refine_cameras = {f"lr_{k}": v for k, v in rates.items()} or True
     loss_scale = api.loss_scaler(growth_interval=a.growth_interval) if a.loss_scale == "dynamic" else float(a.loss_scale)
     schedule = a.lr_schedule
     if schedule and schedule.startswith("cosine:"):
@@ -200,6 +246,11 @@ def main():
     cams_train = cams_hold = None
     if use_cameras:
         model, P = loader.read_cameras(json_path, ds.image_width, ds.image_height)
+        true_P = P[:1] if P.shape[0] == 1 else P[:-n_hold]
+        if a.intrinsics_noise:
+            noise = parse_groups(a.intrinsics_noise, ("focal", "center"), "--intrinsics-noise")
+            P = perturb_cameras(P, noise.get("focal", 0.0), noise.get("center", 0.0))
+        loaded_P = (P[:1] if P.shape[0] == 1 else P[:-n_hold]).copy()
         if P.shape[0] == 1:
             cams_train = cams_hold = api.camera_set(model, P, width=ds.image_width, height=ds.image_height)
         else:                  # one camera per frame: the held-out frames are the last n_hold
@@ -222,7 +273,8 @@ def main():
     tr = Trainer(R, None, lr=1e-2 if a.encoding == "hash" else 2e-3, loss=a.loss, opacity_weight=a.opacity_weight,
                  background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C, distortion_weight=a.distortion_weight,
                  loss_scale=loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite,
-                 max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay, ray_gradients=a.refine_poses is not None, **model)
+                 max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay,
+                 ray_gradients=a.refine_poses is not None or refine_cameras is not None, **model)
     white = (1.0, 1.0, 1.0) if rgba else None
     # the held-out frames stay on the device as they were loaded (flags=2 frames are k/255: one byte per channel holds them exactly)
     hold_ds = loader.ImageDataset(ds.images[-n_hold:], ds.poses[-n_hold:], ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
@@ -241,7 +293,7 @@ def main():
         return score() if a.ema_decay is None else f"{score()} live, {score('ema')} averaged"
 
     if a.device_batches:
-        tr.attach_images(images, refine_poses=None if a.refine_poses is None else dict(lr=a.refine_poses))
+        tr.attach_images(images, refine_poses=None if a.refine_poses is None else dict(lr=a.refine_poses), refine_cameras=refine_cameras)
     g = torch.Generator(device="cuda").manual_seed(0)
     W, H = ds.image_width, ds.image_height
     if use_cameras:
@@ -265,6 +317,21 @@ def main():
             r1, t1 = pose_errors(tr.refined_poses().cpu().numpy(), true_poses)
             line += f"; {r1:.4f} deg, {t1:.5f} after refinement ({int(tr.pose_updates.min().item())}+ updates per image)"
         print(line)
+    if use_cameras and (a.intrinsics_noise or refine_cameras is not None):
+        # a camera shared by every frame is shared with the held-out set too: the scores above are under the refined row
+        f0, c0 = camera_errors(loaded_P, true_P)
+        line = f"training cameras against the file's: mean |log focal ratio| {f0:.5f}, mean principal-point error {c0:.3f} px as loaded"
+        if refine_cameras is not None:
+            tr.check_cameras()                 # the live rows are still invertible over the frame (raises naming camera and pixel)
+            refined = tr.refined_cameras().cpu().numpy()
+            f1, c1 = camera_errors(refined, true_P)
+            line += f"; {f1:.5f}, {c1:.3f} px after refinement ({int(tr.camera_updates.min().item())}+ updates per camera)"
+        print(line)
+        np.set_printoptions(precision=5, suppress=True, linewidth=200)
+        print("rows (fx fy cx cy k1 k2 k3 k4 p1 p2), camera 0:\n  loaded ", loaded_P[0, :10])
+        if refine_cameras is not None:
+            print("  refined", refined[0, :10])
+        print("  true   ", np.asarray(true_P)[0, :10])
     if tr.loss_scale_now is not None:
         print(f"loss scale now {float(tr.loss_scale_now.item()):g}: {int(tr.skipped_steps.item())} steps skipped, "
               f"{int(tr.scale_backoffs.item())} backoffs, {int(tr.scale_growths.item())} growths, {int(tr.clipped_steps.item())} steps clipped, "

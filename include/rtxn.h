@@ -1691,7 +1691,7 @@ int rtxn_train_step_rays(const rtxn_train_step_args* args, const rtxn_train_back
  *     q = (sin(th) xd / thd, sin(th) yd / thd, -cos(th)); thd < 1e-8: q = (xd, yd, -1).   (p1, p2 are not read)
  *   d = normalise(fmaf(la[4k+2], q2, fmaf(la[4k], q0, la[4k+1] q1)))_k=0..2,   o_k = la[4k+3] / 10   (the pinhole launch's origin).
  * There is no per-ray validity flag: the parameters must be invertible over the frame, which is the caller's to establish
- * (rtx_nerf_amd.api.camera_set checks it on the host).  Nothing here refines the parameters; they are only read.
+ * (rtx_nerf_amd.api.camera_set checks it on the host).  These calls only read the parameters; rtxn_camera_refinement below optimises them.
  * rtxn_camera_set_check: host only.  RTXN_ERR_INVALID with a message for a NULL set, an unknown model, n_cameras outside
  *   {1, n_images} or NULL params.
  * rtxn_camera_rays: the rays of launch pixels [ray_begin, ray_begin + ray_count) of a width x height frame of camera `camera`
@@ -1728,6 +1728,80 @@ int rtxn_render_frame_rays(rtxn_render* r, int slot, const float* rays_o, const 
                            uint32_t ray_count, const rtxn_render_outputs* outputs, rtxn_stream_t stream);
 int rtxn_render_count_segments_rays(rtxn_render* r, const float* rays_o, const float* rays_d, uint32_t ray_begin,
                                     uint32_t ray_count, long* segments, rtxn_stream_t stream);
+
+/* ---- intrinsics refinement: the camera rows optimised beside the poses --------------------------------------
+ * instant-ngp's intrinsics optimisation over the rows of rtxn_camera_set, from the dL/d(rays_d) the ray gradients leave.  No
+ * float atomics, every sum in a fixed order: the same bits on every run.  Stream-ordered, no allocation, nothing read on the
+ * host: hipGraph-capturable.
+ *
+ * 1. rtxn_camera_gradients.  For ray r drawn at pixel (px, py) = (pixel % width, pixel / width) of image i (drawn[r] = (i, pixel)),
+ *    camera row cam = params[n_cameras == 1 ? 0 : i] and pose rotation R (la = set_poses[i], R_kc = la[4k+c]), the draw formed
+ *      xd = (px + 0.5 - cx) / fx,  yd = (py + 0.5 - cy) / fy,  q = U(xd, yd; k),  w = R q,  d = w / |w|
+ *    (rtxn_camera_set above) and the kernel forms them again from the live row with the draw's own device functions, so the
+ *    point of linearisation is the ray that was drawn.  With g = d_direction[r]:
+ *      gw = (g - d (g . d)) / |w|,   gq = R^T gw,   (lx, ly) = dL/d(xd, yd) per model,
+ *      dL/dfx = -lx xd / fx,  dL/dfy = -ly yd / fy,  dL/dcx = -lx / fx,  dL/dcy = -ly / fy.
+ *    PINHOLE: (lx, ly) = (gq0, gq1); the six distortion entries are exactly 0.
+ *    OPENCV: (x, y) = (q0, q1) the Newton solution, r2 = x^2 + y^2, J the symmetric Jacobian of the forward map there (implicit
+ *      function theorem):  (lx, ly) = J^-1 (gq0, gq1);  dL/dk_n = -(lx x + ly y) r2^n, n = 1, 2, 3;
+ *      dL/dp1 = -(lx 2xy + ly (r2 + 2y^2));  dL/dp2 = -(lx (r2 + 2x^2) + ly 2xy);  dL/dk4 = 0.
+ *    OPENCV_FISHEYE: thd = |(xd, yd)|, u = (xd, yd) / thd, th the solution, dpoly = d(th poly(th))/dth there:
+ *      gth = cos(th) (gq0 ux + gq1 uy) + sin(th) gq2,  a = sin(th) (gq0, gq1),
+ *      (lx, ly) = (gth / dpoly) u + (a - (a . u) u) / thd;  dL/dk_n = -gth th^(2n+1) / dpoly, n = 1..4;  dL/dp1 = dL/dp2 = 0.
+ *      thd < 1e-8 (the draw's pinhole branch): the pinhole form for fx..cy, 0 for k.
+ *    Two kernels: one thread per ray writes its twelve floats (ten terms, two zeros) into terms[r]; then one block per camera,
+ *    thread t summing its camera's rays r = t, t + 256, ... in ascending order, the wave's xor butterfly, the four waves in
+ *    order -- rtxn_pose_gradients' fold.  A shared camera (n_cameras == 1) receives every ray.
+ *      grad[c] = (dL/dfx, dfy, dcx, dcy, dk1, dk2, dk3, dk4, dp1, dp2, ray count, 0).
+ *    drawn[r][0] must be an image of set_poses (what rtxn_draw_batch records); a ray of a camera >= n_cameras is ignored.
+ * 2. rtxn_camera_step.  delta[c][10] against the untouched params0, in three groups with a rate and a bound each:
+ *      focal       fx = fx0 exp(delta0), fy = fy0 exp(delta1)           gradient of delta: dL/dfx fx, dL/dfy fy (the live fx, fy)
+ *      centre      cx = cx0 + delta2, cy = cy0 + delta3  (pixels)       dL/dcx, dL/dcy
+ *      distortion  k1..k4, p1, p2 = the loaded values + delta4..9       the entries of grad
+ *    An entry is ACTIVE when the model has it (PINHOLE: none of the six; OPENCV: not k4; OPENCV_FISHEYE: not p1, p2) and its
+ *    group's rate is > 0.  Per camera: nothing moves when *skip != 0 (rtxn_optimizer_options.guard + 2), when the ray count is
+ *    0 (the table's sparse rule) or when no entry is active; a non-finite gradient among the active entries moves nothing for
+ *    that camera and adds one to *skipped.  Otherwise steps += 1 and, for every active entry, rtxn_pose_step's Adam with the
+ *    group's rate (1 - b^steps in double, rounded once), delta clamped to +- the group's bound, and the entry recomposed into
+ *    params.  No word of an inactive entry -- delta, moments, parameter -- is written.  delta == 0 composes the loaded word
+ *    itself, so a zero delta gives params0 bit for bit.  The bounds are safety rails, not a guarantee of invertibility over
+ *    the frame: that stays the host's float64 check (rtx_nerf_amd Trainer.check_cameras()).
+ * 3. rtxn_camera_compose: all twelve words of every row from delta and params0 alone (a loaded checkpoint, a reset).
+ * rtxn_camera_refinement_check: host only, the rules without the device buffers.  RTXN_ERR_INVALID with a message naming the
+ * field: an unknown model, n_cameras < 1, a rate < 0 or not finite, a bound < 0 or NaN, a beta outside [0, 1), eps <= 0.  The
+ * device calls also need the seven state buffers, and rtxn_camera_gradients terms (16-byte aligned) and width >= 1. */
+typedef struct rtxn_camera_refinement {
+  int model, n_cameras;  /* as the rtxn_camera_set the rows belong to */
+  uint32_t width;        /* the frames' width: drawn's pixel is py * width + px */
+  float lr_focal, lr_center, lr_distortion;                  /* a rate of 0 freezes the group */
+  float max_log_focal, max_center, max_distortion;           /* |delta| <= the group's bound */
+  float beta1, beta2, eps;
+  const float* params0;  /* DEVICE float[n_cameras][12]: the rows as loaded, never written */
+  float* params;         /* DEVICE float[n_cameras][12]: what rtxn_camera_set.params points at, rewritten by the step */
+  float* delta;          /* DEVICE float[n_cameras][10] */
+  float* m;              /* DEVICE float[n_cameras][10] */
+  float* v;              /* DEVICE float[n_cameras][10] */
+  int* steps;            /* DEVICE int[n_cameras]: updates applied per camera */
+  float* grad;           /* DEVICE float[n_cameras][12]: ten sums, the ray count, one pad */
+  float* terms;          /* DEVICE float[n_rays][12], 16-byte aligned: rtxn_camera_gradients' per-ray scratch (48 B per ray) */
+  const unsigned* skip;  /* optional DEVICE word: != 0 = this step was skipped (rtxn_optimizer_options.guard + 2) */
+  unsigned* skipped;     /* optional DEVICE counter of updates refused for a non-finite gradient */
+  const uint32_t* drawn; /* DEVICE uint32[n_rays][2] as rtxn_draw_batch records it: read by rtxn_train_step_cameras only */
+  const float* poses;    /* DEVICE float[n_images][16], the set's live poses (rtxn_image_set.poses): likewise */
+} rtxn_camera_refinement;
+int rtxn_camera_refinement_check(const rtxn_camera_refinement* cameras);
+int rtxn_camera_gradients(const uint32_t* drawn, const float* d_direction, int n_rays, const float* set_poses,
+                          const rtxn_camera_refinement* cameras, rtxn_stream_t stream);
+int rtxn_camera_step(const rtxn_camera_refinement* cameras, rtxn_stream_t stream);
+int rtxn_camera_compose(const rtxn_camera_refinement* cameras, rtxn_stream_t stream);
+/* rtxn_train_step_rays with the intrinsics refinement.  Behind the optimizer: the pose gradient, the camera gradient (over
+ * cameras->drawn, rays->d_direction and cameras->poses), the pose step, the camera step -- both gradients see the rotation and
+ * the rows the batch was drawn with.  cameras without rays is refused, as is cameras without drawn or poses; cameras == NULL:
+ * exactly rtxn_train_step_rays. */
+int rtxn_train_step_cameras(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                            const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                            const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
+                            const rtxn_pose_refinement* pose, const rtxn_camera_refinement* cameras, rtxn_stream_t stream);
 
 #ifdef __cplusplus
 }

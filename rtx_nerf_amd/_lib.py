@@ -208,6 +208,15 @@ class PoseRefinement(C.Structure):
                 ("beta2", C.c_float), ("eps", C.c_float), ("skip", C.c_void_p), ("skipped", C.c_void_p), ("drawn", C.c_void_p)]
 
 
+class CameraRefinement(C.Structure):
+    """struct rtxn_camera_refinement (include/rtxn.h)."""
+    _fields_ = [("model", C.c_int), ("n_cameras", C.c_int), ("width", C.c_uint32), ("lr_focal", C.c_float), ("lr_center", C.c_float),
+                ("lr_distortion", C.c_float), ("max_log_focal", C.c_float), ("max_center", C.c_float), ("max_distortion", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("params0", C.c_void_p), ("params", C.c_void_p),
+                ("delta", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("steps", C.c_void_p), ("grad", C.c_void_p),
+                ("terms", C.c_void_p), ("skip", C.c_void_p), ("skipped", C.c_void_p), ("drawn", C.c_void_p), ("poses", C.c_void_p)]
+
+
 class RenderConfig(C.Structure):
     """struct rtxn_render_config (include/rtxn.h)."""
     _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("table_fp16", C.c_void_p), ("n_dir_freqs", C.c_int),
@@ -452,6 +461,13 @@ SYMBOLS = {
     "rtxn_train_step_rays": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                   C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma),
                                   C.POINTER(RayGradients), C.POINTER(PoseRefinement), _P]),
+    "rtxn_camera_refinement_check": (_I, [C.POINTER(CameraRefinement)]),
+    "rtxn_camera_gradients": (_I, [_P, _P, _I, _P, C.POINTER(CameraRefinement), _P]),
+    "rtxn_camera_step": (_I, [C.POINTER(CameraRefinement), _P]),
+    "rtxn_camera_compose": (_I, [C.POINTER(CameraRefinement), _P]),
+    "rtxn_train_step_cameras": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                     C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma),
+                                     C.POINTER(RayGradients), C.POINTER(PoseRefinement), C.POINTER(CameraRefinement), _P]),
     "rtxn_camera_set_check": (_I, [C.POINTER(CameraSet), _I]),
     "rtxn_camera_rays": (_I, [C.POINTER(CameraSet), _I, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "rtxn_draw_batch_cameras": (_I, [C.POINTER(DrawBatchArgs), C.POINTER(CameraSet), _P]),

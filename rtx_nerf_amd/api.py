@@ -1464,7 +1464,7 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
 # The rungs of the step and gradients ladders (include/rtxn.h), topmost first: (suffix, how many of the options
 # (background, jitter, loss, regularizer, ...) the rung takes, which of them select it).  The call goes to the topmost rung one of
 # whose own options is given: the lowest entry point that takes everything that is.
-_STEP_LADDER = (("_rays", 9, (7, 8)), ("_ema", 7, (6,)), ("_scaled", 6, (5,)), ("_opt", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)),
+_STEP_LADDER = (("_cameras", 10, (9,)), ("_rays", 9, (7, 8)), ("_ema", 7, (6,)), ("_scaled", 6, (5,)), ("_opt", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)),
                 ("_jitter", 2, (1,)), ("_ex", 1, (0,)), ("", 0, ()))
 _GRADIENTS_LADDER = (("_rays", 6, (5,)), ("_scaled", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)), ("_jitter", 2, (1,)), ("_ex", 1, (0,)),
                      ("", 0, ()))
@@ -1520,7 +1520,8 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
     return b
 
 
-def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None, ema=None, rays=None, pose=None):
+def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None, ema=None, rays=None, pose=None,
+               cameras=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
     jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
@@ -1532,10 +1533,15 @@ def train_step(args, background=None, jitter=None, loss=None, regularizer=None, 
     ema: weight_ema(...) -> rtxn_train_step_ema (needs `optimizer`, which may have nothing switched on; with or without a scaler);
     rays: ray_gradients(...), pose: pose_refinement(...) -> rtxn_train_step_rays (with or without any of the seven; pose needs rays):
     the write pass stores t_start / t_end into rays' buffers, the ray gradients are formed behind the table scatter and the pose
-    gradient and step run behind the optimizer."""
+    gradient and step run behind the optimizer;
+    cameras: camera_refinement(...) with drawn and poses -> rtxn_train_step_cameras (needs rays): behind the optimizer the pose
+    gradient, the camera gradient, the pose step, the camera step."""
     _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
     _check_ray_gradients("train_step", rays, args.batch.n_rays, args.batch.segment_capacity)
-    options = (background, jitter, loss, regularizer, optimizer, scaler, ema, rays, pose)
+    terms = getattr(cameras, "_tensors", {}).get("terms")
+    if terms is not None and terms.numel() < 12 * int(args.batch.n_rays):
+        raise _lib.RtxnError(f"train_step: cameras.terms holds {terms.numel()} elements, {12 * int(args.batch.n_rays)} needed")
+    options = (background, jitter, loss, regularizer, optimizer, scaler, ema, rays, pose, cameras)
     name, n_options = _ladder_entry("rtxn_train_step", _STEP_LADDER, options)
     check(getattr(_lib.lib(), name)(C.byref(args), *map(_byref, options[:n_options]), _stream()), name)
 
@@ -1790,7 +1796,7 @@ class CameraSet:
         """ValueError unless every camera of the set is invertible over a width x height frame: on the host, in float64, at a
         33 x 33 lattice of pixel positions spanning the frame's corners ([0, width] x [0, height]) the Newton solve of the device
         function, run to convergence, must reproduce the position (residual <= 1e-9) with a positive Jacobian determinant at
-        the solution.  Uses the parameters as they were when the set was built."""
+        the solution.  Uses the host copy of the parameters: as they were when the set was built, or at the last refresh_host()."""
         key = (int(width), int(height))
         if key in self._checked:
             return
@@ -1812,6 +1818,13 @@ class CameraSet:
                                  f"({px[0, j]:.2f}, {py[0, j]:.2f}) the float64 solve leaves a residual of {res[c, j]:.3g} with "
                                  f"Jacobian determinant {det[c, j]:.3g}")
         self._checked.add(key)
+
+    def refresh_host(self):
+        """Read the rows back from the device (they may have been refined in place: Trainer.attach_images(refine_cameras=)) and
+        forget every frame size checked so far, so that the next check_invertible() judges the live parameters."""
+        self._host = self.params.detach().cpu().numpy().astype(np.float64)
+        self._checked = set()
+        return self
 
     def c_struct(self):
         s = _lib.CameraSet()
@@ -2036,3 +2049,65 @@ def pose_step(pose):
 def pose_compose(pose):
     """rtxn_pose_compose: poses from delta and poses0 alone (after a checkpoint was loaded into delta, or a reset)."""
     check(_lib.lib().rtxn_pose_compose(C.byref(pose), _stream()), "rtxn_pose_compose")
+
+
+# --------------------------------------------------------------------------- intrinsics refinement
+CAMERA_DELTA = 10          # fx, fy, cx, cy, k1, k2, k3, k4, p1, p2
+# Defaults of camera_refinement() / Trainer.attach_images(refine_cameras=True), chosen on the lens demo of DESIGN 5.21 (one seed):
+# the distortion group is FROZEN by default -- the demo does not recover its coefficients -- and moves only with a rate of its own.
+CAMERA_REFINE_DEFAULTS = dict(lr_focal=1e-3, lr_center=3e-2, lr_distortion=0.0, max_log_focal=0.25, max_center=8.0, max_distortion=0.05,
+                              beta1=0.9, beta2=0.999, eps=1e-15)
+
+
+def camera_refinement(model=CAMERA_PINHOLE, n_cameras=1, width=0, *, lr_focal=None, lr_center=None, lr_distortion=None, max_log_focal=None,
+                      max_center=None, max_distortion=None, beta1=None, beta2=None, eps=None, params0=None, params=None, delta=None, m=None,
+                      v=None, steps=None, grad=None, terms=None, skip=None, skipped=None, drawn=None, poses=None):
+    """struct rtxn_camera_refinement (include/rtxn.h), its rules checked (rtxn_camera_refinement_check) before any buffer is looked
+    at.  model: a CAMERA_* value or name; width: the frames' width.  A rate of 0 freezes its group (focal: fx, fy as
+    fx0 exp(delta); centre: cx, cy in pixels; distortion: k1..k4, p1, p2); max_*: the clamp of the group's |delta|.  Without
+    tensors: the configuration alone.  params0, params float32 [n, 12]; delta, m, v float32 [n, 10]; steps int32 [n]; grad float32
+    [n, 12]; terms float32 [>= n_rays, 12] (the gradient's scratch); skip: the optimizer guard's skip word or None; skipped int32
+    [1] or None; drawn int32 [n_rays, 2] and poses float32 [n_images, 16] (train_step only).  The tensors stay referenced."""
+    s = _lib.CameraRefinement()
+    s.model, s.n_cameras, s.width = int(CAMERA_MODELS.get(model, model)), int(n_cameras), int(width)
+    cfg = dict(CAMERA_REFINE_DEFAULTS)
+    cfg.update({k: val for k, val in dict(lr_focal=lr_focal, lr_center=lr_center, lr_distortion=lr_distortion, max_log_focal=max_log_focal,
+                                          max_center=max_center, max_distortion=max_distortion, beta1=beta1, beta2=beta2, eps=eps).items()
+                if val is not None})
+    for k, val in cfg.items():
+        setattr(s, k, float(val))
+    check(_lib.lib().rtxn_camera_refinement_check(C.byref(s)), "rtxn_camera_refinement_check")
+    n = s.n_cameras
+    s._tensors = dict(params0=params0, params=params, delta=delta, m=m, v=v, steps=steps, grad=grad, terms=terms, skip=skip, skipped=skipped,
+                      drawn=drawn, poses=poses)
+    for nm, t, dt, need in (("params0", params0, torch.float32, CAMERA_PARAMS * n), ("params", params, torch.float32, CAMERA_PARAMS * n),
+                            ("delta", delta, torch.float32, CAMERA_DELTA * n), ("m", m, torch.float32, CAMERA_DELTA * n),
+                            ("v", v, torch.float32, CAMERA_DELTA * n), ("steps", steps, torch.int32, n), ("grad", grad, torch.float32, 12 * n),
+                            ("terms", terms, torch.float32, 12), ("skip", skip, torch.int32, 1), ("skipped", skipped, torch.int32, 1),
+                            ("drawn", drawn, torch.int32, 0), ("poses", poses, torch.float32, 16)):
+        if t is not None and t.numel() < need:
+            raise _lib.RtxnError(f"camera_refinement: {nm} holds {t.numel()} elements, {need} needed for {n} cameras")
+        setattr(s, nm, _ptr(t, dt, nm))
+    return s
+
+
+def camera_gradients(drawn, d_direction, n_rays, set_poses, cameras):
+    """rtxn_camera_gradients: cameras.grad[c] = (dL/d(fx, fy, cx, cy, k1..k4, p1, p2), ray count, 0) summed over the rays drawn
+    with camera c (every ray for a shared camera), from dL/d(rays_d) and the poses the batch was drawn with."""
+    n = int(n_rays)
+    terms = getattr(cameras, "_tensors", {}).get("terms")
+    for nm, t, need in (("drawn", drawn, 2 * n), ("d_direction", d_direction, 3 * n), ("terms", terms, 12 * n)):
+        if t is not None and t.numel() < need:
+            raise _lib.RtxnError(f"camera_gradients: {nm} holds {t.numel()} elements, {need} needed")
+    check(_lib.lib().rtxn_camera_gradients(_ptr(drawn, torch.int32, "drawn"), _ptr(d_direction, torch.float32, "d_direction"), n,
+                                           _ptr(set_poses, torch.float32, "set_poses"), C.byref(cameras), _stream()), "rtxn_camera_gradients")
+
+
+def camera_step(cameras):
+    """rtxn_camera_step: the per-camera three-group Adam on delta from cameras.grad, clamped, then the rows recomposed."""
+    check(_lib.lib().rtxn_camera_step(C.byref(cameras), _stream()), "rtxn_camera_step")
+
+
+def camera_compose(cameras):
+    """rtxn_camera_compose: the rows from delta and params0 alone (after a checkpoint was loaded into delta, or a reset)."""
+    check(_lib.lib().rtxn_camera_compose(C.byref(cameras), _stream()), "rtxn_camera_compose")

@@ -11,22 +11,33 @@ constexpr int kCameraNewtonSteps = 8;   // fp32 stops moving after 3 to 4 on eve
 // host only (camera.hip): the set's rules under `who`; n_images < 0: any n_cameras >= 1
 int check_camera_set(const rtxn_camera_set* cameras, int n_images, const char* who);
 
+// The OpenCV model's forward map at (x, y): the residual's two values before (xd, yd) is subtracted, and the symmetric Jacobian
+// d(xd, yd) / d(x, y).  One body for the Newton solve below and for the intrinsics gradient (camera_refine.hip), which
+// linearises at the solution.
+__device__ __forceinline__ void opencv_forward(const float* __restrict__ cam, float x, float y, float& fx, float& fy, float& j11,
+                                               float& j12, float& j22) {
+  const float k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[8], p2 = cam[9];
+  const float xx = x * x, yy = y * y, xy = x * y;
+  const float r2 = xx + yy;
+  const float rad = fmaf(r2, fmaf(r2, fmaf(r2, k3, k2), k1), 1.0f);
+  const float drad = fmaf(r2, fmaf(r2, 3.0f * k3, 2.0f * k2), k1);            // d rad / d r2
+  fx = fmaf(x, rad, fmaf(2.0f * p1, xy, p2 * fmaf(2.0f, xx, r2)));
+  fy = fmaf(y, rad, fmaf(2.0f * p2, xy, p1 * fmaf(2.0f, yy, r2)));
+  j11 = fmaf(2.0f * xx, drad, rad) + fmaf(2.0f * p1, y, 6.0f * p2 * x);
+  j22 = fmaf(2.0f * yy, drad, rad) + fmaf(2.0f * p2, x, 6.0f * p1 * y);
+  j12 = fmaf(2.0f * xy, drad, 2.0f * fmaf(p1, x, p2 * y));                    // = j21
+}
+
 // (xd, yd) -> the undistorted (x, y) of the OpenCV radial-tangential model
 __device__ __forceinline__ void undistort_opencv(const float* __restrict__ cam, float xd, float yd, float& x, float& y) {
-  const float k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[8], p2 = cam[9];
   x = xd;
   y = yd;
 #pragma unroll
   for (int it = 0; it < kCameraNewtonSteps; ++it) {
-    const float xx = x * x, yy = y * y, xy = x * y;
-    const float r2 = xx + yy;
-    const float rad = fmaf(r2, fmaf(r2, fmaf(r2, k3, k2), k1), 1.0f);
-    const float drad = fmaf(r2, fmaf(r2, 3.0f * k3, 2.0f * k2), k1);            // d rad / d r2
-    const float fx = fmaf(x, rad, fmaf(2.0f * p1, xy, p2 * fmaf(2.0f, xx, r2))) - xd;
-    const float fy = fmaf(y, rad, fmaf(2.0f * p2, xy, p1 * fmaf(2.0f, yy, r2))) - yd;
-    const float j11 = fmaf(2.0f * xx, drad, rad) + fmaf(2.0f * p1, y, 6.0f * p2 * x);
-    const float j22 = fmaf(2.0f * yy, drad, rad) + fmaf(2.0f * p2, x, 6.0f * p1 * y);
-    const float j12 = fmaf(2.0f * xy, drad, 2.0f * fmaf(p1, x, p2 * y));        // = j21
+    float fx, fy, j11, j12, j22;
+    opencv_forward(cam, x, y, fx, fy, j11, j12, j22);
+    fx -= xd;
+    fy -= yd;
     const float det = fmaf(j11, j22, -(j12 * j12));
     const bool ok = det != 0.0f && isfinite(det);
     const float dx = fmaf(j22, fx, -(j12 * fy)) / det;
@@ -34,6 +45,13 @@ __device__ __forceinline__ void undistort_opencv(const float* __restrict__ cam, 
     x = ok ? x - dx : x;
     y = ok ? y - dy : y;
   }
+}
+
+// d (th poly(th)) / d th of the fisheye polynomial: the Newton solve's derivative, and the intrinsics gradient's
+__device__ __forceinline__ float fisheye_dpoly(const float* __restrict__ cam, float th) {
+  const float k1 = cam[4], k2 = cam[5], k3 = cam[6], k4 = cam[7];
+  const float t2 = th * th;
+  return fmaf(t2, fmaf(t2, fmaf(t2, fmaf(t2, 9.0f * k4, 7.0f * k3), 5.0f * k2), 3.0f * k1), 1.0f);
 }
 
 // thd -> the undistorted angle of the OpenCV fisheye (equidistant polynomial) model
@@ -44,7 +62,7 @@ __device__ __forceinline__ float undistort_fisheye(const float* __restrict__ cam
   for (int it = 0; it < kCameraNewtonSteps; ++it) {
     const float t2 = th * th;
     const float poly = fmaf(t2, fmaf(t2, fmaf(t2, fmaf(t2, k4, k3), k2), k1), 1.0f);
-    const float dpoly = fmaf(t2, fmaf(t2, fmaf(t2, fmaf(t2, 9.0f * k4, 7.0f * k3), 5.0f * k2), 3.0f * k1), 1.0f);   // d (th poly) / d th
+    const float dpoly = fisheye_dpoly(cam, th);
     const float f = fmaf(th, poly, -thd);
     const bool ok = dpoly != 0.0f && isfinite(dpoly);
     const float dth = f / dpoly;

@@ -99,6 +99,8 @@ int check_ray_gradients(const char* who, const rtxn_ray_gradients* rays, const r
 // The rules of the pose refinement (rtxn_pose_refinement, include/rtxn.h), host only, pose.hip.  need_buffers: the struct must also
 // carry its device buffers.
 int check_pose_refinement(const rtxn_pose_refinement* pose, const char* who, bool need_buffers);
+// The rules of the intrinsics refinement (rtxn_camera_refinement, include/rtxn.h), host only, camera_refine.hip; need_buffers as above.
+int check_camera_refinement(const rtxn_camera_refinement* cameras, const char* who, bool need_buffers);
 
 // The option structs of the training entry ladders (rtxn_train_step*, rtxn_train_gradients*), library-internal: a
 // public entry point fills the pointers its signature has and leaves the rest NULL.  check_train_options replaces every
@@ -113,11 +115,12 @@ struct TrainOptions {
   const rtxn_weight_ema* ema = nullptr;
   const rtxn_ray_gradients* rays = nullptr;
   const rtxn_pose_refinement* pose = nullptr;
+  const rtxn_camera_refinement* cameras = nullptr;
   rtxn_train_background own_bg;
   rtxn_sample_jitter own_jitter;
 };
 // the rungs of both ladders, in the order they were added (the gradients ladder has no _opt and no _ema)
-enum TrainRung { RUNG_PLAIN, RUNG_EX, RUNG_JITTER, RUNG_LOSS, RUNG_REG, RUNG_OPT, RUNG_SCALED, RUNG_EMA, RUNG_RAYS };
+enum TrainRung { RUNG_PLAIN, RUNG_EX, RUNG_JITTER, RUNG_LOSS, RUNG_REG, RUNG_OPT, RUNG_SCALED, RUNG_EMA, RUNG_RAYS, RUNG_CAMERAS };
 // The one checked path of both ladders, host only, trainer.hip: every struct's rules once, in one order, under the name the
 // rung reports under (the name rule of DESIGN 5.17); then inactive structs become NULL and a step (a: its arguments, b unused)
 // gets its own copies.  A gradients call passes a = NULL and its batch.

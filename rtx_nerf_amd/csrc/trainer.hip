@@ -123,14 +123,16 @@ static int optimizer_step(const rtxn_train_step_args* a, const rtxn_optimizer_op
 
 // ---- the one checked path of the step and gradients ladders (common.h) ----------------------------------------------
 
-// The name rule: a rung reports under its own name while it holds a struct of its own -- _rays: rays or pose, _ema: the EMA,
+// The name rule: a rung reports under its own name while it holds a struct of its own -- _cameras: cameras, _rays: rays or pose, _ema: the EMA,
 // _scaled: the scaler, _opt: options (have_opt: present for the options' own check, ACTIVE from then on) -- and is the rung below
 // otherwise; _reg and the rungs below it always report under their own name.
 static const char* entry_name(bool step, int rung, const rtxn::TrainOptions& o, bool have_opt) {
   static const char* const kStep[] = {"rtxn_train_step", "rtxn_train_step_ex", "rtxn_train_step_jitter", "rtxn_train_step_loss", "rtxn_train_step_reg",
-                                      "rtxn_train_step_opt", "rtxn_train_step_scaled", "rtxn_train_step_ema", "rtxn_train_step_rays"};
+                                      "rtxn_train_step_opt", "rtxn_train_step_scaled", "rtxn_train_step_ema", "rtxn_train_step_rays",
+                                      "rtxn_train_step_cameras"};
   static const char* const kGradients[] = {"rtxn_train_gradients", "rtxn_train_gradients_ex", "rtxn_train_gradients_jitter", "rtxn_train_gradients_loss",
-                                           "rtxn_train_gradients_reg", nullptr, "rtxn_train_gradients_scaled", nullptr, "rtxn_train_gradients_rays"};
+                                           "rtxn_train_gradients_reg", nullptr, "rtxn_train_gradients_scaled", nullptr, "rtxn_train_gradients_rays", nullptr};
+  if (rung == rtxn::RUNG_CAMERAS && !o.cameras) rung = rtxn::RUNG_RAYS;
   if (rung == rtxn::RUNG_RAYS && !o.rays && !o.pose) rung = rtxn::RUNG_EMA;
   if (rung == rtxn::RUNG_EMA && !o.ema) rung = rtxn::RUNG_SCALED;
   if (rung == rtxn::RUNG_SCALED && !o.scaler) rung = rtxn::RUNG_OPT;
@@ -207,6 +209,13 @@ int rtxn::check_train_options(rtxn::TrainRung rung, bool step, const rtxn_train_
     RTXN_REQUIRE(o->pose->drawn && a->trace.rays_d, "%s: pose->drawn = %p, trace.rays_d = %p: the pose gradient reads (image, pixel) per ray "
                  "and the explicit rays", who, (const void*)o->pose->drawn, (const void*)a->trace.rays_d);
   }
+  if (o->cameras) {
+    RTXN_REQUIRE(o->rays, "%s: cameras without rays: the intrinsics gradient is formed from the ray gradients", who);
+    rc = rtxn::check_camera_refinement(o->cameras, who, true);
+    if (rc != RTXN_OK) return rc;
+    RTXN_REQUIRE(o->cameras->drawn && o->cameras->poses, "%s: cameras->drawn = %p, cameras->poses = %p: the intrinsics gradient reads "
+                 "(image, pixel) per ray and the set's poses", who, (const void*)o->cameras->drawn, (const void*)o->cameras->poses);
+  }
   if (!step) return RTXN_OK;
   // RANDOM without a counter of its own: the optimizer's, read by the compositor before the step is advanced; a jitter without one
   // likewise, by the same rule
@@ -278,11 +287,22 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn::TrainOptio
   if (rc != RTXN_OK) return rc;
 
   rc = optimizer_step(a, o.opt, o.scaler, o.ema, stream);
-  if (rc != RTXN_OK || !o.pose) return rc;
-  // ---- the pose gradient and the pose step, behind the optimizer: they see the guard's skip word ----
-  rc = rtxn_pose_gradients(o.pose->drawn, a->trace.rays_d, o.rays->d_origin, o.rays->d_direction, b.n_rays, o.pose, stream);
   if (rc != RTXN_OK) return rc;
-  return rtxn_pose_step(o.pose, stream);
+  // ---- the pose and camera gradients, then their steps, behind the optimizer: the steps see the guard's skip word, and both
+  // gradients the rotation and the rows the batch was drawn with ----
+  if (o.pose) {
+    rc = rtxn_pose_gradients(o.pose->drawn, a->trace.rays_d, o.rays->d_origin, o.rays->d_direction, b.n_rays, o.pose, stream);
+    if (rc != RTXN_OK) return rc;
+  }
+  if (o.cameras) {
+    rc = rtxn_camera_gradients(o.cameras->drawn, o.rays->d_direction, b.n_rays, o.cameras->poses, o.cameras, stream);
+    if (rc != RTXN_OK) return rc;
+  }
+  if (o.pose) {
+    rc = rtxn_pose_step(o.pose, stream);
+    if (rc != RTXN_OK) return rc;
+  }
+  return o.cameras ? rtxn_camera_step(o.cameras, stream) : RTXN_OK;
 }
 
 // ---- the step ladder (include/rtxn.h): every rung fills the option set its signature has and takes the one checked path; what
@@ -290,7 +310,7 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn::TrainOptio
 // _loss: the loss of rtxn_train_loss; _reg: the distortion regulariser; _opt: the optimizer options (optimizer.hip); _scaled: the
 // dynamic loss scale, which implies the non-finite guard; _ema: the weight EMA (the options may have nothing switched on: the
 // step goes through the rate kernel all the same, which advances the EMA's update count); _rays: the ray gradients and the pose
-// refinement (train.hip, pose.hip).
+// refinement (train.hip, pose.hip); _cameras: the intrinsics refinement (camera_refine.hip).
 static int step_entry(rtxn::TrainRung rung, const rtxn_train_step_args* a, rtxn::TrainOptions o, rtxn_stream_t stream) {
   const int rc = rtxn::check_train_options(rung, true, a, nullptr, &o);
   return rc != RTXN_OK ? rc : train_step_impl(a, o, stream);
@@ -340,4 +360,11 @@ extern "C" int rtxn_train_step_rays(const rtxn_train_step_args* a, const rtxn_tr
                                     const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
                                     const rtxn_pose_refinement* pose, rtxn_stream_t stream) {
   return step_entry(rtxn::RUNG_RAYS, a, {bg, jitter, loss, reg, opt, scaler, ema, rays, pose}, stream);
+}
+
+extern "C" int rtxn_train_step_cameras(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                       const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                                       const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
+                                       const rtxn_pose_refinement* pose, const rtxn_camera_refinement* cameras, rtxn_stream_t stream) {
+  return step_entry(rtxn::RUNG_CAMERAS, a, {bg, jitter, loss, reg, opt, scaler, ema, rays, pose, cameras}, stream);
 }

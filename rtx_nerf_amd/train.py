@@ -140,6 +140,7 @@ class Trainer:
                              "d(encoding) to differentiate through")
         self.ray_gradients = bool(ray_gradients)
         self._pose = None          # attach_images(refine_poses=...): the per-image pose correction
+        self._cams = None          # attach_images(refine_cameras=...): the intrinsics refinement
         self.image_set = None      # attach_images(): batches drawn on the device
         self.draw_count = 0        # batches drawn so far: host mirror of the device counter the draw is keyed on
         self._draw_step = None
@@ -536,7 +537,7 @@ class Trainer:
         return api.train_background(self.background, seed=seed, step=step, target_channels=n_channels)
 
     # ------------------------------------------------------------------------------------------ device batches
-    def attach_images(self, image_set, draw_seed=0, refine_poses=None):
+    def attach_images(self, image_set, draw_seed=0, refine_poses=None, refine_cameras=None):
         """Draw this trainer's batches on the device from the resident frames of an api.ImageSet (librtxn: rtxn_draw_batch,
         DESIGN 5.10): step_images(), capture_step(draw=True) and entry_args(draw=True) then need no rays or targets from the
         caller.  The set's channel count must be the trainer's target width (3, or 4 = straight RGBA over its background).
@@ -555,7 +556,18 @@ class Trainer:
         clone of the poses as attached, so the next draw generates its rays from the refined poses with nothing else to change.
         pose_delta [N, 6], pose_updates [N] and pose_skipped [1] are device tensors no stepping method reads; refined_poses()
         returns the poses, reset_poses() restores the attached ones; checkpoints hold delta, moments, counts and the skipped count.
-        An image without a ray in the batch keeps its moments and count; a step the non-finite guard skips moves nothing."""
+        An image without a ray in the batch keeps its moments and count; a step the non-finite guard skips moves nothing.
+        refine_cameras: None, True, or a dict of lr_focal, lr_center, lr_distortion, max_log_focal, max_center, max_distortion,
+        beta1, beta2, eps (defaults api.CAMERA_REFINE_DEFAULTS; librtxn: rtxn_camera_refinement): the rows of the
+        set's cameras (a set built with cameras=; a trainer built with ray_gradients=True; single GPU) optimised on the same three
+        paths, behind the optimizer and beside refine_poses -- pose gradient, camera gradient, pose step, camera step.  Three
+        groups with a rate each (0 freezes the group): fx, fy as fx0 exp(delta), cx, cy in pixels, the distortion coefficients
+        the model has; max_* clamp |delta|.  The CameraSet's tensor is rewritten IN PLACE against a clone of the rows as
+        attached, so the next draw reads the refined rows.  camera_delta [n_cameras, 10], camera_updates [n_cameras] and
+        camera_skipped [1] are device tensors no stepping method reads; refined_cameras() returns a copy of the rows,
+        reset_cameras() restores the attached ones, check_cameras() runs the host's float64 invertibility check on the live rows
+        (the clamps are safety rails, not that guarantee); checkpoints hold delta, moments, counts and the skipped count.
+        A CameraSet shared with a held-out ImageSet is scored by evaluate() with the refined rows: the tensor is the same."""
         if getattr(self, "_g_draw", False) or getattr(self, "_entry_draw", None) is not None:
             raise RuntimeError("Trainer.attach_images: a captured graph or an entry struct of this trainer already draws from the attached "
                                "set (capture_step(draw=True) / entry_args(draw=True) keep its addresses); build a new Trainer")
@@ -582,6 +594,28 @@ class Trainer:
                 api.pose_refinement(int(image_set.n_images), **{k: float(v) for k, v in cfg.items()})
             except (api._lib.RtxnError, TypeError, ValueError) as e:
                 raise ValueError(f"Trainer.attach_images: refine_poses = {refine_poses!r}: {e}") from None
+        ccfg = None
+        if refine_cameras is not None and refine_cameras is not False:  # refused before anything is allocated
+            if not self.ray_gradients:
+                raise ValueError("Trainer.attach_images: refine_cameras needs a trainer built with ray_gradients=True")
+            if getattr(image_set, "cameras", None) is None:
+                raise ValueError("Trainer.attach_images: refine_cameras needs an image set built with cameras= (api.camera_set): "
+                                 "the set's own pinhole has no rows to refine")
+            if _world() > 1:
+                raise ValueError("Trainer.attach_images: refine_cameras is single-GPU (every rank would move its own copy of the rows)")
+            if refine_cameras is not True and not isinstance(refine_cameras, dict):
+                raise ValueError(f"Trainer.attach_images: refine_cameras = {refine_cameras!r}: None, True or a dict of "
+                                 f"{', '.join(api.CAMERA_REFINE_DEFAULTS)}")
+            ccfg = dict(api.CAMERA_REFINE_DEFAULTS)
+            extra = set(refine_cameras) - set(ccfg) if isinstance(refine_cameras, dict) else set()
+            if extra:
+                raise ValueError(f"Trainer.attach_images: refine_cameras has no {sorted(extra)} ({', '.join(ccfg)})")
+            ccfg.update(refine_cameras if isinstance(refine_cameras, dict) else {})
+            try:
+                ccfg = {k: float(v) for k, v in ccfg.items()}
+                api.camera_refinement(image_set.cameras.model, image_set.cameras.n_cameras, int(image_set.width), **ccfg)
+            except (api._lib.RtxnError, TypeError, ValueError) as e:
+                raise ValueError(f"Trainer.attach_images: refine_cameras = {refine_cameras!r}: {e}") from None
         if not image_set.images.is_cuda:
             raise api._lib.RtxnError("Trainer.attach_images: the image set must live on the device (librtxn has no CPU path)")
         d = self.dev
@@ -603,7 +637,50 @@ class Trainer:
                                              delta=self.pose_delta, m=self._pose_m, v=self._pose_v, steps=self.pose_updates,
                                              grad=self._pose_grad, skip=None if self._opt_guard is None else self._opt_guard[2:3],
                                              skipped=self.pose_skipped, drawn=self.drawn)
+        self._cams = None
+        if ccfg is not None:
+            cams = image_set.cameras
+            K = int(cams.n_cameras)
+            self.cameras0 = cams.params.clone()
+            self.camera_delta, self._cam_m, self._cam_v = (torch.zeros((K, api.CAMERA_DELTA), device=d) for _ in range(3))
+            self.camera_updates = torch.zeros(K, dtype=torch.int32, device=d)
+            self.camera_skipped = torch.zeros(1, dtype=torch.int32, device=d)
+            self._cam_grad = torch.zeros((K, 12), device=d)
+            self._cam_terms = torch.zeros((self.B, 12), device=d)
+            self._cams = api.camera_refinement(cams.model, K, int(image_set.width), **ccfg, params0=self.cameras0, params=cams.params,
+                                               delta=self.camera_delta, m=self._cam_m, v=self._cam_v, steps=self.camera_updates,
+                                               grad=self._cam_grad, terms=self._cam_terms,
+                                               skip=None if self._opt_guard is None else self._opt_guard[2:3],
+                                               skipped=self.camera_skipped, drawn=self.drawn, poses=image_set.poses)
         return self
+
+    def refined_cameras(self):
+        """[n_cameras, 12]: the attached set's camera rows as the refinement has left them (a copy)"""
+        if self.image_set is None or getattr(self.image_set, "cameras", None) is None:
+            raise RuntimeError("refined_cameras: attach_images() with a set built with cameras= first")
+        return self.image_set.cameras.params.clone()
+
+    def reset_cameras(self):
+        """Zero the intrinsics correction, its moments and counts, and restore the rows as attached."""
+        if self._cams is None:
+            raise RuntimeError("reset_cameras: attach_images(refine_cameras=...) first")
+        for t in self._camera_arrays().values():
+            t.zero_()
+        self.image_set.cameras.params.copy_(self.cameras0)
+
+    def check_cameras(self):
+        """The host's float64 invertibility check (api.CameraSet.check_invertible) on the LIVE rows over the set's frame: reads
+        the rows back, and raises ValueError naming camera and pixel.  The refinement's clamps do not guarantee this."""
+        if self.image_set is None or getattr(self.image_set, "cameras", None) is None:
+            raise RuntimeError("check_cameras: attach_images() with a set built with cameras= first")
+        self.image_set.cameras.refresh_host().check_invertible(self.image_set.width, self.image_set.height)
+
+    def _camera_arrays(self):
+        """the intrinsics refinement's share of a checkpoint (nothing without refine_cameras): a missing key means zeros on loading"""
+        if self._cams is None:
+            return {}
+        return {"camera_delta": self.camera_delta, "camera_m": self._cam_m, "camera_v": self._cam_v, "camera_steps": self.camera_updates,
+                "camera_skipped": self.camera_skipped}
 
     def refined_poses(self):
         """[N, 4, 4]: the attached set's poses as the refinement has left them (a copy)"""
@@ -627,9 +704,16 @@ class Trainer:
                 "pose_skipped": self.pose_skipped}
 
     def _pose_update(self, n, rays_d):
-        """enqueue: the pose gradient of the batch just stepped (its rays drawn from the attached set) and the pose step"""
-        api.pose_gradients(self.drawn, rays_d, self.rays_o_grad, self.rays_d_grad, n, self._pose)
-        api.pose_step(self._pose)
+        """enqueue: the pose and camera gradients of the batch just stepped (its rays drawn from the attached set), then their
+        steps -- both gradients see the rotation and the rows the batch was drawn with"""
+        if self._pose is not None:
+            api.pose_gradients(self.drawn, rays_d, self.rays_o_grad, self.rays_d_grad, n, self._pose)
+        if self._cams is not None:
+            api.camera_gradients(self.drawn, self.rays_d_grad, n, self.image_set.poses, self._cams)
+        if self._pose is not None:
+            api.pose_step(self._pose)
+        if self._cams is not None:
+            api.camera_step(self._cams)
 
     def _ray_gradients(self, P, n, jit):
         """enqueue: dL/d(ray) of the batch whose backward just ran, from its dencT, live list and segments"""
@@ -660,7 +744,7 @@ class Trainer:
         self._draw(n, self.draw_rays_o, self.draw_rays_d, self.draw_targets)
         self.draw_count += 1
         loss = self.step(self.draw_rays_o[:n], self.draw_rays_d[:n], self.draw_targets[:n])
-        if self._pose is not None and self._stepped:       # behind the optimizer: the step sees the guard's skip word
+        if (self._pose is not None or self._cams is not None) and self._stepped:       # behind the optimizer: the step sees the guard's skip word
             with _Stage(self, "pose"):
                 self._pose_update(n, self.draw_rays_d)
         return loss
@@ -1239,7 +1323,8 @@ class Trainer:
         """The header's "draw_count" is the number of batches DRAWN (attach_images): the loaded trainer draws batch draw_count
         next.  With capture_step(prefetch=True, draw=True) one batch is drawn ahead of the step that trains on it, so a
         checkpoint saved between replays resumes one batch further on: the pending batch is skipped, none is repeated."""
-        arrs = {k: v.detach().cpu().numpy() for k, v in {**self.state_arrays(), **self._ema_arrays(), **self._pose_arrays()}.items()}
+        arrs = {k: v.detach().cpu().numpy() for k, v in {**self.state_arrays(), **self._ema_arrays(), **self._pose_arrays(),
+                                                           **self._camera_arrays()}.items()}
         cfg = self.net.cfg
         header = {"step": self.step_count, "draw_count": self.draw_count,
                   "skipped_steps": 0 if self._opt_guard is None else int(self._opt_guard[1].item()),
@@ -1290,7 +1375,7 @@ class Trainer:
                 for t in ema.values():
                     t.zero_()
                 ema = {}
-            pose = self._pose_arrays()          # optional both ways, as "draw_count" is: a missing array means zeros
+            pose = {**self._pose_arrays(), **self._camera_arrays()}     # optional both ways, as "draw_count" is: a missing array means zeros
             for nm, t in pose.items():
                 if nm not in in_file:
                     t.zero_()
@@ -1320,6 +1405,8 @@ class Trainer:
         self._scaler_restore(header.get("loss_scaler"))
         if self._pose is not None:
             api.pose_compose(self._pose)                         # the poses are not in the file: delta against poses0 is
+        if self._cams is not None:
+            api.camera_compose(self._cams)                       # ... nor are the camera rows
         self.net.set_params(self.params)
         return header
 
@@ -1428,6 +1515,7 @@ class Trainer:
         scaler_state = None if self._scaler_state is None else self._scaler_state.clone()
         ema_state = {k: v.clone() for k, v in self._ema_arrays().items()}
         pose_state = {k: v.clone() for k, v in self._pose_arrays().items()} if draw else {}
+        cam_state = {k: v.clone() for k, v in self._camera_arrays().items()} if draw else {}
         clear_grads = self._clear_grads
         with torch.cuda.stream(side):
             clear_grads()
@@ -1456,6 +1544,10 @@ class Trainer:
             for k, v in self._pose_arrays().items():
                 v.copy_(pose_state[k])              # ... nor of the poses
             api.pose_compose(self._pose)
+        if cam_state:
+            for k, v in self._camera_arrays().items():
+                v.copy_(cam_state[k])               # ... nor of the camera rows
+            api.camera_compose(self._cams)
         self.net.set_params_training(self.params)
         self._g_step.fill_(self.step_count)
         self._g_step_host = self.step_count     # host mirror of the device counter (see _sync_device_step)
@@ -1586,7 +1678,8 @@ class Trainer:
             self._draw_step.add_(1)
             self.draw_count += 1
         api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt, self._scaler, self._ema,
-                       rays=self._rays, pose=self._pose if self._entry_draw is not None else None)
+                       rays=self._rays, pose=self._pose if self._entry_draw is not None else None,
+                       cameras=self._cams if self._entry_draw is not None else None)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -1647,7 +1740,7 @@ class Trainer:
 
     def _captured_pose(self):
         """behind the captured optimizer: the pose gradient and step of a batch the graph drew itself"""
-        if self._pose is not None and self._g_draw:
+        if (self._pose is not None or self._cams is not None) and self._g_draw:
             self._pose_update(self._g_n, self._g_sets[0]["rays_d"])
 
     def _captured_apply(self, grad_divisor):
