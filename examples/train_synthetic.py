@@ -55,10 +55,39 @@ def lens_rays(model, row, pose, res):
     return torch.from_numpy(o.astype(np.float32)).cuda(), torch.from_numpy(d.astype(np.float32)).cuda()
 
 
-def make_demo(path, n_frames=16, res=64, grid=32, lens=None):
+def write_png_gray16(path, values):
+    """uint16 [H, W] -> a 16-bit gray PNG (filter 0 on every row): what a depth sensor's export looks like"""
+    import struct
+    import zlib
+    v = np.ascontiguousarray(values, dtype=np.uint16)
+    h, w = v.shape
+    raw = b"".join(b"\0" + v[y].astype(">u2").tobytes() for y in range(h))
+    chunk = lambda kind, body: struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 0, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw))
+                + chunk(b"IEND", b""))
+
+
+DEMO_DEPTH_UNIT = 1e-3          # the demo's depth maps count thousandths of the poses' unit
+
+
+def teacher_depth(o, d, pose, res):
+    """uint16 [res, res]: the analytic z-depth of the teacher's surface (the sphere of radius 0.5 its density falls off at) along
+    every ray, in DEMO_DEPTH_UNIT of the poses' unit (10 per world unit); 0 where the ray misses it"""
+    o64, d64 = o.double().cpu().numpy(), d.double().cpu().numpy()
+    b = (o64 * d64).sum(1)
+    disc = b * b - (o64 * o64).sum(1) + 0.25
+    t = np.where(disc > 0, -b - np.sqrt(np.maximum(disc, 0.0)), 0.0)
+    axis = -np.asarray(pose, np.float64).reshape(4, 4)[:3, 2]
+    z = t * (d64 @ (axis / np.linalg.norm(axis))) * 10.0 / DEMO_DEPTH_UNIT
+    return np.clip(np.rint(np.where(t > 0, z, 0.0)), 0, 65535).astype(np.uint16).reshape(res, res)
+
+
+def make_demo(path, n_frames=16, res=64, grid=32, lens=None, depth=False):
     """Writes transforms_train.json + PNGs rendered from the analytic teacher field of tools/train_demo.py.  lens: (model,
     coefficients) of parse_lens -- the frames are then rendered through that lens (a centred camera of the same focal length)
-    and the JSON carries its intrinsics in the instant-ngp / nerfstudio keys."""
+    and the JSON carries its intrinsics in the instant-ngp / nerfstudio keys.  depth: also one 16-bit depth PNG per frame
+    (teacher_depth) under depth/, named by the frame's depth_file_path, with depth_unit_scale_factor beside the frames."""
     from train_demo import teacher_field
     os.makedirs(os.path.join(path, "train"), exist_ok=True)
     occ = torch.from_numpy(scenes.pack_occupancy(scenes.sphere_density(grid, 0.72)).view(np.int32).copy()).cuda()
@@ -78,6 +107,12 @@ def make_demo(path, n_frames=16, res=64, grid=32, lens=None):
         img = tr.render_rays(o, d, radiance_fn=teacher_field).reshape(res, res, 3).cpu().numpy()
         loader.write_png(os.path.join(path, "train", f"r_{i}.png"), img)
         frames.append({"file_path": f"./train/r_{i}", "rotation": 0.0, "transform_matrix": pose.tolist()})
+        if depth:
+            os.makedirs(os.path.join(path, "depth"), exist_ok=True)
+            write_png_gray16(os.path.join(path, "depth", f"d_{i}.png"), teacher_depth(o, d, pose, res))
+            frames[-1]["depth_file_path"] = f"./depth/d_{i}.png"
+    if depth:
+        intrinsics["depth_unit_scale_factor"] = DEMO_DEPTH_UNIT
     with open(os.path.join(path, "transforms_train.json"), "w") as f:
         json.dump({"camera_angle_x": scenes.LEGO_CAMERA_ANGLE_X, **intrinsics, "frames": frames}, f)
     return path
@@ -157,6 +192,11 @@ def main():
     ap.add_argument("--distortion-weight", type=float, default=0.0,
                     help="> 0: mip-NeRF 360's distortion regulariser with this weight, for world distances along the ray (a weight quoted "
                          "for distances normalised to [0, 1] is divided by 2 sqrt(3)); raise --loss-scale with it")
+    ap.add_argument("--depth", action="store_true", help="--make-demo also writes analytic 16-bit depth PNGs of the teacher and their JSON keys")
+    ap.add_argument("--depth-weight", type=float, default=0.0,
+                    help="lambda_z of the depth term (Trainer(depth_weight=...), DESIGN 5.22): train with the scene's depth maps "
+                         "(depth_file_path / depth_path in its transforms_train.json); batches are drawn on the device")
+    ap.add_argument("--depth-loss", default="l2", choices=sorted(api.DEPTH_LOSS_KINDS), help="the depth term's loss")
     ap.add_argument("--loss-scale", default="128", metavar="S|dynamic",
                     help="the fp16 gradients' loss scale: the regulariser's gradient is largely rounded away at the default (DESIGN 5.12); "
                          "'dynamic': kept on the device, halved when a step's gradients are not finite and doubled after "
@@ -201,15 +241,18 @@ def main():
     json_path = os.path.join(a.data, "transforms_train.json")
     if a.make_demo:
         torch.cuda.set_device(0)
-        make_demo(a.make_demo, lens=parse_lens(a.lens) if a.lens else None)
-    elif a.lens:
-        sys.exit("--lens describes the scene --make-demo writes; a loaded scene's cameras come from its transforms_train.json")
+        make_demo(a.make_demo, lens=parse_lens(a.lens) if a.lens else None, depth=a.depth)
+    elif a.lens or a.depth:
+        sys.exit("--lens / --depth describe the scene --make-demo writes; a loaded scene's cameras and depth maps come from its "
+                 "transforms_train.json")
     # a scene whose JSON carries intrinsics (fl_x ...) is trained and scored with them: batches drawn on the device through the cameras
     with open(json_path) as f:
         top = json.load(f)
     use_cameras = not a.assume_pinhole and ("fl_x" in top or any("fl_x" in fr for fr in top.get("frames", [])))
     if use_cameras:
         a.device_batches = True
+    if a.depth_weight > 0.0:
+        a.device_batches = True            # the depth targets are formed on the device from the drawn pixels
     if a.refine_poses is not None:
         a.device_batches = True
         if a.encoding != "hash":
@@ -260,7 +303,13 @@ def main():
     train_ds = loader.ImageDataset(ds.images[:-n_hold], train_poses.reshape(ds.poses[:-n_hold].shape), ds.focal, ds.image_width, ds.image_height, C, ds.camera_angle_x)
     if a.device_batches:
         # flags=2 frames are k/255: one byte per channel holds them exactly
-        images, focal = api.ImageSet.from_dataset(train_ds, storage="u8", cameras=cams_train)
+        depth_kw = {}
+        if a.depth_weight > 0.0:
+            maps, unit = loader.read_depth_maps(json_path, ds.image_width, ds.image_height)
+            depth_kw = dict(depth=maps[:-n_hold], depth_unit=unit, depth_kind="z")
+            print(f"depth maps: {maps.dtype} in units of {unit:g}, {100.0 * float((maps[:-n_hold] > 0).mean()):.1f}% of the training pixels "
+                  f"carry a value")
+        images, focal = api.ImageSet.from_dataset(train_ds, storage="u8", cameras=cams_train, **depth_kw)
         n_rays, held = images.n_images * images.width * images.height, images.nbytes()
     else:
         rays, focal = RayDataset.from_images(train_ds, origin_scale=0.1)
@@ -273,7 +322,7 @@ def main():
     tr = Trainer(R, None, lr=1e-2 if a.encoding == "hash" else 2e-3, loss=a.loss, opacity_weight=a.opacity_weight,
                  background=(1.0, 1.0, 1.0) if rgba else None, target_channels=C, distortion_weight=a.distortion_weight,
                  loss_scale=loss_scale, lr_schedule=schedule, weight_decay=a.weight_decay, skip_nonfinite=a.skip_nonfinite,
-                 max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay,
+                 max_grad_norm=a.max_grad_norm, ema_decay=a.ema_decay, depth_weight=a.depth_weight, depth_loss=a.depth_loss,
                  ray_gradients=a.refine_poses is not None or refine_cameras is not None, **model)
     white = (1.0, 1.0, 1.0) if rgba else None
     # the held-out frames stay on the device as they were loaded (flags=2 frames are k/255: one byte per channel holds them exactly)

@@ -1497,6 +1497,11 @@ int rtxn_load_llff(const char* basedir, int factor, int flags, rtxn_image_datase
 void rtxn_free_llff_bounds(float* bounds);
 /* stb_image_write's role (included, never called, main.cu:19-21): 8-bit RGB PNG of a rendered frame. */
 int rtxn_write_png_rgb8(const char* path, const unsigned char* rgb, int width, int height);
+/* A depth map: a gray PNG as uint16 [height][width] (malloc'd; rtxn_free_png_gray16), in the file's own unit.  16-bit samples
+ * keep both bytes, 8-bit samples are widened as v (not v * 257); interlaced or not; a tRNS colour key is ignored.  Any other
+ * colour type, and gray below 8 bits, is refused with a message (RTXN_ERR_IO, as every unreadable file). */
+int rtxn_load_png_gray16(const char* path, int* width, int* height, uint16_t** values);
+void rtxn_free_png_gray16(uint16_t* values);
 
 /* ---- training batches drawn on the device --------------------------------------------------------------------------
  * Replaces the reference's host batch build (a random shuffle + gather, main.cu:612-629) and the per-ray dataset it
@@ -1802,6 +1807,84 @@ int rtxn_train_step_cameras(const rtxn_train_step_args* args, const rtxn_train_b
                             const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
                             const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
                             const rtxn_pose_refinement* pose, const rtxn_camera_refinement* cameras, rtxn_stream_t stream);
+
+/* ---- depth supervision from per-pixel depth maps (instant-ngp's depth loss, depth-nerfacto) ------------------
+ * Per ray r, with w_i, m_i exactly as rtxn_train_regularizer defines them:
+ *   D_r = sum_i w_i m_i     the B the regularised compositor carries; NOT divided by A (as in instant-ngp);
+ *   z_r                     the ray's depth target, a distance along the normalised ray in world units.
+ *   v_r   = z_r > 0 (a finite value; 0, negative, NaN: the ray has no target and the term is 0 for it)
+ *   e_r   = D_r - z_r
+ *   L_z   = (lambda_z / n_rays) sum_r v_r l(e_r)      l: L2, L1 or Huber of rtxn_train_loss (kind, param), not relative L2
+ *   g_D   = loss_scale lambda_z v_r l'(e_r) / n_rays        in fp32, no fp16 hand-off (the rule of k above)
+ *   dL/dw_i gains g_D m_i;      S gains g_D D_r             (D_r is homogeneous of degree 1 in w)
+ * g_D is formed as k_z l'(e_r) with k_z = loss_scale lambda_z / n_rays, the expression and order of the regulariser's k.
+ * m_i stays the stratum midpoint under RTXN_SAMPLING_JITTER_WORLD.  m_i is a constant to the ray gradients, as it is for the
+ * distortion term: rtxn_ray_gradients differentiates the samples' positions with the segment distances held fixed, and the
+ * dependence of D_r on t_start / t_end through m_i is not differentiated.  The normaliser is n_rays, not the number of rays
+ * with a target (the alpha term's rule), so shares of a data-parallel batch add up as the colour loss does.
+ * Outputs (each optional): depth[r] = D_r, depth_loss[r] = v_r l(e_r).  The term has no state.
+ * Rules (RTXN_ERR_INVALID with a message naming the field, before any device is touched): weight finite and >= 0; kind
+ * RTXN_LOSS_L2 | _L1 | _HUBER; HUBER needs a finite param > 0; a weight > 0, or either output, needs target, t_start and t_end,
+ * the RTXN_VR_NERF compositor and sample_type RTXN_SAMPLING_MIDPOINT_WORLD or _JITTER_WORLD; a step needs RTXN_TRACE_DDA;
+ * t_start / t_end must be the buffers of an active regulariser and of the ray gradients when those are given.  In
+ * deterministic mode the scalar is summed in a fixed order behind the compositor; with weight > 0 that sum reads `depth` and
+ * `target`, so `depth` must then be given (the rule `distortion` follows).  depth == NULL, or weight 0 with both outputs
+ * NULL: exactly the call of the rung below -- the same kernels, the same bits. */
+typedef struct rtxn_train_depth {
+  float weight;          /* lambda_z >= 0, finite */
+  int kind;              /* RTXN_LOSS_L2 | RTXN_LOSS_L1 | RTXN_LOSS_HUBER */
+  float param;           /* HUBER: delta */
+  const float* target;   /* DEVICE float[n_rays]: z_r (rtxn_depth_targets writes them) */
+  const float* t_start;  /* DEVICE float per packed segment slot, as rtxn_train_regularizer's */
+  const float* t_end;
+  float* depth;          /* optional DEVICE float[n_rays]: D_r */
+  float* depth_loss;     /* optional DEVICE float[n_rays]: v_r l(e_r) */
+} rtxn_train_depth;
+/* rtxn_volrender_scaled_train with the depth term (bg, loss, reg and scaler may be NULL; scaler == NULL: loss_scale by value) */
+int rtxn_volrender_depth_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                               int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
+                               void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                               const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
+                               const rtxn_loss_scaler* scaler, const rtxn_train_depth* depth, rtxn_stream_t stream);
+/* rtxn_train_gradients_rays / rtxn_train_step_cameras with the depth term; depth == NULL: exactly those calls.  The step's
+ * write pass stores t_start / t_end into the struct's buffers (batch.segment_capacity floats each). */
+int rtxn_train_gradients_depth(const rtxn_train_batch* batch, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                               const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                               const rtxn_ray_gradients* rays, const rtxn_train_depth* depth, rtxn_stream_t stream);
+int rtxn_train_step_depth(const rtxn_train_step_args* args, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                          const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                          const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
+                          const rtxn_pose_refinement* pose, const rtxn_camera_refinement* cameras, const rtxn_train_depth* depth,
+                          rtxn_stream_t stream);
+/* Depth targets of a drawn batch, ONE kernel on `stream`, no allocation, no synchronisation: hipGraph-capturable behind
+ * rtxn_draw_batch[_cameras].  For ray r: (image, pixel) = drawn[r], v = depth[image][pixel], la = poses[image] (the LIVE poses,
+ * so a pose refinement is honoured), d = rays_d[r]:
+ *   t = (float)v * scale             scale: the maps' unit times the world's 0.1 origin scale, formed once on the host
+ *   RTXN_DEPTH_RAY: target[r] = t    (the map holds distances along the ray)
+ *   RTXN_DEPTH_Z:   target[r] = t / c,   c = -(d0 la[2] + d1 la[6] + d2 la[10]) / sqrtf(la[2]^2 + la[6]^2 + la[10]^2)
+ *                   = d . f with f = -normalise(pose column 2), the axis the pinhole ray's -la[2+4k] * focal term points along
+ *                   (sums left to right, no contraction, IEEE division and square root)
+ *   v <= 0, a non-finite v, c <= 2^-6 (or NaN), and an (image, pixel) outside the set write 0: no target.
+ * It takes rays_d, so it is right for every camera model without knowing them.
+ * Rules (RTXN_ERR_INVALID with a message, before any device is touched): no NULL among depth, poses, drawn, rays_d, target;
+ * format U16 | F32; kind Z | RAY; scale finite and > 0; n_images >= 1; n_rays >= 1; width, height >= 1 and
+ * width*height <= 1 << 24 (rtxn_draw_batch's rules). */
+enum rtxn_depth_format { RTXN_DEPTH_U16 = 0, RTXN_DEPTH_F32 = 1 };
+enum rtxn_depth_kind { RTXN_DEPTH_Z = 0, RTXN_DEPTH_RAY = 1 };
+typedef struct rtxn_depth_targets_args {
+  const void* depth;     /* DEVICE: [n_images][height][width], uint16_t or float */
+  const float* poses;    /* DEVICE: float[n_images][16], as rtxn_image_set.poses */
+  int n_images;
+  uint32_t width, height;
+  int format;            /* enum rtxn_depth_format */
+  int kind;              /* enum rtxn_depth_kind */
+  float scale;
+  int n_rays;
+  const uint32_t* drawn; /* DEVICE uint32[n_rays][2] as rtxn_draw_batch records it */
+  const float* rays_d;   /* DEVICE float[n_rays][3], normalised */
+  float* target;         /* DEVICE float[n_rays] */
+} rtxn_depth_targets_args;
+int rtxn_depth_targets(const rtxn_depth_targets_args* a, rtxn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -217,6 +217,19 @@ class CameraRefinement(C.Structure):
                 ("terms", C.c_void_p), ("skip", C.c_void_p), ("skipped", C.c_void_p), ("drawn", C.c_void_p), ("poses", C.c_void_p)]
 
 
+class TrainDepth(C.Structure):
+    """struct rtxn_train_depth (include/rtxn.h)."""
+    _fields_ = [("weight", C.c_float), ("kind", C.c_int), ("param", C.c_float), ("target", C.c_void_p), ("t_start", C.c_void_p),
+                ("t_end", C.c_void_p), ("depth", C.c_void_p), ("depth_loss", C.c_void_p)]
+
+
+class DepthTargetsArgs(C.Structure):
+    """struct rtxn_depth_targets_args (include/rtxn.h)."""
+    _fields_ = [("depth", C.c_void_p), ("poses", C.c_void_p), ("n_images", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("format", C.c_int), ("kind", C.c_int), ("scale", C.c_float), ("n_rays", C.c_int), ("drawn", C.c_void_p),
+                ("rays_d", C.c_void_p), ("target", C.c_void_p)]
+
+
 class RenderConfig(C.Structure):
     """struct rtxn_render_config (include/rtxn.h)."""
     _fields_ = [("mlp", C.c_void_p), ("grid", C.c_void_p), ("table_fp16", C.c_void_p), ("n_dir_freqs", C.c_int),
@@ -468,6 +481,14 @@ SYMBOLS = {
     "rtxn_train_step_cameras": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
                                      C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma),
                                      C.POINTER(RayGradients), C.POINTER(PoseRefinement), C.POINTER(CameraRefinement), _P]),
+    "rtxn_volrender_depth_train": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(TrainBackground), C.POINTER(TrainLoss),
+                                        C.POINTER(TrainRegularizer), C.POINTER(LossScaler), C.POINTER(TrainDepth), _P]),
+    "rtxn_train_gradients_depth": (_I, [C.POINTER(TrainBatch), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                        C.POINTER(TrainRegularizer), C.POINTER(LossScaler), C.POINTER(RayGradients), C.POINTER(TrainDepth), _P]),
+    "rtxn_train_step_depth": (_I, [C.POINTER(TrainStepArgs), C.POINTER(TrainBackground), C.POINTER(SampleJitter), C.POINTER(TrainLoss),
+                                   C.POINTER(TrainRegularizer), C.POINTER(OptimizerOptions), C.POINTER(LossScaler), C.POINTER(WeightEma),
+                                   C.POINTER(RayGradients), C.POINTER(PoseRefinement), C.POINTER(CameraRefinement), C.POINTER(TrainDepth), _P]),
+    "rtxn_depth_targets": (_I, [C.POINTER(DepthTargetsArgs), _P]),
     "rtxn_camera_set_check": (_I, [C.POINTER(CameraSet), _I]),
     "rtxn_camera_rays": (_I, [C.POINTER(CameraSet), _I, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "rtxn_draw_batch_cameras": (_I, [C.POINTER(DrawBatchArgs), C.POINTER(CameraSet), _P]),
@@ -478,6 +499,8 @@ SYMBOLS = {
     "rtxn_load_llff": (_I, [C.c_char_p, _I, _I, C.POINTER(ImageDataset), C.POINTER(C.POINTER(C.c_float))]),
     "rtxn_free_llff_bounds": (None, [C.POINTER(C.c_float)]),
     "rtxn_write_png_rgb8": (_I, [C.c_char_p, _P, _I, _I]),
+    "rtxn_load_png_gray16": (_I, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_uint16))]),
+    "rtxn_free_png_gray16": (None, [C.POINTER(C.c_uint16)]),
 }
 
 _lib = None

@@ -427,6 +427,7 @@ def _composite_train(who, args, structs):
     (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels, loss_gradients, loss_sum,
      radiance_gradients) = args
     loss, regularizer = (tuple(structs) + (None, None, None))[1:3]
+    _check_depth(who, structs[4] if len(structs) > 4 else None, batch_size, ray_hit.numel() // int(num_samples_per_hit))
     if loss is not None and loss.opacity and loss._opacity_tensor.numel() < batch_size:
         raise _lib.RtxnError(f"{who}: opacity holds {loss._opacity_tensor.numel()} elements, {batch_size} rays")
     _check_regularizer(who, regularizer, batch_size, ray_hit.numel() // int(num_samples_per_hit))
@@ -539,6 +540,51 @@ def volrender_reg_train(network_outputs, ray_hit, num_hits, indices, batch_size,
     """volrender_loss_train with the regulariser of train_regularizer(...) (None, or weight 0 without outputs: that very call)."""
     _composite_train("volrender_reg_train", (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale,
                                              pixels, loss_gradients, loss_sum, radiance_gradients), (background, loss, regularizer))
+
+
+DEPTH_LOSS_KINDS = {"l2": LOSS_L2, "l1": LOSS_L1, "huber": LOSS_HUBER}
+
+
+def train_depth(weight=0.0, kind="l2", param=None, target=None, t_start=None, t_end=None, depth=None, depth_loss=None):
+    """struct rtxn_train_depth (include/rtxn.h): depth supervision in the training compositor, (lambda_z / n_rays) sum_r l(D_r - z_r)
+    over the rays with a target z_r > 0, D_r = sum w m.  weight: lambda_z >= 0; kind "l2" | "l1" | "huber", param: Huber's delta
+    (default 0.1); target: device float32[n_rays], distances along the ray in world units (depth_targets() writes them; 0: no
+    target); t_start, t_end: as train_regularizer's (the same tensors when both are given); depth, depth_loss: optional device
+    float32[n_rays] outputs, D_r and l(e_r) of every ray.  The tensors stay referenced by the struct."""
+    if kind not in DEPTH_LOSS_KINDS:
+        raise ValueError(f"depth loss {kind!r}: one of {sorted(DEPTH_LOSS_KINDS)}")
+    s = _lib.TrainDepth()
+    s.weight, s.kind = float(weight), DEPTH_LOSS_KINDS[kind]
+    s.param = float(param) if param is not None else LOSS_DEFAULT_PARAM.get(s.kind, 0.0)
+    s.target = _ptr(target, torch.float32, "target")
+    s.t_start, s.t_end = _ptr(t_start, torch.float32, "t_start"), _ptr(t_end, torch.float32, "t_end")
+    s.depth, s.depth_loss = _ptr(depth, torch.float32, "depth"), _ptr(depth_loss, torch.float32, "depth_loss")
+    s._tensors = {"target": target, "t_start": t_start, "t_end": t_end, "depth": depth, "depth_loss": depth_loss}
+    return s
+
+
+def _check_depth(who, depth, n_rays, n_segments=None):
+    tensors = getattr(depth, "_tensors", None)     # a _lib.TrainDepth filled by hand: nothing to size, the library checks the rest
+    if depth is None or tensors is None:
+        return
+    for nm in ("target", "depth", "depth_loss"):
+        t = tensors[nm]
+        if t is not None and t.numel() < int(n_rays):
+            raise _lib.RtxnError(f"{who}: depth.{nm} holds {t.numel()} elements, {n_rays} rays")
+    if n_segments is not None:
+        for nm in ("t_start", "t_end"):
+            t = tensors[nm]
+            if t is not None and t.numel() < int(n_segments):
+                raise _lib.RtxnError(f"{who}: depth.{nm} holds {t.numel()} elements, {n_segments} segment slots")
+
+
+def volrender_depth_train(network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target, loss_scale, pixels,
+                          loss_gradients, loss_sum, radiance_gradients, background=None, loss=None, regularizer=None, scaler=None, depth=None):
+    """volrender_reg_train / volrender_scaled_train (scaler given: loss_scale is not read) with the depth term of train_depth(...)
+    (None, or weight 0 without outputs: that very call)."""
+    _composite_train("volrender_depth_train", (network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
+                                               0.0 if scaler is not None else loss_scale, pixels, loss_gradients, loss_sum, radiance_gradients),
+                     (background, loss, regularizer, scaler, depth))
 
 
 # --------------------------------------------------------------------------- MLP
@@ -1443,7 +1489,7 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
                     total_segments, segment_capacity, n_rays, sample_type, t_scale=1.0, vr_mode, targets, loss_scale,
                     encT, dencT=None, workspace=None, output_half, radiance, t_vals, radiance_gradients, pixels, loss_gradients,
                     loss_sum=None, dparams, dtable=None, dtable_hashed_half=None, live_ws=None, skip_table_backward=False,
-                    workspace_lean=False, background=None, jitter=None, loss=None, regularizer=None, scaler=None, rays=None):
+                    workspace_lean=False, background=None, jitter=None, loss=None, regularizer=None, scaler=None, rays=None, depth=None):
     """rtxn_train_gradients: sampler ... backward of one batch with the segment count taken on the device (main.cu:703-781).
     rays: ray_gradients(...) -> rtxn_train_gradients_rays (with or without any of the five below): dL/d(rays_o), dL/d(rays_d)
     behind the table scatter; its t_start / t_end must already hold the batch's distances (trace_grid, TRACE_DDA).
@@ -1451,12 +1497,14 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
     jitter: sample_jitter(...) with SAMPLING_JITTER_WORLD -> rtxn_train_gradients_jitter (with or without a background);
     loss: train_loss(...) -> rtxn_train_gradients_loss (with or without either);
     regularizer: train_regularizer(...) -> rtxn_train_gradients_reg (with or without any of the three);
-    scaler: loss_scaler(...) -> rtxn_train_gradients_scaled (with or without any of the four; loss_scale is then not read)."""
-    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer", "scaler", "rays")}
+    scaler: loss_scaler(...) -> rtxn_train_gradients_scaled (with or without any of the four; loss_scale is then not read);
+    depth: train_depth(...) -> rtxn_train_gradients_depth (with or without any of the six)."""
+    kw = {k: v for k, v in locals().items() if k not in ("background", "jitter", "regularizer", "scaler", "rays", "depth")}
     _check_regularizer("train_gradients", regularizer, n_rays, segment_capacity)
+    _check_depth("train_gradients", depth, n_rays, segment_capacity)
     _check_ray_gradients("train_gradients", rays, n_rays, segment_capacity)
     b = train_batch(**kw, target_channels=background.target_channels if background is not None else 3)
-    options = (background, jitter, loss, regularizer, scaler, rays)
+    options = (background, jitter, loss, regularizer, scaler, rays, depth)
     name, n_options = _ladder_entry("rtxn_train_gradients", _GRADIENTS_LADDER, options)
     check(getattr(_lib.lib(), name)(C.byref(b), *map(_byref, options[:n_options]), _stream()), name)
 
@@ -1464,15 +1512,15 @@ def train_gradients(net, *, grid=None, n_dir_freqs=0, table=None, start_points, 
 # The rungs of the step and gradients ladders (include/rtxn.h), topmost first: (suffix, how many of the options
 # (background, jitter, loss, regularizer, ...) the rung takes, which of them select it).  The call goes to the topmost rung one of
 # whose own options is given: the lowest entry point that takes everything that is.
-_STEP_LADDER = (("_cameras", 10, (9,)), ("_rays", 9, (7, 8)), ("_ema", 7, (6,)), ("_scaled", 6, (5,)), ("_opt", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)),
+_STEP_LADDER = (("_depth", 11, (10,)), ("_cameras", 10, (9,)), ("_rays", 9, (7, 8)), ("_ema", 7, (6,)), ("_scaled", 6, (5,)), ("_opt", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)),
                 ("_jitter", 2, (1,)), ("_ex", 1, (0,)), ("", 0, ()))
-_GRADIENTS_LADDER = (("_rays", 6, (5,)), ("_scaled", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)), ("_jitter", 2, (1,)), ("_ex", 1, (0,)),
+_GRADIENTS_LADDER = (("_depth", 7, (6,)), ("_rays", 6, (5,)), ("_scaled", 5, (4,)), ("_reg", 4, (3,)), ("_loss", 3, (2,)), ("_jitter", 2, (1,)), ("_ex", 1, (0,)),
                      ("", 0, ()))
 
 
 def _ladder_entry(prefix, ladder, options):
     for suffix, n_options, own in ladder:
-        if not own or any(options[i] is not None for i in own):
+        if not own or any(i < len(options) and options[i] is not None for i in own):      # a shorter tuple: the rungs it reaches
             return prefix + suffix, n_options
 
 
@@ -1521,7 +1569,7 @@ def train_batch(net, *, grid=None, n_dir_freqs=0, table=None, start_points, end_
 
 
 def train_step(args, background=None, jitter=None, loss=None, regularizer=None, optimizer=None, scaler=None, ema=None, rays=None, pose=None,
-               cameras=None):
+               cameras=None, depth=None):
     """rtxn_train_step(args: _lib.TrainStepArgs): traversal -> gradients -> optimizer of one batch, one call, current stream.
     background: train_background(...) -> rtxn_train_step_ex (RANDOM with step None hashes args.opt.step before the increment);
     jitter: sample_jitter(...) -> rtxn_train_step_jitter (step None: args.opt.step, by the same rule);
@@ -1535,13 +1583,16 @@ def train_step(args, background=None, jitter=None, loss=None, regularizer=None, 
     the write pass stores t_start / t_end into rays' buffers, the ray gradients are formed behind the table scatter and the pose
     gradient and step run behind the optimizer;
     cameras: camera_refinement(...) with drawn and poses -> rtxn_train_step_cameras (needs rays): behind the optimizer the pose
-    gradient, the camera gradient, the pose step, the camera step."""
+    gradient, the camera gradient, the pose step, the camera step;
+    depth: train_depth(...) -> rtxn_train_step_depth (with or without any of the ten): the write pass stores t_start / t_end into
+    its buffers, the compositor adds the depth term."""
     _check_regularizer("train_step", regularizer, args.batch.n_rays, args.batch.segment_capacity)
+    _check_depth("train_step", depth, args.batch.n_rays, args.batch.segment_capacity)
     _check_ray_gradients("train_step", rays, args.batch.n_rays, args.batch.segment_capacity)
     terms = getattr(cameras, "_tensors", {}).get("terms")
     if terms is not None and terms.numel() < 12 * int(args.batch.n_rays):
         raise _lib.RtxnError(f"train_step: cameras.terms holds {terms.numel()} elements, {12 * int(args.batch.n_rays)} needed")
-    options = (background, jitter, loss, regularizer, optimizer, scaler, ema, rays, pose, cameras)
+    options = (background, jitter, loss, regularizer, optimizer, scaler, ema, rays, pose, cameras, depth)
     name, n_options = _ladder_entry("rtxn_train_step", _STEP_LADDER, options)
     check(getattr(_lib.lib(), name)(C.byref(args), *map(_byref, options[:n_options]), _stream()), name)
 
@@ -1611,6 +1662,10 @@ def convert_f16_to_f32(src, dst):
 
 # --------------------------------------------------------------------------- device batches
 IMAGE_F32, IMAGE_U8 = 0, 1                 # enum rtxn_image_format
+DEPTH_U16, DEPTH_F32 = 0, 1                # enum rtxn_depth_format
+DEPTH_Z, DEPTH_RAY = 0, 1                  # enum rtxn_depth_kind
+DEPTH_KINDS = {"z": DEPTH_Z, "ray": DEPTH_RAY}
+WORLD_ORIGIN_SCALE = 0.1                   # o_k = la[4k+3] / 10 (rtxn_draw_batch): a pose-unit length in world units
 
 
 class ImageSet:
@@ -1619,9 +1674,11 @@ class ImageSet:
     (focal_length and aspect_ratio as rtxn_trace_params; aspect_ratio defaults to W / H) for all of them.  A thin holder: it keeps the two tensors
     alive and hands draw_batch() their pointers.  cameras: a CameraSet (camera_set()) of 1 or N cameras on the images' device,
     kept alive here; batches drawn from the set and frames evaluated against it then take their rays from it, and focal_length
-    may be omitted (it is not read)."""
+    may be omitted (it is not read).  depth: per-pixel depth maps, a device tensor [N, H, W], uint16 or float32, on the images'
+    device, in units of depth_unit world-before-origin-scale lengths (the poses' unit); 0 = no measurement.  depth_kind "z": the
+    distance along the optical axis (the usual depth map), "ray": along the pixel's ray.  Kept alive here for depth_targets()."""
 
-    def __init__(self, images, poses, focal_length=None, aspect_ratio=None, cameras=None):
+    def __init__(self, images, poses, focal_length=None, aspect_ratio=None, cameras=None, depth=None, depth_unit=1.0, depth_kind="z"):
         if images.dim() != 4 or images.shape[-1] not in (3, 4) or images.dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"ImageSet: images of shape {tuple(images.shape)} / {images.dtype}: [N, H, W, 3 | 4], float32 or uint8")
         n, h, w, c = (int(v) for v in images.shape)
@@ -1643,16 +1700,29 @@ class ImageSet:
         self.n_images, self.height, self.width, self.channels = n, h, w, c
         self.format = IMAGE_U8 if images.dtype == torch.uint8 else IMAGE_F32
         self.cameras = cameras
+        if depth is not None:
+            if tuple(depth.shape) != (n, h, w) or depth.dtype not in (torch.uint16, torch.float32):
+                raise ValueError(f"ImageSet: depth of shape {tuple(depth.shape)} / {depth.dtype}: [{n}, {h}, {w}], uint16 or float32")
+            if depth.device != images.device:
+                raise ValueError(f"ImageSet: images on {images.device}, depth on {depth.device}")
+            if depth_kind not in DEPTH_KINDS:
+                raise ValueError(f"ImageSet: depth_kind {depth_kind!r}: one of {sorted(DEPTH_KINDS)}")
+            if not (float(depth_unit) > 0.0 and float(depth_unit) < float("inf")):
+                raise ValueError(f"ImageSet: depth_unit = {depth_unit} (finite, > 0)")
+            depth = depth.contiguous()
+        self.depth, self.depth_unit, self.depth_kind = depth, float(depth_unit), depth_kind
         self.focal_length = None if focal_length is None else float(focal_length)
         self.aspect_ratio = float(aspect_ratio) if aspect_ratio is not None else w / h
 
     @classmethod
-    def from_dataset(cls, dataset, corrected_focal=True, storage="u8", device="cuda", cameras=None):
+    def from_dataset(cls, dataset, corrected_focal=True, storage="u8", device="cuda", cameras=None, depth=None, depth_unit=1.0,
+                     depth_kind="z"):
         """dataset: rtx_nerf_amd.loader.ImageDataset; the focal rule is RayDataset.from_images' (corrected_focal:
         1/tan(camera_angle_x/2) instead of the reference's 1/tan(0.5*focal_px), quirk Q1).  storage "f32" keeps the loader's
         floats; "u8" quantises them ONCE on the host with round(v * 255) -- a quarter of the memory, and exact (the drawn
         v / 255 is the loader's float, bit for bit) for datasets loaded with flags bit 1 (v / 255, no gamma), whose values are
-        k / 255 already; gamma-linearised frames (flags 0) are rounded to the nearest 1/255.  cameras: as ImageSet's.
+        k / 255 already; gamma-linearised frames (flags 0) are rounded to the nearest 1/255.  cameras: as ImageSet's.  depth: a numpy array
+        or tensor [N, H, W], uint16 or float32 (loader.read_depth_maps), moved to `device`; depth_unit, depth_kind: as ImageSet's.
         Returns (image_set, focal)."""
         import math
         import numpy as np
@@ -1668,11 +1738,15 @@ class ImageSet:
         if storage == "u8":
             img = np.clip(np.rint(img * np.float32(255.0)), 0, 255).astype(np.uint8)
         poses = np.ascontiguousarray(dataset.poses, dtype=np.float32).reshape(-1, 16)
-        return cls(torch.from_numpy(img).to(device), torch.from_numpy(poses).to(device), focal, cameras=cameras), focal
+        if depth is not None:
+            depth = (depth if isinstance(depth, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(depth))).to(device)
+        return cls(torch.from_numpy(img).to(device), torch.from_numpy(poses).to(device), focal, cameras=cameras, depth=depth,
+                   depth_unit=depth_unit, depth_kind=depth_kind), focal
 
     def nbytes(self):
         """bytes held on the device"""
-        return self.images.numel() * self.images.element_size() + self.poses.numel() * 4
+        return (self.images.numel() * self.images.element_size() + self.poses.numel() * 4 +
+                (self.depth.numel() * self.depth.element_size() if self.depth is not None else 0))
 
     def c_struct(self):
         s = _lib.ImageSet()
@@ -1716,6 +1790,42 @@ def draw_batch(image_set, n, seed, step, rays_o, rays_d, targets, drawn=None, ca
     With cameras (a CameraSet; default the image set's own) rtxn_draw_batch_cameras: the same (image, pixel) and target bits, the
     ray from image's camera."""
     draw_batch_launch(draw_batch_args(image_set, n, seed, step, rays_o, rays_d, targets, drawn, cameras))
+
+
+def depth_targets_args(image_set, n, drawn, rays_d, target):
+    """struct rtxn_depth_targets_args over the set's depth maps and LIVE poses and the given tensors (which the caller keeps alive):
+    drawn int32 [>= n, 2] as draw_batch() recorded it, rays_d float32 [>= n, 3], target float32 [>= n].  scale = the set's
+    depth_unit times the world's origin scale, formed here once, in float32."""
+    import numpy as np
+    if image_set.depth is None:
+        raise _lib.RtxnError("depth_targets: the image set holds no depth maps (ImageSet(..., depth=...))")
+    n = int(n)
+    for t, w, nm in ((drawn, 2, "drawn"), (rays_d, 3, "rays_d")):
+        if t is None or t.dim() != 2 or t.shape[1] != w or t.shape[0] < n:
+            raise _lib.RtxnError(f"depth_targets: {nm} of shape {None if t is None else tuple(t.shape)}: [>= {n}, {w}]")
+    if target is None or target.numel() < n:
+        raise _lib.RtxnError(f"depth_targets: target holds {0 if target is None else target.numel()} elements, {n} rays")
+    a = _lib.DepthTargetsArgs()
+    a.depth, a.poses = _ptr(image_set.depth, name="depth"), _ptr(image_set.poses, torch.float32, "poses")
+    a.n_images, a.width, a.height = image_set.n_images, image_set.width, image_set.height
+    a.format = DEPTH_U16 if image_set.depth.dtype == torch.uint16 else DEPTH_F32
+    a.kind = DEPTH_KINDS[image_set.depth_kind]
+    a.scale = float(np.float32(image_set.depth_unit) * np.float32(WORLD_ORIGIN_SCALE))
+    a.n_rays = n
+    a.drawn, a.rays_d = _ptr(drawn, torch.int32, "drawn"), _ptr(rays_d, torch.float32, "rays_d")
+    a.target = _ptr(target, torch.float32, "target")
+    return a
+
+
+def depth_targets(image_set, n, drawn, rays_d, target):
+    """rtxn_depth_targets: the depth targets of a drawn batch (distances along the rays, world units; 0 = no target) from the set's
+    depth maps, on the current stream, right behind draw_batch()."""
+    depth_targets_launch(depth_targets_args(image_set, n, drawn, rays_d, target))
+
+
+def depth_targets_launch(args):
+    """rtxn_depth_targets over a struct depth_targets_args() built earlier (its tensors still alive), on the current stream."""
+    check(_lib.lib().rtxn_depth_targets(C.byref(args), _stream()), "rtxn_depth_targets")
 
 
 def draw_batch_launch(args):

@@ -49,15 +49,24 @@ int check_train_background(const rtxn_train_background* bg, int vr_mode, const c
 int check_train_loss(const rtxn_train_loss* loss, int target_channels, int vr_mode, const char* who, bool* active);
 // ... and its scalar in deterministic mode (loss.hip, beside l2_loss_fixed_order, same grouping and order): the sum of
 // include/rtxn.h from pixels, targets and, with opacity_weight > 0, loss->opacity; with reg, the regulariser's share is added
-// per ray from reg->distortion.  bg, loss, reg: an ACTIVE struct or NULL (loss: L2).
+// per ray from reg->distortion, with depth the depth term's from depth->depth and depth->target.  bg, loss, reg, depth: an ACTIVE
+// struct or NULL (loss: L2).
 __attribute__((visibility("hidden"))) int loss_fixed_order(const float* pixels, const float* target, int n_rays,
                                                            const rtxn_train_background* bg, const rtxn_train_loss* loss,
-                                                           const rtxn_train_regularizer* reg, float* loss_sum, hipStream_t stream);
+                                                           const rtxn_train_regularizer* reg, const rtxn_train_depth* depth, float* loss_sum,
+                                                           hipStream_t stream);
 
 // The rules of the distortion regulariser (rtxn_train_regularizer, include/rtxn.h), host only, composite_train.hip:
 // RTXN_ERR_INVALID with a message naming the field, or RTXN_OK with *active = whether the regularised compositor runs at all
 // (NULL, or weight 0 with no output: the entry point makes exactly the _loss call).  sample_type < 0: the entry point has none.
 int check_train_regularizer(const rtxn_train_regularizer* reg, int vr_mode, int sample_type, const char* who, bool* active);
+
+// The rules of the depth term (rtxn_train_depth, include/rtxn.h), host only, composite_train.hip: RTXN_ERR_INVALID with a message
+// naming the field, or RTXN_OK with *active = whether the depth compositor runs at all (NULL, or weight 0 with no output: the
+// entry point makes exactly the call of the rung below).  reg: ACTIVE or NULL, rays: NULL where the entry point has none -- an
+// active term shares its t_start / t_end with both.  sample_type < 0: the entry point has none.
+int check_train_depth(const rtxn_train_depth* depth, const rtxn_train_regularizer* reg, const rtxn_ray_gradients* rays, int vr_mode,
+                      int sample_type, const char* who, bool* active);
 
 // The rules of the optimizer options (rtxn_optimizer_options, include/rtxn.h), host only, optimizer.hip: RTXN_ERR_INVALID with a
 // message naming the field, or RTXN_OK with *active = whether anything is switched on (NULL, or a CONSTANT schedule without
@@ -116,11 +125,13 @@ struct TrainOptions {
   const rtxn_ray_gradients* rays = nullptr;
   const rtxn_pose_refinement* pose = nullptr;
   const rtxn_camera_refinement* cameras = nullptr;
+  const rtxn_train_depth* depth = nullptr;
   rtxn_train_background own_bg;
   rtxn_sample_jitter own_jitter;
 };
 // the rungs of both ladders, in the order they were added (the gradients ladder has no _opt and no _ema)
-enum TrainRung { RUNG_PLAIN, RUNG_EX, RUNG_JITTER, RUNG_LOSS, RUNG_REG, RUNG_OPT, RUNG_SCALED, RUNG_EMA, RUNG_RAYS, RUNG_CAMERAS };
+enum TrainRung { RUNG_PLAIN, RUNG_EX, RUNG_JITTER, RUNG_LOSS, RUNG_REG, RUNG_OPT, RUNG_SCALED, RUNG_EMA, RUNG_RAYS, RUNG_CAMERAS,
+                 RUNG_DEPTH };
 // The one checked path of both ladders, host only, trainer.hip: every struct's rules once, in one order, under the name the
 // rung reports under (the name rule of DESIGN 5.17); then inactive structs become NULL and a step (a: its arguments, b unused)
 // gets its own copies.  A gradients call passes a = NULL and its batch.
@@ -147,10 +158,10 @@ struct CompositeArgs {
 // (composite_train.hip): the structs' rules under `who`, then the kernel their active set selects -- nothing active: the plain
 // volrender_l2_fused kernels, a background alone: volrender_l2_bg, else composite_train's, the DEV ones with scale_dev (the
 // scaler's device word, read instead of c.loss_scale).  The shared checks report under the entry point that introduced the
-// topmost active struct, under `who` with scale_dev.
+// topmost active struct, under `who` with scale_dev.  depth (rtxn_train_depth): the DEPTH instantiations of composite_train's.
 __attribute__((visibility("hidden"))) int composite_train(const char* who, const CompositeArgs& c, const rtxn_train_background* bg,
                                                           const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
-                                                          const float* scale_dev, rtxn_stream_t stream);
+                                                          const float* scale_dev, rtxn_stream_t stream, const rtxn_train_depth* depth = nullptr);
 // ... and the launcher of the first two (volrender.hip, whose kernels they are); bg: ACTIVE or NULL
 __attribute__((visibility("hidden"))) int l2_train(const char* who, const CompositeArgs& c, const rtxn_train_background* bg, rtxn_stream_t stream);
 

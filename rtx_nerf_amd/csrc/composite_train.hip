@@ -20,11 +20,19 @@
 // DEV (rtxn_volrender_scaled_train): the loss scale is a word of device memory (rtxn_loss_scaler_state::scale) instead
 // of an argument -- the argument's type and the two reads through scale_value() are all that differs, so DEV = false is the
 // by-value kernel byte for byte (profiles/r14/compositor_scaled_ab.txt).
+// DEPTH (rtxn_train_depth), which implies REG: the ray's expected depth D_r = B = sum w m, which the REG kernels
+// carry already, is fitted to a per-ray target z_r: with e_r = D_r - z_r on rays with a target, the share gains
+// (lambda_z / n_rays) l(e_r), and sweep 2 one more addend, in fp32 as k q_i is:
+//   dL/dw_i = ... + g_D m_i,   S = ... + g_D D_r,   g_D = k_z l'(e_r),  k_z = loss_scale lambda_z / n_rays   (D_r is of degree 1 in w).
+// Everything it adds sits under `if constexpr (DEPTH)`; its arguments ride behind RegArgs in the last kernel argument
+// (RegDepthArgs), so the other instantiations keep their argument block and their machine code
+// (profiles/r25/compositor_fingerprints*.txt).
 #include <cmath>
 #include <type_traits>
 
 #include "background_internal.h"
 #include "common.h"
+#include "depth_internal.h"
 #include "loss_internal.h"
 #include "reg_internal.h"
 #include "wave_scan_internal.h"
@@ -45,13 +53,16 @@ __device__ __forceinline__ float scale_value(const float* s) { return *s; }
 // What a ray's wave does between the sweeps: pixel, loss gradient (fp16, stored and handed on in that form), the ray's share of
 // the loss -- with REG the regulariser's included -- and the per-ray outputs; returns the share.  Every value is wave-uniform;
 // lane 0 stores.
+// DEPTH (rtxn_train_depth): the ray's depth target is read, l(e_r) joins the share and g_D = kz l'(e_r) is handed to
+// sweep 2 in fp32; kz and gD are not touched otherwise.
 struct RayGrad {
   float g0, g1, g2, gA;
 };
-template <bool REG>
-__device__ __forceinline__ float ray_step(const BgArgs& bga, const LossArgs& la, const RegArgs& ra, const float* __restrict__ target, int ray,
+template <bool REG, bool DEPTH>
+__device__ __forceinline__ float ray_step(const BgArgs& bga, const LossArgs& la, const reg_args<DEPTH>& ra, const float* __restrict__ target, int ray,
                                           int batch_size, int lane, float loss_scale, float ar, float ag, float ab, float aw, float L, float B,
-                                          float* __restrict__ pixels, __half* __restrict__ loss_gradients, float (&bg)[3], RayGrad& g) {
+                                          float* __restrict__ pixels, __half* __restrict__ loss_gradients, float (&bg)[3], RayGrad& g, float kz,
+                                          float& gD) {
   const float inv_n = 1.0f / (float)(3L * batch_size), inv_rays = 1.0f / (float)batch_size;
   float tg[3];
   ray_background(bga, target, ray, bg, tg);
@@ -67,6 +78,13 @@ __device__ __forceinline__ float ray_step(const BgArgs& bga, const LossArgs& la,
   float value = ray_loss_term(la, p, tg, aw, alpha, inv_n, inv_rays, dl, dA);
   if constexpr (REG) {
     if (ra.weight > 0.0f) value += reg_loss_share(ra.weight, L, inv_rays);
+  }
+  float lz = 0.0f;
+  if constexpr (DEPTH) {
+    float dlz;
+    lz = depth_term(ra.z, B, ra.z.target[ray], dlz);
+    gD = kz * dlz;
+    if (ra.z.weight > 0.0f) value += depth_loss_share(ra.z.weight, lz, inv_rays);
   }
   const __half h0 = loss_grad_half(loss_scale, dl[0], inv_n), h1 = loss_grad_half(loss_scale, dl[1], inv_n),
                h2 = loss_grad_half(loss_scale, dl[2], inv_n);
@@ -88,6 +106,10 @@ __device__ __forceinline__ float ray_step(const BgArgs& bga, const LossArgs& la,
       if (ra.distortion) ra.distortion[ray] = L;
       if (ra.depth) ra.depth[ray] = B;
     }
+    if constexpr (DEPTH) {
+      if (ra.z.depth) ra.z.depth[ray] = B;
+      if (ra.z.depth_loss) ra.z.depth_loss[ray] = lz;
+    }
   }
   return value;
 }
@@ -100,14 +122,15 @@ __device__ __forceinline__ float ray_step(const BgArgs& bga, const LossArgs& la,
 // ahead of d, wi, mi and q are declared outside the loop and assigned under `if constexpr` (through wi_, mi_), gc is updated
 // in place; in the pair kernel w0, w1, q0, q1 are declared without a value and the loss instantiation forms Ti (1 - ex)
 // inside the product with gc.  Re-run the comparison after moving a declaration in either kernel.
-template <bool REG, bool DEV>
+template <bool REG, bool DEV, bool DEPTH = false>
 __global__ __launch_bounds__(256) void composite_train_kernel(const float4* __restrict__ radiance, const float* __restrict__ step_len,
                                                               const int* __restrict__ num_hits, const int* __restrict__ indices,
                                                               int batch_size, int K, const float* __restrict__ target,
                                                               scale_arg<DEV> loss_scale,
                                                               float* __restrict__ pixels, __half* __restrict__ loss_gradients,
                                                               float* __restrict__ loss_sum, half4* __restrict__ grads, BgArgs bga, LossArgs la,
-                                                              RegArgs ra) {
+                                                              reg_args<DEPTH> ra) {
+  static_assert(REG || !DEPTH, "the depth term needs the regulariser's midpoints and its sum w m");
   using idx_t = sample_index<REG>;
   const int lane = threadIdx.x & 63;
   const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -160,13 +183,18 @@ __global__ __launch_bounds__(256) void composite_train_kernel(const float4* __re
   const float Wt = W_carry, Bt = M_carry;             // REG: A and B as the prefixes of sweep 2 will sum them
   float bg[3];
   RayGrad g;
-  const float value = ray_step<REG>(bga, la, ra, target, ray, batch_size, lane, scale_value(loss_scale), ar, ag, ab, aw, L, Bt, pixels, loss_gradients, bg, g);
+  float gD = 0.0f;                                    // DEPTH: k_z l'(e_r), 0 for a ray without a target
+  float kz = 0.0f;
+  if constexpr (DEPTH) kz = depth_k<DEV>(ra.z, scale_value(loss_scale), batch_size);
+  const float value = ray_step<REG, DEPTH>(bga, la, ra, target, ray, batch_size, lane, scale_value(loss_scale), ar, ag, ab, aw, L, Bt, pixels,
+                                           loss_gradients, bg, g, kz, gD);
   if (lane == 0 && loss_sum) atomicAdd(loss_sum, value);
   const float g0 = g.g0, g1 = g.g1, g2 = g.g2;
   const float gbg = g0 * bg[0] + g1 * bg[1] + g2 * bg[2];
   const float kq = reg_k<DEV>(ra, scale_value(loss_scale), batch_size);
   const float S0 = ((g0 * ar + g1 * ag + g2 * ab) - gbg * aw) + g.gA * aw;     // = sum_k w_k (g . (c_k - bg) + g_A)
-  const float S = REG ? S0 + 2.0f * kq * L : S0;
+  float S = REG ? S0 + 2.0f * kq * L : S0;
+  if constexpr (DEPTH) S += gD * Bt;                  // a ray without a target: gD = 0, every value is that of the call without the term
   // sweep 2: per-sample gradients
   T_carry = 0.0f;
   if constexpr (REG) W_carry = M_carry = 0.0f;
@@ -197,6 +225,7 @@ __global__ __launch_bounds__(256) void composite_train_kernel(const float4* __re
     }
     float gc = ((g0 * c.x + g1 * c.y + g2 * c.z) - gbg) + g.gA;
     if constexpr (REG) gc += kq * q;
+    if constexpr (DEPTH) gc += gD * m;
     const float wgc = act ? Ti * a * gc : 0.0f;
     const float pincl = P_carry + wave_incl_scan_f(wgc);
     if (act) {
@@ -221,13 +250,15 @@ __global__ __launch_bounds__(256) void composite_train_kernel(const float4* __re
 // aligned step lengths, 16-byte aligned gradients.  The loss is reduced per block and added once per block at the very end.
 // REG: a pair never straddles two segments (K even): one t_start / t_end pair per lane and block, turned into the pair's two
 // midpoints and their common width as it is loaded.
-template <bool REG, int U, bool DEV>
+template <bool REG, int U, bool DEV, bool DEPTH = false>
 __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4* __restrict__ radiance, const float* __restrict__ step_len,
                                                                     const int* __restrict__ num_hits, const int* __restrict__ indices,
                                                                     int batch_size, int K, const float* __restrict__ target,
                                                                     scale_arg<DEV> loss_scale, float* __restrict__ pixels,
                                                                     __half* __restrict__ loss_gradients, float* __restrict__ loss_sum,
-                                                                    half4* __restrict__ grads, BgArgs bga, LossArgs la, RegArgs ra) {
+                                                                    half4* __restrict__ grads, BgArgs bga, LossArgs la,
+                                                                    reg_args<DEPTH> ra) {
+  static_assert(REG || !DEPTH, "the depth term needs the regulariser's midpoints and its sum w m");
   using idx_t = sample_index<REG>;
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -312,12 +343,17 @@ __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4
     const float Wt = W_carry, Bt = M_carry;           // REG: A and B as the prefixes of sweep 2 will sum them
     float bg[3];
     RayGrad g;
-    loss_part = ray_step<REG>(bga, la, ra, target, ray, batch_size, lane, scale_value(loss_scale), ar, ag, ab, aw, L, Bt, pixels, loss_gradients, bg, g);
+    float gD = 0.0f;                                  // DEPTH: k_z l'(e_r), 0 for a ray without a target
+    float kz = 0.0f;
+    if constexpr (DEPTH) kz = depth_k<DEV>(ra.z, scale_value(loss_scale), batch_size);
+    loss_part = ray_step<REG, DEPTH>(bga, la, ra, target, ray, batch_size, lane, scale_value(loss_scale), ar, ag, ab, aw, L, Bt, pixels,
+                                     loss_gradients, bg, g, kz, gD);
     const float g0 = g.g0, g1 = g.g1, g2 = g.g2;
     const float gbg = g0 * bg[0] + g1 * bg[1] + g2 * bg[2];
     const float kq = reg_k<DEV>(ra, scale_value(loss_scale), batch_size);
     const float S0 = ((g0 * ar + g1 * ag + g2 * ab) - gbg * aw) + g.gA * aw;     // = sum_k w_k (g . (c_k - bg) + g_A)
-    const float S = REG ? S0 + 2.0f * kq * L : S0;
+    float S = REG ? S0 + 2.0f * kq * L : S0;
+    if constexpr (DEPTH) S += gD * Bt;                // a ray without a target: gD = 0, every value is that of the call without the term
     // sweep 2: per-sample gradients (the radiance is re-read: cache hits)
     T_carry = 0.0f;
     if constexpr (REG) W_carry = M_carry = 0.0f;
@@ -365,6 +401,10 @@ __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4
         if constexpr (REG) gc0[u] += kq * q0;
         gc1[u] = ((g0 * cur[u].c1.x + g1 * cur[u].c1.y + g2 * cur[u].c1.z) - gbg) + g.gA;
         if constexpr (REG) gc1[u] += kq * q1;
+        if constexpr (DEPTH) {
+          gc0[u] += gD * cur[u].m0;
+          gc1[u] += gD * cur[u].m1;
+        }
         const float wgc0 = (REG ? w0 : Ti0[u] * (1.0f - ex0[u])) * gc0[u];
         wgc1[u] = (REG ? w1 : Ti1[u] * (1.0f - ex1[u])) * gc1[u];
         pin[u] = wave_incl_scan_f(wgc0 + wgc1[u]);
@@ -409,8 +449,8 @@ __global__ __launch_bounds__(256) void composite_train_multi_kernel(const float4
 
 // The one RTXN_VR_NERF training compositor (common.h): the five rtxn_volrender_*_train entry points and rtxn_train_gradients.
 int rtxn::composite_train(const char* who, const rtxn::CompositeArgs& c, const rtxn_train_background* bg, const rtxn_train_loss* loss,
-                          const rtxn_train_regularizer* reg, const float* scale_dev, rtxn_stream_t stream) {
-  bool bg_active = false, loss_active = false, reg_active = false;
+                          const rtxn_train_regularizer* reg, const float* scale_dev, rtxn_stream_t stream, const rtxn_train_depth* depth) {
+  bool bg_active = false, loss_active = false, reg_active = false, depth_active = false;
   int rc = rtxn::check_train_background(bg, RTXN_VR_NERF, who, &bg_active);
   if (rc != RTXN_OK) return rc;
   rc = rtxn::check_train_loss(loss, bg_active ? bg->target_channels : 3, RTXN_VR_NERF, who, &loss_active);
@@ -420,11 +460,14 @@ int rtxn::composite_train(const char* who, const rtxn::CompositeArgs& c, const r
   if (!bg_active) bg = nullptr;
   if (!loss_active) loss = nullptr;
   if (!reg_active) reg = nullptr;
+  rc = rtxn::check_train_depth(depth, reg, nullptr, RTXN_VR_NERF, -1, who, &depth_active);
+  if (rc != RTXN_OK) return rc;
+  if (!depth_active) depth = nullptr;
   // An inactive struct runs exactly what the entry point without it runs, under that entry point's name.  With scale_dev nothing
   // falls through: plain L2 is one of loss_term's kinds.
   if (!scale_dev) {
-    if (!reg && !loss) return rtxn::l2_train(bg ? "rtxn_volrender_l2_train_ex" : "rtxn_volrender_l2_train", c, bg, stream);
-    who = reg ? "rtxn_volrender_reg_train" : "rtxn_volrender_loss_train";
+    if (!reg && !loss && !depth) return rtxn::l2_train(bg ? "rtxn_volrender_l2_train_ex" : "rtxn_volrender_l2_train", c, bg, stream);
+    who = depth ? "rtxn_volrender_depth_train" : reg ? "rtxn_volrender_reg_train" : "rtxn_volrender_loss_train";
   }
   const int batch_size = c.batch_size, num_samples_per_hit = c.num_samples_per_hit;
   RTXN_REQUIRE(batch_size >= 0, "%s: batch_size = %d < 0", who, batch_size);
@@ -436,6 +479,9 @@ int rtxn::composite_train(const char* who, const rtxn::CompositeArgs& c, const r
                who);
   RTXN_REQUIRE(!(det_loss && reg && reg->distortion_weight > 0.0f && !reg->distortion),
                "%s: reg->distortion is NULL: in deterministic mode the distortion term of the loss is summed from the L_r the compositor writes there",
+               who);
+  RTXN_REQUIRE(!(det_loss && depth && depth->weight > 0.0f && !depth->depth),
+               "%s: depth->depth is NULL: in deterministic mode the depth term of the loss is summed from the D_r the compositor writes there",
                who);
   RTXN_DEVICE_OR_FAIL();
   hipStream_t s = rtxn::as_stream(stream);
@@ -454,7 +500,23 @@ int rtxn::composite_train(const char* who, const rtxn::CompositeArgs& c, const r
   __half* const lg = static_cast<__half*>(c.loss_gradients_half);
   float* const ls = det_loss ? nullptr : c.loss_sum;
   half4* const rg = static_cast<half4*>(c.radiance_gradients);
-  if (scale_dev) {
+  if (depth) {
+    // the depth term: the REG kernels with one more addend; without a regulariser of its own lambda_d = 0 over the depth struct's distances
+    RegDepthArgs rz{};
+    static_cast<RegArgs&>(rz) = ra;
+    if (!reg) {
+      rz.t_start = depth->t_start;
+      rz.t_end = depth->t_end;
+    }
+    rz.z = make_depth_args(depth, c.loss_scale, batch_size);
+    if (scale_dev) {
+      auto* const kernel = pairs ? composite_train_multi_kernel<true, 4, true, true> : composite_train_kernel<true, true, true>;
+      kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, num_samples_per_hit, c.target, scale_dev, c.pixels, lg, ls, rg, a, la, rz);
+    } else {
+      auto* const kernel = pairs ? composite_train_multi_kernel<true, 4, false, true> : composite_train_kernel<true, false, true>;
+      kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, num_samples_per_hit, c.target, c.loss_scale, c.pixels, lg, ls, rg, a, la, rz);
+    }
+  } else if (scale_dev) {
     auto* const kernel = reg ? (pairs ? composite_train_multi_kernel<true, 4, true> : composite_train_kernel<true, true>)
                              : (pairs ? composite_train_multi_kernel<false, 4, true> : composite_train_kernel<false, true>);
     kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, num_samples_per_hit, c.target, scale_dev, c.pixels, lg, ls, rg, a, la, ra);
@@ -464,7 +526,7 @@ int rtxn::composite_train(const char* who, const rtxn::CompositeArgs& c, const r
     kernel<<<grid, block, 0, s>>>(rad, c.ray_hit, c.num_hits, c.indices, batch_size, num_samples_per_hit, c.target, c.loss_scale, c.pixels, lg, ls, rg, a, la, ra);
   }
   RTXN_LAUNCH_CHECK("composite_train_kernel");
-  if (det_loss) return rtxn::loss_fixed_order(c.pixels, c.target, batch_size, bg, loss, reg, c.loss_sum, s);
+  if (det_loss) return rtxn::loss_fixed_order(c.pixels, c.target, batch_size, bg, loss, reg, depth, c.loss_sum, s);
   return RTXN_OK;
 }
 
@@ -511,6 +573,32 @@ int rtxn::check_train_regularizer(const rtxn_train_regularizer* reg, int vr_mode
   return RTXN_OK;
 }
 
+int rtxn::check_train_depth(const rtxn_train_depth* depth, const rtxn_train_regularizer* reg, const rtxn_ray_gradients* rays, int vr_mode,
+                            int sample_type, const char* who, bool* active) {
+  *active = false;
+  if (!depth) return RTXN_OK;
+  RTXN_REQUIRE(std::isfinite(depth->weight) && depth->weight >= 0.0f, "%s: depth->weight = %g (finite, >= 0)", who, (double)depth->weight);
+  RTXN_REQUIRE(depth->kind == RTXN_LOSS_L2 || depth->kind == RTXN_LOSS_L1 || depth->kind == RTXN_LOSS_HUBER,
+               "%s: depth->kind = %d: unknown depth loss kind (RTXN_LOSS_L2 | _L1 | _HUBER)", who, depth->kind);
+  if (depth->kind == RTXN_LOSS_HUBER)
+    RTXN_REQUIRE(std::isfinite(depth->param) && depth->param > 0.0f, "%s: depth->param = %g: RTXN_LOSS_HUBER needs a finite delta > 0", who,
+                 (double)depth->param);
+  if (!(depth->weight > 0.0f || depth->depth || depth->depth_loss)) return RTXN_OK;
+  RTXN_REQUIRE(depth->target, "%s: depth->target is NULL: the depth term and its outputs need the rays' depth targets", who);
+  RTXN_REQUIRE(depth->t_start && depth->t_end,
+               "%s: depth->t_start / depth->t_end are NULL: the depth term and its outputs need the segments' entry and exit distances", who);
+  RTXN_REQUIRE(vr_mode == RTXN_VR_NERF, "%s: depth->weight / depth / depth_loss need the RTXN_VR_NERF compositor (vr_mode = %d)", who, vr_mode);
+  RTXN_REQUIRE(sample_type < 0 || sample_type == RTXN_SAMPLING_MIDPOINT_WORLD || sample_type == RTXN_SAMPLING_JITTER_WORLD,
+               "%s: depth->weight / depth / depth_loss need sample_type RTXN_SAMPLING_MIDPOINT_WORLD or _JITTER_WORLD (sample_type = %d): "
+               "distances are world units along the ray", who, sample_type);
+  RTXN_REQUIRE(!reg || !reg->t_start || (reg->t_start == depth->t_start && reg->t_end == depth->t_end),
+               "%s: depth->t_start / t_end and reg->t_start / t_end must be the same buffers (the traversal writes them once)", who);
+  RTXN_REQUIRE(!rays || (rays->t_start == depth->t_start && rays->t_end == depth->t_end),
+               "%s: rays->t_start / t_end and depth->t_start / t_end must be the same buffers (the traversal writes them once)", who);
+  *active = true;
+  return RTXN_OK;
+}
+
 extern "C" int rtxn_volrender_loss_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
                                          int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
                                          void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
@@ -542,4 +630,20 @@ extern "C" int rtxn_volrender_scaled_train(const float* network_outputs, const f
   return rtxn::composite_train(who, {network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
                                scaler ? 0.0f : loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients}, bg, loss, reg,
                                scaler ? &scaler->state->scale : nullptr, stream);
+}
+
+// the depth term beside everything below it; scaler as rtxn_volrender_scaled_train's; depth == NULL or inactive: that call
+extern "C" int rtxn_volrender_depth_train(const float* network_outputs, const float* ray_hit, const int* num_hits, const int* indices,
+                                          int batch_size, int num_samples_per_hit, const float* target, float loss_scale, float* pixels,
+                                          void* loss_gradients_half, float* loss_sum, void* radiance_gradients,
+                                          const rtxn_train_background* bg, const rtxn_train_loss* loss, const rtxn_train_regularizer* reg,
+                                          const rtxn_loss_scaler* scaler, const rtxn_train_depth* depth, rtxn_stream_t stream) {
+  const char* who = depth ? "rtxn_volrender_depth_train" : scaler ? "rtxn_volrender_scaled_train" : "rtxn_volrender_reg_train";
+  if (scaler) {
+    const int rc = rtxn::check_loss_scaler(scaler, who, true);
+    if (rc != RTXN_OK) return rc;
+  }
+  return rtxn::composite_train(who, {network_outputs, ray_hit, num_hits, indices, batch_size, num_samples_per_hit, target,
+                               scaler ? 0.0f : loss_scale, pixels, loss_gradients_half, loss_sum, radiance_gradients}, bg, loss, reg,
+                               scaler ? &scaler->state->scale : nullptr, stream, depth);
 }

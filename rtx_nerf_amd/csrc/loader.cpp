@@ -222,8 +222,14 @@ bool inflate_like_stb(const std::vector<unsigned char>& z, bool zlib_header, siz
 // zlib checksum are not verified, scanline data may be longer than the image needs but not shorter, and bit depths below 8
 // are unpacked for any colour type (scaled to 0..255 for grey only) -- tests/golden/loader_stb_fuzz.npz holds what the
 // reference's header returned for a few hundred random files of every such kind.
+// info (rtxn_load_png_gray16): the header's bit depth and colour type, and for a 16-bit file the LOW byte of every sample, in the
+// layout of the 8-bit samples before palette or colour key are applied (width*height*source channels).
+struct PngInfo {
+  int depth = 0, ctype = -1;
+  std::vector<unsigned char> low;
+};
 bool decode_png(const std::vector<unsigned char>& file, int& width, int& height, int& channels,
-                std::vector<unsigned char>& pixels, std::string& err) {
+                std::vector<unsigned char>& pixels, std::string& err, PngInfo* info = nullptr) {
   static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
   if (file.size() < 8 || memcmp(file.data(), sig, 8)) { err = "not a PNG"; return false; }
   size_t pos = 8;
@@ -321,7 +327,7 @@ bool decode_png(const std::vector<unsigned char>& file, int& width, int& height,
   if (raw_total < raw_size) { err = "not enough pixels"; return false; }
   const size_t npx = (size_t)width * height;
   std::vector<unsigned char> s8(npx * src_ch), lo8;          // 8-bit samples of the whole image (16-bit: high bytes; low bytes beside
-  if (depth == 16 && has_key) lo8.resize(npx * src_ch);      // them where a colour key has to be compared)
+  if (depth == 16 && (has_key || info)) lo8.resize(npx * src_ch);      // them where a colour key has to be compared, or the caller asks)
   const unsigned maxv = (1u << depth) - 1;
   size_t raw_pos = 0;
   std::vector<unsigned char> img;
@@ -377,6 +383,11 @@ bool decode_png(const std::vector<unsigned char>& file, int& width, int& height,
         }
       }
     }
+  }
+  if (info) {
+    info->depth = depth;
+    info->ctype = ctype;
+    info->low = lo8;
   }
   if (ctype == 3) {
     channels = pal_alpha ? 4 : 3;
@@ -695,6 +706,56 @@ extern "C" void rtxn_free_image_dataset(rtxn_image_dataset* d) {
   free(d->poses);
   memset(d, 0, sizeof(*d));
 }
+
+// A depth map: a gray PNG as 16-bit samples, row-major, in the file's own unit.  16-bit files keep both bytes (the
+// image path above keeps the high byte only); 8-bit files are widened as v, not v * 257: a depth map's unit is a length, not a
+// fraction of white.  Interlaced or not; a tRNS colour key is ignored.  Every other colour type, and gray below 8 bits, is
+// refused with a message: a depth map that was saved as RGB is a mistake to report, not to guess at.
+extern "C" int rtxn_load_png_gray16(const char* path, int* width, int* height, uint16_t** out) {
+  RTXN_REQUIRE(path && width && height && out, "rtxn_load_png_gray16: NULL argument");
+  *out = nullptr;
+  *width = *height = 0;
+  try {
+    std::vector<unsigned char> file, px;
+    if (!read_file(path, file)) {
+      rtxn::set_error("Failed to load depth map %s: cannot read the file", path);
+      return RTXN_ERR_IO;
+    }
+    int w = 0, h = 0, ch = 0;
+    std::string err;
+    PngInfo info;
+    if (!decode_png(file, w, h, ch, px, err, &info)) {
+      rtxn::set_error("Failed to load depth map %s: %s", path, err.c_str());
+      return RTXN_ERR_IO;
+    }
+    if (info.ctype != 0 || (info.depth != 8 && info.depth != 16)) {
+      rtxn::set_error("Failed to load depth map %s: colour type %d with %d bits: a depth map is a gray PNG of 8 or 16 bits", path, info.ctype,
+                      info.depth);
+      return RTXN_ERR_IO;
+    }
+    const size_t npx = (size_t)w * h;
+    uint16_t* v = static_cast<uint16_t*>(malloc(npx * sizeof(uint16_t)));
+    if (!v) {
+      rtxn::set_error("Failed to load depth map %s: out of memory", path);
+      return RTXN_ERR_IO;
+    }
+    for (size_t i = 0; i < npx; ++i) {                         // ch: 1, or 2 with a colour key's alpha behind the sample
+      const unsigned hi = px[i * ch];
+      v[i] = (uint16_t)(info.depth == 16 ? (hi << 8) | info.low[i] : hi);
+    }
+    *width = w;
+    *height = h;
+    *out = v;
+    return RTXN_OK;
+  } catch (const std::exception& e) {
+    rtxn::set_error("Failed to load depth map %s: %s", path, e.what());
+  } catch (...) {
+    rtxn::set_error("Failed to load depth map %s", path);
+  }
+  return RTXN_ERR_IO;
+}
+
+extern "C" void rtxn_free_png_gray16(uint16_t* values) { free(values); }
 
 // stb_image_write's role (included but never called by the reference, main.cu:19-21): 8-bit RGB PNG.
 extern "C" int rtxn_write_png_rgb8(const char* path, const unsigned char* rgb, int width, int height) {

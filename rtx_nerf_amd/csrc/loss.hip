@@ -16,6 +16,7 @@
 // Also here: the same fixed-order sum and the stand-alone elementwise kernel (rtxn_loss) for the losses of rtxn_train_loss.
 #include "background_internal.h"
 #include "common.h"
+#include "depth_internal.h"
 #include "loss_internal.h"
 #include "reg_internal.h"
 
@@ -56,11 +57,12 @@ __global__ __launch_bounds__(kLossThreads) void l2_loss_fixed_order_kernel(const
 // The same sum for the losses of rtxn_train_loss (composite_train.hip's kernels; include/rtxn.h): the per-ray term is
 // loss_internal.h's ray_loss_term, the function the compositor evaluates, on the pixels it stored and -- with lambda > 0 -- on
 // the opacities it stored; grouping and order are l2_loss_fixed_order_kernel's.  REG: the regulariser's share is added per ray
-// from the L_r the compositor stored, by the expression the compositor itself adds (reg_internal.h).
-template <bool REG>
+// from the L_r the compositor stored, by the expression the compositor itself adds (reg_internal.h).  DEPTH: likewise the depth
+// term's share, from the D_r the compositor stored and the ray's target (depth_internal.h).
+template <bool REG, bool DEPTH>
 __global__ __launch_bounds__(kLossThreads) void loss_fixed_order_kernel(const float* __restrict__ pixels, const float* __restrict__ target,
                                                                         int n_rays, BgArgs bg, LossArgs la, float* __restrict__ loss_sum,
-                                                                        RegArgs ra) {
+                                                                        RegArgs ra, DepthArgs da) {
   __shared__ float red[kLossThreads];
   const float inv_n = 1.0f / (float)(3L * n_rays), inv_rays = 1.0f / (float)n_rays;
   const int groups = (n_rays + 3) / 4;
@@ -80,6 +82,12 @@ __global__ __launch_bounds__(kLossThreads) void loss_fixed_order_kernel(const fl
                              dl, dA);
         if constexpr (REG) {
           if (ra.weight > 0.0f) e[k] += reg_loss_share(ra.weight, ra.distortion[ray], inv_rays);
+        }
+        if constexpr (DEPTH) {
+          if (da.weight > 0.0f) {
+            float dlz;
+            e[k] += depth_loss_share(da.weight, depth_term(da, da.depth[ray], da.target[ray], dlz), inv_rays);
+          }
         }
       }
     }
@@ -126,12 +134,14 @@ __global__ __launch_bounds__(kElemThreads) void loss_kernel(const float* __restr
 namespace rtxn {
 
 int loss_fixed_order(const float* pixels, const float* target, int n_rays, const rtxn_train_background* bg, const rtxn_train_loss* loss,
-                     const rtxn_train_regularizer* reg, float* loss_sum, hipStream_t stream) {
+                     const rtxn_train_regularizer* reg, const rtxn_train_depth* depth, float* loss_sum, hipStream_t stream) {
   const BgArgs a = make_bg_args(bg);
   const LossArgs la = make_loss_args(loss, bg != nullptr);
   const RegArgs ra = make_reg_args(reg, 1.0f, n_rays);      // the loss scale enters sweep 2's factor only: not read here
-  auto* const kernel = reg ? loss_fixed_order_kernel<true> : loss_fixed_order_kernel<false>;
-  kernel<<<1, kLossThreads, 0, stream>>>(pixels, target, n_rays, a, la, loss_sum, ra);
+  const DepthArgs da = make_depth_args(depth, 1.0f, n_rays);
+  auto* const kernel = depth ? (reg ? loss_fixed_order_kernel<true, true> : loss_fixed_order_kernel<false, true>)
+                             : (reg ? loss_fixed_order_kernel<true, false> : loss_fixed_order_kernel<false, false>);
+  kernel<<<1, kLossThreads, 0, stream>>>(pixels, target, n_rays, a, la, loss_sum, ra, da);
   RTXN_LAUNCH_CHECK("loss_fixed_order_kernel");
   return RTXN_OK;
 }

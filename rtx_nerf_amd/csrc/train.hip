@@ -4067,10 +4067,10 @@ int rtxn::train_gradients(const rtxn_train_batch* b, const rtxn::TrainOptions& o
   if (rc != RTXN_OK) return rc;
   // launch_volrender_cuda, loss->evaluate, launch_volrender_backward_cuda (main.cu:737-767): per ray, no sample count needed
   if (b->vr_mode == RTXN_VR_NERF) {                            // with a scaler always: the checked path saw to that
-    rc = rtxn::composite_train(scaler ? "rtxn_volrender_scaled_train" : "rtxn_volrender_reg_train",
+    rc = rtxn::composite_train(scaler ? "rtxn_volrender_scaled_train" : o.depth ? "rtxn_volrender_depth_train" : "rtxn_volrender_reg_train",
                                {b->radiance, b->t_vals, b->num_stored, b->indices, b->n_rays, 32, b->targets, scaler ? 0.0f : b->loss_scale, b->pixels,
                                 b->loss_gradients_half, b->loss_sum, b->radiance_gradients},
-                               o.bg, loss, o.reg, scaler ? &scaler->state->scale : nullptr, stream);
+                               o.bg, loss, o.reg, scaler ? &scaler->state->scale : nullptr, stream, o.depth);
     if (rc != RTXN_OK) return rc;
   } else {
     rc = rtxn_volrender_fwd(nullptr, b->radiance, b->num_stored, b->indices, b->t_vals, b->n_rays, 32, b->pixels, b->vr_mode, stream);
@@ -4162,4 +4162,12 @@ extern "C" int rtxn_train_gradients_rays(const rtxn_train_batch* b, const rtxn_t
                                          const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
                                          const rtxn_ray_gradients* rays, rtxn_stream_t stream) {
   return gradients_entry(rtxn::RUNG_RAYS, b, {bg, jitter, loss, reg, nullptr, scaler, nullptr, rays}, stream);
+}
+
+extern "C" int rtxn_train_gradients_depth(const rtxn_train_batch* b, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                          const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_loss_scaler* scaler,
+                                          const rtxn_ray_gradients* rays, const rtxn_train_depth* depth, rtxn_stream_t stream) {
+  rtxn::TrainOptions o{bg, jitter, loss, reg, nullptr, scaler, nullptr, rays};
+  o.depth = depth;
+  return gradients_entry(rtxn::RUNG_DEPTH, b, o, stream);
 }

@@ -123,15 +123,17 @@ static int optimizer_step(const rtxn_train_step_args* a, const rtxn_optimizer_op
 
 // ---- the one checked path of the step and gradients ladders (common.h) ----------------------------------------------
 
-// The name rule: a rung reports under its own name while it holds a struct of its own -- _cameras: cameras, _rays: rays or pose, _ema: the EMA,
+// The name rule: a rung reports under its own name while it holds a struct of its own -- _depth: depth, _cameras: cameras, _rays: rays or pose, _ema: the EMA,
 // _scaled: the scaler, _opt: options (have_opt: present for the options' own check, ACTIVE from then on) -- and is the rung below
 // otherwise; _reg and the rungs below it always report under their own name.
 static const char* entry_name(bool step, int rung, const rtxn::TrainOptions& o, bool have_opt) {
   static const char* const kStep[] = {"rtxn_train_step", "rtxn_train_step_ex", "rtxn_train_step_jitter", "rtxn_train_step_loss", "rtxn_train_step_reg",
                                       "rtxn_train_step_opt", "rtxn_train_step_scaled", "rtxn_train_step_ema", "rtxn_train_step_rays",
-                                      "rtxn_train_step_cameras"};
+                                      "rtxn_train_step_cameras", "rtxn_train_step_depth"};
   static const char* const kGradients[] = {"rtxn_train_gradients", "rtxn_train_gradients_ex", "rtxn_train_gradients_jitter", "rtxn_train_gradients_loss",
-                                           "rtxn_train_gradients_reg", nullptr, "rtxn_train_gradients_scaled", nullptr, "rtxn_train_gradients_rays", nullptr};
+                                           "rtxn_train_gradients_reg", nullptr, "rtxn_train_gradients_scaled", nullptr, "rtxn_train_gradients_rays", nullptr,
+                                           "rtxn_train_gradients_depth"};
+  if (rung == rtxn::RUNG_DEPTH && !o.depth) rung = step ? rtxn::RUNG_CAMERAS : rtxn::RUNG_RAYS;
   if (rung == rtxn::RUNG_CAMERAS && !o.cameras) rung = rtxn::RUNG_RAYS;
   if (rung == rtxn::RUNG_RAYS && !o.rays && !o.pose) rung = rtxn::RUNG_EMA;
   if (rung == rtxn::RUNG_EMA && !o.ema) rung = rtxn::RUNG_SCALED;
@@ -141,7 +143,7 @@ static const char* entry_name(bool step, int rung, const rtxn::TrainOptions& o, 
 }
 
 // The order: the options (under the name they are present with), then NULL arguments, the EMA's and the scaler's requirements of
-// the options, then jitter, background, loss, regulariser, scaler, rays, pose.  A rung checks what its signature has: the rungs
+// the options, then jitter, background, loss, regulariser, depth, scaler, rays, pose.  A rung checks what its signature has: the rungs
 // below _jitter leave a missing jitter to rtxn_train_gradients, as they always did.
 int rtxn::check_train_options(rtxn::TrainRung rung, bool step, const rtxn_train_step_args* a, const rtxn_train_batch* b, rtxn::TrainOptions* o) {
   bool opt_active = false;
@@ -184,6 +186,12 @@ int rtxn::check_train_options(rtxn::TrainRung rung, bool step, const rtxn_train_
   if (step && reg_active)
     RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the regulariser's t_start / t_end are written by the "
                  "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
+  bool depth_active = false;
+  rc = rtxn::check_train_depth(o->depth, reg_active ? o->reg : nullptr, o->rays, b->vr_mode, b->sample_type, who, &depth_active);
+  if (rc != RTXN_OK) return rc;
+  if (step && depth_active)
+    RTXN_REQUIRE(a->trace.mode == RTXN_TRACE_DDA, "%s: trace.mode = %d: the depth term's t_start / t_end are written by the "
+                 "RTXN_TRACE_DDA walk only, not by RTXN_TRACE_COMPAT", who, a->trace.mode);
   if (o->scaler) {
     if (step)
       RTXN_REQUIRE(b->vr_mode == RTXN_VR_NERF, "%s: the loss scaler needs the RTXN_VR_NERF compositor (batch.vr_mode = %d)", who, b->vr_mode);
@@ -194,6 +202,7 @@ int rtxn::check_train_options(rtxn::TrainRung rung, bool step, const rtxn_train_
   if (!bg_active) o->bg = nullptr;
   if (!loss_active) o->loss = nullptr;
   if (!reg_active) o->reg = nullptr;
+  if (!depth_active) o->depth = nullptr;
   if (!o->ema && !opt_active) o->opt = nullptr;                // the EMA's step goes through the rate kernel, switched on or not
   if (o->rays) {
     rc = rtxn::check_ray_gradients(who, o->rays, b, o->reg);
@@ -275,6 +284,10 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn::TrainOptio
     t.t_start = const_cast<float*>(o.reg->t_start);
     t.t_end = const_cast<float*>(o.reg->t_end);
   }
+  if (o.depth) {                                              // the depth term's likewise
+    t.t_start = const_cast<float*>(o.depth->t_start);
+    t.t_end = const_cast<float*>(o.depth->t_end);
+  }
   if (o.rays) {                                               // ... and the ray gradients': the same buffers when both are given
     t.t_start = o.rays->t_start;
     t.t_end = o.rays->t_end;
@@ -310,7 +323,8 @@ static int train_step_impl(const rtxn_train_step_args* a, const rtxn::TrainOptio
 // _loss: the loss of rtxn_train_loss; _reg: the distortion regulariser; _opt: the optimizer options (optimizer.hip); _scaled: the
 // dynamic loss scale, which implies the non-finite guard; _ema: the weight EMA (the options may have nothing switched on: the
 // step goes through the rate kernel all the same, which advances the EMA's update count); _rays: the ray gradients and the pose
-// refinement (train.hip, pose.hip); _cameras: the intrinsics refinement (camera_refine.hip).
+// refinement (train.hip, pose.hip); _cameras: the intrinsics refinement (camera_refine.hip); _depth: the depth term of
+// rtxn_train_depth (composite_train.hip).
 static int step_entry(rtxn::TrainRung rung, const rtxn_train_step_args* a, rtxn::TrainOptions o, rtxn_stream_t stream) {
   const int rc = rtxn::check_train_options(rung, true, a, nullptr, &o);
   return rc != RTXN_OK ? rc : train_step_impl(a, o, stream);
@@ -367,4 +381,12 @@ extern "C" int rtxn_train_step_cameras(const rtxn_train_step_args* a, const rtxn
                                        const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
                                        const rtxn_pose_refinement* pose, const rtxn_camera_refinement* cameras, rtxn_stream_t stream) {
   return step_entry(rtxn::RUNG_CAMERAS, a, {bg, jitter, loss, reg, opt, scaler, ema, rays, pose, cameras}, stream);
+}
+
+extern "C" int rtxn_train_step_depth(const rtxn_train_step_args* a, const rtxn_train_background* bg, const rtxn_sample_jitter* jitter,
+                                     const rtxn_train_loss* loss, const rtxn_train_regularizer* reg, const rtxn_optimizer_options* opt,
+                                     const rtxn_loss_scaler* scaler, const rtxn_weight_ema* ema, const rtxn_ray_gradients* rays,
+                                     const rtxn_pose_refinement* pose, const rtxn_camera_refinement* cameras, const rtxn_train_depth* depth,
+                                     rtxn_stream_t stream) {
+  return step_entry(rtxn::RUNG_DEPTH, a, {bg, jitter, loss, reg, opt, scaler, ema, rays, pose, cameras, depth}, stream);
 }

@@ -137,6 +137,70 @@ def read_cameras(json_path, width, height):
     return models.pop(), np.asarray(rows, dtype=np.float32)
 
 
+def load_png_gray16(path):
+    """rtxn_load_png_gray16: a gray PNG of 8 or 16 bits as uint16 [H, W] in the file's own unit (16-bit samples whole, 8-bit
+    samples as v); any other colour type raises _lib.RtxnError with the loader's message."""
+    w, h, v = C.c_int(), C.c_int(), C.POINTER(C.c_uint16)()
+    _lib.check(_lib.lib().rtxn_load_png_gray16(str(path).encode(), C.byref(w), C.byref(h), C.byref(v)), "rtxn_load_png_gray16")
+    out = np.ctypeslib.as_array(v, shape=(h.value, w.value)).copy()
+    _lib.lib().rtxn_free_png_gray16(v)
+    return out
+
+
+_DEPTH_KEYS = ("depth_file_path", "depth_path")      # nerfstudio; instant-ngp
+
+
+def read_depth_maps(json_path, width, height):
+    """The per-frame depth maps of an instant-ngp / nerfstudio transforms.json for frames loaded at width x height:
+    (depth, unit) -- what api.ImageSet(depth=, depth_unit=) takes.  Each frame's depth_file_path (nerfstudio) or depth_path
+    (instant-ngp), relative to the JSON, names a gray PNG of 16 or 8 bits (load_png_gray16) or a float32 .npy of shape [H, W];
+    depth is uint16 [N, H, W] for PNGs and float32 [N, H, W] for .npy maps (one kind per set), frames in file order.  A frame
+    without a depth key gets an all-zero map: no target anywhere in it.  unit: the length of one map unit in the poses' unit --
+    the top-level integer_depth_scale (instant-ngp) if present, else depth_unit_scale_factor (nerfstudio), else 1e-3
+    (millimetres) for PNGs and 1.0 for .npy maps.  Refused (ValueError): no frame with a depth key, a map whose size is not
+    width x height (the frame is named), PNG and .npy maps in one set, a unit that is not finite and > 0.  Host only."""
+    import json
+    import os
+    with open(json_path) as f:
+        top = json.load(f)
+    frames = top.get("frames") or []
+    base = os.path.dirname(os.path.abspath(json_path))
+    maps, kinds = [], set()
+    for i, fr in enumerate(frames):
+        name = next((fr[k] for k in _DEPTH_KEYS if k in fr), None)
+        if name is None:
+            maps.append(None)
+            continue
+        path = os.path.join(base, str(name))
+        if not os.path.exists(path) and os.path.exists(path + ".png"):
+            path += ".png"
+        if path.endswith(".npy"):
+            m = np.load(path, allow_pickle=False)
+            if m.dtype != np.float32:
+                raise ValueError(f"read_depth_maps: frame {i} ({name}): a .npy depth map must be float32, got {m.dtype}")
+            kinds.add("npy")
+        else:
+            m = load_png_gray16(path)
+            kinds.add("png")
+        if m.shape != (int(height), int(width)):
+            raise ValueError(f"read_depth_maps: frame {i} ({name}): the depth map is {m.shape[-1]} x {m.shape[0]}, "
+                             f"the frames are {width} x {height}")
+        maps.append(m)
+    if not kinds:
+        raise ValueError(f"read_depth_maps: {json_path}: no frame has a depth_file_path or depth_path")
+    if len(kinds) != 1:
+        raise ValueError(f"read_depth_maps: {json_path}: PNG and .npy depth maps in one set")
+    dtype = np.uint16 if kinds == {"png"} else np.float32
+    unit = float(top.get("integer_depth_scale", top.get("depth_unit_scale_factor", 1e-3 if dtype == np.uint16 else 1.0)))
+    if not (unit > 0.0 and np.isfinite(unit)):
+        raise ValueError(f"read_depth_maps: {json_path}: depth unit {unit} (finite, > 0)")
+    depth = np.zeros((len(frames), int(height), int(width)), dtype)
+    for i, m in enumerate(maps):
+        if m is not None:
+            depth[i] = m
+    return depth, unit
+
+
 def write_png(path, rgb_float):
     """Rendered frame float[H,W,3] in [0,1] -> 8-bit PNG (stb_image_write's unused role, main.cu:19-21)."""
     img = np.ascontiguousarray(np.rint(np.clip(rgb_float, 0.0, 1.0) * 255.0).astype(np.uint8))

@@ -60,8 +60,18 @@ class Trainer:
                  density_scale=1.0, mode="nerf", seed=1337, device="cuda", deterministic=None, background=None, background_seed=0,
                  target_channels=None, sample_jitter=False, jitter_seed=0, loss="l2", loss_param=None, opacity_weight=0.0,
                  distortion_weight=0.0, lr_schedule=None, weight_decay=0.0, skip_nonfinite=False, max_grad_norm=None,
-                 ema_decay=None, ray_gradients=False):
-        """ray_gradients: leave dL/d(rays_o) and dL/d(rays_d) of every step's loss, unscaled, in rays_o_grad / rays_d_grad
+                 ema_decay=None, ray_gradients=False, depth_weight=0.0, depth_loss="l2", depth_loss_param=None):
+        """depth_weight: lambda_z of the depth term (librtxn: rtxn_train_depth, rtxn_volrender_depth_train /
+        rtxn_train_gradients_depth / rtxn_train_step_depth): (lambda_z / n_rays) sum_r l(D_r - z_r) over the rays with a depth target
+        z_r > 0, D_r = sum w m the ray's expected depth (not divided by its opacity), distances in world units along the ray; mode
+        "nerf" and the fused compositor only.  depth_loss: "l2" | "l1" | "huber" (depth_loss_param: delta, default 0.1).  The
+        targets come from the attached image set's depth maps (attach_images() then needs api.ImageSet(depth=...); the target
+        kernel runs right behind every draw) or from the caller: step(..., depth_targets=) / gradients(..., depth_targets=), and
+        graph_depth_targets beside graph_targets for the captured and one-call steps.  Trainer.depth holds D_r and
+        Trainer.depth_loss l(e_r) of every ray of the last batch.  Like distortion_weight its gradient rides the fp16 radiance
+        gradients.  The term has no state: checkpoints do not change.  0.0: nothing is allocated and every call is the one made
+        without the argument.
+        ray_gradients: leave dL/d(rays_o) and dL/d(rays_d) of every step's loss, unscaled, in rays_o_grad / rays_d_grad
         [batch_rays, 3] (the first n rows, after gradients(), step(), step_captured() and step_entry(); librtxn:
         rtxn_hashgrid_input_gradient_segments, rtxn_ray_gradients_reduce, rtxn_train_gradients_rays, rtxn_train_step_rays): the
         gather over d(encoding) behind the table scatter, then the per-ray reduction with the segment distances held fixed
@@ -132,6 +142,7 @@ class Trainer:
         self._init_jitter(sample_jitter, jitter_seed)
         self._init_loss(loss, loss_param, opacity_weight)
         self._init_regularizer(distortion_weight)
+        self._init_depth(depth_weight, depth_loss, depth_loss_param)
         self._init_scaler(loss_scale, max_grad_norm)
         self._init_ema(ema_decay)
         self._init_optimizer(lr_schedule, weight_decay, skip_nonfinite or self._scaler_cfg is not None)
@@ -297,6 +308,13 @@ class Trainer:
             self.dstart, self.dend = torch.zeros((M, 3), device=d), torch.zeros((M, 3), device=d)
             self.rays_o_grad, self.rays_d_grad = torch.zeros((B, 3), device=d), torch.zeros((B, 3), device=d)
             self._rays = api.ray_gradients(self.t_start, self.t_end, self.dstart, self.dend, self.rays_o_grad, self.rays_d_grad)
+        # the depth term: the rays' targets, D_r and l(e_r) per ray, over the same segment distances
+        self.depth_targets = self.depth = self.depth_loss = self._depth = None
+        if self.depth_weight > 0.0:
+            if self.t_start is None:
+                self.t_start, self.t_end = torch.zeros(M, device=d), torch.zeros(M, device=d)
+            self.depth_targets, self.depth, self.depth_loss = torch.zeros(B, device=d), torch.zeros(B, device=d), torch.zeros(B, device=d)
+            self._depth = self._depth_struct(self.depth_targets, self.t_start, self.t_end)
         # data parallel (world > 1): the MLP gradient's all-reduce is issued from inside gradients(), right behind the MLP
         # backward, and runs beside the hash scatter; the hashed levels go through dp.Half2GradExchange (lists where a level
         # is sparse, RTXN_DP_SPARSE=0: always the dense fp16 level)
@@ -365,6 +383,28 @@ class Trainer:
             raise ValueError("Trainer: distortion_weight > 0 needs the fused training compositor (RTXN_TRAIN_FUSE_COMPOSITOR=0 selects "
                              "the three-launch compositor, which has no regulariser)")
         self.distortion_weight = lam
+
+    def _init_depth(self, depth_weight, kind, param):
+        lam = float(depth_weight)
+        if not (lam >= 0.0 and np.isfinite(lam)):
+            raise ValueError(f"Trainer: depth_weight = {depth_weight!r} (finite, >= 0)")
+        if kind not in api.DEPTH_LOSS_KINDS:
+            raise ValueError(f"Trainer: depth_loss {kind!r}: one of {sorted(api.DEPTH_LOSS_KINDS)}")
+        if param is not None and kind == "huber" and not (float(param) > 0.0 and np.isfinite(float(param))):
+            raise ValueError(f"Trainer: depth_loss_param = {param!r}: huber needs a finite value > 0")
+        if lam > 0.0 and self.mode != "nerf":
+            raise ValueError("Trainer: depth_weight > 0 needs mode='nerf': the depth term lives in the fused NeRF compositor and "
+                             "measures world distances, which mode='compat' does not sample")
+        if lam > 0.0 and os.environ.get("RTXN_TRAIN_FUSE_COMPOSITOR", "1") == "0":
+            raise ValueError("Trainer: depth_weight > 0 needs the fused training compositor (RTXN_TRAIN_FUSE_COMPOSITOR=0 selects the "
+                             "three-launch compositor, which has no depth term)")
+        self.depth_weight, self.depth_loss_kind = lam, kind
+        self.depth_loss_param = float(param) if param is not None else None
+
+    def _depth_struct(self, target, t_start, t_end):
+        """api.train_depth over a target buffer and the segment distances of the buffer set it is trained on"""
+        return api.train_depth(self.depth_weight, self.depth_loss_kind, self.depth_loss_param, target, t_start, t_end, self.depth,
+                               self.depth_loss)
 
     def _init_ema(self, ema_decay):
         """the library's own rule (rtxn_weight_ema_check), before anything is allocated"""
@@ -616,6 +656,8 @@ class Trainer:
                 api.camera_refinement(image_set.cameras.model, image_set.cameras.n_cameras, int(image_set.width), **ccfg)
             except (api._lib.RtxnError, TypeError, ValueError) as e:
                 raise ValueError(f"Trainer.attach_images: refine_cameras = {refine_cameras!r}: {e}") from None
+        if self.depth_weight > 0.0 and getattr(image_set, "depth", None) is None:
+            raise ValueError("Trainer.attach_images: depth_weight > 0 needs an image set with depth maps (api.ImageSet(depth=...))")
         if not image_set.images.is_cuda:
             raise api._lib.RtxnError("Trainer.attach_images: the image set must live on the device (librtxn has no CPU path)")
         d = self.dev
@@ -729,9 +771,12 @@ class Trainer:
             seed = (seed + 0x632BE5AB * dist.get_rank()) & 0xFFFFFFFF
         return seed
 
-    def _draw(self, n, rays_o, rays_d, targets):
-        """enqueue: the next batch of the sequence into the given buffers, then the device counter + 1 (the host's is the caller's)"""
+    def _draw(self, n, rays_o, rays_d, targets, depth_targets=None):
+        """enqueue: the next batch of the sequence into the given buffers, then the device counter + 1 (the host's is the caller's);
+        depth_targets (a depth_weight trainer): the batch's depth targets right behind the draw, from the rays and the live poses"""
         api.draw_batch(self.image_set, n, self._draw_seed(), self._draw_step, rays_o, rays_d, targets, self.drawn)
+        if depth_targets is not None:
+            api.depth_targets(self.image_set, n, self.drawn, rays_d, depth_targets)
         self._draw_step.add_(1)
 
     def step_images(self, n=None):
@@ -741,9 +786,10 @@ class Trainer:
         n = self.B if n is None else int(n)
         if n < 1 or n > self.B:
             raise ValueError(f"step_images: n = {n} outside [1, batch_rays = {self.B}]")
-        self._draw(n, self.draw_rays_o, self.draw_rays_d, self.draw_targets)
+        self._draw(n, self.draw_rays_o, self.draw_rays_d, self.draw_targets, self.depth_targets)
         self.draw_count += 1
-        loss = self.step(self.draw_rays_o[:n], self.draw_rays_d[:n], self.draw_targets[:n])
+        loss = self.step(self.draw_rays_o[:n], self.draw_rays_d[:n], self.draw_targets[:n],
+                         None if self._depth is None else self.depth_targets[:n])
         if (self._pose is not None or self._cams is not None) and self._stepped:       # behind the optimizer: the step sees the guard's skip word
             with _Stage(self, "pose"):
                 self._pose_update(n, self.draw_rays_d)
@@ -979,7 +1025,10 @@ class Trainer:
         trainer has (an inactive one below it falls through in the library)."""
         batch = (self.radiance, self.t_vals, self.num_stored, self.indices, n, api.NUM_SAMPLES_PER_SEGMENT, targets)
         out = (self.pixels[:n], self.loss_grads[:n], self.loss, self.dout)
-        if self._scaler is not None:             # the loss scale is the scaler's device word
+        if self._depth is not None:              # with or without a scaler, whose device word is then the loss scale
+            api.volrender_depth_train(*batch, self.loss_scale if self._scaler is None else 0.0, *out, bg, self._loss, self._reg, self._scaler,
+                                      self._depth)
+        elif self._scaler is not None:           # the loss scale is the scaler's device word
             api.volrender_scaled_train(*batch, self._scaler, *out, bg, self._loss, self._reg)
         elif self._reg is not None:
             api.volrender_reg_train(*batch, self.loss_scale, *out, bg, self._loss, self._reg)
@@ -990,8 +1039,9 @@ class Trainer:
         else:
             api.volrender_l2_train(*batch, self.loss_scale, *out)
 
-    def gradients(self, rays_o, rays_d, targets):
-        """Everything of a step up to (not including) the optimizer: traversal ... backward.  Leaves the loss-scaled
+    def gradients(self, rays_o, rays_d, targets, depth_targets=None):
+        """Everything of a step up to (not including) the optimizer: traversal ... backward.  depth_targets (a depth_weight trainer,
+        which needs them): float32 [n], the rays' depth targets in world units along the ray, 0 = none.  Leaves the loss-scaled
         gradient SUMS of this batch in self.dparams (MLP, tcnn layout) and self.dtable / self.dtable_h (hash grid: fp32 for the
         densely stored levels, fp16 for the hashed ones; table_grad() assembles them) and returns the number of samples.  The
         loss is the mean over THIS batch's 3n pixel components (tcnn L2, main.cu:759)."""
@@ -999,6 +1049,14 @@ class Trainer:
         K = api.NUM_SAMPLES_PER_SEGMENT
         vr = api.VR_NERF if self.mode == "nerf" else api.VR_COMPAT
         bg = self._bg(self._bg_step, self._target_width(targets, n))
+        if (depth_targets is None) != (self._depth is None):
+            raise ValueError("Trainer: depth_targets go with depth_weight > 0: " + ("this trainer has no depth term" if self._depth is None
+                             else "pass depth_targets [n] (0 = no target), or step_images() over a set with depth maps"))
+        if depth_targets is not None:
+            if depth_targets.dtype != torch.float32 or depth_targets.numel() != n:
+                raise ValueError(f"Trainer: depth_targets of shape {tuple(depth_targets.shape)} / {depth_targets.dtype}: float32 [{n}]")
+            if depth_targets.data_ptr() != self.depth_targets.data_ptr():        # step_images(): the target kernel wrote them in place
+                self.depth_targets[:n].copy_(depth_targets.reshape(n))
         if self.opacity_weight > 0.0 and targets.shape[-1] != 4:
             raise ValueError(f"Trainer: opacity_weight > 0 needs [n, 4] (straight RGBA) targets, got {tuple(targets.shape)}")
         if self._bg_step is not None and self._bg_step_host != self.step_count:
@@ -1022,7 +1080,7 @@ class Trainer:
                     self.dtable.zero_()
         self._dp_pending = None
         if S == 0:                        # every pixel is its background: loss and pixels, no radiance to differentiate
-            loss_only = self._scaler is None and self._reg is None and bg is None
+            loss_only = self._scaler is None and self._reg is None and self._depth is None and bg is None
             if loss_only and (self._loss is None or not (self.mode == "nerf" and self.fuse_compositor)):
                 self.loss.zero_()
             else:
@@ -1176,15 +1234,15 @@ class Trainer:
         out[self.hashed_lo:] = self.dtable_h.float()
         return out
 
-    def step(self, rays_o, rays_d, targets):
-        """One optimisation step on a batch of rays; returns the (device) loss scalar.
+    def step(self, rays_o, rays_d, targets, depth_targets=None):
+        """One optimisation step on a batch of rays; returns the (device) loss scalar.  depth_targets: as gradients()'.
 
         Data parallel (torch.distributed initialised, SURVEY 8e): every rank holds B_local rays of the global batch;
         gradients are SUMMED across ranks and the mean over ranks is folded into Adam's loss_scale divisor.  EVERY rank
         takes part in the all-reduces and runs Adam in every step -- also a rank whose rays all miss the grid (its
         gradients are zero) -- so the ranks can neither deadlock nor drift apart in step count."""
         world = _world()
-        S = self.gradients(rays_o, rays_d, targets)
+        S = self.gradients(rays_o, rays_d, targets, depth_targets)
         self._stepped = not (S == 0 and world == 1)
         if not self._stepped:
             return self.loss                  # nothing to learn from: no Adam step, step_count unchanged
@@ -1455,6 +1513,7 @@ class Trainer:
         self.graph_rays_d = torch.zeros((n, 3), device=d)
         self.graph_rays_d[:, 2] = 1.0
         self.graph_targets = torch.zeros((n, self.target_channels), device=d)
+        self.graph_depth_targets = torch.zeros(n, device=d) if self._depth is not None else None
         self._g_n, self._g_cap, self._g_prefetch, self._g_draw = n, cap, bool(prefetch), bool(draw)
         # the traversal's outputs, once per buffer set (set 0 = the trainer's own buffers)
         names = ("view_dirs", "num_hits", "indices", "num_stored", "sub_hits", "total", "start", "end", "seg_view")
@@ -1470,6 +1529,10 @@ class Trainer:
         for k, st in enumerate(sets):           # the regulariser reads the t_start / t_end of the set it trains on
             st["reg"] = (None if self._reg is None else self._reg if k == 0 else
                          api.train_regularizer(self.distortion_weight, st["t_start"], st["t_end"], self.distortion))
+            # ... and the depth term the targets of that set's own batch, through a struct of its own
+            st["depth_targets"] = None if self._depth is None else self.depth_targets if k == 0 else torch.zeros_like(self.depth_targets)
+            st["depth"] = (None if self._depth is None else self._depth if k == 0 else
+                           self._depth_struct(st["depth_targets"], st["t_start"], st["t_end"]))
         for st in sets:
             st["targets"] = torch.zeros((n, self.target_channels), device=d)
             st["total_host"] = torch.zeros(1, dtype=torch.int32).pin_memory()
@@ -1607,7 +1670,8 @@ class Trainer:
         graph_rays_o / graph_rays_d / graph_targets (created here if capture_step() has not).  The step counter the call
         advances lives on the device (entry_step).  draw=True (attach_images() first): returns (args, draw_args), draw_args the
         struct rtxn_draw_batch_args that fills those three inputs from the image set -- what the host passes to rtxn_draw_batch in
-        front of rtxn_train_step, as step_entry() then does."""
+        front of rtxn_train_step, as step_entry() then does.  A depth_weight trainer reads its depth targets from
+        graph_depth_targets [n_rays]; with draw=True step_entry() launches rtxn_depth_targets between the two calls instead."""
         if draw and self.image_set is None:
             raise RuntimeError("entry_args(draw=True): call attach_images() first")
         if _world() > 1:
@@ -1623,6 +1687,8 @@ class Trainer:
             self.graph_rays_d = torch.zeros((n, 3), device=d)
             self.graph_rays_d[:, 2] = 1.0
             self.graph_targets = torch.zeros((n, self.target_channels), device=d)
+        if self._depth is not None and (getattr(self, "graph_depth_targets", None) is None or self.graph_depth_targets.numel() != n):
+            self.graph_depth_targets = torch.zeros(n, device=d)
         self.entry_step = torch.full((1,), self.step_count, dtype=torch.int32, device=d)
         self._entry_lr = torch.zeros(1, device=d)
         hash_ = self.encoding == "hash"
@@ -1653,10 +1719,12 @@ class Trainer:
         self._entry_step_host = self.step_count      # what the device counter holds now (an eager step() in between is noticed by step_entry)
         self._entry_inputs = (self.graph_rays_o.data_ptr(), self.graph_rays_d.data_ptr(), self.graph_targets.data_ptr())
         self._clear_grads()            # the call's optimizer clears what it consumes; it must start from zeros
-        self._entry_draw = None
+        self._entry_draw = self._entry_depth_targets = None
         if draw:
             self._entry_draw = api.draw_batch_args(self.image_set, n, self._draw_seed(), self._draw_step, self.graph_rays_o,
                                                    self.graph_rays_d, self.graph_targets, self.drawn)
+            if self._depth is not None:         # rtxn_depth_targets behind the draw: what the host passes between the two calls
+                self._entry_depth_targets = api.depth_targets_args(self.image_set, n, self.drawn, self.graph_rays_d, self.depth_targets)
             return a, self._entry_draw
         return a
 
@@ -1675,11 +1743,15 @@ class Trainer:
             self.entry_step.fill_(self.step_count)
         if getattr(self, "_entry_draw", None) is not None:      # the next batch of the sequence, in front of the step
             api.draw_batch_launch(self._entry_draw)
+            if self._entry_depth_targets is not None:
+                api.depth_targets_launch(self._entry_depth_targets)
             self._draw_step.add_(1)
             self.draw_count += 1
+        elif self._depth is not None:
+            self.depth_targets[:self.graph_depth_targets.numel()].copy_(self.graph_depth_targets)
         api.train_step(self._entry_args, self._entry_bg, self._entry_jit, self._loss, self._reg, self._opt, self._scaler, self._ema,
                        rays=self._rays, pose=self._pose if self._entry_draw is not None else None,
-                       cameras=self._cams if self._entry_draw is not None else None)
+                       cameras=self._cams if self._entry_draw is not None else None, depth=self._depth)
         self._grads_clean = True       # the call's optimizer cleared every gradient it consumed
         self.step_count += 1
         self._entry_step_host = self.step_count
@@ -1697,10 +1769,12 @@ class Trainer:
         st, n, cap = self._g_sets[k], self._g_n, self._g_cap
         if self._g_draw:                        # the batch is drawn here, straight into this set's rays and targets
             rays_o, rays_d = st["rays_o"], st["rays_d"]
-            self._draw(n, rays_o, rays_d, st["targets"])
+            self._draw(n, rays_o, rays_d, st["targets"], st["depth_targets"])
         else:
             rays_o, rays_d = self.graph_rays_o, self.graph_rays_d
             st["targets"].copy_(self.graph_targets)
+            if st["depth_targets"] is not None:
+                st["depth_targets"][:n].copy_(self.graph_depth_targets)
         kw = dict(grid_res=self.R, rays_o=rays_o, rays_d=rays_d, width=n, height=1, ray_begin=0, ray_count=n,
                   occupancy=self.occ, occupancy_coarse=self.coarse, occupancy_bricks=self.bricks, occupancy_super=self.super_mip,
                   mode=api.TRACE_DDA, viewing_direction=st["view_dirs"], num_hits=st["num_hits"], sub_rays=api.auto_sub_rays(n),
@@ -1715,7 +1789,8 @@ class Trainer:
         st, n, cap = self._g_sets[k], self._g_n, self._g_cap
         # no fills: the captured Adam clears every gradient as it consumes it (zero_grads), capture_step() clears them once
         api.train_gradients(self.net, **self._batch_kw(st, n, cap, self._g_jit), skip_table_backward=self._g_split, background=self._g_bg,
-                            jitter=self._g_jit, loss=self._loss, regularizer=st["reg"], scaler=self._scaler, rays=self._rays)
+                            jitter=self._g_jit, loss=self._loss, regularizer=st["reg"], scaler=self._scaler, rays=self._rays,
+                            depth=st["depth"])
 
     def _batch_kw(self, st, n, cap, jitter):
         """The keywords of api.train_batch (struct rtxn_train_batch) over this trainer's buffers; st: the segments, per-ray counts
